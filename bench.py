@@ -32,10 +32,16 @@ pll_compute_edge_loglikelihood at the root edge, which synchronises and returns 
                          torch.distributed.run it is one of the ranks. --gpus N with another WORLD_SIZE is
                          an error.
 
-The timed region is `blocks` (default 5) blocks of exactly `steps` steps, each bracketed by a barrier and a
-device synchronise on both sides, max over ranks per block; ms_per_step / value come from the MEDIAN block,
+The timed region is exactly `steps` steps, split into `blocks` (default 5) blocks of (nearly) equal size, each
+bracketed by a barrier and a device synchronise on both sides, max over ranks per block; ms_per_step / value come from the MEDIAN block,
 ms_per_step_min / _max give the spread. The steps themselves are issued by a C loop over the library's two
 C-ABI calls (csrc/workload/step_loop.c, --driver python for the ctypes loop): an application is C / C++.
+
+A plain run sets up, warms up, times the steps and prints the line: the contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step), the workload and the last step's lnL. --dump-outputs DIR also writes what
+the last timed step left for its caller (dump_outputs). Everything else below - roofline, the live HBM-counter
+passes, cpu_baseline, the pinned and reference lnL comparisons, the class-map forms of a SITE_REPEATS step and,
+at N > 1, t1 / speedup, the un-sharded comparison and the RCCL leg - is measured with --full.
 
 Inputs are SURVEY.md section 8d to the letter (xorshift64 alignment, seed 88172645463325252, balanced
 tree, branch lengths 0.05 + 0.01 (i mod 10), GTR / LG / 61-state stand-in, Gamma(0.5) x 4 mean rates).
@@ -44,7 +50,7 @@ for the same inputs: tests/golden/section8d_lnl.json (made by tools/gen_section8
 authoring container) -> lnl_rel_err_pinned; at N = 1 the reference itself also runs in cpu_baseline
 -> lnl_rel_err.
 
-Besides the contract fields the JSON line carries
+With --full, besides the contract fields the JSON line carries
     roofline      HIP-event timing of the dominant CLV-update kernel's launches on the partition's
                   stream vs the 8 TB/s HBM3E peak; algorithmic bytes per DESIGN.md section 5
     cpu_baseline  the reference's own AVX2 path (oracle/_ref/libpll_ref.so, built from the reference
@@ -681,14 +687,15 @@ class Runner:
             self.h.barrier()
 
     def timed(self, warmup, steps, blocks=1):
-        """`warmup` untimed steps, then `blocks` blocks of exactly `steps` steps, each between two fences, max over
-        ranks per block. Returns (block times, last lnL)."""
+        """`warmup` untimed steps, then `blocks` blocks of exactly `steps` steps (a list: one block of each size,
+        split_steps), each between two fences, max over ranks per block. Returns (block times, last lnL)."""
         lnl = self.steps(warmup)
+        sizes = list(steps) if isinstance(steps, (list, tuple)) else [steps] * blocks
         out = []
-        for _ in range(blocks):
+        for n in sizes:
             self.fence()
             t0 = time.perf_counter()
-            lnl = self.steps(steps)
+            lnl = self.steps(n)
             self.fence()
             dt = time.perf_counter() - t0
             out.append(self.h.max_over_ranks(dt) if self.collective else dt)
@@ -737,11 +744,61 @@ class Runner:
         self.sess.close()
 
 
+def split_steps(steps, blocks):
+    """exactly `steps` timed steps in `blocks` blocks of (nearly) equal size (fewer blocks when steps < blocks)"""
+    return [n for n in (steps // blocks + (1 if i < steps % blocks else 0) for i in range(blocks)) if n]
+
+
 def block_stats(block_s, steps):
-    """median block -> ms per step; min / max for the spread"""
+    """median block -> ms per step; min / max for the spread. steps: per block (an int: the same for every block)"""
     import numpy as np
-    ms = sorted(b / steps * 1e3 for b in block_s)
+    sizes = list(steps) if isinstance(steps, (list, tuple)) else [steps] * len(block_s)
+    ms = sorted(b / n * 1e3 for b, n in zip(block_s, sizes))
     return float(np.median(ms)), ms[0], ms[-1]
+
+
+def timed_note(sizes, fences):
+    if len(sizes) == 1:
+        return f"one block of {sizes[0]} steps, {fences.replace('each block ', '')}"
+    per = f"{sizes[0]}" if sizes[0] == sizes[-1] else f"{sizes[-1]}-{sizes[0]}"
+    return f"median of {len(sizes)} blocks of {per} steps ({sum(sizes)} timed steps in all), {fences}"
+
+
+DUMP_SEED = 20240917
+DUMP_CLV_BYTES = 48 << 20  # the sampled CLVs and their scalers; site_lnl adds at most 8 MB
+DUMP_SITE_LNL = 1 << 20    # site_lnl in full up to this many sites, at `sites` beyond
+
+
+def dump_outputs(dirpath, runner, lnl):
+    """--dump-outputs: what the last timed step left for its caller, as float64 .npy files
+        lnl       [1]                             the log-likelihood the step returned
+        site_lnl  [sites or k]                    per-site log-likelihoods at the same edge on the state the step left
+        sites     [k]                             the site indices sampled below (fixed seed, same for every run of a shape)
+        clv       [parents, k, rate_cats, states] the CLV of every parent of the traversal, in operation order, at `sites`
+        scaler    [parents, k, 1 or rate_cats]    their scalers at `sites` (-1 where a parent has none)
+    k is as many sites as fit in DUMP_CLV_BYTES; site_lnl is taken at `sites` too beyond DUMP_SITE_LNL sites."""
+    import numpy as np
+    sess, case = runner.sess, runner.case
+    os.makedirs(dirpath, exist_ok=True)
+    _, site_lnl = sess.edge_lnl(runner.edge, persite=True)
+    parents = [(op[0], op[1]) for batch in case.op_batches for op in batch]
+    per_rate = case.rate_cats if (case.attributes & runner.api.RATE_SCALERS) else 1
+    per_site = len(parents) * (case.rate_cats * case.states + per_rate) * 8
+    k = int(max(1, min(case.sites, DUMP_CLV_BYTES // per_site)))
+    sites = np.sort(np.random.default_rng(DUMP_SEED).choice(case.sites, size=k, replace=False))
+    if case.sites > DUMP_SITE_LNL:
+        site_lnl = site_lnl[sites]
+    clv = np.empty((len(parents), k, case.rate_cats, case.states))
+    scaler = np.full((len(parents), k, per_rate), -1.0)
+    for i, (c, s) in enumerate(parents):
+        a = sess.read_clv(c, expand=False)
+        sid = runner.lib.pll_get_site_id(sess.p, c)
+        rows = runner.api.as_np(sid, case.sites, np.uint32)[sites] if sid else sites
+        clv[i] = a[rows]
+        if s >= 0:
+            scaler[i] = sess.read_scaler(s, c, expand=False)[rows]
+    for name, arr in (("lnl", np.array([lnl])), ("site_lnl", site_lnl), ("sites", sites), ("clv", clv), ("scaler", scaler)):
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def roofline_leg(args, cfg, lib, api, runner, reps=20):
@@ -900,7 +957,7 @@ def live_traffic(args, kernel):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, counter)
             cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__),
-                   "--config", args.config, "--steps", "3", "--warmup", "1", "--blocks", "1", "--no-cpu", "--no-traffic"]
+                   "--config", args.config, "--steps", "3", "--warmup", "1", "--blocks", "1", "--full", "--no-cpu", "--no-traffic"]
             try:
                 r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=60)
             except subprocess.TimeoutExpired:
@@ -923,7 +980,7 @@ def live_traffic(args, kernel):
         measured="in this run", kernel=kernel, dispatches=[sums["FETCH_SIZE"][1], sums["WRITE_SIZE"][1]],
         fetch_KiB_mean=round(sums["FETCH_SIZE"][0], 2), write_KiB_mean=round(sums["WRITE_SIZE"][0], 2),
         method="two child passes of this command under rocprofv3 (--pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes, --kernel-trace only, "
-               "--steps 3 --warmup 1 --no-cpu); mean over the kernel's dispatches; counters are KiB; FETCH_SIZE doubled (gfx950 counts 64 B per "
+               "--steps 3 --warmup 1 --full --no-cpu); mean over the kernel's dispatches; counters are KiB; FETCH_SIZE doubled (gfx950 counts 64 B per "
                "128-B read request, tools/pmc_calib.hip); WRITE_SIZE exact")
 
 
@@ -970,11 +1027,31 @@ def main_single(args, h):
         case = sharding.sort_columns(lib, case)
     nops = len(case.op_batches[0])
     runner = Runner(h, lib, api, driver, case, cfg.get("repeats"), reduce="rccl" if h.dist else None, c_driver=args.driver == "c")
-    blocks_s, lnl = runner.timed(args.warmup, args.steps, args.blocks)
+    sizes = split_steps(args.steps, args.blocks)
+    blocks_s, lnl = runner.timed(args.warmup, sizes)
     if not np.isfinite(lnl) and not os.environ.get("PLL_BENCH_MEASUREMENT_BUILD"):  # (tools/r3_wide_experiments.sh: builds whose results are wrong on purpose)
         raise SystemExit(f"hot path failed: lnL = {lnl} [{lib.errno()}] {lib.errmsg()}")
-    ms, ms_min, ms_max = block_stats(blocks_s, args.steps)
+    ms, ms_min, ms_max = block_stats(blocks_s, sizes)
     value = total_sites * nops / (ms * 1e-3) / 1e6
+    if args.dump_outputs and h.rank == 0:
+        dump_outputs(args.dump_outputs, runner, lnl)
+    out = {
+        "metric": "M site-CLV-updates/s", "value": round(value, 1), "unit": "M site-CLV-updates/s",
+        "n_gpus": h.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
+        "blocks": len(sizes), "ms_per_step_min": round(ms_min, 4), "ms_per_step_max": round(ms_max, 4),
+        "higher_is_better": True, "scaling": None, "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic (SURVEY 8d: xorshift64 alignment, seed 88172645463325252)",
+        "config": {"workload": cfg["desc"] + tip_note(case, api, args),
+                   "sites_per_gpu": total_sites, "ops_per_traversal": nops, "states": cfg["states"], "rate_cats": 4,
+                   "taxa": cfg["tips"], "step": STEP_REUSED if cfg.get("repeats") else STEP_PLAIN,
+                   "timed": timed_note(sizes, "each block between two device synchronises"),
+                   "driver": "C loop over the two C-ABI calls (csrc/workload/step_loop.c)" if args.driver == "c" and not h.dist else "Python ctypes loop",
+                   "parallelism": "1 GPU"},
+        "lnl": lnl,
+    }
+    if not args.full:
+        runner.close()
+        return out
     roofline, codes = roofline_leg(args, cfg, lib, api, runner)
     step_roofline(roofline, ms)
     if roofline.get("bound") == "hbm" and roofline.get("traffic_source") and not args.no_cpu and not args.no_traffic and h.world == 1:
@@ -988,31 +1065,18 @@ def main_single(args, h):
                     got / roofline["algorithmic_bytes_per_launch"])
             else:
                 roofline["traffic_source"]["live_passes"] = "not taken: " + str(src)
-    out = {
-        "metric": "M site-CLV-updates/s", "value": round(value, 1), "unit": "M site-CLV-updates/s",
-        "n_gpus": h.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
-        "blocks": args.blocks, "ms_per_step_min": round(ms_min, 4), "ms_per_step_max": round(ms_max, 4),
-        "higher_is_better": True, "scaling": None, "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic (SURVEY 8d: xorshift64 alignment, seed 88172645463325252)",
-        "config": {"workload": cfg["desc"] + tip_note(case, api, args),
-                   "sites_per_gpu": total_sites, "ops_per_traversal": nops, "states": cfg["states"], "rate_cats": 4,
-                   "taxa": cfg["tips"], "step": STEP_REUSED if cfg.get("repeats") else STEP_PLAIN,
-                   "timed": f"median of {args.blocks} blocks of {args.steps} steps, each block between two device synchronises",
-                   "driver": "C loop over the two C-ABI calls (csrc/workload/step_loop.c)" if args.driver == "c" and not h.dist else "Python ctypes loop",
-                   "parallelism": "1 GPU"},
-        "lnl": lnl, "roofline": roofline,
-    }
+    out["roofline"] = roofline
     if cfg.get("repeats"):
         # THREE timed figures of the same blocks x steps: maps re-used (value, above); the reference's default call on the
         # unchanged tree; every class map forced to be computed again by every step
-        bdc, lnl_dc = runner.timed_with_class_maps(args.warmup, args.steps, args.blocks, mode="default")
-        ms_dc = block_stats(bdc, args.steps)[0]
+        bdc, lnl_dc = runner.timed_with_class_maps(args.warmup, sizes, mode="default")
+        ms_dc = block_stats(bdc, sizes)[0]
         out["config"]["step_default_call"] = STEP_DEFAULT
         out["ms_per_step_default_call"] = round(ms_dc, 4)
         out["value_default_call"] = round(total_sites * nops / (ms_dc * 1e-3) / 1e6, 1)
         out["lnl_default_call"] = lnl_dc
-        bcm, lnl_cm = runner.timed_with_class_maps(args.warmup, args.steps, args.blocks, mode="forced")
-        ms_cm = block_stats(bcm, args.steps)[0]
+        bcm, lnl_cm = runner.timed_with_class_maps(args.warmup, sizes, mode="forced")
+        ms_cm = block_stats(bcm, sizes)[0]
         out["config"]["step_with_class_maps"] = STEP_MAPS
         out["ms_per_step_with_class_maps"] = round(ms_cm, 4)
         out["value_with_class_maps"] = round(total_sites * nops / (ms_cm * 1e-3) / 1e6, 1)
@@ -1054,15 +1118,46 @@ def main_strong(args, h):
     mine = sharding.shard_case(full, h.rank, h.world, bounds)
     reduce = args.reduce
     runner = Runner(h, lib, api, driver, mine, True, reduce=reduce, c_driver=args.driver == "c")
-    blocks_s, lnl = runner.timed(args.warmup, args.steps, args.blocks)
+    sizes = split_steps(args.steps, args.blocks)
+    blocks_s, lnl = runner.timed(args.warmup, sizes)
     if not np.isfinite(lnl):
         raise SystemExit(f"hot path failed: lnL = {lnl} [{lib.errno()}] {lib.errmsg()}")
-    tN_ms, tN_min, tN_max = block_stats(blocks_s, args.steps)
+    tN_ms, tN_min, tN_max = block_stats(blocks_s, sizes)
     value = total_sites * nops / (tN_ms * 1e-3) / 1e6
     exchange = {"reduce": reduce, reduce + "_ms_per_step": round(tN_ms, 4)}
     # the same steps with the other exchange, for the record (both in one line): RCCL needs the nccl backend
     if reduce == "rccl":
         exchange["rccl_via"] = runner.rccl_via
+    if args.dump_outputs and h.rank == 0:
+        dump_outputs(args.dump_outputs, runner, lnl)  # rank 0's shard; lnl is the sum over the shards
+    shard_sites = h.gather_ints([mine.sites])
+
+    def headline():
+        return {
+            "metric": "M site-CLV-updates/s", "value": round(value, 1), "unit": "M site-CLV-updates/s",
+            "n_gpus": h.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(tN_ms, 4),
+            "blocks": len(sizes), "ms_per_step_min": round(tN_min, 4), "ms_per_step_max": round(tN_max, 4),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+            "data": "synthetic (SURVEY 8d: xorshift64 alignment, seed 88172645463325252; the same alignment on every rank)",
+            "config": {"workload": cfg["desc"] + f", pattern-sorted (pll_compress_site_patterns) and cut into {h.world} contiguous site ranges"
+                       + (" of equal cost (sites + 0.19 x class entries of the tip-only subtrees)" if args.cut == "balanced" else " of equal site count")
+                       + tip_note(full, api, args),
+                       "total_sites": total_sites, "patterns": full.sites, "sites_per_gpu": [s[0] for s in shard_sites],
+                       "ops_per_traversal": nops, "states": 4, "rate_cats": 4, "taxa": cfg["tips"],
+                       "step": "pll_update_partials_rep(full traversal, update_repeats = 0: the class maps of the first step re-used) + edge log-likelihood + the one exchange: sum of the shard lnLs"
+                               + (" in rank order through shared host memory (pll_gpu_group_edge_loglikelihood)" if reduce == "peer" else " by one RCCL all-reduce on the device"),
+                       "timed": timed_note(sizes, "each block between two barriers + device synchronises, max over ranks per block"),
+                       "driver": "C loop over the two C-ABI calls (csrc/workload/step_loop.c)" if args.driver == "c" and reduce == "peer" else "Python ctypes loop",
+                       "parallelism": f"sites sharded x{h.world}, one sum of one double per step ({reduce}; control plane {h.backend})"},
+            "lnl": lnl, "tN_ms": round(tN_ms, 4),
+            "exchange_timed": reduce,  # which exchange `value` / tN_ms were timed with (never the other one's number)
+            "exchange": exchange,
+        }
+
+    if not args.full:
+        h.barrier()
+        runner.close()
+        return headline() if h.rank == 0 else None
     # what the exchange adds behind a result that is already in host memory: the group sum alone, all ranks in step
     if reduce == "peer":
         v = np.array([1.0])
@@ -1075,14 +1170,13 @@ def main_strong(args, h):
         exchange["peer_exchange_alone_note"] = "2000 group sums back to back through ctypes (~1-2 us of that is the Python call); tools/group_latency.c measures the C call"
     # the same steps with the reference's default call on the unchanged tree, and with every class map forced to be
     # computed again by every step (speedup_with_class_maps is defined on the FORCED figure)
-    bdc, lnl_dc = runner.timed_with_class_maps(args.warmup, args.steps, args.blocks, mode="default")
-    tN_dc_ms = block_stats(bdc, args.steps)[0]
-    bcm, lnl_cm = runner.timed_with_class_maps(args.warmup, args.steps, args.blocks, mode="forced")
-    tN_cm_ms = block_stats(bcm, args.steps)[0]
+    bdc, lnl_dc = runner.timed_with_class_maps(args.warmup, sizes, mode="default")
+    tN_dc_ms = block_stats(bdc, sizes)[0]
+    bcm, lnl_cm = runner.timed_with_class_maps(args.warmup, sizes, mode="forced")
+    tN_cm_ms = block_stats(bcm, sizes)[0]
     rep_extra, rep_full = runner.repeats_update_ms()
     rep_extra = h.max_over_ranks(rep_extra)
     shard_levels = h.gather_ints(runner.level_entries())
-    shard_sites = h.gather_ints([mine.sites])
     affinities = h.gather_objects(h.cpu_affinity)  # per rank: the cores it was pinned to (next to its GPU)
     # roofline of the dominant kernel on this rank's shard (rank 0 reports)
     args.config = "c4"
@@ -1093,49 +1187,34 @@ def main_strong(args, h):
     if h.rank == 0:
         # t1: the un-sharded alignment on ONE GPU, same step, same K/W, nothing else running on the node
         solo = Runner(h, lib, api, driver, full, True, reduce=None, c_driver=args.driver == "c")
-        b1, lnl1 = solo.timed(args.warmup, args.steps, args.blocks)
-        t1_ms = block_stats(b1, args.steps)[0]
-        b1dc, _ = solo.timed_with_class_maps(args.warmup, args.steps, args.blocks, mode="default")
-        t1_dc_ms = block_stats(b1dc, args.steps)[0]
-        b1cm, _ = solo.timed_with_class_maps(args.warmup, args.steps, args.blocks, mode="forced")
-        t1_cm_ms = block_stats(b1cm, args.steps)[0]
+        b1, lnl1 = solo.timed(args.warmup, sizes)
+        t1_ms = block_stats(b1, sizes)[0]
+        b1dc, _ = solo.timed_with_class_maps(args.warmup, sizes, mode="default")
+        t1_dc_ms = block_stats(b1dc, sizes)[0]
+        b1cm, _ = solo.timed_with_class_maps(args.warmup, sizes, mode="forced")
+        t1_cm_ms = block_stats(b1cm, sizes)[0]
         global_levels = solo.level_entries()
         rep1_extra, _ = solo.repeats_update_ms(reps=3)
         solo.close()
         pin = pinned_lnl("c4") if not args.sites else None
-        out = {
-            "metric": "M site-CLV-updates/s", "value": round(value, 1), "unit": "M site-CLV-updates/s",
-            "n_gpus": h.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(tN_ms, 4),
-            "blocks": args.blocks, "ms_per_step_min": round(tN_min, 4), "ms_per_step_max": round(tN_max, 4),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic (SURVEY 8d: xorshift64 alignment, seed 88172645463325252; the same alignment on every rank)",
-            "config": {"workload": cfg["desc"] + f", pattern-sorted (pll_compress_site_patterns) and cut into {h.world} contiguous site ranges"
-                       + (" of equal cost (sites + 0.19 x class entries of the tip-only subtrees)" if args.cut == "balanced" else " of equal site count")
-                       + tip_note(full, api, args),
-                       "total_sites": total_sites, "patterns": full.sites, "sites_per_gpu": [s[0] for s in shard_sites],
-                       "ops_per_traversal": nops, "states": 4, "rate_cats": 4, "taxa": cfg["tips"],
-                       "step_with_class_maps": STEP_MAPS.replace("pll_compute_edge_loglikelihood", "edge log-likelihood + the same exchange"),
-                       "step_default_call": STEP_DEFAULT.replace("pll_compute_edge_loglikelihood", "edge log-likelihood + the same exchange"),
-                       "step": "pll_update_partials_rep(full traversal, update_repeats = 0: the class maps of the first step re-used) + edge log-likelihood + the one exchange: sum of the shard lnLs"
-                               + (" in rank order through shared host memory (pll_gpu_group_edge_loglikelihood)" if reduce == "peer" else " by one RCCL all-reduce on the device"),
-                       "timed": f"median of {args.blocks} blocks of {args.steps} steps, each block between two barriers + device synchronises, max over ranks per block",
-                       "driver": "C loop over the two C-ABI calls (csrc/workload/step_loop.c)" if args.driver == "c" and reduce == "peer" else "Python ctypes loop",
-                       "parallelism": f"sites sharded x{h.world}, one sum of one double per step ({reduce}; control plane {h.backend})"},
-            "lnl": lnl, "t1_ms": round(t1_ms, 4), "tN_ms": round(tN_ms, 4), "speedup": round(t1_ms / tN_ms, 3),
+        out = headline()
+        out.update({
+            "t1_ms": round(t1_ms, 4), "speedup": round(t1_ms / tN_ms, 3),
             "t1_value": round(total_sites * nops / (t1_ms * 1e-3) / 1e6, 1), "lnl_unsharded": lnl1,
-            "exchange_timed": reduce,  # which exchange `value` / tN_ms were timed with (never the other one's number)
             "cpu_affinity": affinities,
             "ms_per_step_with_class_maps": round(tN_cm_ms, 4), "value_with_class_maps": round(total_sites * nops / (tN_cm_ms * 1e-3) / 1e6, 1),
             "t1_ms_with_class_maps": round(t1_cm_ms, 4), "speedup_with_class_maps": round(t1_cm_ms / tN_cm_ms, 3),
             "lnl_with_class_maps": lnl_cm,
             "ms_per_step_default_call": round(tN_dc_ms, 4), "value_default_call": round(total_sites * nops / (tN_dc_ms * 1e-3) / 1e6, 1),
             "t1_ms_default_call": round(t1_dc_ms, 4), "speedup_default_call": round(t1_dc_ms / tN_dc_ms, 3), "lnl_default_call": lnl_dc,
-            "lnl_rel_err_vs_unsharded": abs(lnl - lnl1) / abs(lnl1), "exchange": exchange,
+            "lnl_rel_err_vs_unsharded": abs(lnl - lnl1) / abs(lnl1),
             "repeats_update_ms": round(rep_extra, 4), "repeats_update_ms_unsharded": round(rep1_extra, 4),
             "entries_per_level": {"unsharded": global_levels, "shards": shard_levels,
                                   "sum_over_shards_div_unsharded": round(sum(sum(s) for s in shard_levels) / max(sum(global_levels), 1), 4)},
             "roofline": roofline,
-        }
+        })
+        out["config"]["step_with_class_maps"] = STEP_MAPS.replace("pll_compute_edge_loglikelihood", "edge log-likelihood + the same exchange")
+        out["config"]["step_default_call"] = STEP_DEFAULT.replace("pll_compute_edge_loglikelihood", "edge log-likelihood + the same exchange")
         if pin is not None:
             out["lnl_pinned_reference"] = pin
             out["lnl_rel_err_pinned"] = abs(lnl - pin) / abs(pin)
@@ -1166,9 +1245,9 @@ def main_strong(args, h):
         try:
             runner.reduce = "rccl"
             runner.setup_rccl()
-            b2, lnl2 = runner.timed(args.warmup, args.steps, args.blocks)
+            b2, lnl2 = runner.timed(args.warmup, sizes)
             if out is not None:
-                out["exchange"]["rccl_ms_per_step"] = round(block_stats(b2, args.steps)[0], 4)
+                out["exchange"]["rccl_ms_per_step"] = round(block_stats(b2, sizes)[0], 4)
                 out["exchange"]["rccl_lnl_rel_diff"] = abs(lnl2 - lnl) / abs(lnl)
                 out["exchange"]["rccl_via"] = runner.rccl_via
         except Exception as exc:  # noqa: BLE001
@@ -1185,7 +1264,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of `steps` steps each; the line reports the median block")
+    ap.add_argument("--blocks", type=int, default=5,
+                    help="the --steps timed steps are split into this many blocks of (nearly) equal size; the line reports the median block")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: roofline, live HBM-counter passes, cpu_baseline, the class-map "
+                         "forms of the step, the pinned reference lnL; N > 1: t1 / speedup and the RCCL leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--sites", type=int, default=0, help="override the number of sites (N > 1: of the whole alignment)")
     ap.add_argument("--pattern-tip", action="store_true", help="PLL_ATTRIB_PATTERN_TIP variant")
@@ -1194,15 +1279,15 @@ def main():
     ap.add_argument("--tree", default="balanced", choices=["balanced", "random", "caterpillar"],
                     help="topology (BASELINE's configs are balanced; the others show what irregular level structures cost)")
     ap.add_argument("--taxa", type=int, default=0, help="override the number of taxa")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (and the live HBM-counter passes)")
-    ap.add_argument("--no-traffic", action="store_true", help="roofline.traffic from the committed summary instead of two rocprofv3 counter passes of this command")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg (and the live HBM-counter passes)")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: roofline.traffic from the committed summary instead of two rocprofv3 counter passes of this command")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend of the control plane (barriers, max over ranks) and of --reduce rccl; "
                          "gloo + PLL_BENCH_SAME_DEVICE=1 rehearses the N>1 flow on a one-GPU box")
     ap.add_argument("--reduce", default="peer", choices=["peer", "rccl"],
                     help="N > 1: how the shard log-likelihoods are summed (see the docstring)")
     ap.add_argument("--cut", default="equal", choices=["equal", "balanced"],
-                    help="N > 1: shards of equal site count (default) or of equal modelled cost with a size cap (pllamd/sharding.py: balanced_bounds - about 2 % better on one GPU, inside the spread: see there)")
+                    help="N > 1: shards of equal site count (default) or of equal modelled cost with a size cap (pllamd/sharding.py: balanced_bounds - about 2 %% better on one GPU, inside the spread: see there)")
     ap.add_argument("--driver", default="c", choices=["c", "python"], help="who issues the steps of the timed region")
     args = ap.parse_args()
     if args.gpus < 1 or args.blocks < 1 or args.steps < 1:

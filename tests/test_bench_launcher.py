@@ -66,3 +66,16 @@ def test_the_time_limit_reaps_the_ranks_and_keeps_what_rank_zero_said(tmp_path):
 def test_a_failing_rank_stops_the_others_and_its_code_is_returned(tmp_path):
     rc, out, dt = run(tmp_path, "fail", gpus=3, limit=120)
     assert rc == 7 and dt < 60
+
+
+def test_bench_has_the_full_and_dump_options():
+    """a plain run is the headline alone; the other legs are behind --full, the last step's outputs behind --dump-outputs"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    # --steps is the number of timed steps: split over the blocks, never multiplied by them
+    for steps, blocks, sizes in ((20, 5, [4] * 5), (7, 5, [2, 2, 1, 1, 1]), (3, 5, [1, 1, 1]), (50, 1, [50])):
+        assert bench.split_steps(steps, blocks) == sizes
+    assert bench.block_stats([0.004, 0.002, 0.001], [4, 2, 1]) == (1.0, 1.0, 1.0)
+    assert bench.timed_note([7], "each block between two device synchronises") == "one block of 7 steps, between two device synchronises"
+    assert "7 timed steps in all" in bench.timed_note([2, 2, 1, 1, 1], "each block between two device synchronises")

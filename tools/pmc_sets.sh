@@ -9,7 +9,7 @@ i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_VMEM_RD" "SQ_INST_CYCLES_VMEM SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_WAIT_ANY SQ_INSTS_MFMA" "TA_BUSY_avr TA_TA_BUSY_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum" "SQ_INSTS_WAVE32_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_VALU"; do
   i=$((i+1))
   echo "set $i: $set"
-  timeout -k 5 150 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/pmc_$i -- python3 $R/bench.py "$@" --steps 2 --warmup 1 --no-cpu > $O/pmc_$i.log 2>&1 || echo "pmc set $i failed"
+  timeout -k 5 150 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/pmc_$i -- python3 $R/bench.py "$@" --steps 2 --warmup 1 --full --no-cpu > $O/pmc_$i.log 2>&1 || echo "pmc set $i failed"
 done
 NAME=$NAME KSUB="$KSUB" python3 - <<'PY'
 import csv,glob,os,collections

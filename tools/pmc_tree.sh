@@ -5,8 +5,8 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 T=${1:-random}
 O=gpurun_out
 rm -rf $O/pt_fetch $O/pt_write
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pt_fetch -- python3 bench.py --tree $T --steps 3 --warmup 1 --no-cpu > $O/pt_fetch.log 2>&1 || exit 1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pt_write -- python3 bench.py --tree $T --steps 3 --warmup 1 --no-cpu > $O/pt_write.log 2>&1 || exit 1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pt_fetch -- python3 bench.py --tree $T --steps 3 --warmup 1 --full --no-cpu > $O/pt_fetch.log 2>&1 || exit 1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pt_write -- python3 bench.py --tree $T --steps 3 --warmup 1 --full --no-cpu > $O/pt_write.log 2>&1 || exit 1
 python3 - <<'PY'
 import csv, glob, collections, json, re
 def rows(d, name):

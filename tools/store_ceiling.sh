@@ -8,8 +8,8 @@ mkdir -p $O
 rm -rf $O/sc_probe $O/sc_c2 $O/sc_c3
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/store_probe3.hip -o /tmp/stp3 || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/sc_probe -- /tmp/stp3 > $O/sc_probe.log 2>&1 || { tail -5 $O/sc_probe.log; exit 1; }
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/sc_c2 -- python3 bench.py --steps 20 --no-cpu > $O/sc_c2.log 2>&1 || { tail -5 $O/sc_c2.log; exit 1; }
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/sc_c3 -- python3 bench.py --config c3 --steps 10 --no-cpu > $O/sc_c3.log 2>&1 || { tail -5 $O/sc_c3.log; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/sc_c2 -- python3 bench.py --steps 20 --full --no-cpu > $O/sc_c2.log 2>&1 || { tail -5 $O/sc_c2.log; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/sc_c3 -- python3 bench.py --config c3 --steps 10 --full --no-cpu > $O/sc_c3.log 2>&1 || { tail -5 $O/sc_c3.log; exit 1; }
 python3 - "$O" > $O/store_ceiling.txt <<'PY'
 import csv, glob, sys
 O = sys.argv[1]
