@@ -47,6 +47,15 @@ static void drop_chain_plan(pllgpu_ctx *c)
   c->plan = nullptr;
 }
 
+// a plan beyond the kernarg packs keeps its descriptors in the context's device block: the heads, the loads, the step ops
+static void chain_steps_on_device(const pllgpu_ctx *c, const ChainPlan &pl, const ChainStepLoad *&lp, const ChainStepOp *&op)
+{
+  const unsigned char *base = c->chain_dev.p;
+  const size_t heads_bytes = pl.heads.size() * sizeof(ChainHead), loads_bytes = pl.loads.size() * sizeof(ChainStepLoad);
+  lp = reinterpret_cast<const ChainStepLoad *>(base + heads_bytes);
+  op = reinterpret_cast<const ChainStepOp *>(base + heads_bytes + loads_bytes);
+}
+
 // one launch over the heads [first_head, first_head + nchains) of a plan
 static void launch_chain_heads(pllgpu_ctx *c, const ChainPlan &pl, unsigned first_head, unsigned nchains, unsigned variant)
 {
@@ -66,52 +75,19 @@ static void launch_chain_heads(pllgpu_ctx *c, const ChainPlan &pl, unsigned firs
       ns += hd.nsteps + 1;
       pack.heads[h] = hd;
     }
-#define CHAIN_PACK(SMV, C0, S1, C1) hipLaunchKernelGGL((k_partials_dna_chain_pack<SMV, C0, S1, C1>), grid, block, 0, c->stream, pack, pl.entries)
-#define CHAIN_PACK_V(SMV)                              \
-  switch (variant)                                     \
-  {                                                    \
-  case 0: CHAIN_PACK(SMV, false, false, false); break; \
-  case 1: CHAIN_PACK(SMV, false, true, false); break;  \
-  case 2: CHAIN_PACK(SMV, true, false, false); break;  \
-  default: CHAIN_PACK(SMV, true, true, true); break;   \
-  }
-    if (c->gg.scale_mode == 2)
-    {
-      CHAIN_PACK_V(2)
-    }
-    else
-    {
-      CHAIN_PACK_V(1)
-    }
-#undef CHAIN_PACK_V
-#undef CHAIN_PACK
+    with_chain_variant(c->gg.scale_mode, variant, [&](auto SMV, auto C0, auto S1, auto C1) {
+      hipLaunchKernelGGL((k_partials_dna_chain_pack<SMV(), C0(), S1(), C1()>), grid, block, 0, c->stream, pack, pl.entries);
+    });
   }
   else
   {
-    const unsigned char *base = c->chain_dev.p;
-    const size_t heads_bytes = pl.heads.size() * sizeof(ChainHead), loads_bytes = pl.loads.size() * sizeof(ChainStepLoad);
-    const ChainHead *hp = reinterpret_cast<const ChainHead *>(base) + first_head;
-    const ChainStepLoad *lp = reinterpret_cast<const ChainStepLoad *>(base + heads_bytes);
-    const ChainStepOp *op = reinterpret_cast<const ChainStepOp *>(base + heads_bytes + loads_bytes);
-#define CHAIN_MEM(SMV, C0, S1, C1) hipLaunchKernelGGL((k_partials_dna_chain<SMV, C0, S1, C1>), grid, block, 0, c->stream, hp, lp, op, pl.entries)
-#define CHAIN_MEM_V(SMV)                              \
-  switch (variant)                                    \
-  {                                                   \
-  case 0: CHAIN_MEM(SMV, false, false, false); break; \
-  case 1: CHAIN_MEM(SMV, false, true, false); break;  \
-  case 2: CHAIN_MEM(SMV, true, false, false); break;  \
-  default: CHAIN_MEM(SMV, true, true, true); break;   \
-  }
-    if (c->gg.scale_mode == 2)
-    {
-      CHAIN_MEM_V(2)
-    }
-    else
-    {
-      CHAIN_MEM_V(1)
-    }
-#undef CHAIN_MEM_V
-#undef CHAIN_MEM
+    const ChainHead *hp = reinterpret_cast<const ChainHead *>(c->chain_dev.p) + first_head;
+    const ChainStepLoad *lp;
+    const ChainStepOp *op;
+    chain_steps_on_device(c, pl, lp, op);
+    with_chain_variant(c->gg.scale_mode, variant, [&](auto SMV, auto C0, auto S1, auto C1) {
+      hipLaunchKernelGGL((k_partials_dna_chain<SMV(), C0(), S1(), C1()>), grid, block, 0, c->stream, hp, lp, op, pl.entries);
+    });
   }
 }
 
@@ -128,9 +104,7 @@ static int launch_chain_plan(pllgpu_ctx *c, const ChainPlan &pl, bool hold)
   c->chain_held = hold && upto < pl.stages.size();
   c->last_launches = pl.launches - (unsigned)(pl.stages.size() - upto);
   c->last_bytes = pl.bytes;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PLLGPU_ERUNTIME, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
+  return launch_status();
 }
 
 static int launch_held_chains(pllgpu_ctx *c)
@@ -143,9 +117,7 @@ static int launch_held_chains(pllgpu_ctx *c)
     launch_chain_heads(c, pl, pl.stages[i].first_head, pl.stages[i].nchains, pl.stages[i].variant);
     ++c->last_launches;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PLLGPU_ERUNTIME, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
+  return launch_status();
 }
 
 struct PChain
@@ -157,12 +129,14 @@ struct PChain
 struct ChainPartition
 {
   std::vector<int> pr_of[2];  // producer op of the left / right child, or -1
-  std::vector<int> role;      // != 0: member of a cherry-cherry group (plan_fusion)
+  std::vector<Role> role;     // not Role::Plain: member of a cherry-cherry group (plan_fusion)
   std::vector<FusedGroup> groups;
   std::vector<unsigned> S;    // launch stage of every chain op
   std::vector<unsigned char> acc_side, absorb, form; // form: 0 top of a chain, 1 step below the next op of its chain, 2 formed on the fly as a sibling
   std::vector<int> chain_of;
   std::vector<PChain> chains;
+  // is child sd of op i computed by a chain op of this list
+  bool is_chain_op(unsigned i, int sd) const { return pr_of[sd][i] >= 0 && role[pr_of[sd][i]] == Role::Plain; }
 };
 
 // host logic only (no device state): does the list qualify, and how is it partitioned
@@ -204,7 +178,7 @@ static bool partition_chains(const pllgpu_op_t *ops, unsigned count, unsigned no
     }
   }
   // a tip child whose codes were replaced by a dense CLV arrives as an inner child: nothing to do here
-  std::vector<int> &role = P.role;
+  std::vector<Role> &role = P.role;
   std::vector<FusedGroup> &groups = P.groups;
   plan_fusion(true, fuse_cc, nodes, ops, count, role, groups, true, fuse_cc16); // cherry-cherry groups (and groups of two of them) only
   // ---- stages, bottom-up
@@ -215,13 +189,13 @@ static bool partition_chains(const pllgpu_op_t *ops, unsigned count, unsigned no
   absorb.assign(count, 0);
   auto leaf_ready = [&](unsigned i, int sd) -> unsigned { // stage after which a non-chain child exists in HBM
     const int pr = pr_of[sd][i];
-    return (pr >= 0 && role[pr] != 0) ? 1u : 0u; // cherry-cherry groups run in stage 1
+    return (pr >= 0 && role[pr] != Role::Plain) ? 1u : 0u; // cherry-cherry groups run in stage 1
   };
-  auto is_chain_op = [&](unsigned i, int sd) { return pr_of[sd][i] >= 0 && role[pr_of[sd][i]] == 0; };
+  auto is_chain_op = [&](unsigned i, int sd) { return P.is_chain_op(i, sd); };
   auto ready_in_hbm = [&](unsigned i, int sd) -> unsigned { return is_chain_op(i, sd) ? S[pr_of[sd][i]] : leaf_ready(i, sd); };
   for (unsigned i = 0; i < count; ++i)
   {
-    if (role[i]) continue;
+    if (role[i] != Role::Plain) continue;
     unsigned best = ~0u, best_cost = ~0u;
     for (int a = 0; a < 2; ++a)
     {
@@ -280,7 +254,7 @@ static bool partition_chains(const pllgpu_op_t *ops, unsigned count, unsigned no
   for (unsigned ii = count; ii-- > 0;)
   {
     const unsigned i = ii;
-    if (role[i] || form[i] == 2) continue;
+    if (role[i] != Role::Plain || form[i] == 2) continue;
     if (form[i] == 0)
     {
       chain_of[i] = (int)chains.size();
@@ -308,12 +282,12 @@ extern "C" int pllgpu_debug_chain_plan(const pllgpu_op_t *ops, unsigned count, u
   unsigned stages = 0;
   for (unsigned i = 0; i < count; ++i)
   {
-    const bool member = P.role[i] != 0;
+    const bool member = P.role[i] != Role::Plain;
     unsigned st = member ? 1u : P.S[i];
     if (!member && P.chain_of[i] >= 0) st = P.chains[P.chain_of[i]].stage; // a chain runs where its top runs
     if (!member && P.form[i] == 2)
       for (unsigned j = i + 1; j < count; ++j) // the step that forms it on the fly
-        if (P.role[j] == 0 && P.absorb[j] && P.pr_of[1 - P.acc_side[j]][j] == (int)i) st = P.chains[P.chain_of[j]].stage;
+        if (P.role[j] == Role::Plain && P.absorb[j] && P.pr_of[1 - P.acc_side[j]][j] == (int)i) st = P.chains[P.chain_of[j]].stage;
     if (stage) stage[i] = st;
     if (chain) chain[i] = member ? -1 : (P.form[i] == 2 ? -2 : P.chain_of[i]);
     if (form) form[i] = member ? 3 : P.form[i];
@@ -332,58 +306,17 @@ static bool use_cc16(const pllgpu_ctx *c, unsigned entries, unsigned count)
   return (size_t)entries * count >= (size_t)9000000;
 }
 
-// returns 0 and sets used = true when the list was planned and launched as chains
-static int try_chain_plan(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count, bool &used)
+// what a plan's descriptors are built from: the list, its partition, every chain op resolved
+struct ChainBuild
 {
-  used = false;
-  if (!c->chains || !c->fuse || count < 4 || c->any_aos) return 0; // up to three ops the level scheduler + tail kernel is as fast (tools/path_latency.py)
-  if (c->plan && c->plan->epoch == c->alloc_epoch && c->plan->key.size() == count &&
-      memcmp(c->plan->key.data(), ops, count * sizeof(pllgpu_op_t)) == 0)
+  const pllgpu_op_t *ops;
+  const ChainPartition &part;
+  std::vector<DevOp> dev;
+  unsigned entries, clv_bytes, sc_bytes;
+
+  // child sd of op i as a chain reads it from HBM
+  ChainLeaf leaf(unsigned i, int sd, bool &tip, ChainLeafBytes &lb) const
   {
-    used = true;
-    ++c->plan_replays;
-    return launch_chain_plan(c, *c->plan, c->defer_tail);
-  }
-  const unsigned entries = ops[0].parent_entries;
-  if (entries == 0 || aos_entries(c, entries) || (size_t)entries * 128u >= ((size_t)1 << 31)) return 0; // 32-bit buffer offsets
-  const unsigned nodes = c->geo.nodes, nsb = c->geo.scale_buffers;
-  ChainPartition part;
-  if (!partition_chains(ops, count, nodes, nsb, entries, c->fuse_cc, use_cc16(c, entries, count), part)) return 0;
-  ChainPlan *pl = new ChainPlan();
-  std::vector<int> (&pr_of)[2] = part.pr_of;
-  std::vector<int> &role = part.role;
-  std::vector<FusedGroup> &groups = part.groups;
-  std::vector<unsigned> &S = part.S;
-  std::vector<unsigned char> &acc_side = part.acc_side, &absorb = part.absorb;
-  std::vector<PChain> &chains = part.chains;
-  auto is_chain_op = [&](unsigned i, int sd) { return pr_of[sd][i] >= 0 && role[pr_of[sd][i]] == 0; };
-  (void)S;
-  // ---- descriptors: resolve every op once, in list order (a producer's buffers exist before its consumer looks)
-  std::vector<DevOp> dev(count);
-  c->last_bytes = 0.0;
-  for (unsigned i = 0; i < count; ++i)
-    if (role[i] == 0)
-      if (int rc = resolve_op(c, ops[i], dev[i]))
-      {
-        delete pl;
-        return rc;
-      }
-  {
-    sort_groups_by_level(groups); // (ga / gb of the fifteen-op groups are indices into this list: they move with it)
-    if (int rc = build_cc_launches(c, ops, groups, 0, groups.size(), pl->cc))
-    {
-      delete pl;
-      return rc;
-    }
-    if (int rc = build_cc16_launches(c, ops, groups, pl->cc16))
-    {
-      delete pl;
-      return rc;
-    }
-  }
-  const unsigned clv_bytes = (unsigned)(clv_elems(c, entries) * sizeof(double));
-  const unsigned sc_bytes = entries * (c->gg.scale_mode == 2 ? 16u : 4u);
-  auto leaf_of = [&](unsigned i, int sd, bool &tip, ChainLeafBytes &lb) -> ChainLeaf {
     ChainLeaf l;
     tip = ops[i].flags & (sd ? PLLGPU_OP_RIGHT_TIP : PLLGPU_OP_LEFT_TIP);
     lb.clv = lb.aux = lb.pad = 0u;
@@ -401,166 +334,211 @@ static int try_chain_plan(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count,
       lb.aux = l.scaler ? sc_bytes : 0u;
     }
     return l;
-  };
+  }
+};
+
+// what a chain's steps have to fetch decides the kernel variant it runs under (kernels_dna.h)
+static unsigned chain_variant(const pllgpu_op_t *ops, const ChainPartition &part, const PChain &ch)
+{
+  bool c0 = false, s1 = false, c1 = false;
+  for (unsigned i : ch.ops)
+  {
+    const int b = 1 - part.acc_side[i];
+    if (part.is_chain_op(i, b) && part.absorb[i])
+    {
+      const unsigned q = (unsigned)part.pr_of[b][i];
+      const bool t0 = ops[q].flags & PLLGPU_OP_LEFT_TIP, t1 = ops[q].flags & PLLGPU_OP_RIGHT_TIP;
+      s1 = true;
+      if (!t0) c0 = true;
+      if (!t1) c1 = true;
+    }
+    else if (!(ops[i].flags & (b ? PLLGPU_OP_RIGHT_TIP : PLLGPU_OP_LEFT_TIP)))
+      c0 = true;
+  }
+  if (c1 || (c0 && s1)) return 3u;
+  return c0 ? 2u : s1 ? 1u : 0u;
+}
+
+// one chain's head and steps (bottom first, then the terminal step) appended to the plan, its bytes counted; returns
+// the steps added. stream_all: this launch's tops are streamed out as well.
+static unsigned add_chain(const pllgpu_ctx *c, const ChainBuild &b, const PChain &ch, unsigned variant, bool stream_all, ChainPlan *pl)
+{
+  const pllgpu_op_t *ops = b.ops;
+  ChainHead hd;
+  memset(&hd, 0, sizeof hd);
+  hd.first = (unsigned)pl->loads.size();
+  hd.nsteps = (unsigned)ch.ops.size();
+  for (size_t t = ch.ops.size(); t-- > 0;) // bottom first
+  {
+    const unsigned i = ch.ops[t];
+    const int a = b.part.acc_side[i], sib = 1 - a;
+    const bool bottom = t + 1 == ch.ops.size(), top = t == 0;
+    if (bottom)
+    {
+      bool tip;
+      hd.acc0 = b.leaf(i, a, tip, hd.bacc);
+      hd.acc_tip = tip ? 1u : 0u;
+    }
+    ChainStepLoad ld;
+    ChainStepOp so;
+    memset(&ld, 0, sizeof ld);
+    memset(&so, 0, sizeof so);
+    so.parent = b.dev[i].parent;
+    so.pscaler = b.dev[i].pscaler;
+    so.mat_acc = a ? b.dev[i].rmat : b.dev[i].lmat;
+    so.mat_sib = sib ? b.dev[i].rmat : b.dev[i].lmat;
+    so.p_bytes = b.clv_bytes;
+    so.psc_bytes = so.pscaler ? b.sc_bytes : 0u;
+    if (!top || stream_all) ld.flags |= kChStream;
+    bool read_sib = true;
+    if (b.part.is_chain_op(i, sib) && b.part.absorb[i])
+    {
+      const unsigned q = (unsigned)b.part.pr_of[sib][i];
+      bool t0, t1;
+      ld.s0 = b.leaf(q, 0, t0, ld.b0); // a tip-inner op carries its tip on the left
+      ld.s1 = b.leaf(q, 1, t1, ld.b1);
+      ld.flags |= (t0 && t1) ? CS_OTT : t0 ? CS_OTC : CS_OCC;
+      so.bparent = b.dev[q].parent;
+      so.bpscaler = b.dev[q].pscaler;
+      so.bmat0 = b.dev[q].lmat;
+      so.bmat1 = b.dev[q].rmat;
+      so.b_bytes = b.clv_bytes;
+      so.bsc_bytes = so.bpscaler ? b.sc_bytes : 0u;
+      pl->bytes += op_traffic(c, ops[q], true, true);
+      read_sib = false;
+    }
+    else
+    {
+      bool t0;
+      ld.s0 = b.leaf(i, sib, t0, ld.b0);
+      ld.flags |= t0 ? CS_T : CS_C;
+    }
+    pl->bytes += op_traffic(c, ops[i], a == 0 ? bottom : read_sib, a == 0 ? read_sib : bottom);
+    pl->loads.push_back(ld);
+    pl->sops.push_back(so);
+  }
+  {
+    // the terminal step: what the last trip "prefetches" - every size 0
+    ChainStepLoad ld;
+    ChainStepOp so;
+    memset(&ld, 0, sizeof ld);
+    memset(&so, 0, sizeof so);
+    ld.flags = CS_END;
+    pl->loads.push_back(ld);
+    pl->sops.push_back(so);
+  }
+  pl->heads.push_back(hd);
+  pl->head_top_clv.push_back(ops[ch.ops[0]].parent_clv);
+  pl->head_top_scaler.push_back(ops[ch.ops[0]].parent_scaler);
+  pl->head_variant.push_back((unsigned char)variant);
+  return hd.nsteps + 1;
+}
+
+// the last stage may wait for the edge evaluation if it is at most the two ends of an edge and the
+// tail kernel can reproduce k_edge_dna's summation order (one tile per wave there: <= 4096 tiles)
+static void choose_held_stage(const pllgpu_ctx *c, ChainPlan *pl)
+{
+  if (pl->held_from == (size_t)-1) pl->held_from = pl->stages.size();
+  unsigned held_chains = 0;
+  for (size_t i = pl->held_from; i < pl->stages.size(); ++i) held_chains += pl->stages[i].nchains;
+  if (held_chains > 2 || (c->geo.sites + 63) / 64 > 4096u) pl->held_from = pl->stages.size();
+  // the tail kernel takes BOTH ends in one descriptor pack (an end that is not held counts one
+  // terminal step); every stage record was sized against the pack on its own, two records of the last
+  // stage (different fetch variants) together may not fit: such a plan keeps its descriptors in memory
+  unsigned tail_steps = 0, tail_heads = 0;
+  for (size_t i = pl->held_from; i < pl->stages.size(); ++i)
+    for (unsigned h = pl->stages[i].first_head; h < pl->stages[i].first_head + pl->stages[i].nchains; ++h, ++tail_heads)
+      tail_steps += pl->heads[h].nsteps + 1;
+  if (tail_heads && tail_steps + (2u - std::min(tail_heads, 2u)) > (unsigned)kChainPackSteps) pl->in_kernarg = false;
+}
+
+// the plan of a partitioned list: cherry-cherry launches, then per (stage, fetch variant) one launch over its chains
+static int build_chain_plan(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count, unsigned entries, ChainPartition &part, ChainPlan *pl)
+{
+  const std::vector<PChain> &chains = part.chains;
+  ChainBuild b{ops, part, std::vector<DevOp>(count), entries, (unsigned)(clv_elems(c, entries) * sizeof(double)),
+               entries * (c->gg.scale_mode == 2 ? 16u : 4u)};
+  // ---- descriptors: resolve every op once, in list order (a producer's buffers exist before its consumer looks)
+  c->last_bytes = 0.0;
+  for (unsigned i = 0; i < count; ++i)
+    if (part.role[i] == Role::Plain)
+      if (int rc = resolve_op(c, ops[i], b.dev[i])) return rc;
+  sort_groups_by_level(part.groups); // (ga / gb of the fifteen-op groups are indices into this list: they move with it)
+  if (int rc = build_cc_launches(c, ops, part.groups, 0, part.groups.size(), pl->cc)) return rc;
+  if (int rc = build_cc16_launches(c, ops, part.groups, pl->cc16)) return rc;
   unsigned max_stage = 0;
   for (const PChain &ch : chains) max_stage = std::max(max_stage, ch.stage);
   pl->entries = entries;
   pl->in_kernarg = true;
   pl->held_from = (size_t)-1;
-  // what a chain's steps have to fetch decides the kernel variant it runs under (kernels_dna.h)
-  auto variant_of = [&](const PChain &ch) -> unsigned {
-    bool c0 = false, s1 = false, c1 = false;
-    for (unsigned i : ch.ops)
-    {
-      const int b = 1 - acc_side[i];
-      if (is_chain_op(i, b) && absorb[i])
-      {
-        const unsigned q = (unsigned)pr_of[b][i];
-        const bool t0 = ops[q].flags & PLLGPU_OP_LEFT_TIP, t1 = ops[q].flags & PLLGPU_OP_RIGHT_TIP;
-        s1 = true;
-        if (!t0) c0 = true;
-        if (!t1) c1 = true;
-      }
-      else if (!(ops[i].flags & (b ? PLLGPU_OP_RIGHT_TIP : PLLGPU_OP_LEFT_TIP)))
-        c0 = true;
-    }
-    if (c1 || (c0 && s1)) return 3u;
-    return c0 ? 2u : s1 ? 1u : 0u;
-  };
-  std::vector<unsigned> chain_variant(chains.size());
-  for (unsigned k = 0; k < chains.size(); ++k) chain_variant[k] = variant_of(chains[k]);
+  std::vector<unsigned> variant_of(chains.size());
+  for (unsigned k = 0; k < chains.size(); ++k) variant_of[k] = chain_variant(ops, part, chains[k]);
   for (unsigned st = 1; st <= max_stage; ++st)
-   for (unsigned variant = 0; variant < 4; ++variant)
-  {
-    std::vector<unsigned> ids;
-    for (unsigned k = 0; k < chains.size(); ++k)
-      if (chains[k].stage == st && chain_variant[k] == variant) ids.push_back(k);
-    if (ids.empty()) continue;
-    // the longest chains first: their workgroups are dispatched first
-    std::stable_sort(ids.begin(), ids.end(), [&](unsigned x, unsigned y) { return chains[x].ops.size() > chains[y].ops.size(); });
-    ChainLaunchRec rec;
-    rec.first_head = (unsigned)pl->heads.size();
-    rec.nchains = (unsigned)ids.size();
-    rec.variant = variant;
-    const bool stream_tops = (size_t)ids.size() * entries * 128u > c->stream_parent_bytes;
-    unsigned stage_steps = 0;
-    for (unsigned k : ids)
+    for (unsigned variant = 0; variant < 4; ++variant)
     {
-      const PChain &ch = chains[k];
-      ChainHead hd;
-      memset(&hd, 0, sizeof hd);
-      hd.first = (unsigned)pl->loads.size();
-      hd.nsteps = (unsigned)ch.ops.size();
-      stage_steps += hd.nsteps;
-      for (size_t t = ch.ops.size(); t-- > 0;) // bottom first
-      {
-        const unsigned i = ch.ops[t];
-        const int a = acc_side[i], b = 1 - a;
-        const bool bottom = t + 1 == ch.ops.size(), top = t == 0;
-        if (bottom)
-        {
-          bool tip;
-          hd.acc0 = leaf_of(i, a, tip, hd.bacc);
-          hd.acc_tip = tip ? 1u : 0u;
-        }
-        ChainStepLoad ld;
-        ChainStepOp so;
-        memset(&ld, 0, sizeof ld);
-        memset(&so, 0, sizeof so);
-        so.parent = dev[i].parent;
-        so.pscaler = dev[i].pscaler;
-        so.mat_acc = a ? dev[i].rmat : dev[i].lmat;
-        so.mat_sib = b ? dev[i].rmat : dev[i].lmat;
-        so.p_bytes = clv_bytes;
-        so.psc_bytes = so.pscaler ? sc_bytes : 0u;
-        // the tops of the last stage are the ends of the edge evaluated next (from registers, chain tail):
-        // nobody reads them back soon either
-        if (!top || stream_tops || (c->defer_tail && st == max_stage)) ld.flags |= kChStream;
-        bool read_sib = true;
-        if (is_chain_op(i, b) && absorb[i])
-        {
-          const unsigned q = (unsigned)pr_of[b][i];
-          bool t0, t1;
-          ld.s0 = leaf_of(q, 0, t0, ld.b0); // a tip-inner op carries its tip on the left
-          ld.s1 = leaf_of(q, 1, t1, ld.b1);
-          ld.flags |= (t0 && t1) ? CS_OTT : t0 ? CS_OTC : CS_OCC;
-          so.bparent = dev[q].parent;
-          so.bpscaler = dev[q].pscaler;
-          so.bmat0 = dev[q].lmat;
-          so.bmat1 = dev[q].rmat;
-          so.b_bytes = clv_bytes;
-          so.bsc_bytes = so.bpscaler ? sc_bytes : 0u;
-          pl->bytes += op_traffic(c, ops[q], true, true);
-          read_sib = false;
-        }
-        else
-        {
-          bool t0;
-          ld.s0 = leaf_of(i, b, t0, ld.b0);
-          ld.flags |= t0 ? CS_T : CS_C;
-        }
-        pl->bytes += op_traffic(c, ops[i], a == 0 ? bottom : read_sib, a == 0 ? read_sib : bottom);
-        pl->loads.push_back(ld);
-        pl->sops.push_back(so);
-      }
-      {
-        // the terminal step: what the last trip "prefetches" - every size 0
-        ChainStepLoad ld;
-        ChainStepOp so;
-        memset(&ld, 0, sizeof ld);
-        memset(&so, 0, sizeof so);
-        ld.flags = CS_END;
-        pl->loads.push_back(ld);
-        pl->sops.push_back(so);
-        ++stage_steps;
-      }
-      pl->heads.push_back(hd);
-      pl->head_top_clv.push_back(ops[ch.ops[0]].parent_clv);
-      pl->head_top_scaler.push_back(ops[ch.ops[0]].parent_scaler);
-      pl->head_variant.push_back((unsigned char)variant);
+      std::vector<unsigned> ids;
+      for (unsigned k = 0; k < chains.size(); ++k)
+        if (chains[k].stage == st && variant_of[k] == variant) ids.push_back(k);
+      if (ids.empty()) continue;
+      // the longest chains first: their workgroups are dispatched first
+      std::stable_sort(ids.begin(), ids.end(), [&](unsigned x, unsigned y) { return chains[x].ops.size() > chains[y].ops.size(); });
+      ChainLaunchRec rec;
+      rec.first_head = (unsigned)pl->heads.size();
+      rec.nchains = (unsigned)ids.size();
+      rec.variant = variant;
+      // the tops of the last stage are the ends of the edge evaluated next (from registers, chain tail):
+      // nobody reads them back soon either
+      const bool stream_tops = (size_t)ids.size() * entries * 128u > c->stream_parent_bytes || (c->defer_tail && st == max_stage);
+      unsigned stage_steps = 0;
+      for (unsigned k : ids) stage_steps += add_chain(c, b, chains[k], variant, stream_tops, pl);
+      if (st == max_stage && pl->held_from == (size_t)-1) pl->held_from = pl->stages.size();
+      if (rec.nchains > (unsigned)kChainPackHeads || stage_steps + 1 > (unsigned)kChainPackSteps) pl->in_kernarg = false; // + 1: a chain of no steps in the tail
+      pl->stages.push_back(rec);
     }
-    if (st == max_stage && pl->held_from == (size_t)-1) pl->held_from = pl->stages.size();
-    if (rec.nchains > (unsigned)kChainPackHeads || stage_steps + 1 > (unsigned)kChainPackSteps) pl->in_kernarg = false; // + 1: a chain of no steps in the tail
-    pl->stages.push_back(rec);
-  }
-  {
-    // the last stage may wait for the edge evaluation if it is at most the two ends of an edge and the
-    // tail kernel can reproduce k_edge_dna's summation order (one tile per wave there: <= 4096 tiles)
-    if (pl->held_from == (size_t)-1) pl->held_from = pl->stages.size();
-    unsigned held_chains = 0;
-    for (size_t i = pl->held_from; i < pl->stages.size(); ++i) held_chains += pl->stages[i].nchains;
-    if (held_chains > 2 || (c->geo.sites + 63) / 64 > 4096u) pl->held_from = pl->stages.size();
-    // the tail kernel takes BOTH ends in one descriptor pack (an end that is not held counts one
-    // terminal step); every stage record was sized against the pack on its own, two records of the last
-    // stage (different fetch variants) together may not fit: such a plan keeps its descriptors in memory
-    unsigned tail_steps = 0, tail_heads = 0;
-    for (size_t i = pl->held_from; i < pl->stages.size(); ++i)
-      for (unsigned h = pl->stages[i].first_head; h < pl->stages[i].first_head + pl->stages[i].nchains; ++h, ++tail_heads)
-        tail_steps += pl->heads[h].nsteps + 1;
-    if (tail_heads && tail_steps + (2u - std::min(tail_heads, 2u)) > (unsigned)kChainPackSteps) pl->in_kernarg = false;
-  }
+  choose_held_stage(c, pl);
   pl->bytes += c->last_bytes; // the cherry-cherry groups (build_cc_launches counted them)
   pl->launches = (unsigned)(pl->cc.size() + pl->cc16.size() + pl->stages.size());
-  if (!pl->in_kernarg)
+  return 0;
+}
+
+// a plan beyond the kernarg packs: heads, loads and step ops to the context's device block
+static int upload_chain_plan(pllgpu_ctx *c, const ChainPlan &pl)
+{
+  const size_t hb = pl.heads.size() * sizeof(ChainHead), lb = pl.loads.size() * sizeof(ChainStepLoad), ob = pl.sops.size() * sizeof(ChainStepOp);
+  if (int rc = c->chain_dev.ensure(hb + lb + ob)) return rc;
+  // pageable sources are staged before hipMemcpyAsync returns; the stream orders the copies behind the
+  // kernels of the previous plan that still read the old descriptors
+  // (through the context's pinned block: a tree search plans a new list after every move)
+  hipError_t e = copy_up(c, c->chain_dev.p, pl.heads.data(), hb);
+  if (e == hipSuccess) e = copy_up(c, c->chain_dev.p + hb, pl.loads.data(), lb);
+  if (e == hipSuccess) e = copy_up(c, c->chain_dev.p + hb + lb, pl.sops.data(), ob);
+  if (e != hipSuccess) return fail(PLLGPU_ERUNTIME, "descriptor upload failed: %s", hipGetErrorString(e));
+  return 0;
+}
+
+// returns 0 and sets used = true when the list was planned and launched as chains
+static int try_chain_plan(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count, bool &used)
+{
+  used = false;
+  if (!c->chains || !c->fuse || count < 4 || c->any_aos) return 0; // up to three ops the level scheduler + tail kernel is as fast (tools/path_latency.py)
+  if (c->plan && c->plan->epoch == c->alloc_epoch && c->plan->key.size() == count &&
+      memcmp(c->plan->key.data(), ops, count * sizeof(pllgpu_op_t)) == 0)
   {
-    const size_t hb = pl->heads.size() * sizeof(ChainHead), lb = pl->loads.size() * sizeof(ChainStepLoad),
-                 ob = pl->sops.size() * sizeof(ChainStepOp);
-    if (int rc = c->chain_dev.ensure(hb + lb + ob))
-    {
-      delete pl;
-      return rc;
-    }
-    // pageable sources are staged before hipMemcpyAsync returns; the stream orders the copies behind the
-    // kernels of the previous plan that still read the old descriptors
-    // (through the context's pinned block: a tree search plans a new list after every move)
-    hipError_t e = copy_up(c, c->chain_dev.p, pl->heads.data(), hb);
-    if (e == hipSuccess) e = copy_up(c, c->chain_dev.p + hb, pl->loads.data(), lb);
-    if (e == hipSuccess) e = copy_up(c, c->chain_dev.p + hb + lb, pl->sops.data(), ob);
-    if (e != hipSuccess)
-    {
-      delete pl;
-      return fail(PLLGPU_ERUNTIME, "descriptor upload failed: %s", hipGetErrorString(e));
-    }
+    used = true;
+    ++c->plan_replays;
+    return launch_chain_plan(c, *c->plan, c->defer_tail);
+  }
+  const unsigned entries = ops[0].parent_entries;
+  if (entries == 0 || aos_entries(c, entries) || (size_t)entries * 128u >= ((size_t)1 << 31)) return 0; // 32-bit buffer offsets
+  ChainPartition part;
+  if (!partition_chains(ops, count, c->geo.nodes, c->geo.scale_buffers, entries, c->fuse_cc, use_cc16(c, entries, count), part)) return 0;
+  ChainPlan *pl = new ChainPlan();
+  int rc = build_chain_plan(c, ops, count, entries, part, pl);
+  if (!rc && !pl->in_kernarg) rc = upload_chain_plan(c, *pl);
+  if (rc)
+  {
+    delete pl;
+    return rc;
   }
   pl->key.assign(ops, ops + count);
   pl->epoch = c->alloc_epoch;
@@ -569,4 +547,3 @@ static int try_chain_plan(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count,
   used = true;
   return launch_chain_plan(c, *pl, c->defer_tail);
 }
-

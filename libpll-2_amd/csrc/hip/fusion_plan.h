@@ -2,6 +2,16 @@
 // launch helpers): which ops of a level-scheduled list are evaluated together (three-op groups,
 // seven-op cherry-cherry groups; kernels_dna.h), and the launches of those groups.
 #pragma once
+// what the planners make of each op of a list
+enum class Role
+{
+  Plain,         // launched at its level by itself
+  GroupParent,   // parent of a fused group: evaluated with its producers, at their level
+  GroupProducer, // fused into a group as a child
+  HeldTail,      // a plain op of the last level, held back for the edge evaluation (tail fusion)
+  SubtreeMember  // site repeats: part of an all-tip subtree, evaluated before the levels (subtree_plan.h)
+};
+
 // ---- producer/consumer fusion (DNA) ---------------------------------------------------------------
 // A group = an op P plus the ops that produce its children in the SAME call, evaluated by one
 // kernel at the producers' level (kernels_dna.h: k_partials_dna_fused). P may move one level up
@@ -46,11 +56,10 @@ static int child_kind(const pllgpu_op_t &prod)
   return (lt && rt) ? CK_FTT : lt ? CK_FTI : CK_FII;
 }
 
-static void plan_fusion(bool fuse, bool fuse_cc, unsigned nodes, const pllgpu_op_t *ops, unsigned count, std::vector<int> &role,
+static void plan_fusion(bool fuse, bool fuse_cc, unsigned nodes, const pllgpu_op_t *ops, unsigned count, std::vector<Role> &role,
                         std::vector<FusedGroup> &groups, bool cc_only = false, bool cc16 = false)
 {
-  // role: 0 plain, 1 parent of a group, 2 fused into a group as a child
-  role.assign(count, 0);
+  role.assign(count, Role::Plain);
   groups.clear();
   if (!fuse) return;
   std::vector<int> producer(nodes, -1), prod_l(count, -1), prod_r(count, -1);
@@ -71,16 +80,16 @@ static void plan_fusion(bool fuse, bool fuse_cc, unsigned nodes, const pllgpu_op
     for (unsigned i = 0; i < count; ++i)
     {
       const pllgpu_op_t &P = ops[i];
-      if (role[i] || (P.flags & PLLGPU_OP_GATHER) || P.level < 2) continue;
+      if (role[i] != Role::Plain || (P.flags & PLLGPU_OP_GATHER) || P.level < 2) continue;
       const unsigned L = P.level - 2;
       if (P.war_level >= (int)L) continue;
       auto cherry = [&](int pr, int pscal, unsigned entries) {
-        return pr >= 0 && role[pr] == 0 && ops[pr].level == L && !(ops[pr].flags & PLLGPU_OP_GATHER) &&
+        return pr >= 0 && role[pr] == Role::Plain && ops[pr].level == L && !(ops[pr].flags & PLLGPU_OP_GATHER) &&
                (ops[pr].flags & PLLGPU_OP_LEFT_TIP) && (ops[pr].flags & PLLGPU_OP_RIGHT_TIP) && ops[pr].parent_scaler == pscal &&
                ops[pr].parent_entries == entries;
       };
       auto cc = [&](int pr, int pscal) {
-        if (pr < 0 || role[pr] != 0 || ops[pr].level != L + 1 || (ops[pr].flags & (PLLGPU_OP_GATHER | PLLGPU_OP_LEFT_TIP | PLLGPU_OP_RIGHT_TIP)))
+        if (pr < 0 || role[pr] != Role::Plain || ops[pr].level != L + 1 || (ops[pr].flags & (PLLGPU_OP_GATHER | PLLGPU_OP_LEFT_TIP | PLLGPU_OP_RIGHT_TIP)))
           return false;
         const pllgpu_op_t &A = ops[pr];
         return A.parent_scaler == pscal && A.parent_entries == P.parent_entries && A.war_level < (int)L &&
@@ -98,19 +107,19 @@ static void plan_fusion(bool fuse, bool fuse_cc, unsigned nodes, const pllgpu_op
       g.lk = cl ? CK_FCC : ltip ? CK_TIP : CK_INNER;
       g.rk = cr ? CK_FCC : rtip ? CK_TIP : CK_INNER;
       g.level = L;
-      role[i] = 1;
+      role[i] = Role::GroupParent;
       eff[i] = L;
       if (cl)
       {
         g.aa = prod_l[g.a];
         g.ab = prod_r[g.a];
-        role[g.a] = role[g.aa] = role[g.ab] = 2;
+        role[g.a] = role[g.aa] = role[g.ab] = Role::GroupProducer;
       }
       if (cr)
       {
         g.ba = prod_l[g.b];
         g.bb = prod_r[g.b];
-        role[g.b] = role[g.ba] = role[g.bb] = 2;
+        role[g.b] = role[g.ba] = role[g.bb] = Role::GroupProducer;
       }
       groups.push_back(g);
     }
@@ -125,7 +134,7 @@ static void plan_fusion(bool fuse, bool fuse_cc, unsigned nodes, const pllgpu_op
     for (unsigned i = 0; i < count; ++i)
     {
       const pllgpu_op_t &P = ops[i];
-      if (role[i] || (P.flags & (PLLGPU_OP_GATHER | PLLGPU_OP_LEFT_TIP | PLLGPU_OP_RIGHT_TIP)) || P.level < 3) continue;
+      if (role[i] != Role::Plain || (P.flags & (PLLGPU_OP_GATHER | PLLGPU_OP_LEFT_TIP | PLLGPU_OP_RIGHT_TIP)) || P.level < 3) continue;
       const unsigned L = P.level - 3;
       if (P.war_level >= (int)L) continue;
       const int pa = prod_l[i], pb = prod_r[i];
@@ -145,8 +154,8 @@ static void plan_fusion(bool fuse, bool fuse_cc, unsigned nodes, const pllgpu_op
       g.ga = ga;
       g.gb = gb;
       groups[ga].absorbed = groups[gb].absorbed = true;
-      role[i] = 1;
-      role[pa] = role[pb] = 2;
+      role[i] = Role::GroupParent;
+      role[pa] = role[pb] = Role::GroupProducer;
       eff[i] = L;
       groups.push_back(g);
     }
@@ -155,11 +164,11 @@ static void plan_fusion(bool fuse, bool fuse_cc, unsigned nodes, const pllgpu_op
   for (unsigned i = 0; i < count; ++i)
   {
     const pllgpu_op_t &P = ops[i];
-    if (role[i] || (P.flags & PLLGPU_OP_GATHER) || P.level == 0) continue;
+    if (role[i] != Role::Plain || (P.flags & PLLGPU_OP_GATHER) || P.level == 0) continue;
     const unsigned L = P.level - 1;
     if (P.war_level >= (int)L) continue;
     auto fusable = [&](int pr, int pscal) {
-      return pr >= 0 && role[pr] == 0 && eff[pr] == L && ops[pr].level == L && !(ops[pr].flags & PLLGPU_OP_GATHER) &&
+      return pr >= 0 && role[pr] == Role::Plain && eff[pr] == L && ops[pr].level == L && !(ops[pr].flags & PLLGPU_OP_GATHER) &&
              ops[pr].parent_scaler == pscal && ops[pr].parent_entries == P.parent_entries;
     };
     auto older = [&](int pr) { return pr < 0 || eff[pr] < L; };
@@ -173,10 +182,10 @@ static void plan_fusion(bool fuse, bool fuse_cc, unsigned nodes, const pllgpu_op
     g.lk = fl ? child_kind(ops[g.a]) : (P.flags & PLLGPU_OP_LEFT_TIP) ? CK_TIP : CK_INNER;
     g.rk = fr ? child_kind(ops[g.b]) : (P.flags & PLLGPU_OP_RIGHT_TIP) ? CK_TIP : CK_INNER;
     g.level = L;
-    role[i] = 1;
+    role[i] = Role::GroupParent;
     eff[i] = L;
-    if (fl) role[g.a] = 2;
-    if (fr) role[g.b] = 2;
+    if (fl) role[g.a] = Role::GroupProducer;
+    if (fr) role[g.b] = Role::GroupProducer;
     groups.push_back(g);
   }
 }
@@ -243,27 +252,23 @@ static int launch_cc16(pllgpu_ctx *c, const CC16Pack &pack, unsigned ngroups, un
 
 static int launch_cc(pllgpu_ctx *c, const CCPack &pack, unsigned ngroups, unsigned entries, int lk, int rk)
 {
-  if (lk == CK_INNER && rk == CK_FCC) launch_cc_t<CK_INNER, CK_FCC>(c, pack, ngroups, entries);
-  else if (lk == CK_TIP && rk == CK_FCC) launch_cc_t<CK_TIP, CK_FCC>(c, pack, ngroups, entries);
-  else if (lk == CK_FCC && rk == CK_FCC) launch_cc_t<CK_FCC, CK_FCC>(c, pack, ngroups, entries);
-  else return fail(PLLGPU_EINVAL, "no cherry-cherry kernel for child kinds (%d, %d)", lk, rk);
+  const bool known = with_kind_pair(
+      lk, rk, [&](auto LK, auto RK) { launch_cc_t<LK(), RK()>(c, pack, ngroups, entries); },
+      KindPair<CK_INNER, CK_FCC>(), KindPair<CK_TIP, CK_FCC>(), KindPair<CK_FCC, CK_FCC>());
+  if (!known) return fail(PLLGPU_EINVAL, "no cherry-cherry kernel for child kinds (%d, %d)", lk, rk);
   return 0;
 }
 
 static int launch_fused(pllgpu_ctx *c, const FusePack &pack, unsigned ngroups, unsigned entries, int lk, int rk)
 {
-#define FZ(A, B)                                          \
-  if (lk == A && rk == B)                                 \
-  {                                                       \
-    launch_fused_t<A, B>(c, pack, ngroups, entries);      \
-    return 0;                                             \
-  }
-  FZ(CK_INNER, CK_FTT) FZ(CK_INNER, CK_FTI) FZ(CK_INNER, CK_FII)
-  FZ(CK_TIP, CK_FTT) FZ(CK_TIP, CK_FTI) FZ(CK_TIP, CK_FII)
-  FZ(CK_FTT, CK_FTT) FZ(CK_FTT, CK_FTI) FZ(CK_FTT, CK_FII)
-  FZ(CK_FTI, CK_FTI) FZ(CK_FTI, CK_FII) FZ(CK_FII, CK_FII)
-#undef FZ
-  return fail(PLLGPU_EINVAL, "no fused kernel for child kinds (%d, %d)", lk, rk);
+  const bool known = with_kind_pair(
+      lk, rk, [&](auto LK, auto RK) { launch_fused_t<LK(), RK()>(c, pack, ngroups, entries); },
+      KindPair<CK_INNER, CK_FTT>(), KindPair<CK_INNER, CK_FTI>(), KindPair<CK_INNER, CK_FII>(),
+      KindPair<CK_TIP, CK_FTT>(), KindPair<CK_TIP, CK_FTI>(), KindPair<CK_TIP, CK_FII>(),
+      KindPair<CK_FTT, CK_FTT>(), KindPair<CK_FTT, CK_FTI>(), KindPair<CK_FTT, CK_FII>(),
+      KindPair<CK_FTI, CK_FTI>(), KindPair<CK_FTI, CK_FII>(), KindPair<CK_FII, CK_FII>());
+  if (!known) return fail(PLLGPU_EINVAL, "no fused kernel for child kinds (%d, %d)", lk, rk);
+  return 0;
 }
 
 // bytes one CLV update has to move: inner children, tip codes, the parent, the scaler vectors

@@ -15,6 +15,8 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "kernels_common.h"
@@ -272,7 +274,7 @@ struct pllgpu_ctx
   std::vector<unsigned char> map_widened; // per node: a launch reads the 32-bit form although the class kernels write bytes (wide_map)
   std::vector<struct LevelPlan *> level_plans;
   struct LevelPlan *recording = nullptr;
-  int launch_rc = 0;                // a launch helper that failed inside emit()
+  int launch_rc = 0;                // a launch helper that failed inside emit_launch()
   int fenced = 0;                   // PLL_AMD_FENCED_HANDOFF=1 (kernels_common.h: handoff_*)
   unsigned long long plan_stamp = 0;
   unsigned long long plan_replays = 0; // op lists that were launched from a kept plan (chain or level), ever
@@ -327,7 +329,7 @@ struct LevelPlan
 {
   std::vector<pllgpu_op_t> key;
   unsigned long long alloc_epoch = 0, maps_epoch = 0;
-  std::vector<std::function<void()>> launches;
+  std::vector<std::function<int()>> launches; // each returns 0 or the error of its launcher
   std::vector<pllgpu_op_t> deferred;
   std::vector<std::pair<unsigned, unsigned char>> aos; // (node, entry-contiguous?) as the list leaves them
   unsigned nlaunches = 0;
@@ -337,12 +339,16 @@ struct LevelPlan
 };
 constexpr size_t kLevelPlans = 4;
 
-// run a launch now and, while a plan is being recorded, keep it
+// the one way the level scheduler launches: run `launch` now and, while a plan is being recorded, keep it for the
+// replays. Its error, if any, stays in launch_rc (a replay leaves it there as well); `count` = the launches it stands
+// for in pllgpu_last_launch_count. Returns launch_rc.
 template <class F>
-static inline void emit(pllgpu_ctx *c, F &&fn)
+static inline int emit_launch(pllgpu_ctx *c, F &&launch, unsigned count = 1)
 {
-  fn();
-  if (c->recording) c->recording->launches.emplace_back(std::forward<F>(fn));
+  if (int rc = launch()) c->launch_rc = rc;
+  if (c->recording) c->recording->launches.emplace_back(std::forward<F>(launch));
+  c->last_launches += count;
+  return c->launch_rc;
 }
 
 static inline int use(pllgpu_ctx *c)
@@ -375,8 +381,6 @@ struct DeviceScope
 };
 
 // hipFuncSetAttribute applies to the CURRENT device: once per (kernel, device), not once per process
-#include <mutex>
-#include <map>
 static void raise_lds_limit(const void *fn, int device, size_t dynamic_bytes)
 {
   // dynamic LDS beyond the default limit has to be announced per kernel; the kernel's static LDS counts
@@ -1072,6 +1076,91 @@ static int narrow_map(pllgpu_ctx *c, unsigned node)
 }
 
 // ---- launches --------------------------------------------------------------------------------
+// Run-time values that select a template instantiation: each helper hands its generic lambda the values as
+// std::integral_constant arguments (LT() etc. are constant expressions there) - for exactly the combinations
+// that have a kernel, no others are instantiated.
+template <bool B>
+using Bool = std::integral_constant<bool, B>;
+template <int I>
+using Int = std::integral_constant<int, I>;
+
+// two flags, e.g. (the child end of an edge is a tip, gather) -> fn(CT, GA)
+template <class F>
+static void with_bools(bool a, bool b, F &&fn)
+{
+  if (a)
+  {
+    if (b) fn(Bool<true>(), Bool<true>()); else fn(Bool<true>(), Bool<false>());
+  }
+  else
+  {
+    if (b) fn(Bool<false>(), Bool<true>()); else fn(Bool<false>(), Bool<false>());
+  }
+}
+
+// the children of a level launch, kind = number of tip children (a tip-inner op carries its tip on the left) -> fn(LT, RT)
+template <class F>
+static void with_child_tips(unsigned kind, F &&fn)
+{
+  if (kind == 0) fn(Bool<false>(), Bool<false>());
+  else if (kind == 1) fn(Bool<true>(), Bool<false>());
+  else fn(Bool<true>(), Bool<true>());
+}
+
+// ... and whether the launch gathers -> fn(LT, RT, GA)
+template <class F>
+static void with_children(unsigned kind, bool gather, F &&fn)
+{
+  with_child_tips(kind, [&](auto LT, auto RT) {
+    if (gather) fn(LT, RT, Bool<true>()); else fn(LT, RT, Bool<false>());
+  });
+}
+
+// an index below N -> fn(Int<i>)
+template <class F, int... I>
+static void with_index(unsigned i, F &&fn, std::integer_sequence<int, I...>)
+{
+  ((i == (unsigned)I ? (void)fn(Int<I>()) : (void)0), ...);
+}
+
+// the chain kernels (kernels_dna.h): the scaling mode and which fetch groups a chain's steps issue (ChainLaunchRec::variant)
+// -> fn(SMV, C0, S1, C1). One table for the chain launches and for the edge kernels that take held chains over: they
+// must agree on it.
+template <class F>
+static void with_chain_variant(int scale_mode, unsigned variant, F &&fn)
+{
+  auto fetches = [&](auto SMV) {
+    switch (variant)
+    {
+      case 0: fn(SMV, Bool<false>(), Bool<false>(), Bool<false>()); break;
+      case 1: fn(SMV, Bool<false>(), Bool<true>(), Bool<false>()); break;
+      case 2: fn(SMV, Bool<true>(), Bool<false>(), Bool<false>()); break;
+      default: fn(SMV, Bool<true>(), Bool<true>(), Bool<true>()); break;
+    }
+  };
+  if (scale_mode == 2) fetches(Int<2>()); else fetches(Int<1>());
+}
+
+// a pair of DnaChildKind out of the listed ones -> fn(A, B) and true; false for a pair that is not listed (no kernel)
+template <int A, int B>
+struct KindPair
+{
+};
+template <class F, int... A, int... B>
+static bool with_kind_pair(int a, int b, F &&fn, KindPair<A, B>...)
+{
+  return ((a == A && b == B ? (fn(Int<A>(), Int<B>()), true) : false) || ...);
+}
+
+// what the launches issued so far have left behind
+static int launch_status()
+{
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(PLLGPU_ERUNTIME, "kernel launch failed: %s", hipGetErrorString(e));
+  return 0;
+}
+
+static const unsigned long long *tipmap_ptr(const pllgpu_ctx *c) { return c->tipmap_set ? c->tipmap.p : nullptr; }
 static int resolve_op(pllgpu_ctx *c, const pllgpu_op_t &o, DevOp &d)
 {
   const pllgpu_geometry_t &g = c->geo;
@@ -1165,7 +1254,7 @@ static void launch_generic(pllgpu_ctx *c, const OpPack &pack, unsigned nops, uns
 {
   // one workgroup per 64-entry tile; min(R,4) waves share the tile's rate categories
   const unsigned tiles = (maxent + 63) / 64;
-  const unsigned long long *tm = c->tipmap_set ? c->tipmap.p : nullptr;
+  const unsigned long long *tm = tipmap_ptr(c);
   // tip children: room in LDS for the staged matrices of every wave (kernels_generic.h: tip_stage)
   const unsigned nw = std::min(c->gg.R, 4u);
   const bool stage = kind != 0 && c->gg.S * c->gg.SPT <= 1024u && !c->no_tip_columns;
@@ -1185,46 +1274,29 @@ static void launch_generic(pllgpu_ctx *c, const OpPack &pack, unsigned nops, uns
   // tiles per workgroup and >= 4096 workgroups, 247 us with up to 16 and >= 2048, 268 us with 32 / 1024)
   if (stage) tpb = std::max(1u, std::min(16u, (unsigned)(((size_t)tiles * nops) / 2048u)));
   dim3 grid((tiles + tpb - 1) / tpb, nops), block(64u * nw);
-  if (gather && ICH == 20)
-  {
-    // the protein shape: when every op of the launch has the same CLV layouts (the rule: a level of a tree), the
-    // instantiation that knows them at compile time
-    const unsigned lay = pack.ops[0].layout & 7u;
-    bool same = true;
-    for (unsigned i = 1; i < nops; ++i) same = same && (pack.ops[i].layout & 7u) == lay;
-    if (same)
+  // the kernel and, for the same instantiation, its LDS limit
+  auto launch = [&](auto LT, auto RT, auto GA, auto LAY) {
+    const auto kernel = k_partials_tiled<ICH, LT(), RT(), GA(), LAY()>;
+    if (par_lds) raise_lds_limit((const void *)kernel, c->device, lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, pack, c->gg, tm, tip_lds, tpb, par_lds);
+  };
+  if constexpr (ICH == 20)
+    if (gather)
     {
-#define GEN_LAY(LT, RT, L) \
-  case L: if (par_lds) raise_lds_limit((const void *)k_partials_tiled<ICH == 20 ? 20 : ICH, LT, RT, true, ICH == 20 ? L : -1>, c->device, lds); \
-    hipLaunchKernelGGL((k_partials_tiled<ICH == 20 ? 20 : ICH, LT, RT, true, ICH == 20 ? L : -1>), grid, block, lds, c->stream, pack, c->gg, tm, tip_lds, tpb, par_lds); return;
-#define GEN_LAYS(LT, RT) \
-  switch (lay)             \
-  {                        \
-    GEN_LAY(LT, RT, 0) GEN_LAY(LT, RT, 1) GEN_LAY(LT, RT, 2) GEN_LAY(LT, RT, 3) GEN_LAY(LT, RT, 4) GEN_LAY(LT, RT, 5) GEN_LAY(LT, RT, 6) GEN_LAY(LT, RT, 7) \
-  }
-      if (kind == 0) { GEN_LAYS(false, false) }
-      else if (kind == 1) { GEN_LAYS(true, false) }
-      else { GEN_LAYS(true, true) }
-#undef GEN_LAYS
-#undef GEN_LAY
+      // the protein shape: when every op of the launch has the same CLV layouts (the rule: a level of a tree), the
+      // instantiation that knows them at compile time
+      const unsigned lay = pack.ops[0].layout & 7u;
+      bool same = true;
+      for (unsigned i = 1; i < nops; ++i) same = same && (pack.ops[i].layout & 7u) == lay;
+      if (same)
+      {
+        with_child_tips(kind, [&](auto LT, auto RT) {
+          with_index(lay, [&](auto LAY) { launch(LT, RT, Bool<true>(), LAY); }, std::make_integer_sequence<int, 8>());
+        });
+        return;
+      }
     }
-  }
-#define GEN_LAUNCH(LT, RT, GA) \
-  do { if (par_lds) raise_lds_limit((const void *)k_partials_tiled<ICH, LT, RT, GA>, c->device, lds); \
-  hipLaunchKernelGGL((k_partials_tiled<ICH, LT, RT, GA>), grid, block, lds, c->stream, pack, c->gg, tm, tip_lds, tpb, par_lds); } while (0)
-  if (kind == 0)
-  {
-    if (gather) GEN_LAUNCH(false, false, true); else GEN_LAUNCH(false, false, false);
-  }
-  else if (kind == 1)
-  {
-    if (gather) GEN_LAUNCH(true, false, true); else GEN_LAUNCH(true, false, false);
-  }
-  else
-  {
-    if (gather) GEN_LAUNCH(true, true, true); else GEN_LAUNCH(true, true, false);
-  }
-#undef GEN_LAUNCH
+  with_children(kind, gather, [&](auto LT, auto RT, auto GA) { launch(LT, RT, GA, Int<-1>()); });
 }
 
 static void launch_dna(pllgpu_ctx *c, const OpPack &pack, unsigned nops, unsigned maxent, unsigned kind, bool gather)
@@ -1238,20 +1310,9 @@ static void launch_dna(pllgpu_ctx *c, const OpPack &pack, unsigned nops, unsigne
   // gathering launches: a pattern-sorted alignment's neighbouring sites gather neighbouring entries, and with the XCD-aware
   // order (kernels_common.h) an XCD's L2 holds the entries of ITS run of sites, not a copy of everybody's
   const unsigned xcd = (c->xcd_order && gather) ? 1u : 0u;
-#define DNA_LAUNCH(LT, RT, GA) hipLaunchKernelGGL((k_partials_dna<LT, RT, GA>), grid, block, 0, c->stream, pack, mode, tpw, nx, nops, xcd)
-  if (kind == 0)
-  {
-    if (gather) DNA_LAUNCH(false, false, true); else DNA_LAUNCH(false, false, false);
-  }
-  else if (kind == 1)
-  {
-    if (gather) DNA_LAUNCH(true, false, true); else DNA_LAUNCH(true, false, false);
-  }
-  else
-  {
-    if (gather) DNA_LAUNCH(true, true, true); else DNA_LAUNCH(true, true, false);
-  }
-#undef DNA_LAUNCH
+  with_children(kind, gather, [&](auto LT, auto RT, auto GA) {
+    hipLaunchKernelGGL((k_partials_dna<LT(), RT(), GA()>), grid, block, 0, c->stream, pack, mode, tpw, nx, nops, xcd);
+  });
 }
 
 // site repeats: (gathering, gathering -> inner x inner) groups (kernels_dna.h: k_partials_dna_gg)
@@ -1304,35 +1365,66 @@ static bool launch_wide(pllgpu_ctx *c, const OpPack &pack, unsigned nops, unsign
 
 static inline unsigned tt_stream_ld_host(unsigned S) { return (S + 1u) | 1u; } // (kernels_mfma.h: tt_stream_ld)
 
+// Does a matrix-pipe launch rescale, and where do its kernels leave the flag bytes that k_mfma_scale_epilogue reads.
+// min_bytes: k_partials_mfma_wide forms a buffer descriptor over the block even when nothing is rescaled (size 0, every
+// lane dropped: kernels_mfma_wide.h), so its launch is given 64 real bytes to point at; the other kernels do not look at
+// the pointer then and reserve nothing.
+struct MfmaScaling
+{
+  bool scaling = false;
+  unsigned fstride = 0;
+  unsigned char *flags = nullptr;
+};
+
+static int mfma_scaling(pllgpu_ctx *c, bool any_parent_scaler, unsigned entries, size_t min_bytes, MfmaScaling &s)
+{
+  s.scaling = any_parent_scaler && c->gg.scale_mode != 0;
+  s.fstride = (entries + 63u) & ~63u;
+  if (c->mfma_flags.ensure(std::max(min_bytes, s.scaling ? (size_t)kMaxOpsPerLaunch * c->gg.R * s.fstride : (size_t)0))) return PLLGPU_ENOMEM;
+  s.flags = c->mfma_flags.p;
+  return 0;
+}
+
+static int mfma_scaling(pllgpu_ctx *c, const OpPack &pack, unsigned nops, unsigned entries, size_t min_bytes, MfmaScaling &s)
+{
+  bool any = false;
+  for (unsigned i = 0; i < nops; ++i) any = any || pack.ops[i].pscaler != nullptr;
+  return mfma_scaling(c, any, entries, min_bytes, s);
+}
+
+// the parents' scalers from the flag bytes; gather: the parents' entries are found through their class maps
+static void launch_scale_epilogue(pllgpu_ctx *c, const OpPack &pack, unsigned nops, unsigned entries, const MfmaScaling &s, bool gather)
+{
+  if (!s.scaling) return;
+  dim3 eg((entries + 255) / 256, nops);
+  if (gather)
+    hipLaunchKernelGGL((k_mfma_scale_epilogue<true>), eg, dim3(256), 0, c->stream, pack, c->gg, s.flags, s.fstride);
+  else
+    hipLaunchKernelGGL((k_mfma_scale_epilogue<false>), eg, dim3(256), 0, c->stream, pack, c->gg, s.flags, s.fstride);
+}
+
 template <int NG>
 static int launch_mfma_t(pllgpu_ctx *c, const OpPack &pack, unsigned nops, unsigned maxent, unsigned kind, bool gather)
 {
   const unsigned R = c->gg.R;
   const unsigned items = (maxent + 31) / 32; // 32 sites per item
+  MfmaScaling s;
   if (NG == 16 && kind == 0 && !gather && c->mfma_wide)
   {
     // 33..64 states, inner x inner, tiled CLVs: the second-generation kernel (kernels_mfma_wide.h). Work is dealt in
     // half tiles: every SIMD gets two waves and the pair the same number of half tiles, give or take one
-    bool scaling = false;
-    for (unsigned i = 0; i < nops; ++i) scaling = scaling || pack.ops[i].pscaler != nullptr;
-    scaling = scaling && c->gg.scale_mode != 0;
-    const unsigned fstride = (maxent + 63u) & ~63u;
-    if (c->mfma_flags.ensure(std::max<size_t>(64, scaling ? (size_t)kMaxOpsPerLaunch * R * fstride : 0))) return PLLGPU_ENOMEM;
-    unsigned char *fb = c->mfma_flags.p;
+    if (int rc = mfma_scaling(c, pack, nops, maxent, 64, s)) return rc;
     const bool exact61 = c->gg.S == 61 && !c->mfma_pad;
     // (8-wave workgroups, one per CU: against two of 4 waves the matrices are staged once per CU and a SIMD's two waves
     // split an odd share - C5's 2-op launch 66 -> 58 us, the step 0.549 -> 0.537 ms, profiles/README.md round 3)
-    const bool done = exact61 ? launch_wide<15, 1, 8>(c, pack, nops, items, fb, fstride) : launch_wide<16, 0, 8>(c, pack, nops, items, fb, fstride);
+    const bool done = exact61 ? launch_wide<15, 1, 8>(c, pack, nops, items, s.flags, s.fstride) : launch_wide<16, 0, 8>(c, pack, nops, items, s.flags, s.fstride);
     if (done)
     {
-      if (scaling)
-      {
-        dim3 eg((maxent + 255) / 256, nops);
-        hipLaunchKernelGGL((k_mfma_scale_epilogue<false>), eg, dim3(256), 0, c->stream, pack, c->gg, fb, fstride);
-      }
+      launch_scale_epilogue(c, pack, nops, maxent, s, false);
       return 0;
     }
   }
+  if (int rc = mfma_scaling(c, pack, nops, maxent, 0, s)) return rc;
   if (kind == 2 && !gather && NG > 8 && c->tt_stream && !c->no_tip_columns)
   {
     // plain tip x tip level of a large state space: a store stream, lane = site (kernels_mfma.h: k_partials_tt_stream)
@@ -1346,19 +1438,9 @@ static int launch_mfma_t(pllgpu_ctx *c, const OpPack &pack, unsigned nops, unsig
     const unsigned nx = (tiles + nw * tpw - 1u) / (nw * tpw);
     const unsigned S = c->gg.S;
     const size_t lds = 2u * (size_t)(S + 1u) * tt_stream_ld_host(S) * sizeof(double);
-    const unsigned long long *tm = c->tipmap_set ? c->tipmap.p : nullptr;
-    bool scaling = false;
-    for (unsigned i = 0; i < nops; ++i) scaling = scaling || pack.ops[i].pscaler != nullptr;
-    scaling = scaling && c->gg.scale_mode != 0;
-    const unsigned fstride = (maxent + 63u) & ~63u;
-    if (scaling && c->mfma_flags.ensure((size_t)kMaxOpsPerLaunch * R * fstride)) return PLLGPU_ENOMEM;
     raise_lds_limit((const void *)k_partials_tt_stream, c->device, lds);
-    hipLaunchKernelGGL(k_partials_tt_stream, xcd_grid(nx, nops, R), dim3(kTtStreamThreads), lds, c->stream, pack, c->gg, tm, tpw, c->mfma_flags.p, fstride, nx, nops, c->xcd_order);
-    if (scaling)
-    {
-      dim3 eg((maxent + 255) / 256, nops);
-      hipLaunchKernelGGL((k_mfma_scale_epilogue<false>), eg, dim3(256), 0, c->stream, pack, c->gg, c->mfma_flags.p, fstride);
-    }
+    hipLaunchKernelGGL(k_partials_tt_stream, xcd_grid(nx, nops, R), dim3(kTtStreamThreads), lds, c->stream, pack, c->gg, tipmap_ptr(c), tpw, s.flags, s.fstride, nx, nops, c->xcd_order);
+    launch_scale_epilogue(c, pack, nops, maxent, s, false);
     return 0;
   }
   // aim at two workgroups of four waves on every CU (2048 waves) - four where the small shapes leave room;
@@ -1372,40 +1454,13 @@ static int launch_mfma_t(pllgpu_ctx *c, const OpPack &pack, unsigned nops, unsig
   // (round 5 ran the plain tip x tip levels - store traffic and nothing else, C5's: 625 MB - in the XCD-aware order of the
   // other store-bound launches as well: 119.7 -> 122.7 us, profiles/README.md; the switch and its code are gone)
   const size_t lds = MfmaGeo<NG>::lds_doubles * sizeof(double);
-  const unsigned long long *tm = c->tipmap_set ? c->tipmap.p : nullptr;
-  bool scaling = false;
-  for (unsigned i = 0; i < nops; ++i) scaling = scaling || pack.ops[i].pscaler != nullptr;
-  scaling = scaling && c->gg.scale_mode != 0;
-  const unsigned fstride = (maxent + 63u) & ~63u;
-  if (scaling && c->mfma_flags.ensure((size_t)kMaxOpsPerLaunch * R * fstride)) return PLLGPU_ENOMEM;
-  unsigned char *fb = c->mfma_flags.p;
-#define MF_LAUNCH(LT, RT, GA)                                                                                   \
-  do                                                                                                            \
-  {                                                                                                             \
-    raise_lds_limit((const void *)k_partials_mfma<NG, LT, RT, GA>, c->device, lds);                             \
-    hipLaunchKernelGGL((k_partials_mfma<NG, LT, RT, GA>), grid, block, lds, c->stream, pack, c->gg, tm, ipw, fb, fstride); \
-  } while (0)
-  if (kind == 0)
-  {
-    if (gather) MF_LAUNCH(false, false, true); else MF_LAUNCH(false, false, false);
-  }
-  else if (kind == 1)
-  {
-    if (gather) MF_LAUNCH(true, false, true); else MF_LAUNCH(true, false, false);
-  }
-  else
-  {
-    if (gather) MF_LAUNCH(true, true, true); else MF_LAUNCH(true, true, false);
-  }
-#undef MF_LAUNCH
-  if (scaling)
-  {
-    dim3 eg((maxent + 255) / 256, nops);
-    if (gather)
-      hipLaunchKernelGGL((k_mfma_scale_epilogue<true>), eg, dim3(256), 0, c->stream, pack, c->gg, fb, fstride);
-    else
-      hipLaunchKernelGGL((k_mfma_scale_epilogue<false>), eg, dim3(256), 0, c->stream, pack, c->gg, fb, fstride);
-  }
+  const unsigned long long *tm = tipmap_ptr(c);
+  with_children(kind, gather, [&](auto LT, auto RT, auto GA) {
+    const auto kernel = k_partials_mfma<NG, LT(), RT(), GA()>;
+    raise_lds_limit((const void *)kernel, c->device, lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, pack, c->gg, tm, ipw, s.flags, s.fstride);
+  });
+  launch_scale_epilogue(c, pack, nops, maxent, s, gather);
   return 0;
 }
 
@@ -1424,7 +1479,7 @@ static int launch_mfma_cc_t(pllgpu_ctx *c, const FusePack &pack, unsigned ngroup
   ipw = std::max(1u, std::min(ipw, 4u));
   const unsigned nx = (items + 4 * ipw - 1) / (4 * ipw);
   dim3 grid = xcd_grid(nx, ngroups, R), block(256);
-  const unsigned long long *tm = c->tipmap_set ? c->tipmap.p : nullptr;
+  const unsigned long long *tm = tipmap_ptr(c);
   const unsigned ncodes = c->tip_ncodes;
   const size_t lds = CcGeo<NG>::lds_bytes(ncodes);
   // which cherries are rescaled: per pair of tip codes, every rate's answer (k_cherry_bits) - a table per pair of
@@ -1445,7 +1500,7 @@ static int launch_mfma_cc_t(pllgpu_ctx *c, const FusePack &pack, unsigned ngroup
   memset(&slots, 0, sizeof slots);
   OpPack parents; // the group parents as plain ops: what the scaling epilogue works on
   memset(&parents, 0, sizeof parents);
-  bool scaling = false;
+  bool any_parent_scaler = false;
   if (c->cherry_slot_of.size() + 2 * ngroups > kCherrySlots)
   {
     // full: start over (launches already in the stream read their tables before any of them is overwritten)
@@ -1485,9 +1540,8 @@ static int launch_mfma_cc_t(pllgpu_ctx *c, const FusePack &pack, unsigned ngroup
     d.lscaler = pack.g[i].a.pscaler;
     d.rscaler = pack.g[i].b.pscaler;
     d.entries = entries;
-    scaling = scaling || d.pscaler != nullptr;
+    any_parent_scaler = any_parent_scaler || d.pscaler != nullptr;
   }
-  scaling = scaling && c->gg.scale_mode != 0;
   if (nstale)
   {
     size_t bits_lds = ((size_t)2 * S * S + (size_t)2 * ncodes * S) * sizeof(double);
@@ -1497,16 +1551,14 @@ static int launch_mfma_cc_t(pllgpu_ctx *c, const FusePack &pack, unsigned ngroup
     hipLaunchKernelGGL(k_cherry_bits, dim3(nstale, R), dim3(256), bits_lds, c->stream, stale, c->gg, tm, ncodes, c->cherry_bits.p,
                        nullptr, staged);
   }
-  const unsigned fstride = (entries + 63u) & ~63u;
-  if (scaling && c->mfma_flags.ensure((size_t)kMaxOpsPerLaunch * R * fstride)) return PLLGPU_ENOMEM;
+  MfmaScaling s;
+  if (int rc = mfma_scaling(c, any_parent_scaler, entries, 0, s)) return rc;
   raise_lds_limit((const void *)k_partials_mfma_cc<NG>, c->device, lds);
   // parents beyond what the Infinity Cache keeps for the next level: streamed out like the cherries (as the 4x4 groups do)
   const unsigned stream_parent = ((size_t)ngroups * entries * S * R * 8u > c->stream_parent_bytes) ? 1u : 0u;
-  hipLaunchKernelGGL((k_partials_mfma_cc<NG>), grid, block, lds, c->stream, pack, c->gg, tm, entries, ipw, c->mfma_flags.p, fstride,
+  hipLaunchKernelGGL((k_partials_mfma_cc<NG>), grid, block, lds, c->stream, pack, c->gg, tm, entries, ipw, s.flags, s.fstride,
                      c->cherry_bits.p, slots, ncodes, stream_parent, nx, ngroups, c->xcd_order);
-  if (scaling)
-    hipLaunchKernelGGL((k_mfma_scale_epilogue<false>), dim3((entries + 255) / 256, ngroups), dim3(256), 0, c->stream, parents, c->gg,
-                       c->mfma_flags.p, fstride);
+  launch_scale_epilogue(c, parents, ngroups, entries, s, false);
   return 0;
 }
 
@@ -1540,28 +1592,13 @@ static int launch_lean(pllgpu_ctx *c, const OpPack &pack, unsigned nops, unsigne
   if (kind == 2 && !gather) ipb = std::max(2u, std::min((unsigned)(((size_t)items * nops) / 1536u), 32u));
   dim3 grid((items + ipb - 1) / ipb, nops), block(64u * R);
   const size_t lds = LeanGeo<5>::lds_bytes(R, gather);
-  if (gather)
-  {
-    raise_lds_limit((const void *)k_partials_lean<5, false, false, true>, c->device, lds);
-    raise_lds_limit((const void *)k_partials_lean<5, true, false, true>, c->device, lds);
-    raise_lds_limit((const void *)k_partials_lean<5, true, true, true>, c->device, lds);
-  }
-  const unsigned long long *tm = c->tipmap_set ? c->tipmap.p : nullptr;
+  const unsigned long long *tm = tipmap_ptr(c);
   const unsigned ncodes = std::min(c->tip_ncodes, 256u);
-#define LEAN_LAUNCH(LT, RT, GA) hipLaunchKernelGGL((k_partials_lean<5, LT, RT, GA>), grid, block, lds, c->stream, pack, c->gg, tm, ipb, ncodes)
-  if (kind == 0)
-  {
-    if (gather) LEAN_LAUNCH(false, false, true); else LEAN_LAUNCH(false, false, false);
-  }
-  else if (kind == 1)
-  {
-    if (gather) LEAN_LAUNCH(true, false, true); else LEAN_LAUNCH(true, false, false);
-  }
-  else
-  {
-    if (gather) LEAN_LAUNCH(true, true, true); else LEAN_LAUNCH(true, true, false);
-  }
-#undef LEAN_LAUNCH
+  with_children(kind, gather, [&](auto LT, auto RT, auto GA) {
+    const auto kernel = k_partials_lean<5, LT(), RT(), GA()>;
+    if (GA()) raise_lds_limit((const void *)kernel, c->device, lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, pack, c->gg, tm, ipb, ncodes);
+  });
   return 0;
 }
 
@@ -1626,286 +1663,293 @@ static int flush_deferred(pllgpu_ctx *c)
     if (int rc = launch_partials(c, pack, nops, maxent, kind, false)) return rc;
     ++c->last_launches;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PLLGPU_ERUNTIME, "kernel launch failed: %s", hipGetErrorString(e));
+  return launch_status();
+}
+
+// ---- the level scheduler: plan the list and launch it (every launch through emit_launch(), so that a plan being
+// recorded keeps it). The steps below run in this order; each resolves its ops (resolve_op creates the buffers) and
+// counts their bytes where it forms their launch.
+static void dissolve_group(std::vector<Role> &role, const FusedGroup &g)
+{
+  role[g.p] = Role::Plain;
+  if (g.a >= 0) role[g.a] = Role::Plain;
+  if (g.b >= 0) role[g.b] = Role::Plain;
+}
+
+// of the groups the 4x4 planner knows, the other shapes have one: both children cherries
+static void keep_cherry_pairs(std::vector<Role> &role, std::vector<FusedGroup> &groups)
+{
+  std::vector<FusedGroup> keep;
+  for (const FusedGroup &gq : groups)
+    if (gq.lk == CK_FTT && gq.rk == CK_FTT && gq.a >= 0 && gq.b >= 0)
+      keep.push_back(gq);
+    else
+      dissolve_group(role, gq);
+  groups.swap(keep);
+}
+
+// site repeats (4x4 kernels): an uncompressed op over two GATHERING inner x inner ops of the level below, all four
+// of their children class-compressed, is evaluated with them (kernels_dna.h: k_partials_dna_gg). Such an op may
+// have been taken as a producer by the op above it; that group gives way (its parent is usually one of the last
+// level's ops, which then wait for the edge evaluation).
+static void plan_gg_groups(const pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count, std::vector<Role> &role, std::vector<FusedGroup> &groups)
+{
+  std::vector<int> producer(c->geo.nodes, -1), pl(count, -1), pr(count, -1);
+  for (unsigned q = 0; q < count; ++q)
+  {
+    if (!(ops[q].flags & PLLGPU_OP_LEFT_TIP)) pl[q] = producer[ops[q].left_clv];
+    if (!(ops[q].flags & PLLGPU_OP_RIGHT_TIP)) pr[q] = producer[ops[q].right_clv];
+    producer[ops[q].parent_clv] = (int)q;
+  }
+  auto gathering = [&](int x, int pscal, const pllgpu_op_t &P, unsigned L) {
+    if (x < 0 || role[x] != Role::Plain) return false;
+    const pllgpu_op_t &o = ops[x];
+    return o.level == L && (o.flags & PLLGPU_OP_GATHER) && !(o.flags & (PLLGPU_OP_LEFT_TIP | PLLGPU_OP_RIGHT_TIP)) &&
+           o.parent_entries == P.parent_entries && o.parent_entries == c->geo.sites_alloc && o.parent_scaler == pscal &&
+           c->ids[o.left_clv] && c->ids[o.right_clv];
+  };
+  for (unsigned q = 0; q < count; ++q)
+  {
+    const pllgpu_op_t &P = ops[q];
+    if ((P.flags & (PLLGPU_OP_GATHER | PLLGPU_OP_LEFT_TIP | PLLGPU_OP_RIGHT_TIP)) || P.level == 0 || role[q] == Role::GroupParent) continue;
+    const unsigned L = P.level - 1;
+    if (P.war_level >= (int)L || pl[q] == pr[q]) continue;
+    if (!gathering(pl[q], P.left_scaler, P, L) || !gathering(pr[q], P.right_scaler, P, L)) continue;
+    if (role[q] == Role::GroupProducer)
+    {
+      // dissolve the group that took P as a producer
+      for (size_t gi = 0; gi < groups.size(); ++gi)
+        if ((groups[gi].a == (int)q || groups[gi].b == (int)q) && groups[gi].lk != CK_FCC && groups[gi].rk != CK_FCC)
+        {
+          dissolve_group(role, groups[gi]);
+          groups.erase(groups.begin() + gi);
+          break;
+        }
+      if (role[q] != Role::Plain) continue; // (a cherry-cherry side: leave it)
+    }
+    FusedGroup gq;
+    gq.p = q;
+    gq.a = pl[q];
+    gq.b = pr[q];
+    gq.lk = gq.rk = CK_FGG;
+    gq.level = L;
+    role[q] = Role::GroupParent;
+    role[gq.a] = role[gq.b] = Role::GroupProducer;
+    groups.push_back(gq);
+  }
+}
+
+// tail fusion: the plain ops of the last level (at most two: the ends of the edge a caller evaluates
+// next) are accepted but not launched yet - Role::HeldTail
+static void hold_tail(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count, std::vector<Role> &role)
+{
+  const unsigned top = ops[count - 1].level;
+  unsigned n = 0;
+  bool ok = true;
+  for (unsigned o = 0; o < count && ok; ++o)
+    if (ops[o].level == top)
+    {
+      if (role[o] == Role::GroupParent) continue; // a group parent hoisted away from this level
+      ok = role[o] == Role::Plain && !(ops[o].flags & PLLGPU_OP_GATHER) && ops[o].parent_entries == c->geo.sites_alloc && ++n <= 2;
+    }
+  for (unsigned o = 0; o < count && ok; ++o)
+    if (ops[o].level == top && role[o] == Role::Plain)
+    {
+      role[o] = Role::HeldTail;
+      c->deferred.push_back(ops[o]);
+      c->last_bytes += op_traffic(c, ops[o], true, true);
+    }
+}
+
+// site repeats: every all-tip subtree of up to three ops' depth in one launch, before the levels (Role::SubtreeMember)
+static int launch_subtree_ops(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count, std::vector<Role> &role)
+{
+  unsigned nsub = 0, sub_entries = 0;
+  if (int rc = plan_subtrees(c, ops, count, role, nsub, sub_entries)) return rc;
+  if (!nsub) return 0;
+  return emit_launch(c, [c, items = c->sub_build]() {
+    if (int rc = upload_subtrees(c, items)) return rc;
+    launch_subtrees(c, (unsigned)items.size());
+    return 0;
+  }, (nsub + (unsigned)kSubItemsPerLaunch - 1) / (unsigned)kSubItemsPerLaunch);
+}
+
+// plain ops [i, j) of one level: one launch group per (child kinds, gather) in packs of kMaxOpsPerLaunch
+static int launch_plain_packs(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned i, unsigned j, const std::vector<Role> &role)
+{
+  for (unsigned kind = 0; kind < 3; ++kind)
+    for (unsigned ga = 0; ga < 2; ++ga)
+    {
+      OpPack pack;
+      unsigned nops = 0, maxent = 0;
+      auto flush = [&]() -> int {
+        if (!nops) return 0;
+        const bool gather = ga != 0;
+        const int rc = emit_launch(c, [c, pack, nops, maxent, kind, gather]() { return launch_partials(c, pack, nops, maxent, kind, gather); });
+        nops = 0;
+        maxent = 0;
+        return rc;
+      };
+      for (unsigned o = i; o < j; ++o)
+      {
+        const unsigned f = ops[o].flags;
+        const unsigned tips = ((f & PLLGPU_OP_LEFT_TIP) ? 1u : 0u) + ((f & PLLGPU_OP_RIGHT_TIP) ? 1u : 0u);
+        if ((f & PLLGPU_OP_RIGHT_TIP) && !(f & PLLGPU_OP_LEFT_TIP))
+          return fail(PLLGPU_EINVAL, "tip-inner operations must carry the tip as the left child");
+        if (role[o] != Role::Plain || tips != kind || ((f & PLLGPU_OP_GATHER) ? 1u : 0u) != ga) continue;
+        if (ops[o].parent_entries == 0) continue;
+        if (int rc = resolve_op(c, ops[o], pack.ops[nops])) return rc;
+        c->last_bytes += op_traffic(c, ops[o], true, true);
+        maxent = std::max(maxent, ops[o].parent_entries);
+        if (++nops == (unsigned)kMaxOpsPerLaunch)
+          if (int rc = flush()) return rc;
+      }
+      if (int rc = flush()) return rc;
+    }
   return 0;
 }
 
-// the level scheduler: plan the list and launch it (every launch through emit(), so that a plan being
-// recorded keeps it)
+// cherry-cherry groups (kind CK_FCC on at least one side) have their own descriptor and kernel
+static int launch_cc_groups(pllgpu_ctx *c, const pllgpu_op_t *ops, const std::vector<FusedGroup> &groups, size_t g0, size_t g1)
+{
+  std::vector<CCLaunch> ccl;
+  if (int rc = build_cc_launches(c, ops, groups, g0, g1, ccl)) return rc;
+  for (const CCLaunch &l : ccl)
+    if (int rc = emit_launch(c, [c, l]() { return launch_cc(c, l.pack, l.n, l.entries, l.lk, CK_FCC); })) return rc;
+  return 0;
+}
+
+// groups over two gathering producers (site repeats)
+static int launch_gg_packs(pllgpu_ctx *c, const pllgpu_op_t *ops, const std::vector<FusedGroup> &groups, size_t g0, size_t g1)
+{
+  GGPack gp;
+  unsigned n = 0, entries = 0;
+  auto flush = [&]() -> int {
+    if (!n) return 0;
+    const int rc = emit_launch(c, [c, gp, n, entries]() {
+      launch_gg(c, gp, n, entries);
+      return 0;
+    });
+    n = 0;
+    return rc;
+  };
+  for (size_t gi = g0; gi < g1; ++gi)
+  {
+    const FusedGroup &gq = groups[gi];
+    if (gq.lk != CK_FGG) continue;
+    const pllgpu_op_t &P = ops[gq.p];
+    if (P.parent_entries == 0) continue;
+    if (n && P.parent_entries != entries)
+      if (int rc = flush()) return rc;
+    entries = P.parent_entries;
+    GGroup &gg = gp.g[n];
+    memset(&gg, 0, sizeof gg);
+    DevOp d;
+    if (int rc = resolve_op(c, ops[gq.a], gg.a)) return rc;
+    if (int rc = resolve_op(c, ops[gq.b], gg.b)) return rc;
+    if (int rc = resolve_op(c, P, d)) return rc;
+    to_fop(d, gg.p);
+    c->last_bytes += op_traffic(c, ops[gq.a], true, true) + op_traffic(c, ops[gq.b], true, true) + op_traffic(c, P, false, false);
+    if (++n == (unsigned)kMaxGGroups)
+      if (int rc = flush()) return rc;
+  }
+  return flush();
+}
+
+// the other fused groups [g0, g1) executing at one level, one launch per pair of child kinds
+static int launch_fused_packs(pllgpu_ctx *c, const pllgpu_op_t *ops, const std::vector<FusedGroup> &groups, size_t g0, size_t g1)
+{
+  for (int lk = 0; lk <= CK_FII; ++lk)
+    for (int rk = lk; rk <= CK_FII; ++rk)
+    {
+      FusePack pack;
+      unsigned n = 0, entries = 0;
+      auto flush = [&]() -> int {
+        if (!n) return 0;
+        const int rc = c->dna_fast ? emit_launch(c, [c, pack, n, entries, lk, rk]() { return launch_fused(c, pack, n, entries, lk, rk); })
+                                   : emit_launch(c, [c, pack, n, entries]() { return launch_mfma_cc(c, pack, n, entries); });
+        n = 0;
+        return rc;
+      };
+      for (size_t gi = g0; gi < g1; ++gi)
+      {
+        FusedGroup g = groups[gi];
+        if (g.lk == CK_FCC || g.rk == CK_FCC || g.lk == CK_FGG) continue; // launched by launch_cc_groups / launch_gg_packs
+        const bool swap = g.lk > g.rk; // canonical order: the "smaller" kind on the left
+        if ((swap ? g.rk : g.lk) != lk || (swap ? g.lk : g.rk) != rk) continue;
+        const pllgpu_op_t &P = ops[g.p];
+        if (P.parent_entries == 0) continue;
+        if (n && P.parent_entries != entries)
+          if (int rc = flush()) return rc;
+        entries = P.parent_entries;
+        DevOp dp, da, db;
+        FGroup &fg = pack.g[n];
+        memset(&fg, 0, sizeof fg);
+        // producers first: their parent buffers must exist before P's children are resolved
+        if (g.a >= 0)
+        {
+          if (int rc = resolve_op(c, ops[g.a], da)) return rc;
+          c->last_bytes += op_traffic(c, ops[g.a], true, true);
+        }
+        if (g.b >= 0)
+        {
+          if (int rc = resolve_op(c, ops[g.b], db)) return rc;
+          c->last_bytes += op_traffic(c, ops[g.b], true, true);
+        }
+        if (int rc = resolve_op(c, P, dp)) return rc;
+        c->last_bytes += op_traffic(c, P, g.a < 0, g.b < 0);
+        to_fop(dp, fg.p);
+        if (g.a >= 0) to_fop(da, fg.a);
+        if (g.b >= 0) to_fop(db, fg.b);
+        if (swap)
+        {
+          std::swap(fg.p.left, fg.p.right);
+          std::swap(fg.p.ltip, fg.p.rtip);
+          std::swap(fg.p.lscaler, fg.p.rscaler);
+          std::swap(fg.p.lmat, fg.p.rmat);
+          std::swap(fg.a, fg.b);
+        }
+        if (++n == (unsigned)kMaxGroups)
+          if (int rc = flush()) return rc;
+      }
+      if (int rc = flush()) return rc;
+    }
+  return 0;
+}
+
 static int plan_and_launch_levels(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count)
 {
   c->launch_rc = 0;
-  std::vector<int> role;
+  std::vector<Role> role;
   std::vector<FusedGroup> groups;
   // the groups look their cherries' scaling decisions up in a table over all pairs of tip codes: only for a sane number of codes
   const bool cherry_groups = c->fuse_mfma && c->tipmap_set && c->tip_ncodes <= 32u;
   const bool generic_groups = cherry_groups;
   plan_fusion(c->fuse || generic_groups, c->fuse_cc, c->geo.nodes, ops, count, role, groups);
-  if (generic_groups)
-  {
-    // of the groups the 4x4 planner knows, the other shapes have one: both children cherries
-    std::vector<FusedGroup> keep;
-    for (const FusedGroup &gq : groups)
-      if (gq.lk == CK_FTT && gq.rk == CK_FTT && gq.a >= 0 && gq.b >= 0)
-        keep.push_back(gq);
-      else
-      {
-        role[gq.p] = 0;
-        if (gq.a >= 0) role[gq.a] = 0;
-        if (gq.b >= 0) role[gq.b] = 0;
-      }
-    groups.swap(keep);
-  }
-  // site repeats (4x4 kernels): an uncompressed op over two GATHERING inner x inner ops of the level below, all four
-  // of their children class-compressed, is evaluated with them (kernels_dna.h: k_partials_dna_gg). Such an op may
-  // have been taken as a producer by the op above it; that group gives way (its parent is usually one of the last
-  // level's ops, which then wait for the edge evaluation).
-  if (c->dna_fast && c->fuse && c->fuse_gg)
-  {
-    std::vector<int> producer(c->geo.nodes, -1), pl(count, -1), pr(count, -1);
-    for (unsigned q = 0; q < count; ++q)
-    {
-      if (!(ops[q].flags & PLLGPU_OP_LEFT_TIP)) pl[q] = producer[ops[q].left_clv];
-      if (!(ops[q].flags & PLLGPU_OP_RIGHT_TIP)) pr[q] = producer[ops[q].right_clv];
-      producer[ops[q].parent_clv] = (int)q;
-    }
-    auto gathering = [&](int x, int pscal, const pllgpu_op_t &P, unsigned L) {
-      if (x < 0 || role[x] != 0) return false;
-      const pllgpu_op_t &o = ops[x];
-      return o.level == L && (o.flags & PLLGPU_OP_GATHER) && !(o.flags & (PLLGPU_OP_LEFT_TIP | PLLGPU_OP_RIGHT_TIP)) &&
-             o.parent_entries == P.parent_entries && o.parent_entries == c->geo.sites_alloc && o.parent_scaler == pscal &&
-             c->ids[o.left_clv] && c->ids[o.right_clv];
-    };
-    for (unsigned q = 0; q < count; ++q)
-    {
-      const pllgpu_op_t &P = ops[q];
-      if ((P.flags & (PLLGPU_OP_GATHER | PLLGPU_OP_LEFT_TIP | PLLGPU_OP_RIGHT_TIP)) || P.level == 0 || role[q] == 1) continue;
-      const unsigned L = P.level - 1;
-      if (P.war_level >= (int)L || pl[q] == pr[q]) continue;
-      if (!gathering(pl[q], P.left_scaler, P, L) || !gathering(pr[q], P.right_scaler, P, L)) continue;
-      if (role[q] == 2)
-      {
-        // dissolve the group that took P as a producer
-        for (size_t gi = 0; gi < groups.size(); ++gi)
-          if ((groups[gi].a == (int)q || groups[gi].b == (int)q) && groups[gi].lk != CK_FCC && groups[gi].rk != CK_FCC)
-          {
-            role[groups[gi].p] = 0;
-            if (groups[gi].a >= 0) role[groups[gi].a] = 0;
-            if (groups[gi].b >= 0) role[groups[gi].b] = 0;
-            groups.erase(groups.begin() + gi);
-            break;
-          }
-        if (role[q] != 0) continue; // (a cherry-cherry side: leave it)
-      }
-      FusedGroup gq;
-      gq.p = q;
-      gq.a = pl[q];
-      gq.b = pr[q];
-      gq.lk = gq.rk = CK_FGG;
-      gq.level = L;
-      role[q] = 1;
-      role[gq.a] = role[gq.b] = 2;
-      groups.push_back(gq);
-    }
-  }
-  // tail fusion: the plain ops of the last level (at most two: the ends of the edge a caller evaluates
-  // next) are accepted but not launched yet - role 3
-  if (c->defer_tail && count)
-  {
-    const unsigned top = ops[count - 1].level;
-    unsigned n = 0;
-    bool ok = true;
-    for (unsigned o = 0; o < count && ok; ++o)
-      if (ops[o].level == top)
-      {
-        if (role[o] == 1) continue; // a group parent hoisted away from this level
-        ok = role[o] == 0 && !(ops[o].flags & PLLGPU_OP_GATHER) && ops[o].parent_entries == c->geo.sites_alloc && ++n <= 2;
-      }
-    for (unsigned o = 0; o < count && ok; ++o)
-      if (ops[o].level == top && role[o] == 0)
-      {
-        role[o] = 3;
-        c->deferred.push_back(ops[o]);
-        c->last_bytes += op_traffic(c, ops[o], true, true);
-      }
-  }
-  // site repeats: every all-tip subtree of up to three ops' depth in one launch, before the levels (role 4)
-  {
-    unsigned nsub = 0, sub_entries = 0;
-    if (int rc = plan_subtrees(c, ops, count, role, nsub, sub_entries)) return rc;
-    if (nsub)
-    {
-      c->last_launches += (nsub + (unsigned)kSubItemsPerLaunch - 1) / (unsigned)kSubItemsPerLaunch;
-      emit(c, [c, items = c->sub_build]() {
-        if (int rc = upload_subtrees(c, items)) c->launch_rc = rc;
-        else launch_subtrees(c, (unsigned)items.size());
-      });
-      if (c->launch_rc) return c->launch_rc;
-    }
-  }
+  if (generic_groups) keep_cherry_pairs(role, groups);
+  if (c->dna_fast && c->fuse && c->fuse_gg) plan_gg_groups(c, ops, count, role, groups);
+  if (c->defer_tail && count) hold_tail(c, ops, count, role);
+  if (int rc = launch_subtree_ops(c, ops, count, role)) return rc;
   size_t gi_sorted = 0;
   if (!groups.empty())
     sort_groups_by_level(groups);
   unsigned i = 0;
-  unsigned level = 0;
   const unsigned last_level = count ? ops[count - 1].level : 0;
-  for (level = 0; level <= last_level; ++level)
+  for (unsigned level = 0; level <= last_level; ++level)
   {
     // [i, j) = the ops of this dependency level
     unsigned j = i;
     while (j < count && ops[j].level == level) ++j;
-    // plain ops: one launch group per (child kinds, gather) in packs of kMaxOpsPerLaunch
-    for (unsigned kind = 0; kind < 3; ++kind)
-      for (unsigned ga = 0; ga < 2; ++ga)
-      {
-        OpPack pack;
-        unsigned nops = 0, maxent = 0;
-        int lrc = 0;
-        auto flush = [&]() {
-          if (!nops) return;
-          const bool gather = ga != 0;
-          emit(c, [c, pack, nops, maxent, kind, gather]() {
-            if (int rc = launch_partials(c, pack, nops, maxent, kind, gather)) c->launch_rc = rc;
-          });
-          if (c->launch_rc) lrc = c->launch_rc;
-          ++c->last_launches;
-          nops = 0;
-          maxent = 0;
-        };
-        for (unsigned o = i; o < j; ++o)
-        {
-          const unsigned f = ops[o].flags;
-          const unsigned tips = ((f & PLLGPU_OP_LEFT_TIP) ? 1u : 0u) + ((f & PLLGPU_OP_RIGHT_TIP) ? 1u : 0u);
-          if ((f & PLLGPU_OP_RIGHT_TIP) && !(f & PLLGPU_OP_LEFT_TIP))
-            return fail(PLLGPU_EINVAL, "tip-inner operations must carry the tip as the left child");
-          if (role[o] || tips != kind || ((f & PLLGPU_OP_GATHER) ? 1u : 0u) != ga) continue;
-          if (ops[o].parent_entries == 0) continue;
-          if (int rc = resolve_op(c, ops[o], pack.ops[nops])) return rc;
-          c->last_bytes += op_traffic(c, ops[o], true, true);
-          maxent = std::max(maxent, ops[o].parent_entries);
-          if (++nops == (unsigned)kMaxOpsPerLaunch) flush();
-        }
-        flush();
-        if (lrc) return lrc;
-      }
-    // fused groups executing at this level, one launch per pair of child kinds
+    if (int rc = launch_plain_packs(c, ops, i, j, role)) return rc;
+    // [g0, gi_sorted) = the fused groups executing at this level
     const size_t g0 = gi_sorted;
     while (gi_sorted < groups.size() && groups[gi_sorted].level == level) ++gi_sorted;
-    // cherry-cherry groups (kind CK_FCC on at least one side) have their own descriptor and kernel
-    {
-      std::vector<CCLaunch> ccl;
-      if (int rc = build_cc_launches(c, ops, groups, g0, gi_sorted, ccl)) return rc;
-      for (const CCLaunch &l : ccl)
-      {
-        emit(c, [c, l]() {
-          if (int rc = launch_cc(c, l.pack, l.n, l.entries, l.lk, CK_FCC)) c->launch_rc = rc;
-        });
-        if (c->launch_rc) return c->launch_rc;
-        ++c->last_launches;
-      }
-    }
-    // groups over two gathering producers (site repeats)
-    {
-      GGPack gp;
-      unsigned n = 0, entries = 0;
-      auto flushg = [&]() -> int {
-        if (!n) return 0;
-        emit(c, [c, gp, n, entries]() { launch_gg(c, gp, n, entries); });
-        ++c->last_launches;
-        n = 0;
-        return c->launch_rc;
-      };
-      for (size_t gi = g0; gi < gi_sorted; ++gi)
-      {
-        const FusedGroup &gq = groups[gi];
-        if (gq.lk != CK_FGG) continue;
-        const pllgpu_op_t &P = ops[gq.p];
-        if (P.parent_entries == 0) continue;
-        if (n && P.parent_entries != entries)
-          if (int rc = flushg()) return rc;
-        entries = P.parent_entries;
-        GGroup &gg = gp.g[n];
-        memset(&gg, 0, sizeof gg);
-        DevOp d;
-        if (int rc = resolve_op(c, ops[gq.a], gg.a)) return rc;
-        if (int rc = resolve_op(c, ops[gq.b], gg.b)) return rc;
-        if (int rc = resolve_op(c, P, d)) return rc;
-        to_fop(d, gg.p);
-        c->last_bytes += op_traffic(c, ops[gq.a], true, true) + op_traffic(c, ops[gq.b], true, true) + op_traffic(c, P, false, false);
-        if (++n == (unsigned)kMaxGGroups)
-          if (int rc = flushg()) return rc;
-      }
-      if (int rc = flushg()) return rc;
-    }
-    for (int lk = 0; lk <= CK_FII; ++lk)
-      for (int rk = lk; rk <= CK_FII; ++rk)
-      {
-        FusePack pack;
-        unsigned n = 0, entries = 0;
-        auto flush = [&]() -> int {
-          if (!n) return 0;
-          if (!c->dna_fast)
-            emit(c, [c, pack, n, entries]() {
-              if (int rc = launch_mfma_cc(c, pack, n, entries)) c->launch_rc = rc;
-            });
-          else
-            emit(c, [c, pack, n, entries, lk, rk]() {
-              if (int rc = launch_fused(c, pack, n, entries, lk, rk)) c->launch_rc = rc;
-            });
-          if (c->launch_rc) return c->launch_rc;
-          ++c->last_launches;
-          n = 0;
-          return 0;
-        };
-        for (size_t gi = g0; gi < gi_sorted; ++gi)
-        {
-          FusedGroup g = groups[gi];
-          if (g.lk == CK_FCC || g.rk == CK_FCC || g.lk == CK_FGG) continue; // launched above
-          const bool swap = g.lk > g.rk; // canonical order: the "smaller" kind on the left
-          if ((swap ? g.rk : g.lk) != lk || (swap ? g.lk : g.rk) != rk) continue;
-          const pllgpu_op_t &P = ops[g.p];
-          if (P.parent_entries == 0) continue;
-          if (n && P.parent_entries != entries)
-            if (int rc = flush()) return rc;
-          entries = P.parent_entries;
-          DevOp dp, da, db;
-          FGroup &fg = pack.g[n];
-          memset(&fg, 0, sizeof fg);
-          // producers first: their parent buffers must exist before P's children are resolved
-          if (g.a >= 0)
-          {
-            if (int rc = resolve_op(c, ops[g.a], da)) return rc;
-            c->last_bytes += op_traffic(c, ops[g.a], true, true);
-          }
-          if (g.b >= 0)
-          {
-            if (int rc = resolve_op(c, ops[g.b], db)) return rc;
-            c->last_bytes += op_traffic(c, ops[g.b], true, true);
-          }
-          if (int rc = resolve_op(c, P, dp)) return rc;
-          c->last_bytes += op_traffic(c, P, g.a < 0, g.b < 0);
-          to_fop(dp, fg.p);
-          if (g.a >= 0) to_fop(da, fg.a);
-          if (g.b >= 0) to_fop(db, fg.b);
-          if (swap)
-          {
-            std::swap(fg.p.left, fg.p.right);
-            std::swap(fg.p.ltip, fg.p.rtip);
-            std::swap(fg.p.lscaler, fg.p.rscaler);
-            std::swap(fg.p.lmat, fg.p.rmat);
-            std::swap(fg.a, fg.b);
-          }
-          if (++n == (unsigned)kMaxGroups)
-            if (int rc = flush()) return rc;
-        }
-        if (int rc = flush()) return rc;
-      }
+    if (int rc = launch_cc_groups(c, ops, groups, g0, gi_sorted)) return rc;
+    if (int rc = launch_gg_packs(c, ops, groups, g0, gi_sorted)) return rc;
+    if (int rc = launch_fused_packs(c, ops, groups, g0, gi_sorted)) return rc;
     i = j;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PLLGPU_ERUNTIME, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
+  return launch_status();
 }
 
 extern "C" int pllgpu_update_partials(pllgpu_ctx_t *c, const pllgpu_op_t *ops, unsigned count)
@@ -1931,15 +1975,13 @@ extern "C" int pllgpu_update_partials(pllgpu_ctx_t *c, const pllgpu_op_t *ops, u
         if (lp->any_aos) c->any_aos = true;
         c->deferred = lp->deferred;
         c->launch_rc = 0;
-        for (const auto &fn : lp->launches) fn();
+        for (const auto &fn : lp->launches)
+          if (int rc = fn()) c->launch_rc = rc;
         ++c->plan_replays;
         c->last_launches = lp->nlaunches;
         c->last_bytes = lp->bytes;
         lp->used = ++c->plan_stamp;
-        if (c->launch_rc) return c->launch_rc;
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(PLLGPU_ERUNTIME, "kernel launch failed: %s", hipGetErrorString(e));
-        return 0;
+        return c->launch_rc ? c->launch_rc : launch_status();
       }
   }
   LevelPlan *lp = c->plan_cache ? new LevelPlan() : nullptr;
@@ -1980,18 +2022,11 @@ extern "C" double pllgpu_last_algorithmic_bytes(const pllgpu_ctx_t *c) { return 
 template <int ICH>
 static void launch_edge_generic(pllgpu_ctx *c, const DevEdge &e, unsigned blocks, unsigned tpw, bool ctip, bool gather)
 {
-  const unsigned long long *tm = c->tipmap_set ? c->tipmap.p : nullptr;
+  const unsigned long long *tm = tipmap_ptr(c);
   const unsigned threads = 64u * std::min(c->gg.R, 4u); // one wave per rate category of the tile, up to 4
-#define EG(CT, GA) hipLaunchKernelGGL((k_edge_tiled<ICH, CT, GA>), dim3(blocks), dim3(threads), 0, c->stream, e, c->gg, tm, tpw)
-  if (ctip)
-  {
-    if (gather) EG(true, true); else EG(true, false);
-  }
-  else
-  {
-    if (gather) EG(false, true); else EG(false, false);
-  }
-#undef EG
+  with_bools(ctip, gather, [&](auto CT, auto GA) {
+    hipLaunchKernelGGL((k_edge_tiled<ICH, CT(), GA()>), dim3(blocks), dim3(threads), 0, c->stream, e, c->gg, tm, tpw);
+  });
 }
 
 // the tail-fused evaluation: kinds of the two ends and the descriptors of the held ops
@@ -2003,18 +2038,17 @@ struct TailCall
 
 static int launch_edge_tail(pllgpu_ctx *c, const DevEdge &e, const TailCall &t, unsigned blocks, unsigned tpw)
 {
-#define TZ(A, B)                                                                                                      \
-  if (t.kp == A && t.kc == B)                                                                                         \
-  {                                                                                                                   \
-    hipLaunchKernelGGL((k_edge_dna_tail<A, B>), dim3(blocks), dim3(256), 0, c->stream, e, t.g, c->gg.scale_mode, tpw); \
-    return 0;                                                                                                         \
-  }
-  TZ(CK_INNER, CK_FTT) TZ(CK_INNER, CK_FTI) TZ(CK_INNER, CK_FII)
-  TZ(CK_FTT, CK_INNER) TZ(CK_FTT, CK_TIP) TZ(CK_FTT, CK_FTT) TZ(CK_FTT, CK_FTI) TZ(CK_FTT, CK_FII)
-  TZ(CK_FTI, CK_INNER) TZ(CK_FTI, CK_TIP) TZ(CK_FTI, CK_FTT) TZ(CK_FTI, CK_FTI) TZ(CK_FTI, CK_FII)
-  TZ(CK_FII, CK_INNER) TZ(CK_FII, CK_TIP) TZ(CK_FII, CK_FTT) TZ(CK_FII, CK_FTI) TZ(CK_FII, CK_FII)
-#undef TZ
-  return fail(PLLGPU_EINVAL, "no tail kernel for end kinds (%d, %d)", t.kp, t.kc);
+  const bool known = with_kind_pair(
+      t.kp, t.kc,
+      [&](auto KP, auto KC) {
+        hipLaunchKernelGGL((k_edge_dna_tail<KP(), KC()>), dim3(blocks), dim3(256), 0, c->stream, e, t.g, c->gg.scale_mode, tpw);
+      },
+      KindPair<CK_INNER, CK_FTT>(), KindPair<CK_INNER, CK_FTI>(), KindPair<CK_INNER, CK_FII>(),
+      KindPair<CK_FTT, CK_INNER>(), KindPair<CK_FTT, CK_TIP>(), KindPair<CK_FTT, CK_FTT>(), KindPair<CK_FTT, CK_FTI>(), KindPair<CK_FTT, CK_FII>(),
+      KindPair<CK_FTI, CK_INNER>(), KindPair<CK_FTI, CK_TIP>(), KindPair<CK_FTI, CK_FTT>(), KindPair<CK_FTI, CK_FTI>(), KindPair<CK_FTI, CK_FII>(),
+      KindPair<CK_FII, CK_INNER>(), KindPair<CK_FII, CK_TIP>(), KindPair<CK_FII, CK_FTT>(), KindPair<CK_FII, CK_FTI>(), KindPair<CK_FII, CK_FII>());
+  if (!known) return fail(PLLGPU_EINVAL, "no tail kernel for end kinds (%d, %d)", t.kp, t.kc);
+  return 0;
 }
 
 // chain tail (kernels_dna.h: k_edge_dna_chain): the two ends of the edge as chains - held ones, or chains of
@@ -2032,53 +2066,89 @@ static void launch_edge_chain(pllgpu_ctx *c, const DevEdge &e, const ChainTailCa
   const ChainPlan &pl = *c->plan;
   dim3 grid((pl.entries + 63) / 64), block(256);
   if (t.in_kernarg)
+    with_chain_variant(c->gg.scale_mode, t.variant, [&](auto SMV, auto C0, auto S1, auto C1) {
+      hipLaunchKernelGGL((k_edge_dna_chain_pack<SMV(), C0(), S1(), C1()>), grid, block, 0, c->stream, e, t.pack, pl.entries);
+    });
+  else
   {
-#define EC(SMV, C0, S1, C1) hipLaunchKernelGGL((k_edge_dna_chain_pack<SMV, C0, S1, C1>), grid, block, 0, c->stream, e, t.pack, pl.entries)
-#define EC_V(SMV)                              \
-  switch (t.variant)                           \
-  {                                            \
-  case 0: EC(SMV, false, false, false); break; \
-  case 1: EC(SMV, false, true, false); break;  \
-  case 2: EC(SMV, true, false, false); break;  \
-  default: EC(SMV, true, true, true); break;   \
+    const ChainStepLoad *lp;
+    const ChainStepOp *op;
+    chain_steps_on_device(c, pl, lp, op);
+    with_chain_variant(c->gg.scale_mode, t.variant, [&](auto SMV, auto C0, auto S1, auto C1) {
+      hipLaunchKernelGGL((k_edge_dna_chain<SMV(), C0(), S1(), C1()>), grid, block, 0, c->stream, e, t.hp, t.hc, lp, op, pl.entries);
+    });
   }
-    if (c->gg.scale_mode == 2)
+}
+
+// 33..64 states: P x on the matrix pipe (kernels_mfma.h: k_edge_mfma), one rate category per workgroup
+static int launch_edge_mfma(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather)
+{
+  const pllgpu_geometry_t &g = c->geo;
+  const unsigned items = (g.sites + 31) / 32, R = c->gg.R;
+  // a workgroup's life is a chain of round trips (matrix, child, parent, ticket, partials, block sum: ~30 us at C5's
+  // size) around 3 us of MFMAs per item, and two workgroups fit a CU: ONE round of at most 512 workgroups - C5's 625
+  // items as 628 workgroups of one item per wave took two rounds, 67 us; as 316 of two items per wave 3x us
+  const unsigned max_ib = std::max(1u, 512u / R);
+  const unsigned ipw = std::max(1u, (items + 4u * max_ib - 1) / (4u * max_ib));
+  const unsigned nib = (items + 4u * ipw - 1) / (4u * ipw);
+  const unsigned blocks = nib * R;
+  const unsigned pstride = (g.sites + 63u) & ~63u;
+  if (c->block_sums.ensure(std::max<size_t>(4096, blocks)) || c->edge_partials.ensure((size_t)R * 4u * pstride)) return PLLGPU_ENOMEM;
+  if (c->edge_tickets.cap < nib)
+  {
+    if (c->edge_tickets.ensure(std::max(1024u, nib))) return PLLGPU_ENOMEM;
+    HIP_TRY(hipMemsetAsync(c->edge_tickets.p, 0, c->edge_tickets.cap * sizeof(unsigned), c->stream));
+  }
+  e.block_sums = c->block_sums.p;
+  const size_t lds = (kFragArray + 64) * sizeof(double);
+  const unsigned long long *tm = tipmap_ptr(c);
+  with_bools(ctip, gather, [&](auto CT, auto GA) {
+    hipLaunchKernelGGL((k_edge_mfma<CT(), GA()>), dim3(blocks), dim3(256), lds, c->stream, e, c->gg, tm, ipw, c->edge_partials.p, pstride, c->edge_tickets.p);
+  });
+  return 0;
+}
+
+// the evaluation's one launch: which kernel family takes it
+static int launch_edge(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather, const TailCall *tail, const ChainTailCall *ctail)
+{
+  const unsigned tiles = (c->geo.sites + 63) / 64;
+  const unsigned max_blocks = 1024;
+  if (c->use_mfma && c->mfma_ng == 16 && !e.is_root) return launch_edge_mfma(c, e, ctip, gather);
+  if (c->dna_fast && ctail)
+  {
+    launch_edge_chain(c, e, *ctail);
+    ++c->last_launches;
+  }
+  else if (c->dna_fast)
+  {
+    // 4 waves = 4 tiles per workgroup, tpw consecutive tiles per wave
+    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
+    const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
+    if (tail)
     {
-      EC_V(2)
+      if (int rc = launch_edge_tail(c, e, *tail, blocks, tpw)) return rc;
+      ++c->last_launches;
     }
     else
-    {
-      EC_V(1)
-    }
-#undef EC_V
-#undef EC
+      with_bools(ctip, gather, [&](auto CT, auto GA) {
+        hipLaunchKernelGGL((k_edge_dna<CT(), GA()>), dim3(blocks), dim3(256), 0, c->stream, e, tpw);
+      });
   }
   else
   {
-    const unsigned char *base = c->chain_dev.p;
-    const size_t heads_bytes = pl.heads.size() * sizeof(ChainHead), loads_bytes = pl.loads.size() * sizeof(ChainStepLoad);
-    const ChainStepLoad *lp = reinterpret_cast<const ChainStepLoad *>(base + heads_bytes);
-    const ChainStepOp *op = reinterpret_cast<const ChainStepOp *>(base + heads_bytes + loads_bytes);
-#define EC(SMV, C0, S1, C1) hipLaunchKernelGGL((k_edge_dna_chain<SMV, C0, S1, C1>), grid, block, 0, c->stream, e, t.hp, t.hc, lp, op, pl.entries)
-#define EC_V(SMV)                              \
-  switch (t.variant)                           \
-  {                                            \
-  case 0: EC(SMV, false, false, false); break; \
-  case 1: EC(SMV, false, true, false); break;  \
-  case 2: EC(SMV, true, false, false); break;  \
-  default: EC(SMV, true, true, true); break;   \
-  }
-    if (c->gg.scale_mode == 2)
+    // one tile per workgroup pass (the waves split its rate categories), tpw tiles per workgroup
+    const unsigned tpw = (tiles + max_blocks - 1) / max_blocks;
+    const unsigned blocks = (tiles + tpw - 1) / tpw;
+    switch (c->ich)
     {
-      EC_V(2)
+      case 4: launch_edge_generic<4>(c, e, blocks, tpw, ctip, gather); break;
+      case 8: launch_edge_generic<8>(c, e, blocks, tpw, ctip, gather); break;
+      case 16: launch_edge_generic<16>(c, e, blocks, tpw, ctip, gather); break;
+      case 20: launch_edge_generic<20>(c, e, blocks, tpw, ctip, gather); break;
+      default: launch_edge_generic<32>(c, e, blocks, tpw, ctip, gather); break;
     }
-    else
-    {
-      EC_V(1)
-    }
-#undef EC_V
-#undef EC
   }
+  return 0;
 }
 
 static int run_lnl(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather, const unsigned *freqs_indices,
@@ -2112,84 +2182,7 @@ static int run_lnl(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather, const unsi
   e.sites = g.sites;
   e.per_rate = g.per_rate_scalers ? 1 : 0;
   e.fenced = c->fenced;
-
-  const unsigned tiles = (g.sites + 63) / 64;
-  const unsigned max_blocks = 1024;
-  unsigned blocks, tpw;
-  if (c->use_mfma && c->mfma_ng == 16 && !e.is_root)
-  {
-    // 33..64 states: P x on the matrix pipe (kernels_mfma.h: k_edge_mfma), one rate category per workgroup
-    const unsigned items = (g.sites + 31) / 32, R = c->gg.R;
-    // a workgroup's life is a chain of round trips (matrix, child, parent, ticket, partials, block sum: ~30 us at C5's
-    // size) around 3 us of MFMAs per item, and two workgroups fit a CU: ONE round of at most 512 workgroups - C5's 625
-    // items as 628 workgroups of one item per wave took two rounds, 67 us; as 316 of two items per wave 3x us
-    const unsigned max_ib = std::max(1u, 512u / R);
-    const unsigned ipw = std::max(1u, (items + 4u * max_ib - 1) / (4u * max_ib));
-    const unsigned nib = (items + 4u * ipw - 1) / (4u * ipw);
-    blocks = nib * R;
-    const unsigned pstride = (g.sites + 63u) & ~63u;
-    if (c->block_sums.ensure(std::max<size_t>(4096, blocks)) || c->edge_partials.ensure((size_t)R * 4u * pstride)) return PLLGPU_ENOMEM;
-    if (c->edge_tickets.cap < nib)
-    {
-      if (c->edge_tickets.ensure(std::max(1024u, nib))) return PLLGPU_ENOMEM;
-      HIP_TRY(hipMemsetAsync(c->edge_tickets.p, 0, c->edge_tickets.cap * sizeof(unsigned), c->stream));
-    }
-    e.block_sums = c->block_sums.p;
-    const size_t lds = (kFragArray + 64) * sizeof(double);
-    const unsigned long long *tm = c->tipmap_set ? c->tipmap.p : nullptr;
-#define EM(CT, GA) hipLaunchKernelGGL((k_edge_mfma<CT, GA>), dim3(blocks), dim3(256), lds, c->stream, e, c->gg, tm, ipw, c->edge_partials.p, pstride, c->edge_tickets.p)
-    if (ctip)
-    {
-      if (gather) EM(true, true); else EM(true, false);
-    }
-    else
-    {
-      if (gather) EM(false, true); else EM(false, false);
-    }
-#undef EM
-  }
-  else if (c->dna_fast && ctail)
-  {
-    launch_edge_chain(c, e, *ctail);
-    ++c->last_launches;
-  }
-  else if (c->dna_fast && tail)
-  {
-    tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
-    blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
-    if (int rc = launch_edge_tail(c, e, *tail, blocks, tpw)) return rc;
-    ++c->last_launches;
-  }
-  else if (c->dna_fast)
-  {
-    // 4 waves = 4 tiles per workgroup, tpw consecutive tiles per wave
-    tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
-    blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
-#define ED(CT, GA) hipLaunchKernelGGL((k_edge_dna<CT, GA>), dim3(blocks), dim3(256), 0, c->stream, e, tpw)
-    if (ctip)
-    {
-      if (gather) ED(true, true); else ED(true, false);
-    }
-    else
-    {
-      if (gather) ED(false, true); else ED(false, false);
-    }
-#undef ED
-  }
-  else
-  {
-    // one tile per workgroup pass (the waves split its rate categories), tpw tiles per workgroup
-    tpw = (tiles + max_blocks - 1) / max_blocks;
-    blocks = (tiles + tpw - 1) / tpw;
-    switch (c->ich)
-    {
-      case 4: launch_edge_generic<4>(c, e, blocks, tpw, ctip, gather); break;
-      case 8: launch_edge_generic<8>(c, e, blocks, tpw, ctip, gather); break;
-      case 16: launch_edge_generic<16>(c, e, blocks, tpw, ctip, gather); break;
-      case 20: launch_edge_generic<20>(c, e, blocks, tpw, ctip, gather); break;
-      default: launch_edge_generic<32>(c, e, blocks, tpw, ctip, gather); break;
-    }
-  }
+  if (int rc = launch_edge(c, e, ctip, gather, tail, ctail)) return rc;
   HIP_TRY(hipGetLastError());
   if (device_result) return 0; // asynchronous: the value stays on the device
   if (persite_host)
@@ -2263,127 +2256,112 @@ struct ClaimedWork
   }
 };
 
-extern "C" int pllgpu_edge_loglikelihood(pllgpu_ctx_t *c, const pllgpu_edge_t *ed, double *persite_host, double *lnl_out)
+// everything about an edge evaluation that can be checked without touching the held state
+static int check_edge(const pllgpu_ctx *c, const pllgpu_edge_t *ed, const double *persite_host)
 {
-  CHECK_CTX_KEEP(c);
   const pllgpu_geometry_t &g = c->geo;
-  // everything that can be checked without touching the held state comes first
   if (ed->parent_clv >= g.nodes || ed->child_clv >= g.nodes || ed->matrix >= g.prob_matrices)
     return fail(PLLGPU_EINVAL, "edge references an index out of range");
   if (ed->parent_scaler >= (int)g.scale_buffers || ed->child_scaler >= (int)g.scale_buffers)
     return fail(PLLGPU_EINVAL, "edge references a scale buffer out of range");
   if (ed->device_result && persite_host) return fail(PLLGPU_EINVAL, "per-site values are not available from an asynchronous evaluation");
   if (ed->sequence != 0.0 && !ed->device_result) return fail(PLLGPU_EINVAL, "a caller-numbered evaluation needs device_result");
-  struct SeqScope
-  {
-    pllgpu_ctx *c;
-    ~SeqScope() { c->seq_override = 0.0; }
-  } seq_scope_{c};
-  c->seq_override = ed->sequence;
   if (ed->child_is_tip && (ed->child_clv >= g.tips || !c->tipchars[ed->child_clv].p))
     return fail(PLLGPU_EINVAL, "tip %u has no codes on the device", ed->child_clv);
   for (unsigned k = 0; k < g.rate_cats; ++k)
     if (ed->freqs_indices[k] >= g.rate_matrices) return fail(PLLGPU_EINVAL, "freqs_indices[%u] = %u out of range", k, ed->freqs_indices[k]);
-  ClaimedWork claimed(c);
-  // held ops (tail fusion): if they produce an end of THIS edge they are evaluated inside the lnL
-  // kernel; whatever else is held goes out as ordinary updates first
-  TailCall tail;
-  bool use_tail = false;
-  int held_p = -1, held_c = -1; // heads of the held chains that end in this edge's parent / child end
-  if (c->chain_held)
+  return 0;
+}
+
+// held chains: the heads of those that end in this edge's parent / child end (held_p / held_c, or -1) are claimed for
+// the log-likelihood kernel; whatever else is held goes out as ordinary chain launches
+static int claim_held_chains(pllgpu_ctx *c, const pllgpu_edge_t *ed, ClaimedWork &claimed, int &held_p, int &held_c)
+{
+  held_p = held_c = -1;
+  if (!c->chain_held) return 0;
+  const ChainPlan &pl = *c->plan;
+  if (c->dna_fast && !ed->gather)
+    for (size_t i = pl.held_from; i < pl.stages.size(); ++i)
+      for (unsigned h = pl.stages[i].first_head; h < pl.stages[i].first_head + pl.stages[i].nchains; ++h)
+      {
+        if (pl.head_top_clv[h] == ed->parent_clv && pl.head_top_scaler[h] == ed->parent_scaler) held_p = (int)h;
+        else if (!ed->child_is_tip && pl.head_top_clv[h] == ed->child_clv && pl.head_top_scaler[h] == ed->child_scaler) held_c = (int)h;
+      }
+  // a tail that would not fit its kernarg pack (try_chain_plan keeps such plans in memory: cannot happen
+  // there; defensive): nothing is claimed, both chains go out as ordinary launches
+  if ((held_p >= 0 || held_c >= 0) && pl.in_kernarg)
   {
-    const ChainPlan &pl = *c->plan;
-    if (c->dna_fast && !ed->gather)
-      for (size_t i = pl.held_from; i < pl.stages.size(); ++i)
-        for (unsigned h = pl.stages[i].first_head; h < pl.stages[i].first_head + pl.stages[i].nchains; ++h)
-        {
-          if (pl.head_top_clv[h] == ed->parent_clv && pl.head_top_scaler[h] == ed->parent_scaler) held_p = (int)h;
-          else if (!ed->child_is_tip && pl.head_top_clv[h] == ed->child_clv && pl.head_top_scaler[h] == ed->child_scaler) held_c = (int)h;
-        }
-    if (held_p < 0 && held_c < 0)
-    {
-      if (int rc = launch_held_chains(c)) return rc;
-    }
-    else
-    {
-      // a tail that would not fit its kernarg pack (try_chain_plan keeps such plans in memory: cannot happen
-      // there; defensive): nothing is claimed, both chains go out as ordinary launches
-      if (pl.in_kernarg)
-      {
-        const unsigned np = held_p >= 0 ? pl.heads[held_p].nsteps + 1 : 1u, nc = held_c >= 0 ? pl.heads[held_c].nsteps + 1 : 1u;
-        if (np + nc > (unsigned)kChainPackSteps) held_p = held_c = -1;
-      }
-      if (held_p < 0 && held_c < 0)
-      {
-        if (int rc = launch_held_chains(c)) return rc;
-      }
-      else
-      {
-        if (int rc = c->block_sums.ensure((pl.entries + 63) / 64)) return rc; // before anything is claimed
-        // whatever else is held goes out as an ordinary chain launch
-        c->chain_held = false;
-        claimed.heads[0] = held_p;
-        claimed.heads[1] = held_c;
-        claimed.armed = true;
-        for (size_t i = pl.held_from; i < pl.stages.size(); ++i)
-          for (unsigned h = pl.stages[i].first_head; h < pl.stages[i].first_head + pl.stages[i].nchains; ++h)
-            if ((int)h != held_p && (int)h != held_c)
-            {
-              launch_chain_heads(c, pl, h, 1, pl.stages[i].variant);
-              ++c->last_launches;
-            }
-      }
-    }
+    const unsigned np = held_p >= 0 ? pl.heads[held_p].nsteps + 1 : 1u, nc = held_c >= 0 ? pl.heads[held_c].nsteps + 1 : 1u;
+    if (np + nc > (unsigned)kChainPackSteps) held_p = held_c = -1;
   }
+  if (held_p < 0 && held_c < 0) return launch_held_chains(c);
+  if (int rc = c->block_sums.ensure((pl.entries + 63) / 64)) return rc; // before anything is claimed
+  // whatever else is held goes out as an ordinary chain launch
+  c->chain_held = false;
+  claimed.heads[0] = held_p;
+  claimed.heads[1] = held_c;
+  claimed.armed = true;
+  for (size_t i = pl.held_from; i < pl.stages.size(); ++i)
+    for (unsigned h = pl.stages[i].first_head; h < pl.stages[i].first_head + pl.stages[i].nchains; ++h)
+      if ((int)h != held_p && (int)h != held_c)
+      {
+        launch_chain_heads(c, pl, h, 1, pl.stages[i].variant);
+        ++c->last_launches;
+      }
+  return 0;
+}
+
+// held ops (tail fusion): if they produce an end of THIS edge they are evaluated inside the lnL
+// kernel (use_tail, their descriptors and kinds in tail); whatever else is held goes out as ordinary updates first
+static int claim_held_ops(pllgpu_ctx *c, const pllgpu_edge_t *ed, ClaimedWork &claimed, TailCall &tail, bool &use_tail)
+{
+  use_tail = false;
+  if (c->deferred.empty()) return 0;
+  int ia = -1, ib = -1;
+  if (c->dna_fast && !ed->gather)
+    for (size_t i = 0; i < c->deferred.size(); ++i)
+    {
+      const pllgpu_op_t &o = c->deferred[i];
+      if (o.parent_clv == ed->parent_clv && o.parent_scaler == ed->parent_scaler) ia = (int)i;
+      else if (!ed->child_is_tip && o.parent_clv == ed->child_clv && o.parent_scaler == ed->child_scaler) ib = (int)i;
+    }
+  if (ia < 0 && ib < 0) return flush_deferred(c);
+  std::vector<pllgpu_op_t> held;
+  held.swap(c->deferred);
+  for (size_t i = 0; i < held.size(); ++i)
+    if ((int)i != ia && (int)i != ib) c->deferred.push_back(held[i]);
+  if (ia >= 0) claimed.ops.push_back(held[ia]);
+  if (ib >= 0) claimed.ops.push_back(held[ib]);
+  claimed.armed = true;
   if (!c->deferred.empty())
+    if (int rc = flush_deferred(c)) return rc;
+  memset(&tail.g, 0, sizeof tail.g);
+  DevOp d;
+  if (ia >= 0)
   {
-    int ia = -1, ib = -1;
-    if (c->dna_fast && !ed->gather)
-      for (size_t i = 0; i < c->deferred.size(); ++i)
-      {
-        const pllgpu_op_t &o = c->deferred[i];
-        if (o.parent_clv == ed->parent_clv && o.parent_scaler == ed->parent_scaler) ia = (int)i;
-        else if (!ed->child_is_tip && o.parent_clv == ed->child_clv && o.parent_scaler == ed->child_scaler) ib = (int)i;
-      }
-    if (ia < 0 && ib < 0)
-    {
-      if (int rc = flush_deferred(c)) return rc;
-    }
-    else
-    {
-      std::vector<pllgpu_op_t> held;
-      held.swap(c->deferred);
-      for (size_t i = 0; i < held.size(); ++i)
-        if ((int)i != ia && (int)i != ib) c->deferred.push_back(held[i]);
-      if (ia >= 0) claimed.ops.push_back(held[ia]);
-      if (ib >= 0) claimed.ops.push_back(held[ib]);
-      claimed.armed = true;
-      if (!c->deferred.empty())
-        if (int rc = flush_deferred(c)) return rc;
-      memset(&tail.g, 0, sizeof tail.g);
-      DevOp d;
-      if (ia >= 0)
-      {
-        if (int rc = resolve_op(c, held[ia], d)) return rc;
-        to_fop(d, tail.g.a);
-      }
-      if (ib >= 0)
-      {
-        if (int rc = resolve_op(c, held[ib], d)) return rc;
-        to_fop(d, tail.g.b);
-      }
-      tail.kp = ia >= 0 ? child_kind(held[ia]) : CK_INNER;
-      tail.kc = ib >= 0 ? child_kind(held[ib]) : (ed->child_is_tip ? CK_TIP : CK_INNER);
-      use_tail = true;
-    }
+    if (int rc = resolve_op(c, held[ia], d)) return rc;
+    to_fop(d, tail.g.a);
   }
-  DevEdge e;
+  if (ib >= 0)
+  {
+    if (int rc = resolve_op(c, held[ib], d)) return rc;
+    to_fop(d, tail.g.b);
+  }
+  tail.kp = ia >= 0 ? child_kind(held[ia]) : CK_INNER;
+  tail.kc = ib >= 0 ? child_kind(held[ib]) : (ed->child_is_tip ? CK_TIP : CK_INNER);
+  use_tail = true;
+  return 0;
+}
+
+// the edge as the kernels read it: its two ends in HBM
+static int build_edge(pllgpu_ctx *c, const pllgpu_edge_t *ed, DevEdge &e)
+{
   memset(&e, 0, sizeof e);
   if (!c->clv[ed->parent_clv].p) return fail(PLLGPU_EINVAL, "CLV %u was never computed or uploaded", ed->parent_clv);
   e.parent = c->clv[ed->parent_clv].p;
   if (ed->child_is_tip)
   {
-    if (ed->child_clv >= g.tips || !c->tipchars[ed->child_clv].p) return fail(PLLGPU_EINVAL, "tip %u has no codes on the device", ed->child_clv);
+    if (ed->child_clv >= c->geo.tips || !c->tipchars[ed->child_clv].p) return fail(PLLGPU_EINVAL, "tip %u has no codes on the device", ed->child_clv);
     e.ctip = c->tipchars[ed->child_clv].p;
   }
   else
@@ -2402,72 +2380,97 @@ extern "C" int pllgpu_edge_loglikelihood(pllgpu_ctx_t *c, const pllgpu_edge_t *e
     e.csid = c->ids[ed->child_clv] ? wide_map(c, ed->child_clv) : nullptr;
   }
   e.is_root = 0;
+  return 0;
+}
+
+// the two ends of the edge as chains: the held ones, a chain of no steps around an end that is in HBM
+static int build_chain_tail(pllgpu_ctx *c, const pllgpu_edge_t *ed, const DevEdge &e, int held_p, int held_c, ChainTailCall &ct)
+{
+  const ChainPlan &pl = *c->plan;
+  memset(&ct.hp, 0, sizeof ct.hp);
+  memset(&ct.hc, 0, sizeof ct.hc);
+  const unsigned clv_bytes = (unsigned)(clv_elems(c, pl.entries) * sizeof(double));
+  const unsigned sc_bytes = pl.entries * (c->gg.scale_mode == 2 ? 16u : 4u);
+  const unsigned any_end = pl.heads[0].first + pl.heads[0].nsteps; // a CS_END step: what a chain of no steps "fetches"
+  if (held_p >= 0)
+    ct.hp = pl.heads[held_p];
+  else
+  {
+    ct.hp.acc0.data = e.parent;
+    ct.hp.acc0.scaler = e.pscaler;
+    ct.hp.bacc.clv = clv_bytes;
+    ct.hp.bacc.aux = e.pscaler ? sc_bytes : 0u;
+    ct.hp.first = any_end;
+  }
+  if (held_c >= 0)
+    ct.hc = pl.heads[held_c];
+  else if (ed->child_is_tip)
+  {
+    ct.hc.acc0.data = e.ctip;
+    ct.hc.bacc.aux = (pl.entries + 3u) & ~3u;
+    ct.hc.acc_tip = 1u;
+    ct.hc.first = any_end;
+  }
+  else
+  {
+    ct.hc.acc0.data = e.child;
+    ct.hc.acc0.scaler = e.cscaler;
+    ct.hc.bacc.clv = clv_bytes;
+    ct.hc.bacc.aux = e.cscaler ? sc_bytes : 0u;
+    ct.hc.first = any_end;
+  }
+  const int vp = held_p >= 0 ? (int)pl.head_variant[held_p] : -1, vc = held_c >= 0 ? (int)pl.head_variant[held_c] : -1;
+  ct.variant = (unsigned)((vp < 0) ? vc : (vc < 0) ? vp : (vp == vc ? vp : 3));
+  ct.in_kernarg = pl.in_kernarg;
+  if (!ct.in_kernarg) return 0;
+  memset(&ct.pack, 0, sizeof ct.pack);
+  unsigned ns = 0;
+  ChainHead *hh[2] = {&ct.hp, &ct.hc};
+  const int held[2] = {held_p, held_c};
+  for (int k = 0; k < 2; ++k)
+  {
+    const unsigned nst = held[k] >= 0 ? hh[k]->nsteps : 0u;
+    if (ns + nst + 1 > (unsigned)kChainPackSteps) return fail(PLLGPU_ERUNTIME, "chain tail does not fit its descriptor pack");
+    if (held[k] >= 0)
+    {
+      memcpy(&ct.pack.loads[ns], &pl.loads[hh[k]->first], (nst + 1) * sizeof(ChainStepLoad));
+      memcpy(&ct.pack.ops[ns], &pl.sops[hh[k]->first], (nst + 1) * sizeof(ChainStepOp));
+    }
+    else
+      ct.pack.loads[ns].flags = CS_END;
+    hh[k]->first = ns;
+    ns += nst + 1;
+    ct.pack.heads[k] = *hh[k];
+  }
+  return 0;
+}
+
+extern "C" int pllgpu_edge_loglikelihood(pllgpu_ctx_t *c, const pllgpu_edge_t *ed, double *persite_host, double *lnl_out)
+{
+  CHECK_CTX_KEEP(c);
+  if (int rc = check_edge(c, ed, persite_host)) return rc;
+  struct SeqScope
+  {
+    pllgpu_ctx *c;
+    ~SeqScope() { c->seq_override = 0.0; }
+  } seq_scope_{c};
+  c->seq_override = ed->sequence;
+  ClaimedWork claimed(c);
+  TailCall tail;
+  bool use_tail = false;
+  int held_p = -1, held_c = -1;
+  if (int rc = claim_held_chains(c, ed, claimed, held_p, held_c)) return rc;
+  if (int rc = claim_held_ops(c, ed, claimed, tail, use_tail)) return rc;
+  DevEdge e;
+  if (int rc = build_edge(c, ed, e)) return rc;
+  int rc;
   if (held_p >= 0 || held_c >= 0)
   {
-    const ChainPlan &pl = *c->plan;
     ChainTailCall ct;
-    memset(&ct.hp, 0, sizeof ct.hp);
-    memset(&ct.hc, 0, sizeof ct.hc);
-    const unsigned clv_bytes = (unsigned)(clv_elems(c, pl.entries) * sizeof(double));
-    const unsigned sc_bytes = pl.entries * (c->gg.scale_mode == 2 ? 16u : 4u);
-    const unsigned any_end = pl.heads[0].first + pl.heads[0].nsteps; // a CS_END step: what a chain of no steps "fetches"
-    if (held_p >= 0)
-      ct.hp = pl.heads[held_p];
-    else
-    {
-      ct.hp.acc0.data = e.parent;
-      ct.hp.acc0.scaler = e.pscaler;
-      ct.hp.bacc.clv = clv_bytes;
-      ct.hp.bacc.aux = e.pscaler ? sc_bytes : 0u;
-      ct.hp.first = any_end;
-    }
-    if (held_c >= 0)
-      ct.hc = pl.heads[held_c];
-    else if (ed->child_is_tip)
-    {
-      ct.hc.acc0.data = e.ctip;
-      ct.hc.bacc.aux = (pl.entries + 3u) & ~3u;
-      ct.hc.acc_tip = 1u;
-      ct.hc.first = any_end;
-    }
-    else
-    {
-      ct.hc.acc0.data = e.child;
-      ct.hc.acc0.scaler = e.cscaler;
-      ct.hc.bacc.clv = clv_bytes;
-      ct.hc.bacc.aux = e.cscaler ? sc_bytes : 0u;
-      ct.hc.first = any_end;
-    }
-    const int vp = held_p >= 0 ? (int)pl.head_variant[held_p] : -1, vc = held_c >= 0 ? (int)pl.head_variant[held_c] : -1;
-    ct.variant = (unsigned)((vp < 0) ? vc : (vc < 0) ? vp : (vp == vc ? vp : 3));
-    ct.in_kernarg = pl.in_kernarg;
-    if (ct.in_kernarg)
-    {
-      memset(&ct.pack, 0, sizeof ct.pack);
-      unsigned ns = 0;
-      ChainHead *hh[2] = {&ct.hp, &ct.hc};
-      const int held[2] = {held_p, held_c};
-      for (int k = 0; k < 2; ++k)
-      {
-        const unsigned nst = held[k] >= 0 ? hh[k]->nsteps : 0u;
-        if (ns + nst + 1 > (unsigned)kChainPackSteps) return fail(PLLGPU_ERUNTIME, "chain tail does not fit its descriptor pack");
-        if (held[k] >= 0)
-        {
-          memcpy(&ct.pack.loads[ns], &pl.loads[hh[k]->first], (nst + 1) * sizeof(ChainStepLoad));
-          memcpy(&ct.pack.ops[ns], &pl.sops[hh[k]->first], (nst + 1) * sizeof(ChainStepOp));
-        }
-        else
-          ct.pack.loads[ns].flags = CS_END;
-        hh[k]->first = ns;
-        ns += nst + 1;
-        ct.pack.heads[k] = *hh[k];
-      }
-    }
-    const int rc = run_lnl(c, e, ed->child_is_tip != 0, false, ed->freqs_indices, persite_host, lnl_out, ed->device_result, nullptr, &ct);
-    if (rc == 0) claimed.disarm();
-    return rc;
+    if (int brc = build_chain_tail(c, ed, e, held_p, held_c, ct)) return brc;
+    rc = run_lnl(c, e, ed->child_is_tip != 0, false, ed->freqs_indices, persite_host, lnl_out, ed->device_result, nullptr, &ct);
   }
-  if (use_tail)
+  else if (use_tail)
   {
     // memory-side descriptors of the ends that were NOT held
     tail.g.p.left = e.parent;
@@ -2475,11 +2478,12 @@ extern "C" int pllgpu_edge_loglikelihood(pllgpu_ctx_t *c, const pllgpu_edge_t *e
     tail.g.p.right = e.child;
     tail.g.p.rtip = e.ctip;
     tail.g.p.rscaler = e.cscaler;
-    const int rc = run_lnl(c, e, ed->child_is_tip != 0, false, ed->freqs_indices, persite_host, lnl_out, ed->device_result, &tail);
-    if (rc == 0) claimed.disarm();
-    return rc;
+    rc = run_lnl(c, e, ed->child_is_tip != 0, false, ed->freqs_indices, persite_host, lnl_out, ed->device_result, &tail);
   }
-  return run_lnl(c, e, ed->child_is_tip != 0, ed->gather != 0, ed->freqs_indices, persite_host, lnl_out, ed->device_result);
+  else
+    return run_lnl(c, e, ed->child_is_tip != 0, ed->gather != 0, ed->freqs_indices, persite_host, lnl_out, ed->device_result);
+  if (rc == 0) claimed.disarm();
+  return rc;
 }
 
 extern "C" int pllgpu_root_loglikelihood(pllgpu_ctx_t *c, unsigned clv, int scaler, unsigned gather,
@@ -2928,7 +2932,7 @@ extern "C" int pllgpu_asc_terms(pllgpu_ctx_t *c, const pllgpu_edge_t *ed, int is
   a.first = g.sites;
   a.per_rate = g.per_rate_scalers ? 1 : 0;
   a.is_root = is_root;
-  const unsigned long long *tm = c->tipmap_set ? c->tipmap.p : nullptr;
+  const unsigned long long *tm = tipmap_ptr(c);
   hipLaunchKernelGGL(k_asc_terms, dim3(g.states), dim3(64), 0, c->stream, a, c->gg, tm);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));

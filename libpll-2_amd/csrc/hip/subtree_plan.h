@@ -11,7 +11,7 @@
 //     parent whose entries are the sites),
 //   * nothing earlier in the list reads or writes its outputs (war_level): the launch runs before every
 //     level.
-// Returns the ops claimed (role 4) through `role`; descriptors go to the context's device array, which is
+// Returns the ops claimed (Role::SubtreeMember) through `role`; descriptors go to the context's device array, which is
 // re-used as is when the same descriptors come again.
 struct SubOpRec // one qualifying op while the list is planned
 {
@@ -49,7 +49,7 @@ static void flatten_subtree(const std::vector<SubOpRec> &recs, int r, unsigned p
   }
 }
 
-static int plan_subtrees(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count, std::vector<int> &role, unsigned &nsub, unsigned &max_entries)
+static int plan_subtrees(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count, std::vector<Role> &role, unsigned &nsub, unsigned &max_entries)
 {
   nsub = 0;
   max_entries = 0;
@@ -69,7 +69,7 @@ static int plan_subtrees(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count, 
     const int pl = (o.flags & PLLGPU_OP_LEFT_TIP) ? -1 : producer[o.left_clv];
     const int pr = (o.flags & PLLGPU_OP_RIGHT_TIP) ? -1 : producer[o.right_clv];
     producer[o.parent_clv] = (int)i;
-    if (role[i] || !(o.flags & PLLGPU_OP_GATHER) || o.war_level >= 0 || o.parent_entries == 0) continue;
+    if (role[i] != Role::Plain || !(o.flags & PLLGPU_OP_GATHER) || o.war_level >= 0 || o.parent_entries == 0) continue;
     if ((o.flags & PLLGPU_OP_RIGHT_TIP) && !(o.flags & PLLGPU_OP_LEFT_TIP)) continue; // the level path reports it
     unsigned d = 0;
     bool ok = true;
@@ -100,7 +100,7 @@ static int plan_subtrees(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count, 
     item.flags = (rec.d.layout & kAosParent) ? kSubAos : 0u;
     flatten_subtree(recs, sub_of[i], 0, item);
     sub.push_back(item);
-    role[i] = 4;
+    role[i] = Role::SubtreeMember;
     max_entries = std::max(max_entries, o.parent_entries);
     // as grouped: the op's CLV and scaler go out, what comes in is one code per tip of the subtree and the maps
     bytes += (double)o.parent_entries * ((double)c->gg.S * c->gg.R * 8.0 + (o.parent_scaler >= 0 ? (c->geo.per_rate_scalers ? 16.0 : 4.0) : 0.0) +
