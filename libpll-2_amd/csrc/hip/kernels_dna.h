@@ -112,20 +112,183 @@ __device__ __forceinline__ void dna_matvec(double (&r)[4], cdouble_p pt_k, const
     r[i] = fma(pt_k[12 + i], x[3], fma(pt_k[8 + i], x[2], fma(pt_k[4 + i], x[1], pt_k[i] * x[0])));
 }
 
+// The parent's values of one rate category, v[i] = a[i] * b[i]; returns "all four are below the scaling threshold"
+// (src/core_partials.c:729-747: compared after the product, before any rescaling). Every 4x4 route forms its
+// products here - that is what makes the routes agree to the bit.
+__device__ __forceinline__ bool dna_product(double (&v)[4], const double (&a)[4], const double (&b)[4])
+{
+  bool small = true;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+  {
+    v[i] = a[i] * b[i];
+    small = small && (v[i] < PLLGPU_SCALE_THRESHOLD);
+  }
+  return small;
+}
+
 // row stride (doubles) of a wave's LDS transpose buffer: 18 keeps 16-byte accesses of 16 consecutive
 // lanes on distinct banks both when a lane writes its own entry and when it reads the dense order
 constexpr unsigned kAosRow = 18;
+
+// row k of a child: from the wave's cooperative fetch of an entry-contiguous CLV (c), else dense loads / the tip code
+template <bool TIP>
+__device__ __forceinline__ void dna_child_row(double (&x)[4], bool coop, const double (&c)[4][4], const double *__restrict__ base, unsigned k,
+                                              unsigned code)
+{
+  if (!TIP && coop)
+  {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x[j] = c[k][j];
+  }
+  else
+    dna_fetch<TIP>(x, base, k, code);
+}
+
+// scaling decision + scaler words of one op (src/core_partials.c:729-763): v is rescaled in place,
+// sc receives the op's scaler entry (per site in .x, or the four per-rate counts)
+__device__ __forceinline__ void dna_scale(double (&v)[4][4], const bool (&small)[4], int mode, uint4 lsc, uint4 rsc, uint4 &sc)
+{
+  sc = make_uint4(0, 0, 0, 0);
+  if (mode == 1)
+  {
+    const bool s = small[0] && small[1] && small[2] && small[3];
+    if (s)
+    {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[k][i] *= PLLGPU_SCALE_FACTOR;
+    }
+    sc.x = lsc.x + rsc.x + (s ? 1u : 0u);
+  }
+  else if (mode == 2)
+  {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (small[k])
+      {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[k][i] *= PLLGPU_SCALE_FACTOR;
+      }
+    sc.x = lsc.x + rsc.x + small[0];
+    sc.y = lsc.y + rsc.y + small[1];
+    sc.z = lsc.z + rsc.z + small[2];
+    sc.w = lsc.w + rsc.w + small[3];
+  }
+}
+
+__device__ __forceinline__ uint4 dna_load_scaler(const unsigned *s, unsigned n, int scale_mode)
+{
+  if (!s) return make_uint4(0, 0, 0, 0);
+  if (scale_mode == 2) return reinterpret_cast<const uint4 *>(s)[n];
+  return make_uint4(s[n], 0, 0, 0);
+}
+
+__device__ __forceinline__ void dna_store_scaler(unsigned *pscaler, unsigned n, int mode, uint4 sc)
+{
+  if (mode == 1) pscaler[n] = sc.x;
+  if (mode == 2) reinterpret_cast<uint4 *>(pscaler)[n] = sc;
+}
+
+// One op's tiled CLV and scaler entry. STREAM: the CLV of a fused child is not read again by this traversal (its
+// consumer took it from registers), so it goes out with non-temporal stores and leaves L2/MALL to the group parents
+// the next level reads. (For unfused launches non-temporal stores LOSE bandwidth, profiles/README.md - there the
+// next level does want the lines.)
+template <bool STREAM>
+__device__ __forceinline__ void dna_store(double *parent, unsigned *pscaler, size_t off, unsigned n, bool valid, int mode, const double (&v)[4][4],
+                                          uint4 sc)
+{
+  if (!valid) return;
+  dna_store_scaler(pscaler, n, mode, sc);
+  double *__restrict__ out = parent + off;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+    {
+      if (STREAM)
+        __builtin_nontemporal_store(v[k][i], out + (k * 4 + i) * 64);
+      else
+        out[(k * 4 + i) * 64] = v[k][i];
+    }
+}
+
+// a group parent is read by the next level: cacheable unless the level's output cannot stay in L2/MALL anyway
+// (stream: decided by the launcher from the bytes written, wave-uniform)
+__device__ __forceinline__ void dna_store_parent(bool stream, double *parent, unsigned *pscaler, size_t off, unsigned n, bool valid, int mode,
+                                                 const double (&v)[4][4], uint4 sc)
+{
+  if (stream)
+    dna_store<true>(parent, pscaler, off, n, valid, mode, v, sc);
+  else
+    dna_store<false>(parent, pscaler, off, n, valid, mode, v, sc);
+}
+
+// An entry-contiguous parent leaves through the wave's LDS buffer: a lane holds ITS entry's 128 bytes, but 64 lanes
+// writing 16 bytes each at a 128-byte stride reach only half the store bandwidth of dense 1 KB rows
+// (tools/store_probe.hip: 3.3 vs 6.6 TB/s)
+__device__ __forceinline__ void dna_store_aos(double *parent, double *mine, unsigned tile, unsigned lane, unsigned entries, const double (&v)[4][4])
+{
+  __builtin_amdgcn_wave_barrier(); // earlier reads of this buffer are done
+  dbl2 *w = reinterpret_cast<dbl2 *>(mine + lane * kAosRow);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+  {
+    dbl2 lo, hi;
+    lo.x = v[k][0];
+    lo.y = v[k][1];
+    hi.x = v[k][2];
+    hi.y = v[k][3];
+    w[2 * k] = lo;
+    w[2 * k + 1] = hi;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  dbl2 *o = reinterpret_cast<dbl2 *>(parent + (size_t)tile * 64 * 16);
+  const unsigned first = tile * 64u;
+#pragma unroll
+  for (int q = 0; q < 8; ++q)
+  {
+    const unsigned t = q * 64u + lane, ent = t >> 3, pair = t & 7u;
+    const dbl2 x = *reinterpret_cast<const dbl2 *>(mine + ent * kAosRow + pair * 2);
+    if (first + ent < entries) o[t] = x;
+  }
+}
+
+// The tile walk of the one-wave-per-tile kernels: workgroup bx, its wave, the t-th of the wave's tiles.
+struct DnaTile
+{
+  unsigned lane, wave, tile;
+  unsigned n;  // the lane's entry, clamped to the last one (lanes past the end compute, and store nothing)
+  bool valid;
+  size_t off;  // of the lane's entry in a tiled CLV
+};
+
+// false: the wave has no such tile (wave-uniform)
+__device__ __forceinline__ bool dna_tile(DnaTile &w, unsigned bx, unsigned tiles_per_wave, unsigned t, unsigned entries)
+{
+  w.lane = threadIdx.x & 63u;
+  w.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  w.tile = (bx * 4u + w.wave) * tiles_per_wave + t;
+  if (w.tile >= (entries + 63u) / 64u) return false;
+  const unsigned n0 = w.tile * 64u + w.lane;
+  w.valid = n0 < entries;
+  w.n = w.valid ? n0 : entries - 1;
+  w.off = (size_t)(w.n >> 6) * kDnaTile + (w.n & 63u);
+  return true;
+}
 
 #ifndef DNA_GATHER_WAVES
 #define DNA_GATHER_WAVES 3
 #endif
 
 // Tiles a wave of the update kernels walks one after the other. Rounds 1-3 sized it so that a launch had about 4096
-// workgroups (up to 8 tiles per wave at 1M sites); round 4 measured that against one tile per wave wherever more than
-// 4096 workgroups exist (tools/round4_calls/r4_tpw_exp.sh, same box): the seven-op groups at 400k sites 498 -> 468 us
-// (6.0 -> 6.4 TB/s), the plain inner x inner level 207 -> 195 us, the 1M-site site-repeats step 0.749 -> 0.711 ms, the
-// one-level groups unchanged. A second tile behind the first means a wave whose stores are in flight waits before it may
-// ask for the next tile's children; more, shorter waves hide that for each other. The kernels keep the loop.
+// workgroups (up to 8 tiles per wave at 1M sites); one tile per wave is faster wherever more than 4096 workgroups
+// exist (profiles/README.md, "Tiles per wave": the seven-op groups at 400k sites 498 -> 468 us, the plain
+// inner x inner level 207 -> 195 us, the 1M-site site-repeats step 0.749 -> 0.711 ms, the one-level groups unchanged).
+// A second tile behind the first means a wave whose stores are in flight waits before it may ask for the next tile's
+// children; more, shorter waves hide that for each other. The kernels keep the loop.
 constexpr unsigned kDnaTilesPerWave = 1;
 template <bool LTIP, bool RTIP, bool GATHER>
 __global__ __launch_bounds__(256, GATHER ? DNA_GATHER_WAVES : 1) void k_partials_dna(const OpPack pack, int scale_mode, unsigned tiles_per_wave, unsigned nx, unsigned ny,
@@ -133,28 +296,20 @@ __global__ __launch_bounds__(256, GATHER ? DNA_GATHER_WAVES : 1) void k_partials
 {
   unsigned bx, by;
   if (!xcd_block(nx, ny, xcd_order, bx, by)) return;
-  // entry-contiguous parents leave through LDS: a lane holds ITS entry's 128 bytes, but 64 lanes
-  // writing 16 bytes each at a 128-byte stride reach only half the store bandwidth of dense 1 KB
-  // rows (tools/store_probe.hip: 3.3 vs 6.6 TB/s)
-  __shared__ double transpose[GATHER ? 4 * 64 * kAosRow : 1];
+  __shared__ double transpose[GATHER ? 4 * 64 * kAosRow : 1]; // cooperative fetches and entry-contiguous parents (dna_store_aos)
   const DevOp &op = pack.ops[by];
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned ntiles = (op.entries + 63u) / 64u;
   const int mode = op.pscaler ? scale_mode : 0;
   cdouble_p lm = as_const(op.lmat), rm = as_const(op.rmat);
 
   for (unsigned t = 0; t < tiles_per_wave; ++t)
   {
-    const unsigned tile = (bx * 4u + wave) * tiles_per_wave + t;
-    if (tile >= ntiles) break; // wave-uniform
-    const unsigned n = tile * 64u + lane;
-    const bool valid = n < op.entries;
-    const unsigned nn = valid ? n : op.entries - 1;
-    unsigned le = nn, re = nn;
+    DnaTile w;
+    if (!dna_tile(w, bx, tiles_per_wave, t, op.entries)) break;
+    const unsigned lane = w.lane;
+    unsigned le = w.n, re = w.n;
     if (GATHER)
     {
-      gather_entries(op, nn, le, re);
+      gather_entries(op, w.n, le, re);
     }
     const unsigned lcode = LTIP ? op.ltip[le] : 0u;
     const unsigned rcode = RTIP ? op.rtip[re] : 0u;
@@ -162,7 +317,7 @@ __global__ __launch_bounds__(256, GATHER ? DNA_GATHER_WAVES : 1) void k_partials
     const bool laos = GATHER && (op.layout & kAosLeft), raos = GATHER && (op.layout & kAosRight), paos = GATHER && (op.layout & kAosParent);
     const double *__restrict__ lx = LTIP ? nullptr : laos ? op.left + (size_t)le * 16 : op.left + (size_t)(le >> 6) * kDnaTile + (le & 63u);
     const double *__restrict__ rx = RTIP ? nullptr : raos ? op.right + (size_t)re * 16 : op.right + (size_t)(re >> 6) * kDnaTile + (re & 63u);
-    double *__restrict__ out = op.parent + (size_t)tile * kDnaTile + lane;
+    double *mine = transpose + (GATHER ? (size_t)w.wave * 64 * kAosRow : 0);
 
     double v[4][4];
     bool small[4];
@@ -171,10 +326,10 @@ __global__ __launch_bounds__(256, GATHER ? DNA_GATHER_WAVES : 1) void k_partials
       // One child after the other: fetch (entry-contiguous: cooperatively, through LDS), contract, and only then
       // touch the second child. With both children's 16 values and both fetches' pieces alive at once the kernel
       // needed 246 registers = two waves per SIMD (the unified file: architected + accumulation registers), and a
-      // gather launch lives on the number of waves that wait for memory side by side. (Round 4 requested both children's
-      // pieces together, as k_partials_dna_gg now does for its producers: this kernel, with its tiled / entry-contiguous
-      // / tip branches alive side by side, spilled - 300 bytes of scratch at the 168 registers of three waves. Not kept.)
-      double *mine = transpose + (size_t)wave * 64 * kAosRow;
+      // gather launch lives on the number of waves that wait for memory side by side. Requesting both children's
+      // pieces together, as k_partials_dna_gg does for its producers, spilled here (300 bytes of scratch at the 168
+      // registers of three waves, with the tiled / entry-contiguous / tip branches alive side by side; measured in
+      // round 4, record not kept).
       double a[4][4];
       {
         double cl[4][4];
@@ -188,13 +343,7 @@ __global__ __launch_bounds__(256, GATHER ? DNA_GATHER_WAVES : 1) void k_partials
         for (int k = 0; k < 4; ++k)
         {
           double xl[4];
-          if (!LTIP && laos)
-          {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) xl[j] = cl[k][j];
-          }
-          else
-            dna_fetch<LTIP>(xl, lx, k, lcode);
+          dna_child_row<LTIP>(xl, laos, cl, lx, k, lcode);
           dna_matvec(a[k], lm + k * 16, xl);
         }
       }
@@ -211,21 +360,9 @@ __global__ __launch_bounds__(256, GATHER ? DNA_GATHER_WAVES : 1) void k_partials
         for (int k = 0; k < 4; ++k)
         {
           double xr[4], b[4];
-          if (!RTIP && raos)
-          {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) xr[j] = cr[k][j];
-          }
-          else
-            dna_fetch<RTIP>(xr, rx, k, rcode);
+          dna_child_row<RTIP>(xr, raos, cr, rx, k, rcode);
           dna_matvec(b, rm + k * 16, xr);
-          small[k] = true;
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-          {
-            v[k][i] = a[k][i] * b[i];
-            small[k] = small[k] && (v[k][i] < PLLGPU_SCALE_THRESHOLD);
-          }
+          small[k] = dna_product(v[k], a[k], b);
         }
       }
     }
@@ -239,15 +376,11 @@ __global__ __launch_bounds__(256, GATHER ? DNA_GATHER_WAVES : 1) void k_partials
         dna_fetch<RTIP>(xr, rx, k, rcode);
         dna_matvec(a, lm + k * 16, xl);
         dna_matvec(b, rm + k * 16, xr);
-        small[k] = true;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-        {
-          v[k][i] = a[i] * b[i];
-          small[k] = small[k] && (v[k][i] < PLLGPU_SCALE_THRESHOLD);
-        }
+        small[k] = dna_product(v[k], a, b);
       }
     }
+    // k_partials_dna keeps its own scaling blocks: with dna_load_scaler + dna_scale both children's scaler words are alive
+    // across the rescaling, <false, false, false> 88 -> 99 registers = five -> four waves per SIMD
     if (mode == 1)
     {
       const bool s = small[0] && small[1] && small[2] && small[3];
@@ -258,8 +391,8 @@ __global__ __launch_bounds__(256, GATHER ? DNA_GATHER_WAVES : 1) void k_partials
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[k][i] *= PLLGPU_SCALE_FACTOR;
       }
-      if (valid)
-        op.pscaler[n] = (op.lscaler ? op.lscaler[le] : 0u) + (op.rscaler ? op.rscaler[re] : 0u) + (s ? 1u : 0u);
+      if (w.valid)
+        op.pscaler[w.n] = (op.lscaler ? op.lscaler[le] : 0u) + (op.rscaler ? op.rscaler[re] : 0u) + (s ? 1u : 0u);
     }
     else if (mode == 2)
     {
@@ -282,46 +415,12 @@ __global__ __launch_bounds__(256, GATHER ? DNA_GATHER_WAVES : 1) void k_partials
           for (int i = 0; i < 4; ++i) v[k][i] *= PLLGPU_SCALE_FACTOR;
         }
       sc.x += small[0]; sc.y += small[1]; sc.z += small[2]; sc.w += small[3];
-      if (valid) reinterpret_cast<uint4 *>(op.pscaler)[n] = sc;
-    }
-    if (valid)
-    {
-      if (!paos)
-      {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) out[(k * 4 + i) * 64] = v[k][i];
-      }
+      if (w.valid) reinterpret_cast<uint4 *>(op.pscaler)[w.n] = sc;
     }
     if (GATHER && paos) // wave-uniform
-    {
-      double *mine = transpose + (size_t)wave * 64 * kAosRow;
-      __builtin_amdgcn_wave_barrier(); // the previous tile's reads of this buffer are done
-      dbl2 *w = reinterpret_cast<dbl2 *>(mine + lane * kAosRow);
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-      {
-        dbl2 lo, hi;
-        lo.x = v[k][0];
-        lo.y = v[k][1];
-        hi.x = v[k][2];
-        hi.y = v[k][3];
-        w[2 * k] = lo;
-        w[2 * k + 1] = hi;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      dbl2 *o = reinterpret_cast<dbl2 *>(op.parent + (size_t)tile * 64 * 16);
-      const unsigned first = tile * 64u;
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-      {
-        const unsigned t = q * 64u + lane, ent = t >> 3, pair = t & 7u;
-        const dbl2 x = *reinterpret_cast<const dbl2 *>(mine + ent * kAosRow + pair * 2);
-        if (first + ent < op.entries) o[t] = x;
-      }
-    }
+      dna_store_aos(op.parent, mine, w.tile, lane, op.entries, v);
+    else
+      dna_store<false>(op.parent, nullptr, (size_t)w.tile * kDnaTile + lane, w.n, w.valid, 0, v, make_uint4(0, 0, 0, 0));
   }
 }
 
@@ -332,23 +431,70 @@ __global__ __launch_bounds__(256, GATHER ? DNA_GATHER_WAVES : 1) void k_partials
 // (publish_block_sum: deterministic, single launch).
 // Arithmetic: src/core_likelihood.c:1388-1490 (ii), :470-578 (ti 4x4), :1077-1183 (repeats),
 // :163-207 (root).
+//
+// The site likelihood exists once, in three pieces, so that each edge kernel (k_edge_dna, k_edge_dna_tail, the chain
+// tail) keeps its own interleaving of loads and arithmetic and all of them agree to the bit:
+
+// (a) one rate's term: sum_i x[i] * pi[i] * tb[i], tb = P . (child end's values)
+__device__ __forceinline__ double dna_rate_term(const double (&x)[4], cdouble_p pi, const double (&tb)[4])
+{
+  return fma(x[3] * pi[3], tb[3], fma(x[2] * pi[2], tb[2], fma(x[1] * pi[1], tb[1], (x[0] * pi[0]) * tb[0])));
+}
+
+// (b) scaler counts of the two ends added up: per rate in rs with their minimum returned, or the one per-site count
+__device__ __forceinline__ unsigned dna_site_scalers(const DevEdge &e, uint4 p, uint4 c, unsigned (&rs)[4])
+{
+  rs[0] = rs[1] = rs[2] = rs[3] = 0u;
+  if (!e.per_rate) return p.x + c.x;
+  rs[0] = p.x + c.x;
+  rs[1] = p.y + c.y;
+  rs[2] = p.z + c.z;
+  rs[3] = p.w + c.w;
+  return min(min(rs[0], rs[1]), min(rs[2], rs[3]));
+}
+
+// (c) rate k's term folded into the site's sums: per-rate scaling difference, rate weight, invariant-sites mix
+// (inv: the site's invariant state or -1) ...
+__device__ __forceinline__ void dna_site_add(const DevEdge &e, int k, double tr, const unsigned (&rs)[4], unsigned scal, int inv, double &terma,
+                                             double &terminv)
+{
+  const unsigned fi = e.fidx[k];
+  if (e.per_rate)
+  {
+    const unsigned ex = min(rs[k] - scal, PLLGPU_RATE_MAXDIFF);
+    if (ex) tr *= minlh(ex);
+  }
+  const double pinv = e.prop_invar ? e.prop_invar[fi] : 0.0;
+  const double w = e.rate_weights[k];
+  if (pinv > 0.0)
+  {
+    terma += w * tr * (1.0 - pinv);
+    if (inv >= 0) terminv += w * e.freqs[(size_t)fi * 4 + inv] * pinv;
+  }
+  else
+    terma += tr * w;
+}
+
+// ... and after the fourth rate the weighted log-likelihood of (valid) site n
+__device__ __forceinline__ double dna_site_finish(const DevEdge &e, unsigned n, double terma, double terminv, unsigned scal, int is_root)
+{
+  const double site = finish_site(terma, terminv, scal, is_root) * (double)e.pattern_weights[n];
+  if (e.persite) e.persite[n] = site;
+  return site;
+}
+
 template <bool CTIP, bool GATHER>
 __global__ __launch_bounds__(256) void k_edge_dna(const DevEdge e, unsigned tiles_per_wave)
 {
   __shared__ double transpose[GATHER ? 4 * 64 * kAosRow : 1]; // entry-contiguous ends: cooperative fetch (dna_coop_issue)
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned ntiles = (e.sites + 63u) / 64u;
   cdouble_p pm = as_const(e.mat);
   double acc = 0.0;
 
   for (unsigned t = 0; t < tiles_per_wave; ++t)
   {
-    const unsigned tile = (blockIdx.x * 4u + wave) * tiles_per_wave + t;
-    if (tile >= ntiles) break;
-    const unsigned n = tile * 64u + lane;
-    const bool valid = n < e.sites;
-    const unsigned nn = valid ? n : e.sites - 1;
+    DnaTile w;
+    if (!dna_tile(w, blockIdx.x, tiles_per_wave, t, e.sites)) break;
+    const unsigned lane = w.lane, nn = w.n;
     unsigned pe = nn, ce = nn;
     if (GATHER)
     {
@@ -361,23 +507,16 @@ __global__ __launch_bounds__(256) void k_edge_dna(const DevEdge e, unsigned tile
     const double *__restrict__ cx = (CTIP || e.is_root) ? nullptr
                                     : caos ? e.child + (size_t)ce * 16 : e.child + (size_t)(ce >> 6) * kDnaTile + (ce & 63u);
 
-    unsigned rs[4] = {0, 0, 0, 0}, scal;
-    if (e.per_rate)
-    {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        rs[k] = (e.pscaler ? e.pscaler[(size_t)pe * 4 + k] : 0u) + (e.cscaler ? e.cscaler[(size_t)ce * 4 + k] : 0u);
-      scal = min(min(rs[0], rs[1]), min(rs[2], rs[3]));
-    }
-    else
-      scal = (e.pscaler ? e.pscaler[pe] : 0u) + (e.cscaler ? e.cscaler[ce] : 0u);
+    unsigned rs[4];
+    const int smode = e.per_rate ? 2 : 1;
+    const unsigned scal = dna_site_scalers(e, dna_load_scaler(e.pscaler, pe, smode), dna_load_scaler(e.cscaler, ce, smode), rs);
     const int inv = e.invariant ? e.invariant[nn] : -1;
 
     double cp[4][4], cc[4][4];
     if (GATHER)
     {
       DnaCoop qp, qc;
-      double *mine = transpose + (size_t)wave * 64 * kAosRow;
+      double *mine = transpose + (size_t)w.wave * 64 * kAosRow;
       const bool cfetch = !CTIP && !e.is_root && caos;
       if (paos) dna_coop_issue(qp, e.parent, pe, lane, (e.layout & kStreamLeft) != 0);
       if (cfetch) dna_coop_issue(qc, e.child, ce, lane, (e.layout & kStreamRight) != 0);
@@ -389,13 +528,7 @@ __global__ __launch_bounds__(256) void k_edge_dna(const DevEdge e, unsigned tile
     for (int k = 0; k < 4; ++k)
     {
       double xp[4], xc[4], tb[4];
-      if (GATHER && paos)
-      {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xp[j] = cp[k][j];
-      }
-      else
-        dna_fetch<false>(xp, px, k, 0u);
+      dna_child_row<false>(xp, paos, cp, px, k, 0u);
       if (e.is_root)
       {
 #pragma unroll
@@ -403,39 +536,12 @@ __global__ __launch_bounds__(256) void k_edge_dna(const DevEdge e, unsigned tile
       }
       else
       {
-        if (GATHER && !CTIP && caos)
-        {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) xc[j] = cc[k][j];
-        }
-        else
-          dna_fetch<CTIP>(xc, cx, k, ccode);
+        dna_child_row<CTIP>(xc, caos, cc, cx, k, ccode);
         dna_matvec(tb, pm + k * 16, xc);
       }
-      const unsigned fi = e.fidx[k];
-      cdouble_p pi = as_const(e.freqs) + (size_t)fi * 4;
-      double tr = fma(xp[3] * pi[3], tb[3], fma(xp[2] * pi[2], tb[2], fma(xp[1] * pi[1], tb[1], (xp[0] * pi[0]) * tb[0])));
-      if (e.per_rate)
-      {
-        const unsigned ex = min(rs[k] - scal, PLLGPU_RATE_MAXDIFF);
-        if (ex) tr *= minlh(ex);
-      }
-      const double pinv = e.prop_invar ? e.prop_invar[fi] : 0.0;
-      const double w = e.rate_weights[k];
-      if (pinv > 0.0)
-      {
-        terma += w * tr * (1.0 - pinv);
-        if (inv >= 0) terminv += w * e.freqs[(size_t)fi * 4 + inv] * pinv;
-      }
-      else
-        terma += tr * w;
+      dna_site_add(e, k, dna_rate_term(xp, as_const(e.freqs) + (size_t)e.fidx[k] * 4, tb), rs, scal, inv, terma, terminv);
     }
-    if (valid)
-    {
-      const double site = finish_site(terma, terminv, scal, e.is_root) * (double)e.pattern_weights[n];
-      if (e.persite) e.persite[n] = site;
-      acc += site;
-    }
+    if (w.valid) acc += dna_site_finish(e, nn, terma, terminv, scal, e.is_root);
   }
   publish_block_sum(e, wave_sum(acc), 4u);
 }
@@ -482,67 +588,30 @@ struct FusePack
   FGroup g[kMaxGroups];
 };
 
-// scaling decision + scaler words of one op (src/core_partials.c:729-763): v is rescaled in place,
-// sc receives the op's scaler entry (per site in .x, or the four per-rate counts)
-__device__ __forceinline__ void dna_scale(double (&v)[4][4], const bool (&small)[4], int mode, uint4 lsc, uint4 rsc, uint4 &sc)
+// an inner x inner op from two register-resident children (values + scaler words); OP: FOp or TOp
+template <class OP>
+__device__ __forceinline__ void dna_combine(const OP &op, int scale_mode, const double (&va)[4][4], uint4 sca, const double (&vb)[4][4], uint4 scb,
+                                            double (&v)[4][4], uint4 &sc, int &mode)
 {
-  sc = make_uint4(0, 0, 0, 0);
-  if (mode == 1)
-  {
-    const bool s = small[0] && small[1] && small[2] && small[3];
-    if (s)
-    {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[k][i] *= PLLGPU_SCALE_FACTOR;
-    }
-    sc.x = lsc.x + rsc.x + (s ? 1u : 0u);
-  }
-  else if (mode == 2)
-  {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (small[k])
-      {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[k][i] *= PLLGPU_SCALE_FACTOR;
-      }
-    sc.x = lsc.x + rsc.x + small[0];
-    sc.y = lsc.y + rsc.y + small[1];
-    sc.z = lsc.z + rsc.z + small[2];
-    sc.w = lsc.w + rsc.w + small[3];
-  }
-}
-
-__device__ __forceinline__ uint4 dna_load_scaler(const unsigned *s, unsigned n, int scale_mode)
-{
-  if (!s) return make_uint4(0, 0, 0, 0);
-  if (scale_mode == 2) return reinterpret_cast<const uint4 *>(s)[n];
-  return make_uint4(s[n], 0, 0, 0);
-}
-
-// STREAM: the CLV of a fused child is not read again by this traversal (its consumer took it from
-// registers), so it goes out with non-temporal stores and leaves L2/MALL to the group parents the
-// next level reads. (For unfused launches non-temporal stores LOSE bandwidth, profiles/README.md -
-// there the next level does want the lines.)
-template <bool STREAM>
-__device__ __forceinline__ void dna_store(const FOp &op, size_t off, unsigned n, bool valid, int mode, const double (&v)[4][4], uint4 sc)
-{
-  if (!valid) return;
-  if (mode == 1) op.pscaler[n] = sc.x;
-  if (mode == 2) reinterpret_cast<uint4 *>(op.pscaler)[n] = sc;
-  double *__restrict__ out = op.parent + off;
+  mode = op.pscaler ? scale_mode : 0;
+  cdouble_p lm = as_const(op.lmat), rm = as_const(op.rmat);
+  bool small[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k)
+  {
+    double a[4], b[4];
+    dna_matvec(a, lm + k * 16, va[k]);
+    dna_matvec(b, rm + k * 16, vb[k]);
+    small[k] = dna_product(v[k], a, b);
+  }
+  dna_scale(v, small, mode, sca, scb, sc);
+}
+
+// the 0/1 rows of a tip child (the same for every rate)
+__device__ __forceinline__ void dna_tip_rows(double (&x)[4][4], unsigned code)
+{
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-    {
-      if (STREAM)
-        __builtin_nontemporal_store(v[k][i], out + (k * 4 + i) * 64);
-      else
-        out[(k * 4 + i) * 64] = v[k][i];
-    }
+  for (int k = 0; k < 4; ++k) dna_fetch<true>(x[k], nullptr, k, code);
 }
 
 // A child of the group parent in three steps, so that the kernel can put the NEXT loads in front of
@@ -628,28 +697,31 @@ __device__ __forceinline__ void dna_child_compute(const FOp &pop, bool left_side
   else
   {
     constexpr bool LT = (KIND == CK_FTT || KIND == CK_FTI), RT = (KIND == CK_FTT);
-    const int mode = cop.pscaler ? scale_mode : 0;
-    cdouble_p lm = as_const(cop.lmat), rm = as_const(cop.rmat);
-    bool small[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
+    if (KIND == CK_FII)
     {
-      double xl[4], xr[4], a[4], b[4];
-      if (LT) dna_fetch<true>(xl, nullptr, k, raw.lcode);
-      if (RT) dna_fetch<true>(xr, nullptr, k, raw.rcode);
-      dna_matvec(a, lm + k * 16, LT ? xl : raw.xl[k]);
-      dna_matvec(b, rm + k * 16, RT ? xr : raw.xr[k]);
-      small[k] = true;
+      // CK_FII keeps its own loop: through dna_combine (scaler words loaded ahead of the arithmetic) k_partials_dna_fused<., 4>
+      // takes 135 registers instead of 128 = four -> three waves per SIMD
+      const int mode = cop.pscaler ? scale_mode : 0;
+      cdouble_p lm = as_const(cop.lmat), rm = as_const(cop.rmat);
+      bool small[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+      for (int k = 0; k < 4; ++k)
       {
-        v[k][i] = a[i] * b[i];
-        small[k] = small[k] && (v[k][i] < PLLGPU_SCALE_THRESHOLD);
+        double a[4], b[4];
+        dna_matvec(a, lm + k * 16, raw.xl[k]);
+        dna_matvec(b, rm + k * 16, raw.xr[k]);
+        small[k] = dna_product(v[k], a, b);
       }
+      dna_scale(v, small, mode, dna_load_scaler(cop.lscaler, n, scale_mode), dna_load_scaler(cop.rscaler, n, scale_mode), sc);
+      return;
     }
+    double tl[4][4], tr[4][4];
+    if (LT) dna_tip_rows(tl, raw.lcode);
+    if (RT) dna_tip_rows(tr, raw.rcode);
     const uint4 lsc = dna_load_scaler(LT ? nullptr : cop.lscaler, n, scale_mode);
     const uint4 rsc = dna_load_scaler(RT ? nullptr : cop.rscaler, n, scale_mode);
-    dna_scale(v, small, mode, lsc, rsc, sc);
+    int mode;
+    dna_combine(cop, scale_mode, LT ? tl : raw.xl, lsc, RT ? tr : raw.xr, rsc, v, sc, mode);
   }
 }
 
@@ -657,7 +729,7 @@ template <int KIND>
 __device__ __forceinline__ void dna_child_store(const FOp &cop, size_t off, unsigned n, bool valid, int scale_mode,
                                                 const double (&v)[4][4], uint4 sc)
 {
-  if (KIND >= CK_FTT) dna_store<true>(cop, off, n, valid, cop.pscaler ? scale_mode : 0, v, sc);
+  if (KIND >= CK_FTT) dna_store<true>(cop.parent, cop.pscaler, off, n, valid, cop.pscaler ? scale_mode : 0, v, sc);
 }
 
 template <int LK, int RK>
@@ -667,11 +739,10 @@ __global__ __launch_bounds__(256) void k_partials_dna_fused(const FusePack pack,
   unsigned bx, by;
   if (!xcd_block(nx, ny, xcd_order, bx, by)) return;
   const FGroup &g = pack.g[by];
+  // the tile walk stays written out here: through dna_tile, <2, 4> and <3, 4> take 129 registers instead of 128 = four -> three waves per SIMD
   const unsigned lane = threadIdx.x & 63u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const unsigned ntiles = (entries + 63u) / 64u;
-  const int mode = g.p.pscaler ? scale_mode : 0;
-  cdouble_p lm = as_const(g.p.lmat), rm = as_const(g.p.rmat);
 
   for (unsigned t = 0; t < tiles_per_wave; ++t)
   {
@@ -684,6 +755,7 @@ __global__ __launch_bounds__(256) void k_partials_dna_fused(const FusePack pack,
 
     double va[4][4], vb[4][4], v[4][4];
     uint4 sca, scb, sc;
+    int mode;
     {
       DnaRaw ra, rb;
       dna_child_load<LK>(g.p, true, g.a, off, n, ra);
@@ -694,28 +766,8 @@ __global__ __launch_bounds__(256) void k_partials_dna_fused(const FusePack pack,
       dna_child_compute<RK>(g.p, false, g.b, n, scale_mode, rb, vb, scb);
       dna_child_store<RK>(g.b, off, n, valid, scale_mode, vb, scb);
     }
-    bool small[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-    {
-      double a[4], b[4];
-      dna_matvec(a, lm + k * 16, va[k]);
-      dna_matvec(b, rm + k * 16, vb[k]);
-      small[k] = true;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-      {
-        v[k][i] = a[i] * b[i];
-        small[k] = small[k] && (v[k][i] < PLLGPU_SCALE_THRESHOLD);
-      }
-    }
-    dna_scale(v, small, mode, sca, scb, sc);
-    // the group parent is read by the next level: keep it cacheable unless the level's output cannot
-    // stay in L2/MALL anyway (stream_parent: decided by the launcher from the bytes written)
-    if (stream_parent)
-      dna_store<true>(g.p, off, n, valid, mode, v, sc);
-    else
-      dna_store<false>(g.p, off, n, valid, mode, v, sc);
+    dna_combine(g.p, scale_mode, va, sca, vb, scb, v, sc, mode);
+    dna_store_parent(stream_parent != 0, g.p.parent, g.p.pscaler, off, n, valid, mode, v, sc);
   }
 }
 
@@ -742,11 +794,10 @@ struct GGPack
 };
 
 // one gathering inner x inner op for the lane's site: its 16 values, scaled, and its scaler words. The caller has
-// looked the child entries (le, re) up already and - `pl`, `pr` - requested BOTH children's entries: round 2 fetched one
-// child after the other (four dependent round trips per group and tile behind four dependent map look-ups) to stay at
-// three waves per SIMD; with the look-ups of both producers first and a producer's two fetches in flight together a
-// tile waits three times instead of eight and the kernel still fits three waves (round 4: the shard's launch 57 -> see
-// profiles/README.md).
+// looked the child entries (le, re) up already and - `pl`, `pr` - requested BOTH children's entries: with the
+// look-ups of both producers first and a producer's two fetches in flight together a tile waits three times instead of
+// eight (one child after the other: four dependent round trips behind four dependent look-ups) and the kernel still fits
+// three waves per SIMD (profiles/README.md, "Groups over gathering producers": the shard's launch 57 -> 48.5 us).
 __device__ __forceinline__ void dna_gather_op_finish(const DevOp &op, unsigned le, unsigned re, const DnaCoop &pl, const DnaCoop &pr, unsigned lane,
                                                      double *mine, int scale_mode, double (&v)[4][4], uint4 &sc)
 {
@@ -769,13 +820,7 @@ __device__ __forceinline__ void dna_gather_op_finish(const DevOp &op, unsigned l
     {
       double b[4];
       dna_matvec(b, rm + k * 16, cr[k]);
-      small[k] = true;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-      {
-        v[k][i] = a[k][i] * b[i];
-        small[k] = small[k] && (v[k][i] < PLLGPU_SCALE_THRESHOLD);
-      }
+      small[k] = dna_product(v[k], a[k], b);
     }
   }
   dna_scale(v, small, mode, lsc, rsc, sc);
@@ -791,39 +836,18 @@ __global__ __launch_bounds__(256, DNA_GG_WAVES) void k_partials_dna_gg(const GGP
   unsigned bx, by;
   if (!xcd_block(nx, ny, xcd_order, bx, by)) return;
   const GGroup &g = pack.g[by];
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned ntiles = (entries + 63u) / 64u;
-  const int mode = g.p.pscaler ? scale_mode : 0;
-  cdouble_p lm = as_const(g.p.lmat), rm = as_const(g.p.rmat);
-  double *mine = transpose + (size_t)wave * 64 * kAosRow;
 
   for (unsigned t = 0; t < tiles_per_wave; ++t)
   {
-    const unsigned tile = (bx * 4u + wave) * tiles_per_wave + t;
-    if (tile >= ntiles) break; // wave-uniform
-    const unsigned n0 = tile * 64u + lane;
-    const bool valid = n0 < entries;
-    const unsigned n = valid ? n0 : entries - 1;
-    const size_t off = (size_t)tile * kDnaTile + lane;
-    auto put = [&](double *parent, unsigned *pscaler, int m, const double (&x)[4][4], uint4 sc, bool stream) {
-      if (!valid) return;
-      if (m == 1) pscaler[n] = sc.x;
-      if (m == 2) reinterpret_cast<uint4 *>(pscaler)[n] = sc;
-      double *__restrict__ out = parent + off;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-        {
-          if (stream)
-            __builtin_nontemporal_store(x[k][i], out + (k * 4 + i) * 64);
-          else
-            out[(k * 4 + i) * 64] = x[k][i];
-        }
-    };
+    DnaTile w;
+    if (!dna_tile(w, bx, tiles_per_wave, t, entries)) break;
+    const unsigned lane = w.lane, n = w.n;
+    const bool valid = w.valid;
+    const size_t off = w.off;
+    double *mine = transpose + (size_t)w.wave * 64 * kAosRow;
     double va[4][4], v[4][4];
     uint4 sca, scb, sc;
+    int mode;
     // the four look-ups first (independent loads), then producer A's two children together
     unsigned ale = n, are = n, ble = n, bre = n;
     gather_entries(g.a, n, ale, are);
@@ -834,40 +858,23 @@ __global__ __launch_bounds__(256, DNA_GG_WAVES) void k_partials_dna_gg(const GGP
       dna_coop_issue(ar, g.a.right, are, lane, (g.a.layout & kStreamRight) != 0);
       dna_gather_op_finish(g.a, ale, are, al, ar, lane, mine, scale_mode, va, sca);
     }
-    bool small[4];
     {
       double vb[4][4];
       DnaCoop bl, br;
       // producer B's children are requested before A's CLV leaves: the stores and the loads overlap
       dna_coop_issue(bl, g.b.left, ble, lane, (g.b.layout & kStreamLeft) != 0);
       dna_coop_issue(br, g.b.right, bre, lane, (g.b.layout & kStreamRight) != 0);
-      put(g.a.parent, g.a.pscaler, g.a.pscaler ? scale_mode : 0, va, sca, true);
+      dna_store<true>(g.a.parent, g.a.pscaler, off, n, valid, g.a.pscaler ? scale_mode : 0, va, sca);
       dna_gather_op_finish(g.b, ble, bre, bl, br, lane, mine, scale_mode, vb, scb);
-      put(g.b.parent, g.b.pscaler, g.b.pscaler ? scale_mode : 0, vb, scb, true);
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-      {
-        double a[4], b[4];
-        dna_matvec(a, lm + k * 16, va[k]);
-        dna_matvec(b, rm + k * 16, vb[k]);
-        small[k] = true;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-        {
-          v[k][i] = a[i] * b[i];
-          small[k] = small[k] && (v[k][i] < PLLGPU_SCALE_THRESHOLD);
-        }
-      }
+      dna_store<true>(g.b.parent, g.b.pscaler, off, n, valid, g.b.pscaler ? scale_mode : 0, vb, scb);
+      dna_combine(g.p, scale_mode, va, sca, vb, scb, v, sc, mode);
     }
-    dna_scale(v, small, mode, sca, scb, sc);
-    put(g.p.parent, g.p.pscaler, mode, v, sc, stream_parent != 0);
+    dna_store_parent(stream_parent != 0, g.p.parent, g.p.pscaler, off, n, valid, mode, v, sc);
   }
 }
 
-// (Round 4 also built this group with a PAIR of waves per tile, as k_partials_dna_cc16 has it - one wave gathers and forms
-// producer A, the other B, B's values cross through the wave's transpose buffer: 107 registers, four waves per SIMD, half
-// the waits per wave. Same box, alternating: slowest shards 0.1088-0.1125 ms against 0.1077-0.1089 with one wave per
-// tile, the 1M-site step 0.741 against 0.735 ms. Occupancy is not what a shard's launch waits for; removed.)
+// (A pair of waves per tile, as k_partials_dna_cc16 has it, reached four waves per SIMD and was no faster: occupancy is
+// not what a shard's launch waits for. Measured in round 4, record not kept.)
 // ------------------------------------------------------------------------------------------------
 // Two levels of producers: a child of the group parent P may be an inner x inner op A whose own
 // children are both CHERRIES (tip x tip ops) of the level below - kind CK_FCC. The four tip codes are
@@ -900,58 +907,15 @@ struct CCPack
   CCGroup g[kMaxCCGroups];
 };
 
-// a cherry from its two tip codes: the arithmetic of dna_child_compute<CK_FTT>, stored streaming
+// a cherry from its two tip codes (what dna_child_compute<CK_FTT> forms), stored streaming
 __device__ __forceinline__ void dna_cherry(const TOp &t, size_t off, unsigned n, bool valid, int scale_mode, double (&v)[4][4], uint4 &sc)
 {
-  const unsigned lcode = t.ltip[n], rcode = t.rtip[n];
-  const int mode = t.pscaler ? scale_mode : 0;
-  cdouble_p lm = as_const(t.lmat), rm = as_const(t.rmat);
-  bool small[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-  {
-    double xl[4], xr[4], a[4], b[4];
-    dna_fetch<true>(xl, nullptr, k, lcode);
-    dna_fetch<true>(xr, nullptr, k, rcode);
-    dna_matvec(a, lm + k * 16, xl);
-    dna_matvec(b, rm + k * 16, xr);
-    small[k] = true;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-    {
-      v[k][i] = a[i] * b[i];
-      small[k] = small[k] && (v[k][i] < PLLGPU_SCALE_THRESHOLD);
-    }
-  }
-  dna_scale(v, small, mode, make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), sc);
-  FOp st = {};
-  st.parent = t.parent;
-  st.pscaler = t.pscaler;
-  dna_store<true>(st, off, n, valid, mode, v, sc);
-}
-
-// an inner x inner op from two register-resident children (values + scaler words)
-__device__ __forceinline__ void dna_combine(const FOp &op, int scale_mode, const double (&va)[4][4], uint4 sca, const double (&vb)[4][4],
-                                            uint4 scb, double (&v)[4][4], uint4 &sc, int &mode)
-{
-  mode = op.pscaler ? scale_mode : 0;
-  cdouble_p lm = as_const(op.lmat), rm = as_const(op.rmat);
-  bool small[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-  {
-    double a[4], b[4];
-    dna_matvec(a, lm + k * 16, va[k]);
-    dna_matvec(b, rm + k * 16, vb[k]);
-    small[k] = true;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-    {
-      v[k][i] = a[i] * b[i];
-      small[k] = small[k] && (v[k][i] < PLLGPU_SCALE_THRESHOLD);
-    }
-  }
-  dna_scale(v, small, mode, sca, scb, sc);
+  double xl[4][4], xr[4][4];
+  dna_tip_rows(xl, t.ltip[n]);
+  dna_tip_rows(xr, t.rtip[n]);
+  int mode;
+  dna_combine(t, scale_mode, xl, make_uint4(0, 0, 0, 0), xr, make_uint4(0, 0, 0, 0), v, sc, mode);
+  dna_store<true>(t.parent, t.pscaler, off, n, valid, mode, v, sc);
 }
 
 // one child of the group parent: CK_INNER / CK_TIP from HBM, or CK_FCC formed here
@@ -967,7 +931,7 @@ __device__ __forceinline__ void dna_cc_child(const FOp &pop, bool left_side, con
     dna_cherry(x, off, n, valid, scale_mode, vx, scx);
     dna_cherry(y, off, n, valid, scale_mode, vy, scy);
     dna_combine(cop, scale_mode, vx, scx, vy, scy, v, sc, mode);
-    dna_store<true>(cop, off, n, valid, mode, v, sc);
+    dna_store<true>(cop.parent, cop.pscaler, off, n, valid, mode, v, sc);
   }
   else
   {
@@ -984,32 +948,22 @@ __global__ __launch_bounds__(256) void k_partials_dna_cc(const CCPack pack, unsi
   unsigned bx, by;
   if (!xcd_block(nx, ny, xcd_order, bx, by)) return; // a store-bound launch: every XCD on its own run of tiles (kernels_common.h)
   const CCGroup &g = pack.g[by];
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned ntiles = (entries + 63u) / 64u;
   for (unsigned t = 0; t < tiles_per_wave; ++t)
   {
-    const unsigned tile = (bx * 4u + wave) * tiles_per_wave + t;
-    if (tile >= ntiles) break; // wave-uniform
-    const unsigned n0 = tile * 64u + lane;
-    const bool valid = n0 < entries;
-    const unsigned n = valid ? n0 : entries - 1;
-    const size_t off = (size_t)(n >> 6) * kDnaTile + (n & 63u);
+    DnaTile w;
+    if (!dna_tile(w, bx, tiles_per_wave, t, entries)) break;
     double va[4][4], vb[4][4], v[4][4];
     uint4 sca, scb, sc;
     int mode;
-    dna_cc_child<LK>(g.p, true, g.a, g.aa, g.ab, off, n, valid, scale_mode, va, sca);
-    dna_cc_child<RK>(g.p, false, g.b, g.ba, g.bb, off, n, valid, scale_mode, vb, scb);
+    dna_cc_child<LK>(g.p, true, g.a, g.aa, g.ab, w.off, w.n, w.valid, scale_mode, va, sca);
+    dna_cc_child<RK>(g.p, false, g.b, g.ba, g.bb, w.off, w.n, w.valid, scale_mode, vb, scb);
     dna_combine(g.p, scale_mode, va, sca, vb, scb, v, sc, mode);
-    if (stream_parent)
-      dna_store<true>(g.p, off, n, valid, mode, v, sc);
-    else
-      dna_store<false>(g.p, off, n, valid, mode, v, sc);
+    dna_store_parent(stream_parent != 0, g.p.parent, g.p.pscaler, w.off, w.n, w.valid, mode, v, sc);
   }
 }
 
 // ------------------------------------------------------------------------------------------------
-// Three levels of producers (round 4): a parent whose two children are the parents of COMPLETE 8-tip subtrees -
+// Three levels of producers: a parent whose two children are the parents of COMPLETE 8-tip subtrees -
 // (CK_FCC, CK_FCC) groups - is evaluated with both of them: a complete 16-tip subtree, fifteen ops per site from
 // sixteen code bytes, every CLV and scaler stored as always. The left subtree's top CLV waits in registers while the
 // right subtree is formed (four CLVs live instead of three). What it saves over two seven-op groups and a later step:
@@ -1040,7 +994,7 @@ __device__ __forceinline__ void dna_cc8(const CCGroup &g, size_t off, unsigned n
   dna_cc_child<CK_FCC>(g.p, true, g.a, g.aa, g.ab, off, n, valid, scale_mode, va, sca);
   dna_cc_child<CK_FCC>(g.p, false, g.b, g.ba, g.bb, off, n, valid, scale_mode, vb, scb);
   dna_combine(g.p, scale_mode, va, sca, vb, scb, v, sc, mode);
-  dna_store<true>(g.p, off, n, valid, mode, v, sc);
+  dna_store<true>(g.p.parent, g.p.pscaler, off, n, valid, mode, v, sc);
 }
 
 // Work split: a PAIR of waves per 64-site tile - one forms the left 8-tip subtree, the other the right one, the right
@@ -1089,10 +1043,7 @@ __global__ __launch_bounds__(256) void k_partials_dna_cc16(const CC16Pack pack, 
   uint4 sc;
   int mode;
   dna_combine(g.p, scale_mode, v8, sc8, vb, scb, v, sc, mode);
-  if (stream_parent)
-    dna_store<true>(g.p, off, n, valid, mode, v, sc);
-  else
-    dna_store<false>(g.p, off, n, valid, mode, v, sc);
+  dna_store_parent(stream_parent != 0, g.p.parent, g.p.pscaler, off, n, valid, mode, v, sc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1141,11 +1092,9 @@ typedef const SubItem __attribute__((address_space(4))) *csubitem_p;
 // SIMD - 46 us for C4's shard, nearly all of it waiting for the scalar loads of the next matrix. A quarter of
 // that per wave and four times the waves hide it. What the rates of an entry share is the per-site scaling
 // decision (SM 1): one ballot exchange through LDS per LEVEL of the subtree (three barriers).
-// (Round 3 tried the matrices through LDS instead of the scalar path - every op's pair requested at once with vector
-// loads by lanes 0-31 of the rate's wave, coefficients read back as broadcasts: a shard's launch 27 -> 35 us. The
-// scalar path is not what a workgroup's 12 us are made of; removed. Nor is the launch about workgroup count or scalar-cache
-// locality: two tiles per workgroup 27 -> 30 us, the tiles dealt to the eight XCDs in contiguous eighths 27.0 -> 27.7 us.
-// Counters: 49 scalar loads per wave, 36 % of them missing the scalar cache, waves waiting 53 % of their cycles.)
+// The matrices stay on the scalar path: through LDS (vector loads, broadcast reads) a shard's launch took 35 us instead
+// of 27. Nor is the launch about workgroup count or scalar-cache locality: two tiles per workgroup 27 -> 30 us, the tiles
+// dealt to the eight XCDs in contiguous eighths 27.0 -> 27.7 us (measured in round 3, record not kept).
 template <int SM>
 __device__ __forceinline__ void dna_sub_level(csubitem_p it, unsigned node_mask, unsigned scaler_mask, unsigned rate, int first, int count,
                                               const double (*below)[4], const unsigned *sc_below, const unsigned (&code)[15], double (*out)[4],
@@ -1164,13 +1113,7 @@ __device__ __forceinline__ void dna_sub_level(csubitem_p it, unsigned node_mask,
       double a[4], b[4];
       dna_matvec(a, as_const(it->node[pos].lmat) + rate * 16u, below[2 * i]);
       dna_matvec(b, as_const(it->node[pos].rmat) + rate * 16u, below[2 * i + 1]);
-      bool s = true;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-      {
-        out[i][j] = a[j] * b[j];
-        s = s && (out[i][j] < PLLGPU_SCALE_THRESHOLD);
-      }
+      const bool s = dna_product(out[i], a, b);
       small[i] = s && ((scaler_mask >> pos) & 1u);
       if (SM == 1 && ((scaler_mask >> pos) & 1u))
       {
@@ -1562,13 +1505,7 @@ __device__ __forceinline__ void chain_combine(const double *ma, const double *mb
   double a[4], b[4];
   dna_matvec(a, as_const(ma) + g.rate * 16u, xa);
   dna_matvec(b, as_const(mb) + g.rate * 16u, xb);
-  bool small = true;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-  {
-    v[i] = a[i] * b[i];
-    small = small && (v[i] < PLLGPU_SCALE_THRESHOLD);
-  }
+  bool small = dna_product(v, a, b);
   sc = 0u;
   if (!pscaler) return; // no scaler on this op: nothing is rescaled (workgroup-uniform)
   if (SM == 1)
@@ -1743,8 +1680,8 @@ template <int SM, bool C0, bool S1, bool C1, class SRC>
 __device__ __forceinline__ void chain_body(const SRC src, unsigned entries)
 {
   __shared__ unsigned long long ballots[4][4]; // [step parity x decision][rate]
-  // (round 4 tried the XCD-aware workgroup order of the store-bound group launches here, kernels_common.h: random
-  // 64-taxon trees 0.206 -> 0.217 ms per step, the ladder within the spread - the siblings' reads want the natural order)
+  // natural workgroup order, not the XCD-aware one of the store-bound group launches (kernels_common.h): the siblings'
+  // reads want it (profiles/README.md: random 64-taxon trees 0.205-0.208 -> 0.216-0.219 ms per step)
   const ChainHead h = src.head(blockIdx.y);
   const ChainGeo g = chain_geo(entries);
   double acc[4];
@@ -1801,9 +1738,7 @@ __device__ __forceinline__ void chain_edge_body(const DevEdge &e, const SRC src,
   {
     double tb[4];
     dna_matvec(tb, as_const(e.mat) + g.rate * 16u, vc);
-    const unsigned fi = e.fidx[g.rate];
-    cdouble_p pi = as_const(e.freqs) + (size_t)fi * 4;
-    xtr[g.rate][lane] = fma(vp[3] * pi[3], tb[3], fma(vp[2] * pi[2], tb[2], fma(vp[1] * pi[1], tb[1], (vp[0] * pi[0]) * tb[0])));
+    xtr[g.rate][lane] = dna_rate_term(vp, as_const(e.freqs) + (size_t)e.fidx[g.rate] * 4, tb);
     xrs[g.rate][lane] = scp + scc;
   }
   __syncthreads();
@@ -1812,43 +1747,14 @@ __device__ __forceinline__ void chain_edge_body(const DevEdge &e, const SRC src,
     const unsigned n0 = blockIdx.x * 64u + lane;
     const bool valid = n0 < e.sites;
     const unsigned n = valid ? n0 : e.sites - 1;
-    unsigned rs[4] = {0, 0, 0, 0}, scal;
-    if (e.per_rate)
-    {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) rs[k] = xrs[k][lane];
-      scal = min(min(rs[0], rs[1]), min(rs[2], rs[3]));
-    }
-    else
-      scal = xrs[0][lane];
+    unsigned rs[4];
+    // the waves' sums (per site: every wave holds the same one) stand in for the parent end's words
+    const unsigned scal = dna_site_scalers(e, make_uint4(xrs[0][lane], xrs[1][lane], xrs[2][lane], xrs[3][lane]), make_uint4(0, 0, 0, 0), rs);
     const int inv = e.invariant ? e.invariant[n] : -1;
     double terma = 0.0, terminv = 0.0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-    {
-      double tr = xtr[k][lane];
-      const unsigned fi = e.fidx[k];
-      if (e.per_rate)
-      {
-        const unsigned ex = min(rs[k] - scal, PLLGPU_RATE_MAXDIFF);
-        if (ex) tr *= minlh(ex);
-      }
-      const double pinv = e.prop_invar ? e.prop_invar[fi] : 0.0;
-      const double w = e.rate_weights[k];
-      if (pinv > 0.0)
-      {
-        terma += w * tr * (1.0 - pinv);
-        if (inv >= 0) terminv += w * e.freqs[(size_t)fi * 4 + inv] * pinv;
-      }
-      else
-        terma += tr * w;
-    }
-    double site = 0.0;
-    if (valid)
-    {
-      site = finish_site(terma, terminv, scal, 0) * (double)e.pattern_weights[n];
-      if (e.persite) e.persite[n] = site;
-    }
+    for (int k = 0; k < 4; ++k) dna_site_add(e, k, xtr[k][lane], rs, scal, inv, terma, terminv);
+    const double site = valid ? dna_site_finish(e, n, terma, terminv, scal, 0) : 0.0;
     const double tile_sum = wave_sum(site);
     if (lane == 0)
     {
@@ -1929,20 +1835,16 @@ __global__ __launch_bounds__(256) void k_edge_dna_chain(const DevEdge e, const C
 template <int KP, int KC>
 __global__ __launch_bounds__(256) void k_edge_dna_tail(const DevEdge e, const FGroup g, int scale_mode, unsigned tiles_per_wave)
 {
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned ntiles = (e.sites + 63u) / 64u;
   cdouble_p pm = as_const(e.mat);
   double acc = 0.0;
 
   for (unsigned t = 0; t < tiles_per_wave; ++t)
   {
-    const unsigned tile = (blockIdx.x * 4u + wave) * tiles_per_wave + t;
-    if (tile >= ntiles) break; // wave-uniform
-    const unsigned n0 = tile * 64u + lane;
-    const bool valid = n0 < e.sites;
-    const unsigned n = valid ? n0 : e.sites - 1;
-    const size_t off = (size_t)(n >> 6) * kDnaTile + (n & 63u);
+    DnaTile w;
+    if (!dna_tile(w, blockIdx.x, tiles_per_wave, t, e.sites)) break;
+    const unsigned n = w.n;
+    const bool valid = w.valid;
+    const size_t off = w.off;
 
     double vp[4][4], vc[4][4];
     uint4 scp, scc;
@@ -1957,17 +1859,8 @@ __global__ __launch_bounds__(256) void k_edge_dna_tail(const DevEdge e, const FG
       dna_child_compute<KC>(g.p, false, g.b, n, scale_mode, rc, vc, scc);
       dna_child_store<KC>(g.b, off, n, valid, scale_mode, vc, scc);
     }
-    unsigned rs[4] = {0, 0, 0, 0}, scal;
-    if (e.per_rate)
-    {
-      rs[0] = scp.x + scc.x;
-      rs[1] = scp.y + scc.y;
-      rs[2] = scp.z + scc.z;
-      rs[3] = scp.w + scc.w;
-      scal = min(min(rs[0], rs[1]), min(rs[2], rs[3]));
-    }
-    else
-      scal = scp.x + scc.x;
+    unsigned rs[4];
+    const unsigned scal = dna_site_scalers(e, scp, scc, rs);
     const int inv = e.invariant ? e.invariant[n] : -1;
     double terma = 0.0, terminv = 0.0;
 #pragma unroll
@@ -1975,30 +1868,9 @@ __global__ __launch_bounds__(256) void k_edge_dna_tail(const DevEdge e, const FG
     {
       double tb[4];
       dna_matvec(tb, pm + k * 16, vc[k]);
-      const unsigned fi = e.fidx[k];
-      cdouble_p pi = as_const(e.freqs) + (size_t)fi * 4;
-      double tr = fma(vp[k][3] * pi[3], tb[3], fma(vp[k][2] * pi[2], tb[2], fma(vp[k][1] * pi[1], tb[1], (vp[k][0] * pi[0]) * tb[0])));
-      if (e.per_rate)
-      {
-        const unsigned ex = min(rs[k] - scal, PLLGPU_RATE_MAXDIFF);
-        if (ex) tr *= minlh(ex);
-      }
-      const double pinv = e.prop_invar ? e.prop_invar[fi] : 0.0;
-      const double w = e.rate_weights[k];
-      if (pinv > 0.0)
-      {
-        terma += w * tr * (1.0 - pinv);
-        if (inv >= 0) terminv += w * e.freqs[(size_t)fi * 4 + inv] * pinv;
-      }
-      else
-        terma += tr * w;
+      dna_site_add(e, k, dna_rate_term(vp[k], as_const(e.freqs) + (size_t)e.fidx[k] * 4, tb), rs, scal, inv, terma, terminv);
     }
-    if (valid)
-    {
-      const double site = finish_site(terma, terminv, scal, 0) * (double)e.pattern_weights[n];
-      if (e.persite) e.persite[n] = site;
-      acc += site;
-    }
+    if (valid) acc += dna_site_finish(e, n, terma, terminv, scal, 0);
   }
   publish_block_sum(e, wave_sum(acc), 4u);
 }
