@@ -70,6 +70,7 @@ extern "C" {
 #define PLL_ERROR_INVAR_NONEFOUND 120
 #define PLL_ERROR_AB_INVALIDMETHOD 121
 #define PLL_ERROR_AB_NOSUPPORT 122
+#define PLL_ERROR_EINVAL 130
 #define PLL_ERROR_MSA_EMPTY 131
 #define PLL_ERROR_MSA_MAP_INVALID 132
 /* new, outside the reference's range: device problems are reported through the same
@@ -269,6 +270,23 @@ double pll_compute_edge_loglikelihood(pll_partition_t *partition, unsigned int p
 double pll_compute_root_loglikelihood(pll_partition_t *partition, unsigned int clv_index,
                                       int scaler_index, const unsigned int *freqs_indices,
                                       double *persite_lnl);
+/* src/pll.h:799-806, src/likelihood.c:758-823. Marginal ancestral state probabilities of the node whose CLV is
+ * node_clv_index, oriented towards the node at other_clv_index across matrix_index: ancestral[n * states + j],
+ * unpadded, each site's row sums to 1. One kernel and one device-to-host copy; synchronises. The other end may be
+ * a tip of any kind; the node's end must have a CLV (a PLL_ATTRIB_PATTERN_TIP tip is refused with
+ * PLL_ERROR_PARAM_INVALID where the reference dereferences NULL). Site repeats: PLL_ERROR_EINVAL, as in the
+ * reference. prop_invar is ignored, as in the reference. Deliberate difference: with PLL_ATTRIB_RATE_SCALERS the
+ * per-rate scaling counts of both ends are honoured (the reference ignores them, src/likelihood.c:711-743). */
+int pll_compute_node_ancestral(pll_partition_t *partition, unsigned int node_clv_index, int node_scaler_index,
+                               unsigned int other_clv_index, int other_scaler_index, unsigned int matrix_index,
+                               const unsigned int *freqs_indices, double *ancestral);
+/* src/pll.h:808-818, src/likelihood.c:639-756. The same; the three scratch buffers the reference computes in must
+ * not be NULL (PLL_ERROR_PARAM_INVALID) but are neither read nor written here - the product CLV never leaves the
+ * device's registers. Their contents after the call are unspecified. */
+int pll_compute_node_ancestral_extbuf(pll_partition_t *partition, unsigned int node_clv_index, int node_scaler_index,
+                                      unsigned int other_clv_index, int other_scaler_index, unsigned int pmatrix_index,
+                                      const unsigned int *freqs_indices, double *ancestral, double *temp_clv,
+                                      unsigned int *temp_scaler, double *ident_pmat);
 
 /* ---- the flat core seam of the hot path (src/pll.h:1049-1177 and :1295-1414; bodies in
  * src/core_partials.c:48-1210, src/core_likelihood.c:24-1496) ----------------------------------
@@ -528,6 +546,14 @@ int pll_gpu_edge_loglikelihood_async(pll_partition_t *partition, unsigned int pa
                                      int parent_scaler_index, unsigned int child_clv_index,
                                      int child_scaler_index, unsigned int matrix_index,
                                      const unsigned int *freqs_indices, double *device_result);
+/* pll_compute_node_ancestral (src/pll.h:799-806) without the host round trip: the kernel is enqueued on the
+ * partition's stream (pll_gpu_set_stream / pll_gpu_get_stream apply) and leaves the table in the sites * states
+ * doubles of DEVICE memory at device_ancestral; nothing is copied back and the call does not wait. A caller that
+ * reconstructs every inner node queues partial traversals and these calls on one stream and synchronises once.
+ * Returns PLL_SUCCESS when enqueued. */
+int pll_gpu_node_ancestral_async(pll_partition_t *partition, unsigned int node_clv_index, int node_scaler_index,
+                                 unsigned int other_clv_index, int other_scaler_index, unsigned int matrix_index,
+                                 const unsigned int *freqs_indices, void *device_ancestral);
 /* ---- the ONE exchange of a site-sharded run (SURVEY section 8 row e) --------------------------
  * Sites are independent through every CLV update; the only cross-site operation of the path is the sum
  * of the per-site log-likelihoods (src/core_likelihood.c:1489, the sequential `logl += site_lk`). A run

@@ -172,6 +172,15 @@ int pllgpu_root_loglikelihood(pllgpu_ctx_t *ctx, unsigned int clv, int scaler, u
                               const unsigned int *freqs_indices, double *persite_host,
                               double *lnl_out);
 
+/* replaces pll_compute_node_ancestral[_extbuf] (src/likelihood.c:639-823): the marginal state probabilities of
+ * the node at edge->parent_clv, [sites][states] unpadded, given the other end edge->child_clv (a CLV, or tip codes
+ * with child_is_tip) across edge->matrix. Of `edge`, gather must be 0 and want_persite / device_result / sequence
+ * are not used. Exactly one of the outputs is non-NULL: host_out - the table is copied back and the call waits;
+ * device_out - sites * states doubles of DEVICE memory, the call returns once the kernel is enqueued on the
+ * context's stream. One launch, counted into pllgpu_last_launch_count. With per-rate scalers the counts of both
+ * ends are honoured (kernels_ancestral.h), which the reference does not do. */
+int pllgpu_node_ancestral(pllgpu_ctx_t *ctx, const pllgpu_edge_t *edge, double *host_out, void *device_out);
+
 /* ---- transition matrices on the device ---------------------------- */
 /* eigensystem of rate matrix `index` in the reference's layouts: eigenvecs[j*sp+i],
  * inv_eigenvecs[i*sp+j] ([states][states_padded] each), eigenvals[states_padded] */

@@ -27,6 +27,7 @@
 #include "kernels_mfma_wide.h"
 #include "kernels_lean.h"
 #include "kernels_repeats.h"
+#include "kernels_ancestral.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
@@ -244,6 +245,7 @@ struct pllgpu_ctx
   double seq = 0.0;
   double seq_override = 0.0;     // pllgpu_edge_t.sequence of the evaluation being issued (0: number it here)
   DevBuf<double> reduce;         // {lnL, sequence}: the operand of a caller's all-reduce (pllgpu_reduce_buffer)
+  DevBuf<double> ancestral;      // [sites][states] staging of pllgpu_node_ancestral's host output, allocated on first use
   std::vector<double> stage;     // host staging for the P-matrix re-layout
   std::vector<unsigned char> stage8; // ... and for a class map that goes up as bytes
   unsigned last_launches = 0;
@@ -659,6 +661,7 @@ extern "C" void pllgpu_destroy(pllgpu_ctx_t *c)
   c->persite.release();
   c->block_sums.release();
   c->reduce.release();
+  c->ancestral.release();
   c->counter.release();
   c->mfma_flags.release();
   c->eigenvals.release();
@@ -2500,6 +2503,73 @@ extern "C" int pllgpu_root_loglikelihood(pllgpu_ctx_t *c, unsigned clv, int scal
   if (e.layout && !gather) return fail(PLLGPU_EINVAL, "a class-compressed CLV met an evaluation without the gather flag");
   e.is_root = 1;
   return run_lnl(c, e, false, gather != 0, freqs_indices, persite_host, lnl_out);
+}
+
+// ---- marginal ancestral states (kernels_ancestral.h) -------------------------------------------------------
+template <int ICH>
+static void launch_ancestral_generic(pllgpu_ctx *c, const DevAncestral &a, unsigned blocks, unsigned tpw, bool ctip)
+{
+  const unsigned long long *tm = tipmap_ptr(c);
+  const unsigned nw = std::min(c->gg.R, 4u); // one wave per rate category of the tile, up to 4
+  const size_t lds = ((size_t)nw * c->gg.S * 64u + (size_t)nw * 64u) * sizeof(double);
+  with_bools(ctip, false, [&](auto CT, auto) {
+    raise_lds_limit(reinterpret_cast<const void *>(&k_ancestral_tiled<ICH, CT()>), c->device, lds);
+    hipLaunchKernelGGL((k_ancestral_tiled<ICH, CT()>), dim3(blocks), dim3(64u * nw), lds, c->stream, a, c->gg, tm, tpw);
+  });
+}
+
+// the call's one launch: the 4 x 4 form or the tiled one, tile walk as launch_edge
+static void launch_ancestral(pllgpu_ctx *c, const DevAncestral &a, bool ctip)
+{
+  const unsigned tiles = (c->geo.sites + 63) / 64;
+  const unsigned max_blocks = 1024;
+  if (c->dna_fast)
+  {
+    // one tile per wave up to 4096 workgroups (kernels_dna.h, "Tiles per wave"): the kernel is a read stream with a short store
+    const unsigned tpw = (tiles + 4 * 4 * max_blocks - 1) / (4 * 4 * max_blocks);
+    const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
+    with_bools(ctip, false, [&](auto CT, auto) {
+      hipLaunchKernelGGL((k_ancestral_dna<CT()>), dim3(blocks), dim3(256), 0, c->stream, a, tpw);
+    });
+    return;
+  }
+  const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
+  const unsigned blocks = (tiles + tpw - 1) / tpw;
+  switch (c->ich)
+  {
+    case 4: launch_ancestral_generic<4>(c, a, blocks, tpw, ctip); break;
+    case 8: launch_ancestral_generic<8>(c, a, blocks, tpw, ctip); break;
+    case 16: launch_ancestral_generic<16>(c, a, blocks, tpw, ctip); break;
+    case 20: launch_ancestral_generic<20>(c, a, blocks, tpw, ctip); break;
+    default: launch_ancestral_generic<32>(c, a, blocks, tpw, ctip); break;
+  }
+}
+
+extern "C" int pllgpu_node_ancestral(pllgpu_ctx_t *c, const pllgpu_edge_t *ed, double *host_out, void *device_out)
+{
+  CHECK_CTX(c); // (held ops and chains go out as ordinary updates first)
+  const pllgpu_geometry_t &g = c->geo;
+  if ((host_out == nullptr) == (device_out == nullptr)) return fail(PLLGPU_EINVAL, "ancestral states go to the host or to the device, one of the two");
+  if (ed->gather) return fail(PLLGPU_EUNSUPPORTED, "ancestral states of class-compressed CLVs");
+  if (int rc = check_edge(c, ed, nullptr)) return rc;
+  DevAncestral a;
+  if (int rc = build_edge(c, ed, a.e)) return rc;
+  const size_t n = (size_t)g.sites * g.states;
+  if (host_out)
+    if (int rc = c->ancestral.ensure(n)) return rc;
+  a.out = host_out ? c->ancestral.p : static_cast<double *>(device_out);
+  for (unsigned k = 0; k < g.rate_cats; ++k) a.e.fidx[k] = (unsigned char)ed->freqs_indices[k];
+  a.e.freqs = c->freqs.p;
+  a.e.rate_weights = c->rate_weights.p;
+  a.e.sites = g.sites;
+  a.e.per_rate = g.per_rate_scalers ? 1 : 0;
+  launch_ancestral(c, a, ed->child_is_tip != 0);
+  ++c->last_launches;
+  HIP_TRY(hipGetLastError());
+  if (!host_out) return 0; // stream-ordered: the table stays where the caller asked for it
+  HIP_TRY(hipMemcpyAsync(host_out, c->ancestral.p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(stream_wait(c));
+  return 0;
 }
 
 // ---- the flat seam's tip-tip pair: the caller's lookup table in the reference's layout ---------------------

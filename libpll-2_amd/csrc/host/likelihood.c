@@ -63,7 +63,7 @@ static double asc_correction(pll_partition_t *p, pll_amd_ext_t *x, const pllgpu_
   }
 }
 
-static int prepare_end(pll_partition_t *p, pll_amd_ext_t *x, unsigned int clv, int scaler)
+int pll_prepare_end(pll_partition_t *p, pll_amd_ext_t *x, unsigned int clv, int scaler)
 {
   if (!pll_flush_clv(p, x, clv)) return 0;
   if (!pll_tip_by_codes(p, clv) && !pll_flush_scaler(p, x, scaler)) return 0;
@@ -127,8 +127,8 @@ static double edge_lnl(pll_partition_t *p, unsigned int parent_clv_index, int pa
   const int ptip = pll_tip_by_codes(p, parent_clv_index);
   const int ctip = pll_tip_by_codes(p, child_clv_index);
   if (!pll_flush_model(p, x) || !pll_flush_pmatrix(p, x, matrix_index, matrix_index) ||
-      !prepare_end(p, x, parent_clv_index, parent_scaler_index) ||
-      !prepare_end(p, x, child_clv_index, child_scaler_index))
+      !pll_prepare_end(p, x, parent_clv_index, parent_scaler_index) ||
+      !pll_prepare_end(p, x, child_clv_index, child_scaler_index))
     return fail_lnl("pll_compute_edge_loglikelihood");
 
   pllgpu_edge_t e;
@@ -210,7 +210,7 @@ double pll_compute_root_loglikelihood(pll_partition_t *p, unsigned int clv_index
     pll_set_error(PLL_ERROR_PARAM_INVALID, "pll_compute_root_loglikelihood: invalid CLV/scaler index");
     return fail_lnl("pll_compute_root_loglikelihood");
   }
-  if (!pll_flush_model(p, x) || !prepare_end(p, x, clv_index, scaler_index))
+  if (!pll_flush_model(p, x) || !pll_prepare_end(p, x, clv_index, scaler_index))
     return fail_lnl("pll_compute_root_loglikelihood");
   const unsigned int gather = pll_repeats_enabled(p) && p->repeats->pernode_ids[clv_index];
   double lnl = 0;

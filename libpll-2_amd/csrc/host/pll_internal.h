@@ -135,6 +135,8 @@ int pll_update_repeats_device(pll_partition_t *p, pll_amd_ext_t *x, const pll_op
                               unsigned int count, const unsigned int *level, unsigned int nlevels);
 int pll_flush_pmatrix(pll_partition_t *p, pll_amd_ext_t *x, unsigned int first, unsigned int last);
 int pll_flush_repeats(pll_partition_t *p, pll_amd_ext_t *x, unsigned int node);
+/* one end of an edge evaluation: its CLV (or tip codes), its scaler vector and its class map (likelihood.c) */
+int pll_prepare_end(pll_partition_t *p, pll_amd_ext_t *x, unsigned int clv, int scaler);
 /* the class map of `node` (all nodes: node < 0) was written by something other than the class kernels, or must be
  * taken as such: whatever was derived from it is computed again by the next pll_update_repeats */
 void pll_maps_touched(pll_amd_ext_t *x, const pll_partition_t *p, int node);

@@ -140,6 +140,14 @@ _PROTOS = {
         C.c_double,
         [PartitionP, C.c_uint, C.c_int, c_uint_p, c_double_p],
     ),
+    "pll_compute_node_ancestral": (
+        C.c_int,
+        [PartitionP, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p, c_double_p],
+    ),
+    "pll_compute_node_ancestral_extbuf": (
+        C.c_int,
+        [PartitionP, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p, c_double_p, c_double_p, c_uint_p, c_double_p],
+    ),
     "pll_update_sumtable": (C.c_int, [PartitionP, C.c_uint, C.c_uint, C.c_int, C.c_int, c_uint_p, c_double_p]),
     "pll_compute_likelihood_derivatives": (
         C.c_int,
@@ -163,6 +171,7 @@ _GPU_PROTOS = {
     "pll_gpu_sync_scaler": (C.c_int, [PartitionP, C.c_uint]),
     "pll_gpu_sync_pmatrix": (C.c_int, [PartitionP, C.c_int]),
     "pll_gpu_edge_loglikelihood_async": (C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p, C.c_void_p]),
+    "pll_gpu_node_ancestral_async": (C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p, C.c_void_p]),
     "pll_gpu_last_algorithmic_bytes": (C.c_double, [PartitionP]),
     "pll_gpu_sync_repeats": (C.c_int, [PartitionP, C.c_int]),
     "pll_gpu_sync_all": (C.c_int, [PartitionP]),

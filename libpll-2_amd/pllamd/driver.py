@@ -175,6 +175,17 @@ class Session:
             self.p, root[0], root[1], api.uptr(self._fi), api.dptr(ps) if persite else None)
         return v, ps
 
+    def node_ancestral(self, edge):
+        """marginal state probabilities [sites, states] of the node edge[0] (scaler edge[1]) towards the other
+        end edge[2] (scaler edge[3]) across matrix edge[4]"""
+        c = self.case
+        out = np.zeros((c.sites, c.states))
+        ok = self.lib.pll_compute_node_ancestral(
+            self.p, edge[0], edge[1], edge[2], edge[3], edge[4], api.uptr(self._fi), api.dptr(out))
+        if not ok:
+            raise RuntimeError(f"pll_compute_node_ancestral: [{self.lib.errno()}] {self.lib.errmsg()}")
+        return out
+
     def entries(self, clv_index):
         return self.lib.pll_get_sites_number(self.p, clv_index)
 
