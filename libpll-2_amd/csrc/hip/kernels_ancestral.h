@@ -85,11 +85,7 @@ __global__ __launch_bounds__(256) void k_ancestral_dna(const DevAncestral a, uns
       dna_matvec(tb, pm + k * 16, xc[k]);
       cdouble_p pi = as_const(e.freqs) + (size_t)e.fidx[k] * 4;
       double wk = e.rate_weights[k] * PLLGPU_ANCESTRAL_LIFT;
-      if (e.per_rate)
-      {
-        const unsigned ex = min(rs[k] - scal, PLLGPU_RATE_MAXDIFF);
-        if (ex) wk *= minlh(ex);
-      }
+      if (e.per_rate) wk = rate_scaled(wk, rs[k], scal);
 #pragma unroll
       for (int j = 0; j < 4; ++j) s[j] = fma(pi[j] * wk, xp[k][j] * tb[j], s[j]);
     }
@@ -129,32 +125,18 @@ __global__ __launch_bounds__(256) void k_ancestral_tiled(const DevAncestral a, c
     const unsigned n = tile * 64u + lane;
     const unsigned nn = n < e.sites ? n : e.sites - 1; // tail lanes redo the last site, store nothing
     unsigned long long cmask = 0;
-    if (CTIP) cmask = tipmap ? tipmap[e.ctip[nn]] : (unsigned long long)e.ctip[nn];
+    if (CTIP) cmask = tip_mask(tipmap, e.ctip[nn]);
     const double *__restrict__ px = e.parent + tiled_base(nn, g.tile_sz);
     const double *__restrict__ cx = CTIP ? nullptr : e.child + tiled_base(nn, g.tile_sz);
 
-    unsigned scal = 0;
-    if (e.per_rate)
-    {
-      scal = 0xFFFFFFFFu;
-      for (unsigned k = 0; k < g.R; ++k)
-      {
-        const unsigned rs = (e.pscaler ? e.pscaler[(size_t)nn * g.R + k] : 0u) + (e.cscaler ? e.cscaler[(size_t)nn * g.R + k] : 0u);
-        scal = min(scal, rs);
-      }
-    }
+    const unsigned scal = e.per_rate ? scaler_min(e.pscaler, nn, e.cscaler, nn, g.R) : 0u;
 
     // this wave's rate categories into its own slot
     bool first = true;
     for (unsigned k = wave; k < g.R; k += nw)
     {
       double wk = e.rate_weights[k] * PLLGPU_ANCESTRAL_LIFT;
-      if (e.per_rate)
-      {
-        const unsigned rs = (e.pscaler ? e.pscaler[(size_t)nn * g.R + k] : 0u) + (e.cscaler ? e.cscaler[(size_t)nn * g.R + k] : 0u);
-        const unsigned ex = min(rs - scal, PLLGPU_RATE_MAXDIFF);
-        if (ex) wk *= minlh(ex);
-      }
+      if (e.per_rate) wk = rate_scaled(wk, scaler_sum_rate(e.pscaler, nn, e.cscaler, nn, g.R, k), scal);
       for (unsigned c = 0; c < g.nchunks; ++c)
       {
         double B[ICH];

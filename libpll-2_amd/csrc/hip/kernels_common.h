@@ -197,6 +197,58 @@ __device__ __forceinline__ double minlh(unsigned d)
   return ldexp(1.0, -256 * (int)d);
 }
 
+// ---- the scaling count of a site, once (src/core_likelihood.c:1388-1400, :1445-1461) ----------------------------
+// Two ends (parent and child of an edge, or the two children of an op), either of which may carry no scaler; ia /
+// ib: the entry, or entry * R + k with per-rate scalers.
+__device__ __forceinline__ unsigned scaler_sum(const unsigned *a, size_t ia, const unsigned *b, size_t ib)
+{
+  return (a ? a[ia] : 0u) + (b ? b[ib] : 0u);
+}
+__device__ __forceinline__ unsigned scaler_sum_rate(const unsigned *a, unsigned ea, const unsigned *b, unsigned eb, unsigned R, unsigned k)
+{
+  return scaler_sum(a, (size_t)ea * R + k, b, (size_t)eb * R + k);
+}
+// per-rate scalers: the smallest summed count over the rate categories is what the site is scaled by ...
+__device__ __forceinline__ unsigned scaler_min(const unsigned *a, unsigned ea, const unsigned *b, unsigned eb, unsigned R)
+{
+  unsigned mn = 0xFFFFFFFFu;
+  for (unsigned k = 0; k < R; ++k) mn = min(mn, scaler_sum_rate(a, ea, b, eb, R, k));
+  return mn;
+}
+__device__ __forceinline__ unsigned site_scalings(const unsigned *a, unsigned ea, const unsigned *b, unsigned eb, unsigned R, int per_rate)
+{
+  return per_rate ? scaler_min(a, ea, b, eb, R) : scaler_sum(a, ea, b, eb);
+}
+// ... and a rate whose count rs lies above that minimum enters with 2^(-256 min(rs - mn, 4))
+__device__ __forceinline__ unsigned rate_excess(unsigned rs, unsigned mn)
+{
+  return min(rs - mn, PLLGPU_RATE_MAXDIFF);
+}
+__device__ __forceinline__ double rate_scaled(double v, unsigned rs, unsigned mn)
+{
+  const unsigned ex = rate_excess(rs, mn);
+  return ex ? v * minlh(ex) : v;
+}
+
+// state mask of a tip code (null map: the code is the mask, 4 states) and the mask of a full gap
+__device__ __forceinline__ unsigned long long tip_mask(const unsigned long long *__restrict__ tipmap, unsigned code)
+{
+  return tipmap ? tipmap[code] : (unsigned long long)code;
+}
+__device__ __forceinline__ unsigned long long full_mask(unsigned S)
+{
+  return S >= 64 ? ~0ull : ((1ull << S) - 1ull);
+}
+
+// sum of n values at a stride in ASCENDING order: the row sums of a transposed matrix, what a full-gap tip stands
+// for - the order of the reference's set-bit walk (src/core_partials.c:480-489)
+__device__ __forceinline__ double sum_ascending(const double *p, unsigned n, size_t stride)
+{
+  double s = 0.0;
+  for (unsigned j = 0; j < n; ++j) s += p[(size_t)j * stride];
+  return s;
+}
+
 // Every workgroup leaves its partial sum; the workgroup that arrives last adds all partials in
 // index order (fixed tree: the result does not depend on arrival order) and writes the total to
 // host-mapped memory. One launch, no separate reduction kernel, no D2H copy.
@@ -272,11 +324,10 @@ __device__ __forceinline__ double sum_partials_strided(const double *block_sums,
   return a;
 }
 
-// The same when only SOME workgroups hold a value and which ones is decided at run time (k_edge_mfma: the workgroup
-// that finishes an item block last): the value goes to the slot of the ITEM BLOCK, not of the workgroup, so that the
-// final sum adds the same numbers in the same places whichever workgroup produced them - with one slot per
-// workgroup the non-zero entries moved between threads of the last workgroup from run to run and the total with
-// them, by an ulp or two.
+// Which workgroups hold a value may be decided at run time (k_edge_mfma: the workgroup that finishes an item block
+// last): the value goes to the slot of the ITEM BLOCK, not of the workgroup, so that the final sum adds the same
+// numbers in the same places whichever workgroup produced them - with one slot per workgroup the non-zero entries
+// moved between threads of the last workgroup from run to run and the total with them, by an ulp or two.
 __device__ __forceinline__ void publish_block_sum_slot(const DevEdge &e, double wave_value, unsigned nsum_waves, bool has_value, unsigned slot,
                                                        unsigned nslots)
 {
@@ -293,7 +344,7 @@ __device__ __forceinline__ void publish_block_sum_slot(const DevEdge &e, double 
       for (unsigned w = 1; w < nw; ++w) s += ws[w];
       partial_store(&e.block_sums[slot], s);
     }
-    handoff_before_ticket(e.fenced);
+    handoff_before_ticket(e.fenced); // the partial has been performed before the ticket is taken
     const unsigned ticket = __hip_atomic_fetch_add(e.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     last = (ticket == gridDim.x - 1) ? 1u : 0u;
     if (last) handoff_after_last_ticket(e.fenced);
@@ -310,45 +361,16 @@ __device__ __forceinline__ void publish_block_sum_slot(const DevEdge &e, double 
     double s = ws[0];
     for (unsigned w = 1; w < nw; ++w) s += ws[w];
     __hip_atomic_store(e.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(e.result, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    handoff_before_sequence(e.fenced);
-    __hip_atomic_store(e.result + 1, e.sequence, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
-__device__ __forceinline__ void publish_block_sum(const DevEdge &e, double wave_value, unsigned nsum_waves)
-{
-  __shared__ double ws[4];
-  __shared__ unsigned last;
-  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if (lane == 0) ws[wave] = wave < nsum_waves ? wave_value : 0.0;
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    double s = ws[0];
-    for (unsigned w = 1; w < nw; ++w) s += ws[w];
-    partial_store(&e.block_sums[blockIdx.x], s);
-    handoff_before_ticket(e.fenced); // the partial has been performed before the ticket is taken
-    const unsigned ticket = __hip_atomic_fetch_add(e.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = (ticket == gridDim.x - 1) ? 1u : 0u;
-    if (last) handoff_after_last_ticket(e.fenced);
-  }
-  __syncthreads();
-  if (!last) return;
-  double a = sum_partials_strided(e.block_sums, gridDim.x);
-  a = wave_sum(a);
-  __syncthreads();
-  if (lane == 0) ws[wave] = a;
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    double s = ws[0];
-    for (unsigned w = 1; w < nw; ++w) s += ws[w];
-    __hip_atomic_store(e.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // result[0] = value, then result[1] = this call's sequence number with system-scope release:
     // the host polls the sequence word in mapped memory instead of paying a stream synchronise
     __hip_atomic_store(e.result, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     handoff_before_sequence(e.fenced); // the value is in host memory before the sequence word follows
     __hip_atomic_store(e.result + 1, e.sequence, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+}
+
+// the usual case: every workgroup holds a value, one slot per workgroup
+__device__ __forceinline__ void publish_block_sum(const DevEdge &e, double wave_value, unsigned nsum_waves)
+{
+  publish_block_sum_slot(e, wave_value, nsum_waves, true, blockIdx.x, gridDim.x);
 }

@@ -46,21 +46,23 @@ struct DevDiag
   unsigned char fidx[kMaxRates];
 };
 
+// entry idx = k * S + j of the table: (e, l e, l^2 e, 0) into o
+__device__ __forceinline__ void diag_entry(const DevDiag &d, unsigned idx, double *o)
+{
+  const unsigned k = idx / d.S, j = idx % d.S;
+  const unsigned fi = d.fidx[k];
+  const double ki = d.rates[k] / (1.0 - d.prop_invar[fi]);
+  const double lam = d.eigenvals[(size_t)fi * d.SP + j];
+  const double e = exp(lam * ki * d.branch_length);
+  o[0] = e;
+  o[1] = lam * ki * e;
+  o[2] = lam * ki * lam * ki * e;
+  o[3] = 0.0;
+}
+
 __global__ __launch_bounds__(256) void k_diagtable(const DevDiag d)
 {
-  for (unsigned idx = threadIdx.x; idx < d.R * d.S; idx += blockDim.x)
-  {
-    const unsigned k = idx / d.S, j = idx % d.S;
-    const unsigned fi = d.fidx[k];
-    const double ki = d.rates[k] / (1.0 - d.prop_invar[fi]);
-    const double lam = d.eigenvals[(size_t)fi * d.SP + j];
-    const double e = exp(lam * ki * d.branch_length);
-    double *o = d.diag + (size_t)idx * 4;
-    o[0] = e;
-    o[1] = lam * ki * e;
-    o[2] = lam * ki * lam * ki * e;
-    o[3] = 0.0;
-  }
+  for (unsigned idx = threadIdx.x; idx < d.R * d.S; idx += blockDim.x) diag_entry(d, idx, d.diag + (size_t)idx * 4);
 }
 
 // local_diag: every workgroup forms the (small) diag table itself in LDS instead of waiting for a
@@ -79,16 +81,8 @@ __global__ __launch_bounds__(256) void k_derivatives(const DevDeriv d, const Gen
   {
     for (unsigned idx = threadIdx.x; idx < dg.R * dg.S; idx += blockDim.x)
     {
-      const unsigned k = idx / dg.S, j = idx % dg.S;
-      const unsigned fi = dg.fidx[k];
-      const double ki = dg.rates[k] / (1.0 - dg.prop_invar[fi]);
-      const double lam = dg.eigenvals[(size_t)fi * dg.SP + j];
-      const double e = exp(lam * ki * dg.branch_length);
       double *o = ldiag + (size_t)idx * 4;
-      o[0] = e;
-      o[1] = lam * ki * e;
-      o[2] = lam * ki * lam * ki * e;
-      o[3] = 0.0;
+      diag_entry(dg, idx, o);
       if (blockIdx.x == 0)
       {
         double *go = dg.diag + (size_t)idx * 4;
@@ -159,7 +153,9 @@ __global__ __launch_bounds__(256) void k_derivatives(const DevDeriv d, const Gen
   __syncthreads();
   if (threadIdx.x == 0)
   {
-    // hand-off without fences (kernels_common.h: partial_store)
+    // hand-off without fences (kernels_common.h: partial_store). Two values per workgroup, the wave sums paired as
+    // (0 + 1) + (2 + 3) and the partials read one by one: not publish_block_sum_slot's order of additions, so folding
+    // this into it would change bits. The three ordering points (handoff_*) are the shared ones.
     partial_store(&d.block_sums[blockIdx.x], (ws[0][0] + ws[0][1]) + (ws[0][2] + ws[0][3]));
     partial_store(&d.block_sums[1024 + blockIdx.x], (ws[1][0] + ws[1][1]) + (ws[1][2] + ws[1][3]));
     handoff_before_ticket(d.fenced);
@@ -212,17 +208,11 @@ __global__ __launch_bounds__(256) void k_sumtable_excess(const DevExcess e, cons
   if (n >= e.sites) return;
   const unsigned pe = e.psid ? e.psid[n] : n;
   const unsigned ce = e.csid ? e.csid[n] : n;
-  unsigned mn = 0xFFFFFFFFu;
-  for (unsigned k = 0; k < g.R; ++k)
-  {
-    const unsigned rs = (e.pscaler ? e.pscaler[(size_t)pe * g.R + k] : 0u) + (e.cscaler ? e.cscaler[(size_t)ce * g.R + k] : 0u);
-    mn = min(mn, rs);
-  }
+  const unsigned mn = scaler_min(e.pscaler, pe, e.cscaler, ce, g.R);
   double *x = e.table + tiled_base(n, g.tile_sz);
   for (unsigned k = 0; k < g.R; ++k)
   {
-    const unsigned rs = (e.pscaler ? e.pscaler[(size_t)pe * g.R + k] : 0u) + (e.cscaler ? e.cscaler[(size_t)ce * g.R + k] : 0u);
-    const unsigned ex = min(rs - mn, PLLGPU_RATE_MAXDIFF);
+    const unsigned ex = rate_excess(scaler_sum_rate(e.pscaler, pe, e.cscaler, ce, g.R, k), mn);
     if (!ex) continue;
     const double f = minlh(ex);
     for (unsigned j = 0; j < g.S; ++j) x[((size_t)k * g.S + j) * 64] *= f;
@@ -256,11 +246,8 @@ __global__ __launch_bounds__(64) void k_asc_terms(const DevAsc a, const GenGeo g
   const double *xp = a.parent + tiled_base(e, g.tile_sz);
   const double *xc = a.child ? a.child + tiled_base(e, g.tile_sz) : nullptr;
   unsigned long long mask = 0;
-  if (a.ctip) mask = tipmap ? tipmap[a.ctip[e]] : (unsigned long long)a.ctip[e];
-  unsigned mn = 0xFFFFFFFFu;
-  if (a.per_rate)
-    for (unsigned i = 0; i < R; ++i)
-      mn = min(mn, (a.pscaler ? a.pscaler[(size_t)e * R + i] : 0u) + (a.cscaler ? a.cscaler[(size_t)e * R + i] : 0u));
+  if (a.ctip) mask = tip_mask(tipmap, a.ctip[e]);
+  const unsigned sc = site_scalings(a.pscaler, e, a.cscaler, e, R, a.per_rate);
   double term = 0.0;
   for (unsigned i = 0; i < R; ++i)
   {
@@ -283,17 +270,11 @@ __global__ __launch_bounds__(64) void k_asc_terms(const DevAsc a, const GenGeo g
       v = xp[((size_t)i * S + j) * 64] * a.freqs[(size_t)a.fidx[i] * g.SP + j] * termb;
     }
     v = wave_sum(v);
-    if (a.per_rate)
-    {
-      const unsigned rs = (a.pscaler ? a.pscaler[(size_t)e * R + i] : 0u) + (a.cscaler ? a.cscaler[(size_t)e * R + i] : 0u);
-      const unsigned d = min(rs - mn, PLLGPU_RATE_MAXDIFF);
-      if (d) v *= minlh(d);
-    }
+    if (a.per_rate) v = rate_scaled(v, scaler_sum_rate(a.pscaler, e, a.cscaler, e, R, i), sc);
     term += v * a.rate_weights[i];
   }
   if (j == 0)
   {
-    const unsigned sc = a.per_rate ? mn : (a.pscaler ? a.pscaler[e] : 0u) + (a.cscaler ? a.cscaler[e] : 0u);
     a.out[n] = term;
     a.out[S + n] = (double)sc;
   }
@@ -317,7 +298,6 @@ __global__ __launch_bounds__(64) void k_asc_deriv_terms(const DevAscDeriv a, con
   const unsigned e = a.first + n;
   const double *x = a.table + tiled_base(e, g.tile_sz);
   double lk0 = 0.0, lk1 = 0.0, lk2 = 0.0;
-  unsigned mn = 0xFFFFFFFFu;
   for (unsigned k = 0; k < g.R; ++k)
   {
     double c0 = 0.0, c1 = 0.0, c2 = 0.0;
@@ -333,11 +313,9 @@ __global__ __launch_bounds__(64) void k_asc_deriv_terms(const DevAscDeriv a, con
     lk0 += c0 * w;
     lk1 += c1 * w;
     lk2 += c2 * w;
-    if (a.per_rate)
-      mn = min(mn, (a.pscaler ? a.pscaler[(size_t)e * g.R + k] : 0u) + (a.cscaler ? a.cscaler[(size_t)e * g.R + k] : 0u));
   }
   // per-rate scalers: the table columns were already brought to the smallest count (k_sumtable_excess)
-  const unsigned sc = a.per_rate ? mn : (a.pscaler ? a.pscaler[e] : 0u) + (a.cscaler ? a.cscaler[e] : 0u);
+  const unsigned sc = site_scalings(a.pscaler, e, a.cscaler, e, g.R, a.per_rate);
   a.out[n * 3 + 0] = lk0;
   a.out[n * 3 + 1] = lk1;
   a.out[n * 3 + 2] = lk2;

@@ -459,11 +459,7 @@ __device__ __forceinline__ void dna_site_add(const DevEdge &e, int k, double tr,
                                              double &terminv)
 {
   const unsigned fi = e.fidx[k];
-  if (e.per_rate)
-  {
-    const unsigned ex = min(rs[k] - scal, PLLGPU_RATE_MAXDIFF);
-    if (ex) tr *= minlh(ex);
-  }
+  if (e.per_rate) tr = rate_scaled(tr, rs[k], scal);
   const double pinv = e.prop_invar ? e.prop_invar[fi] : 0.0;
   const double w = e.rate_weights[k];
   if (pinv > 0.0)

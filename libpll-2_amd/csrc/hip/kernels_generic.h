@@ -126,11 +126,7 @@ __device__ __forceinline__ void tip_stage(double *staged, const double *pt, unsi
   const unsigned n = g.S * g.SPT, ls = g.SPT | 1u;
   for (unsigned idx = lane; idx < n; idx += 64u) staged[(idx / g.SPT) * ls + idx % g.SPT] = src[idx];
   for (unsigned i = lane; i < g.SPT; i += 64u)
-  {
-    double s = 0.0;
-    for (unsigned j = 0; j < g.S; ++j) s += src[(size_t)j * g.SPT + i];
-    staged[g.S * ls + i] = s;
-  }
+    staged[g.S * ls + i] = sum_ascending(src + i, g.S, g.SPT);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
 }
@@ -166,7 +162,7 @@ __global__ __launch_bounds__(256) void k_partials_tiled(const OpPack pack, const
   const unsigned ntiles = (op.entries + 63u) / 64u;
   if (blockIdx.x * tiles_per_block >= ntiles) return; // whole workgroup
 
-  const unsigned long long full = g.S >= 64 ? ~0ull : ((1ull << g.S) - 1ull);
+  const unsigned long long full = full_mask(g.S);
   const unsigned slot = (g.S + 1u) * (g.SPT | 1u);
   double *lstage = tipmat + (size_t)wave * slot, *rstage = tipmat + (size_t)(nw + wave) * slot;
   // one rate category per wave (R <= 4): the tip matrices are staged once for all tiles of the workgroup
@@ -200,10 +196,10 @@ __global__ __launch_bounds__(256) void k_partials_tiled(const OpPack pack, const
     }
     // per-site mode: the children's counts now, so that their entries need not stay in registers to the end
     unsigned below = 0;
-    if (mode == 1 && wave == 0) below = (op.lscaler ? op.lscaler[le] : 0u) + (op.rscaler ? op.rscaler[re] : 0u);
+    if (mode == 1 && wave == 0) below = scaler_sum(op.lscaler, le, op.rscaler, re);
     unsigned long long lmask = 0, rmask = 0;
-    if (LTIP) lmask = tipmap ? tipmap[op.ltip[le]] : (unsigned long long)op.ltip[le];
-    if (RTIP) rmask = tipmap ? tipmap[op.rtip[re]] : (unsigned long long)op.rtip[re];
+    if (LTIP) lmask = tip_mask(tipmap, op.ltip[le]);
+    if (RTIP) rmask = tip_mask(tipmap, op.rtip[re]);
     // Class-compressed nodes (site repeats) keep their CLV ENTRY-CONTIGUOUS on the device - the host's own
     // [entry][rate][states_padded] - for every shape, as the 4 x 4 kernels do (kernels_dna.h): the children of a
     // gathering op are addressed through class maps, and a lane's 20 states of one rate are then 160 contiguous
@@ -386,9 +382,7 @@ __global__ __launch_bounds__(256) void k_partials_tiled(const OpPack pack, const
         if (valid)
         {
           if (small) rescale_rate(k);
-          op.pscaler[(size_t)n * g.R + k] = (op.lscaler ? op.lscaler[(size_t)le * g.R + k] : 0u) +
-                                            (op.rscaler ? op.rscaler[(size_t)re * g.R + k] : 0u) +
-                                            (small ? 1u : 0u);
+          op.pscaler[(size_t)n * g.R + k] = scaler_sum_rate(op.lscaler, le, op.rscaler, re, g.R, k) + (small ? 1u : 0u);
         }
       }
       else if (mode == 1)
@@ -446,7 +440,7 @@ __global__ __launch_bounds__(256) void k_edge_tiled(const DevEdge e, const GenGe
       ce = e.csid ? e.csid[nn] : nn;
     }
     unsigned long long cmask = 0;
-    if (CTIP) cmask = tipmap ? tipmap[e.ctip[ce]] : (unsigned long long)e.ctip[ce];
+    if (CTIP) cmask = tip_mask(tipmap, e.ctip[ce]);
     const bool paos = GATHER && (e.layout & kAosParent), caos = GATHER && !CTIP && (e.layout & kAosLeft); // entry-contiguous ends
     const unsigned espan = g.R * g.SP;
     const double *__restrict__ px = paos ? e.parent + (size_t)pe * espan : e.parent + tiled_base(pe, g.tile_sz);
@@ -454,19 +448,7 @@ __global__ __launch_bounds__(256) void k_edge_tiled(const DevEdge e, const GenGe
     const unsigned pxs = GATHER ? (paos ? 1u : 64u) : 64u; // without GATHER a compile-time constant
     const size_t pks = (GATHER && paos) ? g.SP : (size_t)g.S * 64;
 
-    unsigned scal;
-    if (e.per_rate)
-    {
-      scal = 0xFFFFFFFFu;
-      for (unsigned k = 0; k < g.R; ++k)
-      {
-        const unsigned rs = (e.pscaler ? e.pscaler[(size_t)pe * g.R + k] : 0u) +
-                            (e.cscaler ? e.cscaler[(size_t)ce * g.R + k] : 0u);
-        scal = min(scal, rs);
-      }
-    }
-    else
-      scal = (e.pscaler ? e.pscaler[pe] : 0u) + (e.cscaler ? e.cscaler[ce] : 0u);
+    const unsigned scal = site_scalings(e.pscaler, pe, e.cscaler, ce, g.R, e.per_rate);
 
     double terma = 0.0, terminv = 0.0;
     for (unsigned k = wave; k < g.R; k += nw)
@@ -494,13 +476,7 @@ __global__ __launch_bounds__(256) void k_edge_tiled(const DevEdge e, const GenGe
         for (int i = 0; i < ICH; ++i)
           if (c * ICH + i < g.S) tr = fma(__builtin_nontemporal_load(pk + (size_t)i * pxs) * pi[i], B[i], tr);
       }
-      if (e.per_rate)
-      {
-        const unsigned rs = (e.pscaler ? e.pscaler[(size_t)pe * g.R + k] : 0u) +
-                            (e.cscaler ? e.cscaler[(size_t)ce * g.R + k] : 0u);
-        const unsigned ex = min(rs - scal, PLLGPU_RATE_MAXDIFF);
-        if (ex) tr *= minlh(ex);
-      }
+      if (e.per_rate) tr = rate_scaled(tr, scaler_sum_rate(e.pscaler, pe, e.cscaler, ce, g.R, k), scal);
       const double pinv = e.prop_invar ? e.prop_invar[fi] : 0.0;
       const double w = e.rate_weights[k];
       if (pinv > 0.0)
@@ -552,7 +528,7 @@ __global__ __launch_bounds__(256) void k_create_lookup(double *__restrict__ tabl
   double v = 0.0;
   if (i < S)
   {
-    unsigned long long mj = tipmap ? tipmap[j] : (unsigned long long)j, mk = tipmap ? tipmap[k] : (unsigned long long)k;
+    unsigned long long mj = tip_mask(tipmap, j), mk = tip_mask(tipmap, k);
     const double *lrow = lmat + ((size_t)n * S + i) * SP, *rrow = rmat + ((size_t)n * S + i) * SP;
     double tj = 0.0, tk = 0.0;
     for (unsigned m = 0; m < S; ++m)

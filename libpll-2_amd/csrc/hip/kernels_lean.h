@@ -64,61 +64,24 @@ __global__ __launch_bounds__(256) void k_partials_lean(const OpPack pack, const 
   const unsigned item_first = blockIdx.x * items_per_block;
   if (item_first >= nitems) return; // whole workgroup
   const unsigned item_end = min(item_first + items_per_block, nitems);
-  const unsigned long long full = S >= 64 ? ~0ull : ((1ull << S) - 1ull);
+  const unsigned long long full = full_mask(S);
   // ---- stage: every wave its own rate's two matrices
   {
     double *ML = M + (size_t)(2u * k) * LG::mat, *MR = ML + LG::mat;
     const double *sl = op.lmat + (size_t)k * S * g.SPT, *sr = op.rmat + (size_t)k * S * g.SPT;
-    {
-      // all requests first: a load / wait / write loop made this seven L2 round trips per workgroup
-      constexpr unsigned N = (LG::rows - 1u) * LD, PER = (N + 63u) / 64u;
-      double vl[PER], vr[PER];
-#pragma unroll
-      for (unsigned q = 0; q < PER; ++q)
-      {
-        const unsigned idx = lane + 64u * q, j = idx / LD, i = idx % LD;
-        const bool in = idx < N && j < S && i < S;
-        const size_t off = in ? (size_t)j * g.SPT + i : 0;
-        const double a = sl[off], b = sr[off];
-        vl[q] = in ? a : 0.0;
-        vr[q] = in ? b : 0.0;
-      }
-#pragma unroll
-      for (unsigned q = 0; q < PER; ++q)
-      {
-        const unsigned idx = lane + 64u * q;
-        if (idx < N)
-        {
-          ML[idx] = vl[q];
-          MR[idx] = vr[q];
-        }
-      }
-    }
+    stage_rows_pair<64u, (LG::rows - 1u) * LD>(ML, MR, sl, sr, lane, LD, LG::rows - 1u, S, g.SPT, LD);
     if (LTIP || RTIP)
       for (unsigned c0 = threadIdx.x; c0 < 256u; c0 += blockDim.x)
-      {
-        unsigned ci = kCcAmbiguous;
-        if (c0 < ncodes)
-        {
-          const unsigned long long mk = tipmap[c0];
-          ci = mk == full ? LG::gap_col : __popcll(mk) == 1 ? (unsigned)__ffsll((long long)mk) - 1u : kCcAmbiguous;
-        }
-        CIDX[c0] = (unsigned char)ci;
-      }
+        CIDX[c0] = c0 < ncodes ? tip_column_index(tipmap[c0], full, LG::gap_col) : (unsigned char)kCcAmbiguous;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     if (LTIP || RTIP)
-    {
-      // row sums in ascending j like the reference's set-bit walk (core_partials.c:480-489)
       for (unsigned i = lane; i < 2u * LD; i += 64u)
       {
         double *Mx = i < LD ? ML : MR;
         const unsigned ii = i % LD;
-        double s = 0.0;
-        for (unsigned j = 0; j < S; ++j) s += Mx[j * LD + ii];
-        Mx[LG::gap_col * LD + ii] = s;
+        Mx[LG::gap_col * LD + ii] = sum_ascending(Mx + ii, S, LD);
       }
-    }
   }
   __syncthreads();
 
@@ -174,7 +137,7 @@ __global__ __launch_bounds__(256) void k_partials_lean(const OpPack pack, const 
     if (!GATHER)
     {
       // parent and child entries coincide: 16 bytes per lane, wave-uniform base
-      const double *ub = clv + (size_t)(item >> 1) * g.tile_sz + (size_t)k * S * 64 + (item & 1u) * 32u;
+      const double *ub = mfma_item_rows(clv, item, k, g);
 #pragma unroll
       for (int jg = 0; jg < NG; ++jg)
       {
@@ -213,49 +176,9 @@ __global__ __launch_bounds__(256) void k_partials_lean(const OpPack pack, const 
   // D = P x for the lane's states of both entries
   auto side = [&](const double *Mx, bool tipc, const double (&x)[NG][2], const unsigned (&code)[2], double (&d)[NG][2]) {
     if (tipc)
-    {
-      const unsigned c0 = CIDX[code[0]], c1 = CIDX[code[1]];
-      if (__all(c0 != kCcAmbiguous && c1 != kCcAmbiguous))
-      {
-        const double *p0 = Mx + c0 * LD + row, *p1 = Mx + c1 * LD + row;
-#pragma unroll
-        for (int ig = 0; ig < NG; ++ig)
-        {
-          d[ig][0] = p0[4 * ig];
-          d[ig][1] = p1[4 * ig];
-        }
-        return;
-      }
-      const unsigned long long m0 = tipmap[code[0]], m1 = tipmap[code[1]];
-#pragma unroll
-      for (int ig = 0; ig < NG; ++ig) d[ig][0] = d[ig][1] = 0.0;
-#pragma unroll
-      for (int jg = 0; jg < NG; ++jg)
-      {
-        const double x0 = mfma_x<true>(nullptr, m0, S, 4 * jg + row), x1 = mfma_x<true>(nullptr, m1, S, 4 * jg + row);
-#pragma unroll
-        for (int ig = 0; ig < NG; ++ig)
-        {
-          const double a = Mx[afrag + 4 * jg * LD + 4 * ig];
-          d[ig][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, x0, d[ig][0], 0, 0, 0);
-          d[ig][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, x1, d[ig][1], 0, 0, 0);
-        }
-      }
-      return;
-    }
-#pragma unroll
-    for (int ig = 0; ig < NG; ++ig) d[ig][0] = d[ig][1] = 0.0;
-#pragma unroll
-    for (int jg = 0; jg < NG; ++jg)
-    {
-#pragma unroll
-      for (int ig = 0; ig < NG; ++ig)
-      {
-        const double a = Mx[afrag + 4 * jg * LD + 4 * ig];
-        d[ig][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, x[jg][0], d[ig][0], 0, 0, 0);
-        d[ig][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, x[jg][1], d[ig][1], 0, 0, 0);
-      }
-    }
+      mfma_rows_tip_side<NG, LD>(Mx, tipmap, code, CIDX[code[0]], CIDX[code[1]], S, row, Mx + afrag, d);
+    else
+      mfma_rows_contract<NG, LD>(Mx + afrag, x, d);
   };
 
   Item cur, nxt;
@@ -287,14 +210,13 @@ __global__ __launch_bounds__(256) void k_partials_lean(const OpPack pack, const 
     {
       if (k == 0 && row == 0)
 #pragma unroll
-        for (int sg = 0; sg < 2; ++sg) below[sg] = (op.lscaler ? op.lscaler[cur.le[sg]] : 0u) + (op.rscaler ? op.rscaler[cur.re[sg]] : 0u);
+        for (int sg = 0; sg < 2; ++sg) below[sg] = scaler_sum(op.lscaler, cur.le[sg], op.rscaler, cur.re[sg]);
     }
     else if (mode == 2)
     {
       if (row == 0)
 #pragma unroll
-        for (int sg = 0; sg < 2; ++sg)
-          below[sg] = (op.lscaler ? op.lscaler[(size_t)cur.le[sg] * R + k] : 0u) + (op.rscaler ? op.rscaler[(size_t)cur.re[sg] * R + k] : 0u);
+        for (int sg = 0; sg < 2; ++sg) below[sg] = scaler_sum_rate(op.lscaler, cur.le[sg], op.rscaler, cur.re[sg], R, k);
     }
 
     double DL[NG][2], DR[NG][2];
@@ -321,13 +243,7 @@ __global__ __launch_bounds__(256) void k_partials_lean(const OpPack pack, const 
     {
       bool scale[2];
 #pragma unroll
-      for (int sg = 0; sg < 2; ++sg)
-      {
-        int sm = small[sg] ? 1 : 0; // an entry's states are spread over the four row groups of the wave
-        sm &= __shfl_xor(sm, 16, 64);
-        sm &= __shfl_xor(sm, 32, 64);
-        scale[sg] = sm != 0;
-      }
+      for (int sg = 0; sg < 2; ++sg) scale[sg] = rows_all(small[sg]);
       if (mode == 1)
       {
         // every rate's answer, through LDS; two flag sets alternate, so one barrier per item
@@ -391,27 +307,7 @@ __global__ __launch_bounds__(256) void k_partials_lean(const OpPack pack, const 
       }
     }
     else
-    {
-      double *ub = op.parent + (size_t)(item >> 1) * g.tile_sz + (size_t)k * S * 64 + (item & 1u) * 32u; // wave-uniform
-#pragma unroll
-      for (int ig = 0; ig < NG; ++ig)
-        if (4u * ig + row < S)
-        {
-          double *q = ub + (lane_off + 256u * ig);
-          if (valid[1])
-          {
-            double2v w;
-            w.x = DL[ig][0];
-            w.y = DL[ig][1];
-            if (LTIP && RTIP)
-              __builtin_nontemporal_store(w, reinterpret_cast<double2v *>(q)); // a tip x tip launch is pure store traffic
-            else
-              *reinterpret_cast<double2v *>(q) = w;
-          }
-          else if (valid[0])
-            q[0] = DL[ig][0];
-        }
-    }
+      mfma_put_rows<NG>(mfma_item_rows(op.parent, item, k, g), lane_off, row, S, valid, DL, LTIP && RTIP); // a tip x tip launch is pure store traffic
     cur = nxt;
     nxt = nn2;
     if (has_next) oc = on;

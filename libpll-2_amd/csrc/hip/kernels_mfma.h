@@ -114,8 +114,8 @@ __device__ __forceinline__ MfmaItem mfma_item(const DevOp &op, const GenGeo &g, 
       gather_entries(op, nn, le, re);
     }
     m.lm[sg] = m.rm[sg] = 0;
-    if (LTIP) m.lm[sg] = tipmap ? tipmap[op.ltip[le]] : (unsigned long long)op.ltip[le];
-    if (RTIP) m.rm[sg] = tipmap ? tipmap[op.rtip[re]] : (unsigned long long)op.rtip[re];
+    if (LTIP) m.lm[sg] = tip_mask(tipmap, op.ltip[le]);
+    if (RTIP) m.rm[sg] = tip_mask(tipmap, op.rtip[re]);
     m.lb[sg] = LTIP ? nullptr : op.left + (size_t)(le >> 6) * g.tile_sz + (le & 63u) + (size_t)k * g.S * 64;
     m.rb[sg] = RTIP ? nullptr : op.right + (size_t)(re >> 6) * g.tile_sz + (re & 63u) + (size_t)k * g.S * 64;
   }
@@ -170,6 +170,158 @@ __device__ __forceinline__ void mfma_rowsums_into_padding(double *__restrict__ f
   for (unsigned t = threadIdx.x; t < 4u * NG; t += 256u) frag[((t >> 2) * NG + (t & 3u)) * kFrag + 16u] = rowsum[t];
 }
 
+// row sum i of a matrix staged as fragments, ascending j (kernels_common.h: sum_ascending)
+template <int NG>
+__device__ __forceinline__ double mfma_frag_rowsum(const double *__restrict__ frag, unsigned i, unsigned S)
+{
+  double s = 0.0;
+  for (unsigned j = 0; j < S; ++j) s += frag[((i >> 2) * NG + (j >> 2)) * kFrag + (j & 3u) * 4 + (i & 3u)];
+  return s;
+}
+
+// "every value of the site below 2^-256": a site's states are spread over the four row groups of the wave - AND them
+__device__ __forceinline__ bool rows_all(bool b)
+{
+  int s = b ? 1 : 0;
+  s &= __shfl_xor(s, 16, 64);
+  s &= __shfl_xor(s, 32, 64);
+  return s != 0;
+}
+
+// that decision for (op, rate, entry), where k_mfma_scale_epilogue looks for it
+__device__ __forceinline__ void flag_store(unsigned char *__restrict__ flagbuf, unsigned op, unsigned R, unsigned k, unsigned flag_stride,
+                                           unsigned entry, bool small)
+{
+  flagbuf[((size_t)op * R + k) * flag_stride + entry] = small ? 1u : 0u;
+}
+
+// ---- matrices in the ROW layout (k_partials_mfma_cc, k_partials_lean, k_partials_tt_stream): PT[j][i] as the host
+// stores it, row stride LD, zero rows up to 4 NG, then one row of row sums. Row j IS tip column j, and element (i, k)
+// of A-block (ig, jg) is at (4 jg + k) * LD + 4 ig + i. A lane owns states 4 ig + row of two sites.
+constexpr unsigned kCcAmbiguous = 255u; // column index of a code that is neither one state nor the full gap
+
+// column index of a code's mask: the state, the row sums for the full gap, or "ambiguous"
+__device__ __forceinline__ unsigned char tip_column_index(unsigned long long mk, unsigned long long full, unsigned gap_col)
+{
+  return (unsigned char)(mk == full ? gap_col : __popcll(mk) == 1 ? (unsigned)__ffsll((long long)mk) - 1u : kCcAmbiguous);
+}
+
+// Two matrices of one rate category into LDS, element (j, i) of the nrows x W walked ones to j * LD + i, zero beyond S:
+// thread t of NT issues ALL its requests before the first LDS write (a load / wait / write loop made this seven L2
+// round trips per workgroup in k_partials_lean). MAXN: compile-time bound of nrows * W.
+template <unsigned NT, unsigned MAXN>
+__device__ __forceinline__ void stage_rows_pair(double *ML, double *MR, const double *__restrict__ sl, const double *__restrict__ sr, unsigned t,
+                                                unsigned W, unsigned nrows, unsigned S, unsigned SPT, unsigned LD)
+{
+  constexpr unsigned PER = (MAXN + NT - 1u) / NT;
+  const unsigned N = nrows * W;
+  double vl[PER], vr[PER];
+#pragma unroll
+  for (unsigned q = 0; q < PER; ++q)
+  {
+    const unsigned lin = t + NT * q, j = lin / W, i = lin - j * W;
+    const bool in = lin < N && j < S && i < S;
+    const size_t off = in ? (size_t)j * SPT + i : 0;
+    const double a = sl[off], b = sr[off];
+    vl[q] = in ? a : 0.0;
+    vr[q] = in ? b : 0.0;
+  }
+#pragma unroll
+  for (unsigned q = 0; q < PER; ++q)
+  {
+    const unsigned lin = t + NT * q, j = lin / W, i = lin - j * W;
+    if (lin < N)
+    {
+      ML[j * LD + i] = vl[q];
+      MR[j * LD + i] = vr[q];
+    }
+  }
+}
+
+// D = P x on the matrix pipe; a = the matrix + row * LD + (lane & 3), the lane's element of block (0, 0); x(jg, sg) =
+// the lane's operand for contraction rows 4 jg + row of site sg: a register, or formed when asked for (a tip's 0 / 1)
+template <int NG, unsigned LD, class X>
+__device__ __forceinline__ void mfma_rows_contract_with(const double *a, X &&x, double (&d)[NG][2])
+{
+#pragma unroll
+  for (int ig = 0; ig < NG; ++ig) d[ig][0] = d[ig][1] = 0.0;
+#pragma unroll
+  for (int jg = 0; jg < NG; ++jg)
+  {
+    const double x0 = x(jg, 0), x1 = x(jg, 1);
+#pragma unroll
+    for (int ig = 0; ig < NG; ++ig)
+    {
+      const double c = a[4 * jg * LD + 4 * ig];
+      d[ig][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(c, x0, d[ig][0], 0, 0, 0);
+      d[ig][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(c, x1, d[ig][1], 0, 0, 0);
+    }
+  }
+}
+template <int NG, unsigned LD>
+__device__ __forceinline__ void mfma_rows_contract(const double *a, const double (&x)[NG][2], double (&d)[NG][2])
+{
+  mfma_rows_contract_with<NG, LD>(a, [&](int jg, int sg) { return x[jg][sg]; }, d);
+}
+
+// (P x) for a tip child given by the codes of the lane's two sites and their column indices c0, c1: a column of P (or
+// its row sums) when no site of the wave is ambiguous, else MFMAs on 0/1 operands, like the level kernel. a = Mx +
+// row * LD + (lane & 3) as for mfma_rows_contract (handed in: formed here again, k_partials_mfma_cc<8> spills 12 bytes more)
+template <int NG, unsigned LD>
+__device__ __forceinline__ void mfma_rows_tip_side(const double *Mx, const unsigned long long *__restrict__ tipmap, const unsigned (&code)[2],
+                                                   unsigned c0, unsigned c1, unsigned S, unsigned row, const double *a, double (&d)[NG][2])
+{
+  if (__all(c0 != kCcAmbiguous && c1 != kCcAmbiguous))
+  {
+    const double *p0 = Mx + c0 * LD + row, *p1 = Mx + c1 * LD + row;
+#pragma unroll
+    for (int ig = 0; ig < NG; ++ig)
+    {
+      d[ig][0] = p0[4 * ig];
+      d[ig][1] = p1[4 * ig];
+    }
+    return;
+  }
+  const unsigned long long m[2] = {tipmap[code[0]], tipmap[code[1]]};
+  mfma_rows_contract_with<NG, LD>(a, [&](int jg, int sg) { return mfma_x<true>(nullptr, m[sg], S, 4 * jg + row); }, d);
+}
+
+// where the rows of item `item` (32 entries) of rate k start in a tiled CLV: wave-uniform
+template <class T>
+__device__ __forceinline__ T *mfma_item_rows(T *clv, unsigned item, unsigned k, const GenGeo &g)
+{
+  return clv + (size_t)(item >> 1) * g.tile_sz + (size_t)k * g.S * 64 + (item & 1u) * 32u;
+}
+
+// one CLV row group per state group out: states 4 ig + row of the lane's two ADJACENT sites, 16 bytes at ub + lane_off
+// (= row * 64 + 2 col) + 256 ig; the last entry of an odd count goes alone. stream: pure store traffic, past the caches
+template <int NG>
+__device__ __forceinline__ void mfma_put_rows(double *ub, unsigned lane_off, unsigned row, unsigned S, const bool (&valid)[2],
+                                              const double (&v)[NG][2], bool stream)
+{
+  typedef double __attribute__((ext_vector_type(2))) double2v;
+#pragma unroll
+  for (int ig = 0; ig < NG; ++ig)
+  {
+    if (4u * ig + row < S)
+    {
+      double *q = ub + (lane_off + 256u * ig);
+      if (valid[1])
+      {
+        double2v w;
+        w.x = v[ig][0];
+        w.y = v[ig][1];
+        if (stream)
+          __builtin_nontemporal_store(w, reinterpret_cast<double2v *>(q));
+        else
+          *reinterpret_cast<double2v *>(q) = w;
+      }
+      else if (valid[0])
+        q[0] = v[ig][0];
+    }
+  }
+}
+
 template <int NG, bool LTIP, bool RTIP, bool GATHER>
 __global__ __launch_bounds__(256, NG > 8 ? 2 : 4) void k_partials_mfma(const OpPack pack, const GenGeo g,
                                                           const unsigned long long *__restrict__ tipmap,
@@ -195,7 +347,7 @@ __global__ __launch_bounds__(256, NG > 8 ? 2 : 4) void k_partials_mfma(const OpP
   if (bx * 4u * items_per_wave >= nitems) return; // whole workgroup
   const int mode = op.pscaler ? g.scale_mode : 0;
   const unsigned fragoff = (row * 4u + (lane & 3u));
-  const unsigned long long full = S >= 64 ? ~0ull : ((1ull << S) - 1ull);
+  const unsigned long long full = full_mask(S);
 
   // stage fragments: frag[ig][jg][kk][ii] = P[4ig+ii][4jg+kk] = PT[k][4jg+kk][4ig+ii]
   {
@@ -208,12 +360,7 @@ __global__ __launch_bounds__(256, NG > 8 ? 2 : 4) void k_partials_mfma(const OpP
   {
     if (threadIdx.x < 8 * NG)
     {
-      // row sums in ascending j like the reference's set-bit walk (core_partials.c:480-489)
-      const double *F = threadIdx.x < 4 * NG ? PL : PR;
-      const unsigned i = threadIdx.x % (4 * NG);
-      double s = 0.0;
-      for (unsigned j = 0; j < S; ++j) s += F[((i >> 2) * NG + (j >> 2)) * kFrag + (j & 3u) * 4 + (i & 3u)];
-      RS[threadIdx.x] = s;
+      RS[threadIdx.x] = mfma_frag_rowsum<NG>(threadIdx.x < 4 * NG ? PL : PR, threadIdx.x % (4 * NG), S);
     }
     __syncthreads();
     mfma_rowsums_into_padding<NG>(PL, RS);
@@ -244,6 +391,9 @@ __global__ __launch_bounds__(256, NG > 8 ? 2 : 4) void k_partials_mfma(const OpP
     if (has_next) nxt = mfma_item<LTIP, RTIP, GATHER>(op, g, tipmap, item0 + it + 1, col, k);
 
     double DL[NG][2];
+    // (The two contractions below stay written out: they interleave the next operand's loads with the MFMAs at 238-256
+    // VGPRs - two waves per SIMD for NG = 16, which already spills 20-52 bytes - and a shared function would hand the
+    // placement of those loads to the compiler.)
     // ---- left child: all 16 parent state groups
     const bool lsimple = LTIP && mfma_simple_tips(cur.lm, full);
     if (lsimple)
@@ -355,15 +505,11 @@ __global__ __launch_bounds__(256, NG > 8 ? 2 : 4) void k_partials_mfma(const OpP
     }
     if (mode)
     {
-      // a site's states are spread over the four row groups of the wave: AND them together
 #pragma unroll
       for (int sg = 0; sg < 2; ++sg)
       {
-        int s = small[sg] ? 1 : 0;
-        s &= __shfl_xor(s, 16, 64);
-        s &= __shfl_xor(s, 32, 64);
-        if (row == 0 && cur.valid[sg])
-          flagbuf[((size_t)by * g.R + k) * flag_stride + cur.e[sg]] = (unsigned char)s;
+        const bool s = rows_all(small[sg]);
+        if (row == 0 && cur.valid[sg]) flag_store(flagbuf, by, g.R, k, flag_stride, cur.e[sg], s);
       }
     }
     cur = nxt;
@@ -384,7 +530,7 @@ __global__ __launch_bounds__(256, NG > 8 ? 2 : 4) void k_partials_mfma(const OpP
 // Scaling decisions go to flagbuf for k_mfma_scale_epilogue exactly like k_partials_mfma's.
 // grid: 1-D, XCD-aware (kernels_common.h: xcd_linear), logical order rate category fastest - the four workgroups of a
 // tile block write one contiguous run; LDS 2 x (S + 1) x LD doubles.
-__device__ __forceinline__ unsigned tt_stream_ld(unsigned S) { return (S + 1u) | 1u; }
+__host__ __device__ __forceinline__ unsigned tt_stream_ld(unsigned S) { return (S + 1u) | 1u; } // (the host sizes the launch's LDS with it)
 
 constexpr unsigned kTtStreamThreads = 1024; // sixteen waves share one copy of the matrices: two workgroups per CU = eight waves per SIMD
 
@@ -397,8 +543,8 @@ __device__ __forceinline__ TtCodes tt_stream_codes(const DevOp &op, const unsign
   const unsigned n = tile * 64u + lane;
   const unsigned nn = n < op.entries ? n : op.entries - 1u;
   TtCodes c;
-  c.ml = tipmap ? tipmap[op.ltip[nn]] : (unsigned long long)op.ltip[nn];
-  c.mr = tipmap ? tipmap[op.rtip[nn]] : (unsigned long long)op.rtip[nn];
+  c.ml = tip_mask(tipmap, op.ltip[nn]);
+  c.mr = tip_mask(tipmap, op.rtip[nn]);
   return c;
 }
 
@@ -421,43 +567,18 @@ __global__ __launch_bounds__(kTtStreamThreads) void k_partials_tt_stream(const O
   // the first tile's codes are on their way while the matrices are staged
   TtCodes cur = tt_stream_codes(op, tipmap, tile0 < ntiles ? tile0 : 0u, lane);
   // ---- the two matrices of this rate category: every request before the first LDS write
-  {
-    constexpr unsigned PER = (64u * 64u + kTtStreamThreads - 1u) / kTtStreamThreads;
-    const double *__restrict__ sl = op.lmat + (size_t)k * S * g.SPT, *__restrict__ sr = op.rmat + (size_t)k * S * g.SPT;
-    double vl[PER], vr[PER];
-#pragma unroll
-    for (unsigned q = 0; q < PER; ++q)
-    {
-      const unsigned lin = threadIdx.x + kTtStreamThreads * q, j = lin / S, i = lin - j * S;
-      const bool in = lin < S * S;
-      const size_t off = in ? (size_t)j * g.SPT + i : 0;
-      vl[q] = sl[off];
-      vr[q] = sr[off];
-    }
-#pragma unroll
-    for (unsigned q = 0; q < PER; ++q)
-    {
-      const unsigned lin = threadIdx.x + kTtStreamThreads * q, j = lin / S, i = lin - j * S;
-      if (lin < S * S)
-      {
-        ML[j * LD + i] = vl[q];
-        MR[j * LD + i] = vr[q];
-      }
-    }
-  }
+  stage_rows_pair<kTtStreamThreads, 64u * 64u>(ML, MR, op.lmat + (size_t)k * S * g.SPT, op.rmat + (size_t)k * S * g.SPT, threadIdx.x, S, S, S, g.SPT, LD);
   __syncthreads();
   if (threadIdx.x < 128u && lane < S)
   {
-    // row sums in ascending j (wave 0: left, wave 1: right) into row S
+    // row sums (wave 0: left, wave 1: right) into row S
     double *M = wave == 0u ? ML : MR;
-    double sum = 0.0;
-    for (unsigned j = 0; j < S; ++j) sum += M[j * LD + lane];
-    M[S * LD + lane] = sum;
+    M[S * LD + lane] = sum_ascending(M + lane, S, LD);
   }
   __syncthreads();
 
   const int mode = op.pscaler ? g.scale_mode : 0;
-  const unsigned long long full = S >= 64 ? ~0ull : ((1ull << S) - 1ull);
+  const unsigned long long full = full_mask(S);
   for (unsigned t = 0; t < tiles_per_wave; ++t)
   {
     const unsigned tile = tile0 + t;
@@ -515,7 +636,7 @@ __global__ __launch_bounds__(kTtStreamThreads) void k_partials_tt_stream(const O
         if (valid) out[(size_t)i * 64] = v;
       }
     }
-    if (mode && valid) flagbuf[((size_t)by * g.R + k) * flag_stride + n] = small ? 1u : 0u;
+    if (mode && valid) flag_store(flagbuf, by, g.R, k, flag_stride, n, small);
   }
 }
 
@@ -540,7 +661,7 @@ __global__ __launch_bounds__(256) void k_mfma_scale_epilogue(const OpPack pack, 
   {
     // (the children's counts are requested before the flags are looked at: one memory round trip, not two - the
     // kernel is nothing but latency, 4 of them per 61-state traversal)
-    const unsigned below = (op.lscaler ? op.lscaler[le] : 0u) + (op.rscaler ? op.rscaler[re] : 0u);
+    const unsigned below = scaler_sum(op.lscaler, le, op.rscaler, re);
     bool all = true;
     for (unsigned k = 0; k < R; ++k) all = all && f[(size_t)k * flag_stride];
     if (all)
@@ -554,8 +675,7 @@ __global__ __launch_bounds__(256) void k_mfma_scale_epilogue(const OpPack pack, 
       const bool sm = f[(size_t)k * flag_stride] != 0;
       if (sm)
         for (unsigned q = 0; q < S; ++q) base[((size_t)k * S + q) * 64] *= PLLGPU_SCALE_FACTOR;
-      op.pscaler[(size_t)n * R + k] = (op.lscaler ? op.lscaler[(size_t)le * R + k] : 0u) +
-                                      (op.rscaler ? op.rscaler[(size_t)re * R + k] : 0u) + (sm ? 1u : 0u);
+      op.pscaler[(size_t)n * R + k] = scaler_sum_rate(op.lscaler, le, op.rscaler, re, R, k) + (sm ? 1u : 0u);
     }
   }
 }
@@ -635,15 +755,12 @@ __global__ __launch_bounds__(256) void k_cherry_bits(const CherryTips mats, cons
   {
     const unsigned which = threadIdx.x >> 6, i = threadIdx.x & 63u;
     const double *Mx = which ? MR : ML;
-    double sum = 0.0;
-    if (i < S)
-      for (unsigned j = 0; j < S; ++j) sum += Mx[(size_t)j * ms + i];
-    rowsums[(((size_t)mats.slot[c] * g.R + k) * 2u + which) * 64u + i] = sum;
+    rowsums[(((size_t)mats.slot[c] * g.R + k) * 2u + which) * 64u + i] = i < S ? sum_ascending(Mx + i, S, ms) : 0.0;
   }
   for (unsigned idx = threadIdx.x; idx < ncodes * S; idx += 256u)
   {
     const unsigned code = idx / S, i = idx % S;
-    const unsigned long long mask = tipmap ? tipmap[code] : (unsigned long long)code;
+    const unsigned long long mask = tip_mask(tipmap, code);
     double a = 0.0, b = 0.0;
     // ascending over the set bits; a clear bit adds +0.0, which changes nothing
     for (unsigned m = 0; m < S; ++m)
@@ -670,8 +787,6 @@ struct CherrySlots // by value: where the tables of a launch's cherries are (che
 {
   unsigned short s[2 * kMaxGroups];
 };
-
-constexpr unsigned kCcAmbiguous = 255u; // column index of a code that is neither one state nor the full gap
 
 template <int NG> struct CcGeo
 {
@@ -705,7 +820,6 @@ __global__ __launch_bounds__(256, 4) void k_partials_mfma_cc(const FusePack pack
   }
   typedef CcGeo<NG> CG;
   constexpr unsigned LD = CG::LD;
-  typedef double __attribute__((ext_vector_type(2))) double2v;
   extern __shared__ double lds[];
   double *M = lds;                                                                  // [6][rows][LD]: a.l a.r b.l b.r p.l p.r
   unsigned short *BITS = reinterpret_cast<unsigned short *>(lds + 6u * CG::mat);    // [2][ncodes * ncodes]
@@ -718,8 +832,10 @@ __global__ __launch_bounds__(256, 4) void k_partials_mfma_cc(const FusePack pack
   const unsigned S = g.S;
   const unsigned nitems = (entries + 31u) / 32u;
   if (bx * 4u * items_per_wave >= nitems) return; // whole workgroup
-  const unsigned long long full = S >= 64 ? ~0ull : ((1ull << S) - 1ull);
+  const unsigned long long full = full_mask(S);
   {
+    // (six matrices at once, a request and its LDS write at a time. Left as it is, not stage_rows_pair's requests held in
+    // registers: the kernel sits at its bound of 128 VGPRs = four waves per SIMD, k_partials_mfma_cc<8> spills 272 bytes)
     const double *src[6] = {grp.a.lmat, grp.a.rmat, grp.b.lmat, grp.b.rmat, grp.p.lmat, grp.p.rmat};
     for (unsigned idx = threadIdx.x; idx < (CG::rows - 1u) * LD; idx += 256u)
     {
@@ -738,20 +854,13 @@ __global__ __launch_bounds__(256, 4) void k_partials_mfma_cc(const FusePack pack
       for (unsigned kk = 0; kk < g.R; ++kk) v |= (unsigned)t[(size_t)kk * npairs] << kk;
       BITS[idx] = (unsigned short)v;
     }
-    if (threadIdx.x < ncodes)
-    {
-      const unsigned long long mk = tipmap[threadIdx.x];
-      CIDX[threadIdx.x] = (unsigned char)(mk == full ? CG::gap_col : __popcll(mk) == 1 ? (unsigned)__ffsll((long long)mk) - 1u : kCcAmbiguous);
-    }
+    if (threadIdx.x < ncodes) CIDX[threadIdx.x] = tip_column_index(tipmap[threadIdx.x], full, CG::gap_col);
   }
   __syncthreads();
   if (threadIdx.x < 4u * LD)
   {
-    // row sums in ascending j like the reference's set-bit walk (core_partials.c:480-489)
     const unsigned m = threadIdx.x / LD, i = threadIdx.x % LD;
-    double s = 0.0;
-    for (unsigned j = 0; j < S; ++j) s += M[m * CG::mat + j * LD + i];
-    M[m * CG::mat + CG::gap_col * LD + i] = s;
+    M[m * CG::mat + CG::gap_col * LD + i] = sum_ascending(M + m * CG::mat + i, S, LD);
   }
   __syncthreads();
   const int ma = grp.a.pscaler ? g.scale_mode : 0, mb = grp.b.pscaler ? g.scale_mode : 0, mp = grp.p.pscaler ? g.scale_mode : 0;
@@ -798,37 +907,9 @@ __global__ __launch_bounds__(256, 4) void k_partials_mfma_cc(const FusePack pack
       scale_a[sg] = ma == 1 ? ba == allr : ma == 2 ? ((ba >> k) & 1u) != 0 : false;
       scale_b[sg] = mb == 1 ? bb == allr : mb == 2 ? ((bb >> k) & 1u) != 0 : false;
     }
-    // (P_t x_t) for the lane's states 4 ig + row of both sites: a column of P_t (or its row sums), else MFMAs on 0/1 x
+    // (P_t x_t) for the lane's states 4 ig + row of both sites
     auto tip_side = [&](int t, double (&d)[NG][2]) {
-      const bool simple = __all(cx[t][0] != kCcAmbiguous && cx[t][1] != kCcAmbiguous);
-      if (simple)
-      {
-        const double *c0 = M + t * CG::mat + cx[t][0] * LD + row, *c1 = M + t * CG::mat + cx[t][1] * LD + row;
-#pragma unroll
-        for (int ig = 0; ig < NG; ++ig)
-        {
-          d[ig][0] = c0[4 * ig];
-          d[ig][1] = c1[4 * ig];
-        }
-      }
-      else
-      {
-        const unsigned long long m0 = tipmap[code[t][0]], m1 = tipmap[code[t][1]];
-#pragma unroll
-        for (int ig = 0; ig < NG; ++ig) d[ig][0] = d[ig][1] = 0.0;
-#pragma unroll
-        for (int jg = 0; jg < NG; ++jg)
-        {
-          const double x0 = mfma_x<true>(nullptr, m0, S, 4 * jg + row), x1 = mfma_x<true>(nullptr, m1, S, 4 * jg + row);
-#pragma unroll
-          for (int ig = 0; ig < NG; ++ig)
-          {
-            const double a = afrag[t * CG::mat + 4 * jg * LD + 4 * ig];
-            d[ig][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, x0, d[ig][0], 0, 0, 0);
-            d[ig][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, x1, d[ig][1], 0, 0, 0);
-          }
-        }
-      }
+      mfma_rows_tip_side<NG, LD>(M + t * CG::mat, tipmap, code[t], cx[t][0], cx[t][1], S, row, afrag + t * CG::mat, d);
     };
     auto cherry = [&](int t0, double (&x)[NG][2]) {
       double r[NG][2];
@@ -841,29 +922,8 @@ __global__ __launch_bounds__(256, 4) void k_partials_mfma_cc(const FusePack pack
         x[ig][1] *= r[ig][1];
       }
     };
-    // one CLV row group of an op: states 4 ig + row of the lane's two sites, 16 bytes
     auto put = [&](const FOp &op, const double (&v)[NG][2], bool stream) {
-      double *ub = op.parent + (size_t)(item >> 1) * g.tile_sz + (size_t)k * S * 64 + (item & 1u) * 32u; // wave-uniform
-#pragma unroll
-      for (int ig = 0; ig < NG; ++ig)
-      {
-        if (4u * ig + row < S)
-        {
-          double *q = ub + (lane_off + 256u * ig);
-          if (valid[1])
-          {
-            double2v w;
-            w.x = v[ig][0];
-            w.y = v[ig][1];
-            if (stream)
-              __builtin_nontemporal_store(w, reinterpret_cast<double2v *>(q));
-            else
-              *reinterpret_cast<double2v *>(q) = w;
-          }
-          else if (valid[0])
-            q[0] = v[ig][0];
-        }
-      }
+      mfma_put_rows<NG>(mfma_item_rows(op.parent, item, k, g), lane_off, row, S, valid, v, stream);
     };
     // a cherry's scaler entry: its own decision (children are tips)
     auto put_scaler = [&](const FOp &op, int mode, const bool (&scaled)[2]) {
@@ -896,30 +956,8 @@ __global__ __launch_bounds__(256, 4) void k_partials_mfma_cc(const FusePack pack
     put(grp.b, xb, true);
     // the parent: both contractions from registers
     double DL[NG][2], DR[NG][2];
-#pragma unroll
-    for (int ig = 0; ig < NG; ++ig) DL[ig][0] = DL[ig][1] = DR[ig][0] = DR[ig][1] = 0.0;
-#pragma unroll
-    for (int jg = 0; jg < NG; ++jg)
-    {
-#pragma unroll
-      for (int ig = 0; ig < NG; ++ig)
-      {
-        const double a = afrag[4 * CG::mat + 4 * jg * LD + 4 * ig];
-        DL[ig][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, xa[jg][0], DL[ig][0], 0, 0, 0);
-        DL[ig][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, xa[jg][1], DL[ig][1], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int jg = 0; jg < NG; ++jg)
-    {
-#pragma unroll
-      for (int ig = 0; ig < NG; ++ig)
-      {
-        const double a = afrag[5 * CG::mat + 4 * jg * LD + 4 * ig];
-        DR[ig][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, xb[jg][0], DR[ig][0], 0, 0, 0);
-        DR[ig][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, xb[jg][1], DR[ig][1], 0, 0, 0);
-      }
-    }
+    mfma_rows_contract<NG, LD>(afrag + 4 * CG::mat, xa, DL);
+    mfma_rows_contract<NG, LD>(afrag + 5 * CG::mat, xb, DR);
     bool sp[2] = {true, true};
 #pragma unroll
     for (int ig = 0; ig < NG; ++ig)
@@ -937,10 +975,8 @@ __global__ __launch_bounds__(256, 4) void k_partials_mfma_cc(const FusePack pack
 #pragma unroll
       for (int sg = 0; sg < 2; ++sg)
       {
-        int sm = sp[sg] ? 1 : 0; // a site's states are spread over the four row groups of the wave
-        sm &= __shfl_xor(sm, 16, 64);
-        sm &= __shfl_xor(sm, 32, 64);
-        if (row == 0 && valid[sg]) flagbuf[((size_t)by * g.R + k) * flag_stride + e0 + sg] = (unsigned char)sm;
+        const bool sm = rows_all(sp[sg]);
+        if (row == 0 && valid[sg]) flag_store(flagbuf, by, g.R, k, flag_stride, e0 + sg, sm);
       }
     }
 #pragma unroll
@@ -976,7 +1012,7 @@ __global__ __launch_bounds__(256, 2) void k_edge_mfma(const DevEdge e, const Gen
   const unsigned k = blockIdx.x % R, ib = blockIdx.x / R;
   const unsigned nitems = (e.sites + 31u) / 32u;
   const unsigned fragoff = row * 4u + (lane & 3u);
-  const unsigned long long full = S >= 64 ? ~0ull : ((1ull << S) - 1ull);
+  const unsigned long long full = full_mask(S);
 
   {
     double *const dst[1] = {PM};
@@ -986,13 +1022,7 @@ __global__ __launch_bounds__(256, 2) void k_edge_mfma(const DevEdge e, const Gen
   __syncthreads();
   if (CTIP)
   {
-    if (threadIdx.x < 64)
-    {
-      const unsigned i = threadIdx.x;
-      double s = 0.0;
-      for (unsigned j = 0; j < S; ++j) s += PM[((i >> 2) * 16 + (j >> 2)) * kFrag + (j & 3u) * 4 + (i & 3u)];
-      RS[i] = s;
-    }
+    if (threadIdx.x < 64) RS[threadIdx.x] = mfma_frag_rowsum<16>(PM, threadIdx.x, S);
     __syncthreads();
     mfma_rowsums_into_padding<16>(PM, RS);
     __syncthreads();
@@ -1027,20 +1057,10 @@ __global__ __launch_bounds__(256, 2) void k_edge_mfma(const DevEdge e, const Gen
           pe[sg] = e.psid ? e.psid[nn] : nn;
           ce[sg] = e.csid ? e.csid[nn] : nn;
         }
-        if (CTIP) cm[sg] = tipmap ? tipmap[e.ctip[ce[sg]]] : (unsigned long long)e.ctip[ce[sg]];
+        if (CTIP) cm[sg] = tip_mask(tipmap, e.ctip[ce[sg]]);
         ex[sg] = 1.0;
         if (e.per_rate)
-        {
-          unsigned mn = 0xFFFFFFFFu, own = 0;
-          for (unsigned q = 0; q < R; ++q)
-          {
-            const unsigned rs = (e.pscaler ? e.pscaler[(size_t)pe[sg] * R + q] : 0u) + (e.cscaler ? e.cscaler[(size_t)ce[sg] * R + q] : 0u);
-            mn = min(mn, rs);
-            if (q == k) own = rs;
-          }
-          const unsigned d = min(own - mn, PLLGPU_RATE_MAXDIFF);
-          if (d) ex[sg] = minlh(d);
-        }
+          ex[sg] = rate_scaled(1.0, scaler_sum_rate(e.pscaler, pe[sg], e.cscaler, ce[sg], R, k), scaler_min(e.pscaler, pe[sg], e.cscaler, ce[sg], R));
       }
       double D[16][2];
       const bool simple = CTIP && mfma_simple_tips(cm, full);
@@ -1132,15 +1152,7 @@ __global__ __launch_bounds__(256, 2) void k_edge_mfma(const DevEdge e, const Gen
         pe = e.psid ? e.psid[n] : n;
         ce = e.csid ? e.csid[n] : n;
       }
-      unsigned scal;
-      if (e.per_rate)
-      {
-        scal = 0xFFFFFFFFu;
-        for (unsigned q = 0; q < R; ++q)
-          scal = min(scal, (e.pscaler ? e.pscaler[(size_t)pe * R + q] : 0u) + (e.cscaler ? e.cscaler[(size_t)ce * R + q] : 0u));
-      }
-      else
-        scal = (e.pscaler ? e.pscaler[pe] : 0u) + (e.cscaler ? e.cscaler[ce] : 0u);
+      const unsigned scal = site_scalings(e.pscaler, pe, e.cscaler, ce, R, e.per_rate);
       double terminv = 0.0;
       const int inv = e.invariant ? e.invariant[n] : -1;
       if (inv >= 0 && e.prop_invar)

@@ -1126,6 +1126,20 @@ static void with_index(unsigned i, F &&fn, std::integer_sequence<int, I...>)
   ((i == (unsigned)I ? (void)fn(Int<I>()) : (void)0), ...);
 }
 
+// the accumulator chunk of the FMA kernels (c->ich: 4, 8, 16, 20, anything else runs as 32) -> fn(Int<ICH>)
+template <class F>
+static void with_ich(int ich, F &&fn)
+{
+  switch (ich)
+  {
+    case 4: fn(Int<4>()); break;
+    case 8: fn(Int<8>()); break;
+    case 16: fn(Int<16>()); break;
+    case 20: fn(Int<20>()); break;
+    default: fn(Int<32>()); break;
+  }
+}
+
 // the chain kernels (kernels_dna.h): the scaling mode and which fetch groups a chain's steps issue (ChainLaunchRec::variant)
 // -> fn(SMV, C0, S1, C1). One table for the chain launches and for the edge kernels that take held chains over: they
 // must agree on it.
@@ -1366,7 +1380,6 @@ static bool launch_wide(pllgpu_ctx *c, const OpPack &pack, unsigned nops, unsign
   return true;
 }
 
-static inline unsigned tt_stream_ld_host(unsigned S) { return (S + 1u) | 1u; } // (kernels_mfma.h: tt_stream_ld)
 
 // Does a matrix-pipe launch rescale, and where do its kernels leave the flag bytes that k_mfma_scale_epilogue reads.
 // min_bytes: k_partials_mfma_wide forms a buffer descriptor over the block even when nothing is rescaled (size 0, every
@@ -1440,7 +1453,7 @@ static int launch_mfma_t(pllgpu_ctx *c, const OpPack &pack, unsigned nops, unsig
     tpw = std::max(1u, tpw);
     const unsigned nx = (tiles + nw * tpw - 1u) / (nw * tpw);
     const unsigned S = c->gg.S;
-    const size_t lds = 2u * (size_t)(S + 1u) * tt_stream_ld_host(S) * sizeof(double);
+    const size_t lds = 2u * (size_t)(S + 1u) * tt_stream_ld(S) * sizeof(double);
     raise_lds_limit((const void *)k_partials_tt_stream, c->device, lds);
     hipLaunchKernelGGL(k_partials_tt_stream, xcd_grid(nx, nops, R), dim3(kTtStreamThreads), lds, c->stream, pack, c->gg, tipmap_ptr(c), tpw, s.flags, s.fstride, nx, nops, c->xcd_order);
     launch_scale_epilogue(c, pack, nops, maxent, s, false);
@@ -1629,14 +1642,7 @@ static int launch_partials(pllgpu_ctx *c, const OpPack &pack, unsigned nops, uns
   else if (c->lean && (kind == 0 || c->tipmap_set) && lean_serves(c, pack, nops, kind, gather))
     return launch_lean(c, pack, nops, maxent, kind, gather);
   else
-    switch (c->ich)
-    {
-      case 4: launch_generic<4>(c, pack, nops, maxent, kind, gather); break;
-      case 8: launch_generic<8>(c, pack, nops, maxent, kind, gather); break;
-      case 16: launch_generic<16>(c, pack, nops, maxent, kind, gather); break;
-      case 20: launch_generic<20>(c, pack, nops, maxent, kind, gather); break;
-      default: launch_generic<32>(c, pack, nops, maxent, kind, gather); break;
-    }
+    with_ich(c->ich, [&](auto ICH) { launch_generic<ICH()>(c, pack, nops, maxent, kind, gather); });
   return 0;
 }
 
@@ -2142,14 +2148,7 @@ static int launch_edge(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather, const 
     // one tile per workgroup pass (the waves split its rate categories), tpw tiles per workgroup
     const unsigned tpw = (tiles + max_blocks - 1) / max_blocks;
     const unsigned blocks = (tiles + tpw - 1) / tpw;
-    switch (c->ich)
-    {
-      case 4: launch_edge_generic<4>(c, e, blocks, tpw, ctip, gather); break;
-      case 8: launch_edge_generic<8>(c, e, blocks, tpw, ctip, gather); break;
-      case 16: launch_edge_generic<16>(c, e, blocks, tpw, ctip, gather); break;
-      case 20: launch_edge_generic<20>(c, e, blocks, tpw, ctip, gather); break;
-      default: launch_edge_generic<32>(c, e, blocks, tpw, ctip, gather); break;
-    }
+    with_ich(c->ich, [&](auto ICH) { launch_edge_generic<ICH()>(c, e, blocks, tpw, ctip, gather); });
   }
   return 0;
 }
@@ -2535,14 +2534,7 @@ static void launch_ancestral(pllgpu_ctx *c, const DevAncestral &a, bool ctip)
   }
   const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
   const unsigned blocks = (tiles + tpw - 1) / tpw;
-  switch (c->ich)
-  {
-    case 4: launch_ancestral_generic<4>(c, a, blocks, tpw, ctip); break;
-    case 8: launch_ancestral_generic<8>(c, a, blocks, tpw, ctip); break;
-    case 16: launch_ancestral_generic<16>(c, a, blocks, tpw, ctip); break;
-    case 20: launch_ancestral_generic<20>(c, a, blocks, tpw, ctip); break;
-    default: launch_ancestral_generic<32>(c, a, blocks, tpw, ctip); break;
-  }
+  with_ich(c->ich, [&](auto ICH) { launch_ancestral_generic<ICH()>(c, a, blocks, tpw, ctip); });
 }
 
 extern "C" int pllgpu_node_ancestral(pllgpu_ctx_t *c, const pllgpu_edge_t *ed, double *host_out, void *device_out)
