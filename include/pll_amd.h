@@ -70,6 +70,7 @@ extern "C" {
 #define PLL_ERROR_INVAR_NONEFOUND 120
 #define PLL_ERROR_AB_INVALIDMETHOD 121
 #define PLL_ERROR_AB_NOSUPPORT 122
+#define PLL_ERROR_STEPWISE_UNSUPPORTED 129 /* src/pll.h:186 */
 #define PLL_ERROR_EINVAL 130
 #define PLL_ERROR_MSA_EMPTY 131
 #define PLL_ERROR_MSA_MAP_INVALID 132
@@ -168,6 +169,37 @@ typedef struct pll_msa_s
   char **sequence;
   char **label;
 } pll_msa_t;
+
+/* src/pll.h:468-492; sizeof == 104, offsets asserted in csrc/host/abi_check.c. Only the "fast unweighted parsimony"
+ * fields are filled by this library (pll_fastparsimony_init); the weighted (Sankoff) fields stay zero. */
+typedef struct pll_parsimony_s
+{
+  unsigned int tips;
+  unsigned int inner_nodes;
+  unsigned int sites;
+  unsigned int states;
+  unsigned int attributes;
+  size_t alignment;
+  unsigned int **packedvector; /* host mirror of the device vectors, see pll_gpu_sync_parsimony below */
+  unsigned int *node_cost;     /* host mirror of the device costs */
+  unsigned int packedvector_count;
+  unsigned int const_cost;
+  int *informative;
+  unsigned int informative_count;
+  unsigned int score_buffers;
+  unsigned int ancestral_buffers;
+  double *score_matrix;
+  double **sbuffer;
+  unsigned int **anc_states;
+} pll_parsimony_t;
+
+/* src/pll.h:495-500; three unsigned int, sizeof == 12 */
+typedef struct pll_pars_buildop_s
+{
+  unsigned int parent_score_index;
+  unsigned int child1_score_index;
+  unsigned int child2_score_index;
+} pll_pars_buildop_t;
 
 /* ---- printers used by the reference's examples and tests (src/pll.h:2590-2600, src/output.c) -- */
 void pll_show_pmatrix(const pll_partition_t *partition, unsigned int index, unsigned int float_precision);
@@ -287,6 +319,73 @@ int pll_compute_node_ancestral_extbuf(pll_partition_t *partition, unsigned int n
                                       unsigned int other_clv_index, int other_scaler_index, unsigned int pmatrix_index,
                                       const unsigned int *freqs_indices, double *ancestral, double *temp_clv,
                                       unsigned int *temp_scaler, double *ident_pmat);
+
+/* ---- fast (bit-parallel Fitch) parsimony (src/pll.h:2559, :2574-2588; src/fast_parsimony.c, src/parsimony.c:69-115) --
+ * What the reference's randomised stepwise addition is built from (src/stepwise.c:377-434, :507-512). Vectors and node
+ * costs live in HBM; every result is an integer and equals the reference's exactly.
+ *
+ * pll_fastparsimony_init (src/pll.h:2574, src/fast_parsimony.c:523-555): classifies the sites (informative[],
+ * informative_count, const_cost - ambiguity codes count as distinct characters, src/fast_parsimony.c:128-194), packs the
+ * tips into states x packedvector_count words per node (pattern weights as repeated bits, the last word and the padding
+ * words filled with ones; packedvector_count rounded to 4 or 8 words by the partition's PLL_ATTRIB_ARCH_* bits and
+ * pll_hardware, src/fast_parsimony.c:247-264). This is one-off integer set-up, O(tips x sites): it runs ON THE HOST, in C,
+ * and the tip vectors are uploaded once, in one copy. Tip data: partition->tipchars for a PLL_ATTRIB_PATTERN_TIP
+ * partition; otherwise the host CLV mirror of each tip (the indicator CLVs pll_set_tip_states keeps there next to its
+ * tip codes, or what pll_set_tip_clv stored; refreshed from the device first if the device copy is newer). More than 20
+ * states without PLL_ATTRIB_PATTERN_TIP: NULL, PLL_ERROR_STEPWISE_UNSUPPORTED, as in the reference.
+ * Deliberate differences: (1) a PLL_ATTRIB_SITE_REPEATS partition is refused with PLL_ERROR_GPU_UNSUPPORTED (the
+ * applications build a separate partition without repeats for parsimony); (2) the inner-node mirrors packedvector[i]
+ * are zero-filled at init, the reference leaves them uninitialised.
+ * The structure is independent of the partition afterwards (the partition may be destroyed): it owns a device record -
+ * the partition's device, a stream of its own, one block for all tips + 3 * inner_nodes vectors and the node costs - kept
+ * in a side table keyed by the structure's address. Under PLL_AMD_HOST_ONLY=1 the host fields (tip vectors included) are
+ * filled and no device is touched.
+ *
+ * Failure convention (the reference has none): a device failure sets pll_errno = PLL_ERROR_GPU_RUNTIME, an index >=
+ * tips + 3 * inner_nodes or a structure this library did not create PLL_ERROR_PARAM_INVALID, a structure without a device
+ * behind it (host-only) PLL_ERROR_GPU_UNAVAILABLE; a score is then UINT_MAX, an update does nothing. */
+pll_parsimony_t *pll_fastparsimony_init(const pll_partition_t *partition);
+/* src/pll.h:2576, src/fast_parsimony.c:709-717. Asynchronous on the structure's stream. The result equals executing the
+ * list in order: the host assigns dependency levels that honour read-after-write, write-after-read and write-after-write
+ * between the entries (an entry whose parent is one of its own children is legal, as in the reference), and every level
+ * is ONE kernel launch - all its operations form one grid - plus one memset per call. */
+void pll_fastparsimony_update_vectors(pll_parsimony_t *parsimony, const pll_pars_buildop_t *operations, unsigned int count);
+/* src/pll.h:2587-2588, :2594-2595; src/fast_parsimony.c:458-521, :557-609: one-operation forms of the above. The reference's
+ * _sse / _avx / _avx2 names are not exported, like those of the core functions. */
+void pll_fastparsimony_update_vector(pll_parsimony_t *parsimony, const pll_pars_buildop_t *op);
+void pll_fastparsimony_update_vector_4x4(pll_parsimony_t *parsimony, const pll_pars_buildop_t *op);
+/* src/pll.h:2583, src/fast_parsimony.c:719-773: mismatches between the two vectors + both node costs + const_cost.
+ * Synchronous: one launch and a 4-byte copy back. */
+unsigned int pll_fastparsimony_edge_score(const pll_parsimony_t *parsimony, unsigned int node1_score_index,
+                                          unsigned int node2_score_index);
+unsigned int pll_fastparsimony_edge_score_4x4(const pll_parsimony_t *parsimony, unsigned int node1_score_index,
+                                              unsigned int node2_score_index); /* src/pll.h:2590, src/fast_parsimony.c:405-456 */
+/* src/pll.h:2580, src/fast_parsimony.c:776-781: node_cost[root_index] + const_cost. No launch, a 4-byte copy back. */
+unsigned int pll_fastparsimony_root_score(const pll_parsimony_t *parsimony, unsigned int root_index);
+/* src/pll.h:2559, src/parsimony.c:69-115. Releases the device record. A structure the library has no record of (one made
+ * by another library's pll_parsimony_create or pll_fastparsimony_init, which reach this symbol under LD_PRELOAD) is freed
+ * exactly as the reference frees it, the weighted-parsimony buffers included. NULL: nothing. */
+void pll_parsimony_destroy(pll_parsimony_t *parsimony);
+/* New. packedvector[node] and node_cost[node] are a lazily refreshed host mirror in the reference's layout: this
+ * downloads one node (node < 0: all). Same contract as pll_gpu_sync_clv. */
+int pll_gpu_sync_parsimony(pll_parsimony_t *parsimony, int node);
+/* New. scores[i] = pll_fastparsimony_edge_score(parsimony, pairs[2i], pairs[2i+1]) for i < count: one launch (the pairs
+ * on a grid axis) and one copy back. PLL_SUCCESS / PLL_FAILURE + pll_errno; nothing is written on failure. */
+int pll_gpu_fastparsimony_edge_scores(const pll_parsimony_t *parsimony, const unsigned int *pairs, unsigned int count,
+                                      unsigned int *scores);
+/* New: all candidate edges of one stepwise-addition step at once. scores[i] = score of the tree that results from
+ * inserting `node` into the edge whose two facing vectors are a = edges[2i], b = edges[2i+1]. With F(a,b) the Fitch
+ * parent vector and U(x,y) the number of bit positions where no state is shared:
+ *   scores[i] = cost[a] + cost[b] + cost[node] + U(a,b) + U(F(a,b), node) + const_cost
+ * - exactly what the reference returns for pll_fastparsimony_update_vector({tmp, a, b}) followed by
+ * pll_fastparsimony_edge_score(tmp, node) (src/stepwise.c:507-512). F(a,b) never leaves the registers, nothing is written
+ * but the scores; one launch and one copy back for all edges. */
+int pll_gpu_fastparsimony_insertion_scores(const pll_parsimony_t *parsimony, unsigned int node, const unsigned int *edges,
+                                           unsigned int count, unsigned int *scores);
+/* kernel launches of the last pll_fastparsimony_* / pll_gpu_fastparsimony_* call on the structure */
+unsigned int pll_gpu_fastparsimony_last_launch_count(const pll_parsimony_t *parsimony);
+/* wait for everything enqueued on the structure's stream */
+int pll_gpu_synchronize_parsimony(pll_parsimony_t *parsimony);
 
 /* ---- the flat core seam of the hot path (src/pll.h:1049-1177 and :1295-1414; bodies in
  * src/core_partials.c:48-1210, src/core_likelihood.c:24-1496) ----------------------------------

@@ -260,6 +260,43 @@ int pllgpu_create_lookup(pllgpu_ctx_t *ctx, double *lookup_host, const double *l
 int pllgpu_tt_from_lookup(pllgpu_ctx_t *ctx, double *parent_host, const unsigned char *left_codes,
                           const unsigned char *right_codes, const double *lookup_host, unsigned int sites, unsigned int ncodes);
 
+/* ---- fast parsimony (src/fast_parsimony.c; csrc/hip/kernels_parsimony.h) ----------------------------------------
+ * A record of its own, independent of any pllgpu_ctx (the reference's pll_parsimony_t outlives the partition it was
+ * made from): a device, a stream and one block holding the packed vectors of `nodes` nodes - `states` rows of `words`
+ * 32-bit words each, state-major as in the reference - and their costs. Vectors and costs start as zero. Node indices
+ * are checked against `nodes` before anything is launched. */
+typedef struct pllgpu_pars pllgpu_pars_t;
+pllgpu_pars_t *pllgpu_pars_create(int device, unsigned int states, unsigned int words, unsigned int nodes);
+void pllgpu_pars_destroy(pllgpu_pars_t *pars);
+/* host[n] = the vector of node n in the reference's layout ([states][words], src/fast_parsimony.c:286-360), for
+ * n in [first, first + count): one copy for all of them. Both synchronise. download also fills cost_host[n]. */
+int pllgpu_pars_upload(pllgpu_pars_t *pars, unsigned int first, unsigned int count, unsigned int *const *host);
+int pllgpu_pars_download(pllgpu_pars_t *pars, unsigned int first, unsigned int count, unsigned int *const *host,
+                         unsigned int *cost_host);
+/* replaces pll_fastparsimony_update_vector[_4x4] (src/fast_parsimony.c:458-521, :557-609) for a whole list: ops sorted
+ * by level, the ops of one level mutually independent (an op may name its parent as one of its children). One memset
+ * and one launch per level; asynchronous on the record's stream. */
+typedef struct pllgpu_pars_op
+{
+  unsigned int parent, child1, child2;
+  unsigned int level;
+} pllgpu_pars_op_t;
+int pllgpu_pars_update(pllgpu_pars_t *pars, const pllgpu_pars_op_t *ops, unsigned int count);
+/* replaces pll_fastparsimony_edge_score[_4x4] (src/fast_parsimony.c:405-456, :611-648) for `count` pairs
+ * (pairs[2i], pairs[2i+1]): mismatches + both costs + const_cost. One launch, one copy back; synchronises. */
+int pllgpu_pars_edge_scores(pllgpu_pars_t *pars, const unsigned int *pairs, unsigned int count, unsigned int const_cost,
+                            unsigned int *scores_host);
+/* replaces the update_vector + edge_score pair of a stepwise-addition step (src/stepwise.c:507-512) for `count`
+ * candidate edges (edges[2i], edges[2i+1]) and one node; the parent vector of each edge stays in registers. One
+ * launch, one copy back; synchronises. */
+int pllgpu_pars_insertion_scores(pllgpu_pars_t *pars, unsigned int node, const unsigned int *edges, unsigned int count,
+                                 unsigned int const_cost, unsigned int *scores_host);
+/* what pll_fastparsimony_root_score reads (src/fast_parsimony.c:776-781): four bytes back, no launch; synchronises */
+int pllgpu_pars_node_cost(pllgpu_pars_t *pars, unsigned int node, unsigned int *cost_host);
+int pllgpu_pars_synchronize(pllgpu_pars_t *pars);
+/* kernel launches of the last update / scores call on the record */
+unsigned int pllgpu_pars_last_launch_count(const pllgpu_pars_t *pars);
+
 /* ---- the exchange of a site-sharded run (pll_gpu_edge_loglikelihood_allreduce) ---------------- */
 /* make the context's device the calling thread's current one while a collective library enqueues on the context's
  * stream from the host side of this boundary; *previous (-1: nothing changed) goes to pllgpu_leave_device afterwards */

@@ -28,6 +28,7 @@
 #include "kernels_lean.h"
 #include "kernels_repeats.h"
 #include "kernels_ancestral.h"
+#include "kernels_parsimony.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
@@ -3546,3 +3547,286 @@ extern "C" int pllgpu_repeats_classes(pllgpu_ctx_t *c, const pllgpu_repop_t *ops
   HIP_TRY(hipGetLastError());
   return 0;
 }
+
+// ---- fast parsimony (src/fast_parsimony.c): kernels_parsimony.h --------------------------------------------------
+// A record of its own, not a pllgpu_ctx: the reference's pll_parsimony_t is independent of the partition it was made
+// from, so it owns its stream and ONE device block: [nodes][states][stride] vector words, then the node costs.
+struct pllgpu_pars
+{
+  int device = 0;
+  hipStream_t stream = nullptr;
+  unsigned states = 0, words = 0, stride = 0, nodes = 0;
+  unsigned *block = nullptr;  // vectors, then costs
+  unsigned *cost = nullptr;   // block + nodes * states * stride
+  unsigned *args = nullptr;   // per-call arguments and results: accumulators or scores, then ops / pairs
+  unsigned char *args_host = nullptr; // pinned: where a call writes its ops / pairs before they are copied up
+  size_t args_bytes = 0;
+  hipEvent_t args_copied = nullptr;   // the last copy out of args_host has been made
+  unsigned last_launches = 0;
+  size_t node_words() const { return (size_t)states * stride; }
+};
+
+struct ParsScope // the record's device for the duration of an entry point, the caller's afterwards
+{
+  int prev = -1, rc = 0;
+  explicit ParsScope(const pllgpu_pars *p)
+  {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != p->device)
+    {
+      if (hipSetDevice(p->device) != hipSuccess) rc = fail(PLLGPU_ERUNTIME, "hipSetDevice(%d) failed", p->device);
+    }
+    else prev = -1;
+  }
+  ~ParsScope()
+  {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+#define PARS_ENTER(p)                                              \
+  if (!(p)) return fail(PLLGPU_EINVAL, "null parsimony record");   \
+  ParsScope pars_scope_(p);                                        \
+  if (pars_scope_.rc) return pars_scope_.rc
+
+static int pars_args(pllgpu_pars *p, size_t bytes)
+{
+  if (bytes <= p->args_bytes) return 0;
+  HIP_TRY(hipStreamSynchronize(p->stream)); // whatever still reads the old block
+  if (p->args) (void)hipFree(p->args);
+  if (p->args_host) (void)hipHostFree(p->args_host);
+  p->args = nullptr;
+  p->args_host = nullptr;
+  p->args_bytes = 0;
+  bytes = (bytes + 4095) & ~(size_t)4095;
+  HIP_TRY(hipMalloc((void **)&p->args, bytes));
+  HIP_TRY(hipHostMalloc((void **)&p->args_host, bytes, hipHostMallocDefault));
+  p->args_bytes = bytes;
+  return 0;
+}
+
+// copy `bytes` at args_host + offset to the same offset of the device block, in stream order. The caller has waited for
+// args_copied before writing there: a call that returns early (update) leaves its copy in flight
+static int pars_args_up(pllgpu_pars *p, size_t offset, size_t bytes)
+{
+  HIP_TRY(hipMemcpyAsync(reinterpret_cast<unsigned char *>(p->args) + offset, p->args_host + offset, bytes, hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipEventRecord(p->args_copied, p->stream));
+  return 0;
+}
+
+// the instantiation that serves a state count (kernels_parsimony.h): fn(SMAX, W, STATES) as integral constants
+template <int N>
+using pars_int = std::integral_constant<int, N>;
+template <class F>
+static void pars_variant(unsigned states, F &&fn)
+{
+  if (states == 4) fn(pars_int<4>(), pars_int<4>(), pars_int<4>());
+  else if (states <= 20) fn(pars_int<20>(), pars_int<4>(), pars_int<0>());
+  else fn(pars_int<64>(), pars_int<1>(), pars_int<0>());
+}
+
+static dim3 pars_grid(const pllgpu_pars *p, unsigned items)
+{
+  const unsigned w = p->states <= 20 ? 4u : 1u; // pars_variant's W
+  const unsigned columns = (p->words + w - 1) / w;
+  const unsigned bx = std::min(kParsMaxBlocksX, std::max(1u, (columns + kParsThreads - 1) / kParsThreads));
+  return dim3(bx, std::min(items, 32768u), 1);
+}
+
+extern "C" pllgpu_pars_t *pllgpu_pars_create(int device, unsigned states, unsigned words, unsigned nodes)
+{
+  if (states < 2 || states > 64 || nodes == 0 || words >= (1u << 26))
+  {
+    fail(PLLGPU_EUNSUPPORTED, "parsimony: unsupported shape: states=%u (2..64) words=%u nodes=%u", states, words, nodes);
+    return nullptr;
+  }
+  pllgpu_pars *p = new pllgpu_pars();
+  p->device = device;
+  p->states = states;
+  p->words = words;
+  p->stride = (words + 3u) & ~3u;
+  p->nodes = nodes;
+  ParsScope scope(p);
+  const size_t vec_words = (size_t)nodes * p->node_words();
+  const size_t bytes = (vec_words + nodes) * sizeof(unsigned);
+  bool ok = scope.rc == 0 && hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) == hipSuccess &&
+            hipEventCreateWithFlags(&p->args_copied, hipEventDisableTiming) == hipSuccess && hipMalloc((void **)&p->block, bytes) == hipSuccess;
+  // inner vectors and every cost start as zero (the reference leaves inner vectors uninitialised)
+  ok = ok && hipMemsetAsync(p->block, 0, bytes, p->stream) == hipSuccess && hipStreamSynchronize(p->stream) == hipSuccess;
+  if (!ok)
+  {
+    fail(PLLGPU_ENOMEM, "parsimony: cannot set up %zu bytes on device %d: %s", bytes, device, hipGetErrorString(hipGetLastError()));
+    if (p->block) (void)hipFree(p->block);
+    if (p->args_copied) (void)hipEventDestroy(p->args_copied);
+    if (p->stream) (void)hipStreamDestroy(p->stream);
+    delete p;
+    return nullptr;
+  }
+  p->cost = p->block + vec_words;
+  return p;
+}
+
+extern "C" void pllgpu_pars_destroy(pllgpu_pars_t *p)
+{
+  if (!p) return;
+  ParsScope scope(p);
+  if (p->stream) (void)hipStreamSynchronize(p->stream);
+  if (p->args) (void)hipFree(p->args);
+  if (p->args_host) (void)hipHostFree(p->args_host);
+  if (p->block) (void)hipFree(p->block);
+  if (p->args_copied) (void)hipEventDestroy(p->args_copied);
+  if (p->stream) (void)hipStreamDestroy(p->stream);
+  delete p;
+}
+
+extern "C" int pllgpu_pars_upload(pllgpu_pars_t *p, unsigned first, unsigned count, unsigned *const *host)
+{
+  PARS_ENTER(p);
+  if (first + count > p->nodes || first + count < first) return fail(PLLGPU_EINVAL, "parsimony upload: nodes %u+%u of %u", first, count, p->nodes);
+  if (!count || !p->words) return 0;
+  // one copy for all nodes: the host rows (packedvector_count words) are laid into device rows (stride words)
+  std::vector<unsigned> staged((size_t)count * p->node_words(), ~0u);
+  for (unsigned n = 0; n < count; ++n)
+    for (unsigned s = 0; s < p->states; ++s)
+      memcpy(&staged[(size_t)n * p->node_words() + (size_t)s * p->stride], host[first + n] + (size_t)s * p->words, p->words * sizeof(unsigned));
+  HIP_TRY(hipMemcpyAsync(p->block + (size_t)first * p->node_words(), staged.data(), staged.size() * sizeof(unsigned), hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+
+extern "C" int pllgpu_pars_download(pllgpu_pars_t *p, unsigned first, unsigned count, unsigned *const *host, unsigned *cost_host)
+{
+  PARS_ENTER(p);
+  if (first + count > p->nodes || first + count < first) return fail(PLLGPU_EINVAL, "parsimony download: nodes %u+%u of %u", first, count, p->nodes);
+  if (!count) return 0;
+  std::vector<unsigned> staged((size_t)count * p->node_words());
+  if (!staged.empty())
+    HIP_TRY(hipMemcpyAsync(staged.data(), p->block + (size_t)first * p->node_words(), staged.size() * sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipMemcpyAsync(cost_host + first, p->cost + first, count * sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  for (unsigned n = 0; n < count && p->words; ++n)
+    for (unsigned s = 0; s < p->states; ++s)
+      memcpy(host[first + n] + (size_t)s * p->words, &staged[(size_t)n * p->node_words() + (size_t)s * p->stride], p->words * sizeof(unsigned));
+  return 0;
+}
+
+extern "C" int pllgpu_pars_update(pllgpu_pars_t *p, const pllgpu_pars_op_t *ops, unsigned count)
+{
+  PARS_ENTER(p);
+  p->last_launches = 0;
+  if (!count || !p->words) return 0; // no informative site: every vector is empty and every cost stays 0
+  for (unsigned i = 0; i < count; ++i)
+    if (ops[i].parent >= p->nodes || ops[i].child1 >= p->nodes || ops[i].child2 >= p->nodes || (i && ops[i].level < ops[i - 1].level))
+      return fail(PLLGPU_EINVAL, "parsimony update: op %u out of range or not sorted by level", i);
+  // arguments of the call in one block: [count] 64-bit accumulators, then [count] {parent, child1, child2}
+  const size_t acc_bytes = (((size_t)count * sizeof(unsigned long long)) + 15) & ~(size_t)15;
+  if (int rc = pars_args(p, acc_bytes + (size_t)count * sizeof(ParsOp))) return rc;
+  HIP_TRY(hipEventSynchronize(p->args_copied)); // the call before has taken its ops out of args_host (its kernels may still run)
+  ParsOp *hops = reinterpret_cast<ParsOp *>(p->args_host + acc_bytes);
+  for (unsigned i = 0; i < count; ++i) hops[i] = ParsOp{ops[i].parent, ops[i].child1, ops[i].child2};
+  unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->args);
+  ParsOp *dops = reinterpret_cast<ParsOp *>(reinterpret_cast<unsigned char *>(p->args) + acc_bytes);
+  HIP_TRY(hipMemsetAsync(acc, 0, acc_bytes, p->stream)); // the call's one memset
+  if (int rc = pars_args_up(p, acc_bytes, (size_t)count * sizeof(ParsOp))) return rc;
+  for (unsigned i = 0; i < count;)
+  {
+    unsigned j = i;
+    while (j < count && ops[j].level == ops[i].level) ++j;
+    const dim3 grid = pars_grid(p, j - i);
+    pars_variant(p->states, [&](auto smax, auto w, auto fixed) {
+      hipLaunchKernelGGL((k_pars_update<decltype(smax)::value, decltype(w)::value, decltype(fixed)::value>), grid, dim3(kParsThreads), 0, p->stream, p->block, p->cost, acc + i, dops + i, j - i,
+                         p->states, p->words, p->stride);
+    });
+    ++p->last_launches;
+    i = j;
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// both score calls: pairs up, one memset, one launch, scores back
+template <class Launch>
+static int pars_scores(pllgpu_pars *p, const unsigned *pairs, unsigned count, unsigned *scores_host, Launch &&launch)
+{
+  const size_t score_bytes = (((size_t)count * sizeof(unsigned)) + 15) & ~(size_t)15;
+  if (int rc = pars_args(p, score_bytes + (size_t)count * sizeof(ParsPair))) return rc;
+  unsigned *scores = p->args;
+  ParsPair *dpairs = reinterpret_cast<ParsPair *>(reinterpret_cast<unsigned char *>(p->args) + score_bytes);
+  HIP_TRY(hipEventSynchronize(p->args_copied));
+  memcpy(p->args_host + score_bytes, pairs, (size_t)count * sizeof(ParsPair));
+  HIP_TRY(hipMemsetAsync(scores, 0, score_bytes, p->stream));
+  if (int rc = pars_args_up(p, score_bytes, (size_t)count * sizeof(ParsPair))) return rc;
+  launch(scores, dpairs);
+  p->last_launches = 1;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(scores_host, scores, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+
+static int pars_check_pairs(const pllgpu_pars *p, const unsigned *pairs, unsigned count, const char *who)
+{
+  for (unsigned i = 0; i < 2u * count; ++i)
+    if (pairs[i] >= p->nodes) return fail(PLLGPU_EINVAL, "%s: node %u of %u", who, pairs[i], p->nodes);
+  return 0;
+}
+
+extern "C" int pllgpu_pars_edge_scores(pllgpu_pars_t *p, const unsigned *pairs, unsigned count, unsigned const_cost, unsigned *scores_host)
+{
+  PARS_ENTER(p);
+  p->last_launches = 0;
+  if (!count) return 0;
+  if (int rc = pars_check_pairs(p, pairs, count, "parsimony edge scores")) return rc;
+  if (!p->words)
+  {
+    for (unsigned i = 0; i < count; ++i) scores_host[i] = const_cost; // nothing informative: every cost is 0
+    return 0;
+  }
+  return pars_scores(p, pairs, count, scores_host, [&](unsigned *scores, const ParsPair *dpairs) {
+    const dim3 grid = pars_grid(p, count);
+    pars_variant(p->states, [&](auto smax, auto w, auto fixed) {
+      hipLaunchKernelGGL((k_pars_edge_scores<decltype(smax)::value, decltype(w)::value, decltype(fixed)::value>), grid, dim3(kParsThreads), 0, p->stream, p->block, p->cost, dpairs, count, scores,
+                         const_cost, p->states, p->words, p->stride);
+    });
+  });
+}
+
+extern "C" int pllgpu_pars_insertion_scores(pllgpu_pars_t *p, unsigned node, const unsigned *edges, unsigned count, unsigned const_cost,
+                                            unsigned *scores_host)
+{
+  PARS_ENTER(p);
+  p->last_launches = 0;
+  if (node >= p->nodes) return fail(PLLGPU_EINVAL, "parsimony insertion scores: node %u of %u", node, p->nodes);
+  if (!count) return 0;
+  if (int rc = pars_check_pairs(p, edges, count, "parsimony insertion scores")) return rc;
+  if (!p->words)
+  {
+    for (unsigned i = 0; i < count; ++i) scores_host[i] = const_cost;
+    return 0;
+  }
+  return pars_scores(p, edges, count, scores_host, [&](unsigned *scores, const ParsPair *dedges) {
+    const dim3 grid = pars_grid(p, count);
+    pars_variant(p->states, [&](auto smax, auto w, auto fixed) {
+      hipLaunchKernelGGL((k_pars_insertion_scores<decltype(smax)::value, decltype(w)::value, decltype(fixed)::value>), grid, dim3(kParsThreads), 0, p->stream, p->block, p->cost, node, dedges, count,
+                         scores, const_cost, p->states, p->words, p->stride);
+    });
+  });
+}
+
+extern "C" int pllgpu_pars_node_cost(pllgpu_pars_t *p, unsigned node, unsigned *cost_host)
+{
+  PARS_ENTER(p);
+  p->last_launches = 0;
+  if (node >= p->nodes) return fail(PLLGPU_EINVAL, "parsimony node cost: node %u of %u", node, p->nodes);
+  HIP_TRY(hipMemcpyAsync(cost_host, p->cost + node, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+
+extern "C" int pllgpu_pars_synchronize(pllgpu_pars_t *p)
+{
+  PARS_ENTER(p);
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+
+extern "C" unsigned pllgpu_pars_last_launch_count(const pllgpu_pars_t *p) { return p ? p->last_launches : 0; }

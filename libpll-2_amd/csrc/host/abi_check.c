@@ -70,5 +70,29 @@ AT(pll_operation_t, child2_matrix_index, 24);
 AT(pll_operation_t, child2_scaler_index, 28);
 _Static_assert(sizeof(pll_state_t) == 8, "pll_state_t size");
 
+/* src/pll.h:468-500 */
+_Static_assert(sizeof(pll_parsimony_t) == 104, "pll_parsimony_t size");
+AT(pll_parsimony_t, tips, 0);
+AT(pll_parsimony_t, inner_nodes, 4);
+AT(pll_parsimony_t, sites, 8);
+AT(pll_parsimony_t, states, 12);
+AT(pll_parsimony_t, attributes, 16);
+AT(pll_parsimony_t, alignment, 24);
+AT(pll_parsimony_t, packedvector, 32);
+AT(pll_parsimony_t, node_cost, 40);
+AT(pll_parsimony_t, packedvector_count, 48);
+AT(pll_parsimony_t, const_cost, 52);
+AT(pll_parsimony_t, informative, 56);
+AT(pll_parsimony_t, informative_count, 64);
+AT(pll_parsimony_t, score_buffers, 68);
+AT(pll_parsimony_t, ancestral_buffers, 72);
+AT(pll_parsimony_t, score_matrix, 80);
+AT(pll_parsimony_t, sbuffer, 88);
+AT(pll_parsimony_t, anc_states, 96);
+_Static_assert(sizeof(pll_pars_buildop_t) == 12, "pll_pars_buildop_t size");
+AT(pll_pars_buildop_t, parent_score_index, 0);
+AT(pll_pars_buildop_t, child1_score_index, 4);
+AT(pll_pars_buildop_t, child2_score_index, 8);
+
 /* the extension block must start 8-byte aligned directly behind the public struct */
 _Static_assert(sizeof(pll_partition_t) % 8 == 0, "extension block alignment");

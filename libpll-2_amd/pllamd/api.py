@@ -107,9 +107,43 @@ class Msa(C.Structure):
     _fields_ = [("count", C.c_int), ("length", C.c_int), ("sequence", C.POINTER(C.c_void_p)), ("label", C.POINTER(C.c_void_p))]
 
 
+class Parsimony(C.Structure):
+    """pll_parsimony_t (src/pll.h:468-492)"""
+    _fields_ = [
+        ("tips", C.c_uint),
+        ("inner_nodes", C.c_uint),
+        ("sites", C.c_uint),
+        ("states", C.c_uint),
+        ("attributes", C.c_uint),
+        ("alignment", C.c_size_t),
+        ("packedvector", C.POINTER(c_uint_p)),
+        ("node_cost", c_uint_p),
+        ("packedvector_count", C.c_uint),
+        ("const_cost", C.c_uint),
+        ("informative", C.POINTER(C.c_int)),
+        ("informative_count", C.c_uint),
+        ("score_buffers", C.c_uint),
+        ("ancestral_buffers", C.c_uint),
+        ("score_matrix", c_double_p),
+        ("sbuffer", C.POINTER(c_double_p)),
+        ("anc_states", C.POINTER(c_uint_p)),
+    ]
+
+
+class ParsBuildOp(C.Structure):
+    """pll_pars_buildop_t (src/pll.h:495-500)"""
+    _fields_ = [("parent_score_index", C.c_uint), ("child1_score_index", C.c_uint), ("child2_score_index", C.c_uint)]
+
+
 assert C.sizeof(Partition) == 232 and C.sizeof(Repeats) == 104 and C.sizeof(Operation) == 32
+assert C.sizeof(Parsimony) == 104 and C.sizeof(ParsBuildOp) == 12
 
 PartitionP = C.POINTER(Partition)
+ParsimonyP = C.POINTER(Parsimony)
+ParsBuildOpP = C.POINTER(ParsBuildOp)
+ERROR_PARAM_INVALID, ERROR_STEPWISE_UNSUPPORTED = 113, 129
+ERROR_GPU_UNAVAILABLE, ERROR_GPU_RUNTIME, ERROR_GPU_UNSUPPORTED = 900, 901, 902
+UINT_MAX = 0xFFFFFFFF
 
 # symbol -> (restype, argtypes); the hot path and what feeds it
 _PROTOS = {
@@ -163,6 +197,15 @@ _PROTOS = {
     "pll_resize_repeats_lookup": (None, [PartitionP, C.c_uint]),
     "pll_compress_site_patterns": (c_uint_p, [C.POINTER(C.c_void_p), c_state_p, C.c_int, C.POINTER(C.c_int)]),
     "pll_compress_site_patterns_msa": (c_uint_p, [C.c_void_p, c_state_p, c_uint_p]),
+    # fast parsimony (src/pll.h:2559, :2574-2596)
+    "pll_fastparsimony_init": (ParsimonyP, [PartitionP]),
+    "pll_fastparsimony_update_vectors": (None, [ParsimonyP, ParsBuildOpP, C.c_uint]),
+    "pll_fastparsimony_update_vector": (None, [ParsimonyP, ParsBuildOpP]),
+    "pll_fastparsimony_update_vector_4x4": (None, [ParsimonyP, ParsBuildOpP]),
+    "pll_fastparsimony_edge_score": (C.c_uint, [ParsimonyP, C.c_uint, C.c_uint]),
+    "pll_fastparsimony_edge_score_4x4": (C.c_uint, [ParsimonyP, C.c_uint, C.c_uint]),
+    "pll_fastparsimony_root_score": (C.c_uint, [ParsimonyP, C.c_uint]),
+    "pll_parsimony_destroy": (None, [C.c_void_p]),
 }
 
 # device-residency extension of libpll_amd.so (include/pll_amd.h); absent from other libraries
@@ -202,6 +245,11 @@ _GPU_PROTOS = {
     "pll_gpu_edge_loglikelihood_allreduce": (
         C.c_double, [PartitionP, C.c_void_p, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p]),
     "pll_gpu_rccl_available": (C.c_int, []),
+    "pll_gpu_sync_parsimony": (C.c_int, [ParsimonyP, C.c_int]),
+    "pll_gpu_fastparsimony_edge_scores": (C.c_int, [ParsimonyP, c_uint_p, C.c_uint, c_uint_p]),
+    "pll_gpu_fastparsimony_insertion_scores": (C.c_int, [ParsimonyP, C.c_uint, c_uint_p, C.c_uint, c_uint_p]),
+    "pll_gpu_fastparsimony_last_launch_count": (C.c_uint, [ParsimonyP]),
+    "pll_gpu_synchronize_parsimony": (C.c_int, [ParsimonyP]),
     "pll_gpu_device_count": (C.c_int, []),
     "pll_gpu_available": (C.c_int, []),
 }
@@ -263,6 +311,15 @@ def make_ops(rows):
     for o, r in zip(arr, rows):
         (o.parent_clv_index, o.parent_scaler_index, o.child1_clv_index, o.child1_matrix_index,
          o.child1_scaler_index, o.child2_clv_index, o.child2_matrix_index, o.child2_scaler_index) = [int(x) for x in r]
+    return arr
+
+
+def make_pars_ops(rows):
+    """rows: iterable of (parent, child1, child2) score indices."""
+    rows = list(rows)
+    arr = (ParsBuildOp * max(len(rows), 1))()
+    for o, r in zip(arr, rows):
+        o.parent_score_index, o.child1_score_index, o.child2_score_index = [int(x) for x in r]
     return arr
 
 

@@ -309,6 +309,117 @@ class Session:
         self.close()
 
 
+class ParsimonySession:
+    """A pll_parsimony_t built from an alignment (pll_fastparsimony_init, src/fast_parsimony.c:523-555) and the calls
+    that drive it. ABI only, like Session: the same sequence runs on libpll_amd.so and on the reference; the batched
+    calls and the mirror refresh exist on libpll_amd.so alone."""
+
+    def __init__(self, lib: api.PllLib, states, sequences, charmap, weights=None, attributes=0):
+        self.lib, self.states = lib, int(states)
+        tips, sites = len(sequences), len(sequences[0])
+        # parsimony reads the tips only: one CLV buffer, one of everything else
+        self.partition = lib.pll_partition_create(tips, 1, states, sites, 1, 1, 1, 0, attributes)
+        if not self.partition:
+            raise RuntimeError(f"pll_partition_create failed: [{lib.errno()}] {lib.errmsg()}")
+        self.pars = None
+        try:
+            cmap = (C.c_ulonglong * 256)(*[int(x) for x in charmap])
+            for t, seq in enumerate(sequences):
+                if not lib.pll_set_tip_states(self.partition, t, cmap, bytes(seq)):
+                    raise RuntimeError(f"pll_set_tip_states: [{lib.errno()}] {lib.errmsg()}")
+            if weights is not None:
+                w = np.ascontiguousarray(weights, dtype=np.uint32)
+                lib.pll_set_pattern_weights(self.partition, api.uptr(w))
+            self.pars = lib.pll_fastparsimony_init(self.partition)
+            if not self.pars:
+                raise RuntimeError(f"pll_fastparsimony_init failed: [{lib.errno()}] {lib.errmsg()}")
+        except Exception:
+            self.close()
+            raise
+        self.s = self.pars.contents
+        self.nodes = self.s.tips + 3 * self.s.inner_nodes
+        self.words = self.s.packedvector_count
+
+    def drop_partition(self):
+        """the structure is independent of the partition it came from"""
+        if self.partition:
+            self.lib.pll_partition_destroy(self.partition)
+            self.partition = None
+
+    def update(self, ops, per_op=False):
+        """run (parent, child1, child2) rows; returns the kernel launches the call(s) took (libpll_amd.so) or None"""
+        ops = list(ops)
+        arr = api.make_pars_ops(ops)
+        count = getattr(self.lib, "pll_gpu_fastparsimony_last_launch_count", None)
+        launches = 0
+        if per_op:
+            for i in range(len(ops)):
+                self.lib.pll_fastparsimony_update_vector(self.pars, C.byref(arr[i]))
+                launches += count(self.pars) if count else 0
+        else:
+            self.lib.pll_fastparsimony_update_vectors(self.pars, arr, len(ops))
+            launches = count(self.pars) if count else 0
+        return launches if count else None
+
+    def edge_score(self, a, b):
+        return int(self.lib.pll_fastparsimony_edge_score(self.pars, a, b))
+
+    def root_score(self, n):
+        return int(self.lib.pll_fastparsimony_root_score(self.pars, n))
+
+    def edge_scores(self, pairs):
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        out = np.full(len(pairs), 0xDEADBEEF, dtype=np.uint32)
+        if not self.lib.pll_gpu_fastparsimony_edge_scores(self.pars, api.uptr(pairs), len(pairs), api.uptr(out)):
+            raise RuntimeError(f"pll_gpu_fastparsimony_edge_scores: [{self.lib.errno()}] {self.lib.errmsg()}")
+        return out
+
+    def insertion_scores(self, node, edges):
+        edges = np.ascontiguousarray(edges, dtype=np.uint32).reshape(-1, 2)
+        out = np.full(len(edges), 0xDEADBEEF, dtype=np.uint32)
+        if not self.lib.pll_gpu_fastparsimony_insertion_scores(self.pars, node, api.uptr(edges), len(edges), api.uptr(out)):
+            raise RuntimeError(f"pll_gpu_fastparsimony_insertion_scores: [{self.lib.errno()}] {self.lib.errmsg()}")
+        return out
+
+    def insertion_scores_per_edge(self, node, edges, spare):
+        """the reference's pattern (src/stepwise.c:507-512): update_vector({spare, a, b}) then edge_score(spare, node)"""
+        out = []
+        for a, b in edges:
+            op = api.make_pars_ops([(spare, a, b)])
+            self.lib.pll_fastparsimony_update_vector(self.pars, op)
+            out.append(self.edge_score(spare, node))
+        return np.array(out, dtype=np.uint32)
+
+    def sync(self, node=-1):
+        if self.lib.is_amd and not self.lib.pll_gpu_sync_parsimony(self.pars, node):
+            raise RuntimeError(f"pll_gpu_sync_parsimony: [{self.lib.errno()}] {self.lib.errmsg()}")
+
+    def vector(self, node):
+        """host copy of a node's packed vector, [states][packedvector_count] (call sync() first on libpll_amd.so)"""
+        n = self.states * self.words
+        if n == 0:
+            return np.zeros((self.states, 0), dtype=np.uint32)
+        return api.as_np(self.s.packedvector[node], n, np.uint32).reshape(self.states, self.words).copy()
+
+    def costs(self):
+        return api.as_np(self.s.node_cost, self.nodes, np.uint32).copy()
+
+    def informative(self):
+        return api.as_np(self.s.informative, self.s.sites, np.int32).copy()
+
+    def close(self):
+        if self.pars:
+            self.lib.pll_parsimony_destroy(self.pars)
+            self.pars = None
+        self.drop_partition()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def run_case(lib: api.PllLib, case: Case, arch: int = api.ARCH_AVX2):
     """Full sequence; returns {'clv': {idx: arr}, 'scaler': {idx: arr}, 'lnl': [...],
     'persite': [...], 'root_lnl': [...], 'root_persite': [...]}. CLVs are scaler-free raw values;
