@@ -645,6 +645,39 @@ int pll_gpu_edge_loglikelihood_async(pll_partition_t *partition, unsigned int pa
                                      int parent_scaler_index, unsigned int child_clv_index,
                                      int child_scaler_index, unsigned int matrix_index,
                                      const unsigned int *freqs_indices, double *device_result);
+/* ---- batched insertion log-likelihoods ---------------------------------
+ * "What is the log-likelihood if the subtree is inserted into edge (child1, child2)?" for `count` candidate edges
+ * in one call: the question an SPR move or a placement asks of tens to hundreds of edges. lnl[i] is the value the
+ * reference returns for pll_update_partials with the one operation {tmp, tmp_scaler, child1..., child2...} of
+ * candidate i (src/partials.c:237-291) followed by pll_compute_edge_loglikelihood(partition, tmp, tmp_scaler,
+ * subtree_clv_index, subtree_scaler_index, subtree_matrix_index, freqs_indices, NULL) (src/likelihood.c:586-636),
+ * with tmp a spare inner CLV and scaler. No such slot is needed: the inserted node's CLV and scaling counts exist
+ * inside the kernel only, and nothing in the partition is written - no CLV, scaler, matrix or cached launch plan.
+ * Any of the three ends may be an inner CLV (with or without a scaler), a PLL_ATTRIB_PATTERN_TIP tip or a tip set
+ * through pll_set_tip_states; a scaler index named for a tip is ignored, as the reference's tip kernels do.
+ * All candidates are read in one launch, so both ends of every candidate edge must hold the orientation the caller
+ * means AT THE SAME TIME: a caller computes the "upward" CLV of each edge into a spare clv_buffers slot first
+ * ("Scoring every regraft edge at once"). What the previous pll_update_partials still holds back
+ * is launched first, so a candidate may name a node that traversal produces.
+ * Synchronous; one copy back for all candidates. Each lnl[i] is formed in an order that depends on the site count
+ * alone: it has the same bits whether the candidate is scored alone or among any others, and from run to run.
+ * PLL_SUCCESS, or PLL_FAILURE with pll_errno and lnl untouched: PLL_ERROR_PARAM_INVALID for any index out of range
+ * or a NULL argument with count > 0 (the whole list is checked before anything is flushed or launched);
+ * PLL_ERROR_GPU_UNSUPPORTED for a PLL_ATTRIB_SITE_REPEATS partition (the inserted node has no class map) and for a
+ * partition with an ascertainment-bias correction; PLL_ERROR_GPU_UNAVAILABLE without a device; count == 0 succeeds
+ * without a launch. pll_gpu_last_launch_count reports the launches of the call. */
+typedef struct pll_gpu_insertion
+{
+  unsigned int child1_clv_index;
+  int child1_scaler_index;
+  unsigned int child1_matrix_index;
+  unsigned int child2_clv_index;
+  int child2_scaler_index;
+  unsigned int child2_matrix_index;
+} pll_gpu_insertion_t;
+int pll_gpu_insertion_loglikelihoods(pll_partition_t *partition, unsigned int subtree_clv_index, int subtree_scaler_index,
+                                     unsigned int subtree_matrix_index, const pll_gpu_insertion_t *candidates,
+                                     unsigned int count, const unsigned int *freqs_indices, double *lnl);
 /* pll_compute_node_ancestral (src/pll.h:799-806) without the host round trip: the kernel is enqueued on the
  * partition's stream (pll_gpu_set_stream / pll_gpu_get_stream apply) and leaves the table in the sites * states
  * doubles of DEVICE memory at device_ancestral; nothing is copied back and the call does not wait. A caller that
@@ -725,7 +758,7 @@ int pll_gpu_rccl_available(void);
  * brackets whatever was enqueued in between; returns elapsed milliseconds from stop(). */
 int pll_gpu_timer_start(pll_partition_t *partition);
 double pll_gpu_timer_stop(pll_partition_t *partition);
-/* number of kernel launches issued by the last pll_update_partials call (bench bookkeeping) */
+/* number of kernel launches issued by the last pll_update_partials or pll_gpu_insertion_loglikelihoods call */
 unsigned int pll_gpu_last_launch_count(const pll_partition_t *partition);
 /* site repeats: class-map operations computed on the device (launches = 0) / class kernels launched (launches != 0)
  * since the partition was created. An unchanged tree adds nothing, a topology move the ops of its partial traversal */

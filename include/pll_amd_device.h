@@ -172,6 +172,28 @@ int pllgpu_root_loglikelihood(pllgpu_ctx_t *ctx, unsigned int clv, int scaler, u
                               const unsigned int *freqs_indices, double *persite_host,
                               double *lnl_out);
 
+/* replaces, for `count` candidate edges at once, the pair pll_update_partials with one op into a spare node
+ * (src/partials.c:237-291) + pll_compute_edge_loglikelihood between that node and the subtree end
+ * (src/likelihood.c:586-636): host_out[i] = the log-likelihood with the subtree inserted into candidate i. The inserted
+ * node exists in registers / LDS only (kernels_insertion.h); nothing the context holds is written. Any of the three
+ * ends may be a tip given by codes (*_is_tip; its scaler index is not read). Every index of the whole list is checked
+ * before held work is launched or anything else happens; class-compressed CLVs anywhere in the context and
+ * ascertainment-bias entries are PLLGPU_EUNSUPPORTED. One launch per kInsMaxCands candidates (counted into
+ * pllgpu_last_launch_count), one copy back, one wait; host_out is written only on success. */
+typedef struct pllgpu_insertion
+{
+  unsigned int child1_clv;
+  int child1_scaler;
+  unsigned int child1_matrix;
+  unsigned int child2_clv;
+  int child2_scaler;
+  unsigned int child2_matrix;
+  unsigned int child1_is_tip, child2_is_tip;
+} pllgpu_insertion_t;
+int pllgpu_insertion_loglikelihoods(pllgpu_ctx_t *ctx, unsigned int subtree_clv, int subtree_scaler, unsigned int subtree_matrix,
+                                    unsigned int subtree_is_tip, const pllgpu_insertion_t *cands, unsigned int count,
+                                    const unsigned int *freqs_indices, double *host_out);
+
 /* replaces pll_compute_node_ancestral[_extbuf] (src/likelihood.c:639-823): the marginal state probabilities of
  * the node at edge->parent_clv, [sites][states] unpadded, given the other end edge->child_clv (a CLV, or tip codes
  * with child_is_tip) across edge->matrix. Of `edge`, gather must be 0 and want_persite / device_result / sequence

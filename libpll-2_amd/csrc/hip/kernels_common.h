@@ -324,12 +324,11 @@ __device__ __forceinline__ double sum_partials_strided(const double *block_sums,
   return a;
 }
 
-// Which workgroups hold a value may be decided at run time (k_edge_mfma: the workgroup that finishes an item block
-// last): the value goes to the slot of the ITEM BLOCK, not of the workgroup, so that the final sum adds the same
-// numbers in the same places whichever workgroup produced them - with one slot per workgroup the non-zero entries
-// moved between threads of the last workgroup from run to run and the total with them, by an ulp or two.
-__device__ __forceinline__ void publish_block_sum_slot(const DevEdge &e, double wave_value, unsigned nsum_waves, bool has_value, unsigned slot,
-                                                       unsigned nslots)
+// The hand-off itself, for one sum: block_sums / counter are THAT sum's slots and ticket, nworkgroups the tickets it
+// expects. true in thread 0 of the workgroup that arrived last, with `total` = the partials added in index order and the
+// ticket back at zero; false everywhere else.
+__device__ __forceinline__ bool handoff_block_sum(double *block_sums, unsigned *counter, unsigned nworkgroups, int fenced, double wave_value,
+                                                  unsigned nsum_waves, bool has_value, unsigned slot, unsigned nslots, double &total)
 {
   __shared__ double ws[4];
   __shared__ unsigned last;
@@ -342,31 +341,56 @@ __device__ __forceinline__ void publish_block_sum_slot(const DevEdge &e, double 
     {
       double s = ws[0];
       for (unsigned w = 1; w < nw; ++w) s += ws[w];
-      partial_store(&e.block_sums[slot], s);
+      partial_store(&block_sums[slot], s);
     }
-    handoff_before_ticket(e.fenced); // the partial has been performed before the ticket is taken
-    const unsigned ticket = __hip_atomic_fetch_add(e.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = (ticket == gridDim.x - 1) ? 1u : 0u;
-    if (last) handoff_after_last_ticket(e.fenced);
+    handoff_before_ticket(fenced); // the partial has been performed before the ticket is taken
+    const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = (ticket == nworkgroups - 1) ? 1u : 0u;
+    if (last) handoff_after_last_ticket(fenced);
   }
   __syncthreads();
-  if (!last) return;
-  double a = sum_partials_strided(e.block_sums, nslots);
+  if (!last) return false;
+  double a = sum_partials_strided(block_sums, nslots);
   a = wave_sum(a);
   __syncthreads();
   if (lane == 0) ws[wave] = a;
   __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    double s = ws[0];
-    for (unsigned w = 1; w < nw; ++w) s += ws[w];
-    __hip_atomic_store(e.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // result[0] = value, then result[1] = this call's sequence number with system-scope release:
-    // the host polls the sequence word in mapped memory instead of paying a stream synchronise
-    __hip_atomic_store(e.result, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    handoff_before_sequence(e.fenced); // the value is in host memory before the sequence word follows
-    __hip_atomic_store(e.result + 1, e.sequence, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  if (threadIdx.x != 0) return false;
+  double s = ws[0];
+  for (unsigned w = 1; w < nw; ++w) s += ws[w];
+  __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  total = s;
+  return true;
+}
+
+// Which workgroups hold a value may be decided at run time (k_edge_mfma: the workgroup that finishes an item block
+// last): the value goes to the slot of the ITEM BLOCK, not of the workgroup, so that the final sum adds the same
+// numbers in the same places whichever workgroup produced them - with one slot per workgroup the non-zero entries
+// moved between threads of the last workgroup from run to run and the total with them, by an ulp or two.
+__device__ __forceinline__ void publish_block_sum_slot(const DevEdge &e, double wave_value, unsigned nsum_waves, bool has_value, unsigned slot,
+                                                       unsigned nslots)
+{
+  double s;
+  if (!handoff_block_sum(e.block_sums, e.counter, gridDim.x, e.fenced, wave_value, nsum_waves, has_value, slot, nslots, s)) return;
+  // result[0] = value, then result[1] = this call's sequence number with system-scope release:
+  // the host polls the sequence word in mapped memory instead of paying a stream synchronise
+  __hip_atomic_store(e.result, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  handoff_before_sequence(e.fenced); // the value is in host memory before the sequence word follows
+  __hip_atomic_store(e.result + 1, e.sequence, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// The per-candidate form (kernels_insertion.h): a launch evaluates many sums at once, candidate `cand` on the grid's y axis
+// and `nslots` = gridDim.x workgroups per candidate. Each candidate owns nslots partial slots and one ticket; its last
+// workgroup leaves the total in results[cand] - device memory, the call copies all of them back at once - so a
+// candidate's bits depend on its own workgroups alone, never on what else the launch carries.
+__device__ __forceinline__ void publish_candidate_sum(double *block_sums, unsigned *tickets, double *results, unsigned cand, int fenced,
+                                                      double wave_value, unsigned nsum_waves)
+{
+  double s;
+  if (!handoff_block_sum(block_sums + (size_t)cand * gridDim.x, tickets + cand, gridDim.x, fenced, wave_value, nsum_waves, true, blockIdx.x,
+                         gridDim.x, s))
+    return;
+  results[cand] = s; // read by the copy that follows the kernel on the stream
 }
 
 // the usual case: every workgroup holds a value, one slot per workgroup

@@ -405,6 +405,23 @@ __global__ __launch_bounds__(256) void k_partials_tiled(const OpPack pack, const
   }
 }
 
+// rate k's term tr of site nn folded into the site's sums: rate weight and invariant-sites mix
+// (src/core_likelihood.c:1462-1475) - once, for k_edge_tiled and k_insertion_tiled (kernels_insertion.h)
+__device__ __forceinline__ void edge_rate_add(const DevEdge &e, const GenGeo &g, unsigned k, double tr, unsigned nn, double &terma, double &terminv)
+{
+  const unsigned fi = e.fidx[k];
+  const double pinv = e.prop_invar ? e.prop_invar[fi] : 0.0;
+  const double w = e.rate_weights[k];
+  if (pinv > 0.0)
+  {
+    terma += w * tr * (1.0 - pinv);
+    const int inv = e.invariant ? e.invariant[nn] : -1;
+    if (inv >= 0) terminv += w * e.freqs[(size_t)fi * g.SP + inv] * pinv;
+  }
+  else
+    terma += tr * w;
+}
+
 // ------------------------------------------------------------------------------------------------
 // edge / root log-likelihood, any states/rates, tiled layout. Workgroup = one tile at a time; wave
 // w of min(R,4) owns the rate categories w, w+nw, ... : it forms (P c)_i in chunks exactly like the
@@ -477,16 +494,7 @@ __global__ __launch_bounds__(256) void k_edge_tiled(const DevEdge e, const GenGe
           if (c * ICH + i < g.S) tr = fma(__builtin_nontemporal_load(pk + (size_t)i * pxs) * pi[i], B[i], tr);
       }
       if (e.per_rate) tr = rate_scaled(tr, scaler_sum_rate(e.pscaler, pe, e.cscaler, ce, g.R, k), scal);
-      const double pinv = e.prop_invar ? e.prop_invar[fi] : 0.0;
-      const double w = e.rate_weights[k];
-      if (pinv > 0.0)
-      {
-        terma += w * tr * (1.0 - pinv);
-        const int inv = e.invariant ? e.invariant[nn] : -1;
-        if (inv >= 0) terminv += w * e.freqs[(size_t)fi * g.SP + inv] * pinv;
-      }
-      else
-        terma += tr * w;
+      edge_rate_add(e, g, k, tr, nn, terma, terminv);
     }
     part[0][wave][lane] = terma;
     part[1][wave][lane] = terminv;

@@ -29,6 +29,7 @@
 #include "kernels_repeats.h"
 #include "kernels_ancestral.h"
 #include "kernels_parsimony.h"
+#include "kernels_insertion.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
@@ -216,6 +217,11 @@ struct pllgpu_ctx
   DevBuf<double> edge_partials;   // k_edge_mfma: [rate][row group][site] partial site likelihoods
   DevBuf<unsigned> edge_tickets;  // ... and the ticket per item block (zero between launches)
   DevBuf<unsigned> counter;
+  // pllgpu_insertion_loglikelihoods (kernels_insertion.h): [candidate][workgroup] partial sums, a ticket per candidate
+  // (zero between launches), the results of a whole call, the candidates' descriptors of one launch
+  DevBuf<double> ins_partials, ins_results;
+  DevBuf<unsigned> ins_tickets;
+  DevBuf<unsigned char> ins_cands;
   DevBuf<unsigned char> mfma_flags;      // [op in launch][rate][entry] scaling decisions (kernels_mfma.h)
   DevBuf<double> eigenvals, rates, diag; // derivatives: [rate_matrices][SP], [R], [R][S][4]
   DevBuf<double> evecs, ievecs, brlen;   // device P-matrices: [rate_matrices][S][SP] x 2, staged branch lengths
@@ -656,6 +662,10 @@ extern "C" void pllgpu_destroy(pllgpu_ctx_t *c)
   c->pmat.release();
   c->edge_partials.release();
   c->edge_tickets.release();
+  c->ins_partials.release();
+  c->ins_results.release();
+  c->ins_tickets.release();
+  c->ins_cands.release();
   c->freqs.release();
   c->rate_weights.release();
   c->prop_invar.release();
@@ -2154,9 +2164,8 @@ static int launch_edge(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather, const 
   return 0;
 }
 
-static int run_lnl(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather, const unsigned *freqs_indices,
-                   double *persite_host, double *lnl_out, double *device_result = nullptr, const TailCall *tail = nullptr,
-                   const ChainTailCall *ctail = nullptr)
+// what an evaluation reads besides its two ends: the model, the weights, the site count and the hand-off's form
+static int fill_edge_model(pllgpu_ctx *c, DevEdge &e, const unsigned *freqs_indices)
 {
   const pllgpu_geometry_t &g = c->geo;
   for (unsigned k = 0; k < g.rate_cats; ++k)
@@ -2169,6 +2178,18 @@ static int run_lnl(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather, const unsi
   e.prop_invar = c->prop_invar.p;
   e.pattern_weights = c->pattern_weights.p;
   e.invariant = c->invariant_set ? c->invariant.p : nullptr;
+  e.sites = g.sites;
+  e.per_rate = g.per_rate_scalers ? 1 : 0;
+  e.fenced = c->fenced;
+  return 0;
+}
+
+static int run_lnl(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather, const unsigned *freqs_indices,
+                   double *persite_host, double *lnl_out, double *device_result = nullptr, const TailCall *tail = nullptr,
+                   const ChainTailCall *ctail = nullptr)
+{
+  const pllgpu_geometry_t &g = c->geo;
+  if (int rc = fill_edge_model(c, e, freqs_indices)) return rc;
   e.persite = persite_host ? c->persite.p : nullptr;
   e.block_sums = c->block_sums.p;
   e.counter = c->counter.p;
@@ -2182,9 +2203,6 @@ static int run_lnl(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather, const unsi
   }
   unsigned long long seq_bits;
   memcpy(&seq_bits, &e.sequence, sizeof seq_bits);
-  e.sites = g.sites;
-  e.per_rate = g.per_rate_scalers ? 1 : 0;
-  e.fenced = c->fenced;
   if (int rc = launch_edge(c, e, ctip, gather, tail, ctail)) return rc;
   HIP_TRY(hipGetLastError());
   if (device_result) return 0; // asynchronous: the value stays on the device
@@ -2356,25 +2374,40 @@ static int claim_held_ops(pllgpu_ctx *c, const pllgpu_edge_t *ed, ClaimedWork &c
   return 0;
 }
 
+// one end of an edge or of an insertion candidate in HBM: its tip codes, or its CLV and scaler vector
+static int end_in_hbm(pllgpu_ctx *c, unsigned clv, int scaler, bool is_tip, const double *&data, const unsigned char *&codes, const unsigned *&sc)
+{
+  data = nullptr;
+  codes = nullptr;
+  if (is_tip)
+  {
+    if (clv >= c->geo.tips || !c->tipchars[clv].p) return fail(PLLGPU_EINVAL, "tip %u has no codes on the device", clv);
+    codes = c->tipchars[clv].p;
+  }
+  else
+  {
+    if (!c->clv[clv].p) return fail(PLLGPU_EINVAL, "CLV %u was never computed or uploaded", clv);
+    data = c->clv[clv].p;
+  }
+  return scaler_ptr(c, scaler, sc);
+}
+
+// the end P is applied on (an edge's child end, an insertion's subtree end) and the matrix
+static int build_edge_child(pllgpu_ctx *c, unsigned clv, int scaler, unsigned matrix, bool is_tip, DevEdge &e)
+{
+  if (int rc = end_in_hbm(c, clv, scaler, is_tip, e.child, e.ctip, e.cscaler)) return rc;
+  e.mat = c->pmat.p + (size_t)matrix * c->pm_stride;
+  return 0;
+}
+
 // the edge as the kernels read it: its two ends in HBM
 static int build_edge(pllgpu_ctx *c, const pllgpu_edge_t *ed, DevEdge &e)
 {
   memset(&e, 0, sizeof e);
   if (!c->clv[ed->parent_clv].p) return fail(PLLGPU_EINVAL, "CLV %u was never computed or uploaded", ed->parent_clv);
   e.parent = c->clv[ed->parent_clv].p;
-  if (ed->child_is_tip)
-  {
-    if (ed->child_clv >= c->geo.tips || !c->tipchars[ed->child_clv].p) return fail(PLLGPU_EINVAL, "tip %u has no codes on the device", ed->child_clv);
-    e.ctip = c->tipchars[ed->child_clv].p;
-  }
-  else
-  {
-    if (!c->clv[ed->child_clv].p) return fail(PLLGPU_EINVAL, "CLV %u was never computed or uploaded", ed->child_clv);
-    e.child = c->clv[ed->child_clv].p;
-  }
+  if (int rc = build_edge_child(c, ed->child_clv, ed->child_scaler, ed->matrix, ed->child_is_tip != 0, e)) return rc;
   if (int rc = scaler_ptr(c, ed->parent_scaler, e.pscaler)) return rc;
-  if (int rc = scaler_ptr(c, ed->child_scaler, e.cscaler)) return rc;
-  e.mat = c->pmat.p + (size_t)ed->matrix * c->pm_stride;
   e.layout = (c->clv_aos[ed->parent_clv] ? kAosParent : 0u) | ((!ed->child_is_tip && c->clv_aos[ed->child_clv]) ? kAosLeft : 0u);
   if (e.layout && !ed->gather) return fail(PLLGPU_EINVAL, "a class-compressed CLV met an evaluation without the gather flag");
   if (ed->gather)
@@ -2503,6 +2536,150 @@ extern "C" int pllgpu_root_loglikelihood(pllgpu_ctx_t *c, unsigned clv, int scal
   if (e.layout && !gather) return fail(PLLGPU_EINVAL, "a class-compressed CLV met an evaluation without the gather flag");
   e.is_root = 1;
   return run_lnl(c, e, false, gather != 0, freqs_indices, persite_host, lnl_out);
+}
+
+// ---- batched insertion log-likelihoods (kernels_insertion.h) -------------------------------------------------
+// candidates of one launch: their descriptors must fit one piece of the pinned block, their partial slots stay modest
+constexpr unsigned kInsMaxCands = 16384;          // 1 MB of descriptors, well below the grid's y limit
+constexpr size_t kInsMaxSlots = (size_t)4 << 20;  // 32 MB of partial sums per launch
+constexpr size_t kInsLdsMax = 144 * 1024;         // the inserted node's tile in LDS, beside the kernel's static 8 KB
+
+// Scratch that no kept plan points at: (re)allocating it must not move the context's allocation epoch, or the first
+// batched call would drop every cached launch plan of the partition.
+struct ScratchEpoch
+{
+  unsigned long long *prev, none = 0;
+  ScratchEpoch() : prev(t_epoch) { t_epoch = &none; }
+  ~ScratchEpoch() { t_epoch = prev; }
+};
+
+static int check_insertion_end(const pllgpu_ctx *c, unsigned clv, int scaler, unsigned matrix, bool is_tip, const char *what, unsigned i)
+{
+  const pllgpu_geometry_t &g = c->geo;
+  if (clv >= g.nodes || matrix >= g.prob_matrices || scaler >= (int)g.scale_buffers)
+    return fail(PLLGPU_EINVAL, "candidate %u: %s references an index out of range", i, what);
+  if (is_tip && clv >= g.tips) return fail(PLLGPU_EINVAL, "candidate %u: %s is marked as a tip and is none", i, what);
+  return 0;
+}
+
+// one launch for candidates [first, first + n): descriptors up through the pinned block, the kernel of the shape
+static int launch_insertions(pllgpu_ctx *c, DevEdge e, const pllgpu_insertion_t *cands, unsigned first, unsigned n, bool stip)
+{
+  const size_t bytes = (size_t)n * sizeof(InsCand);
+  unsigned char *dev = nullptr;
+  InsCand *host = reinterpret_cast<InsCand *>(stage_take(c, bytes, &dev));
+  std::vector<InsCand> pageable;
+  if (!host)
+  {
+    pageable.resize(n);
+    host = pageable.data();
+  }
+  for (unsigned i = 0; i < n; ++i)
+  {
+    const pllgpu_insertion_t &q = cands[first + i];
+    InsCand &d = host[i];
+    if (int rc = end_in_hbm(c, q.child1_clv, q.child1_is_tip ? -1 : q.child1_scaler, q.child1_is_tip != 0, d.left, d.ltip, d.lscaler)) return rc;
+    if (int rc = end_in_hbm(c, q.child2_clv, q.child2_is_tip ? -1 : q.child2_scaler, q.child2_is_tip != 0, d.right, d.rtip, d.rscaler)) return rc;
+    d.lmat = c->pmat.p + (size_t)q.child1_matrix * c->pm_stride;
+    d.rmat = c->pmat.p + (size_t)q.child2_matrix * c->pm_stride;
+  }
+  HIP_TRY(hipMemcpyAsync(c->ins_cands.p, host, bytes, hipMemcpyHostToDevice, c->stream));
+  const InsCand *dc = reinterpret_cast<const InsCand *>(c->ins_cands.p);
+  e.result = c->ins_results.p + first;
+  // the tile walk of launch_edge: the grid's x axis, and with it the order of every candidate's sum, follows from the
+  // site count alone
+  const unsigned tiles = (c->geo.sites + 63) / 64, max_blocks = 1024;
+  if (c->dna_fast)
+  {
+    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
+    const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
+    with_bools(stip, false, [&](auto ST, auto) {
+      hipLaunchKernelGGL((k_insertion_dna<ST()>), dim3(blocks, n), dim3(256), 0, c->stream, e, dc, c->gg.scale_mode, tpw);
+    });
+  }
+  else
+  {
+    const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
+    const unsigned blocks = (tiles + tpb - 1) / tpb;
+    const unsigned threads = 64u * std::min(c->gg.R, 4u);
+    size_t lds = (size_t)c->gg.tile_sz * sizeof(double);
+    const unsigned keep = lds <= kInsLdsMax ? 1u : 0u;
+    if (!keep) lds = 0;
+    const unsigned long long *tm = tipmap_ptr(c);
+    with_ich(c->ich, [&](auto ICH) {
+      with_bools(stip, false, [&](auto ST, auto) {
+        raise_lds_limit(reinterpret_cast<const void *>(&k_insertion_tiled<ICH(), ST()>), c->device, lds);
+        hipLaunchKernelGGL((k_insertion_tiled<ICH(), ST()>), dim3(blocks, n), dim3(threads), lds, c->stream, e, dc, c->gg, tm, tpb, keep);
+      });
+    });
+  }
+  ++c->last_launches;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pllgpu_insertion_loglikelihoods(pllgpu_ctx_t *c, unsigned subtree_clv, int subtree_scaler, unsigned subtree_matrix,
+                                               unsigned subtree_is_tip, const pllgpu_insertion_t *cands, unsigned count,
+                                               const unsigned *freqs_indices, double *host_out)
+{
+  CHECK_CTX_KEEP(c);
+  const pllgpu_geometry_t &g = c->geo;
+  c->last_launches = 0;
+  if (!count) return 0;
+  // everything that needs no device state, for the whole list, before held work is touched
+  if (!cands || !host_out || !freqs_indices) return fail(PLLGPU_EINVAL, "insertion log-likelihoods: null argument");
+  if (g.sites == 0 || g.sites != g.sites_alloc) return fail(PLLGPU_EUNSUPPORTED, "insertion log-likelihoods with ascertainment-bias entries");
+  if (subtree_clv >= g.nodes || subtree_matrix >= g.prob_matrices || subtree_scaler >= (int)g.scale_buffers || (subtree_is_tip && subtree_clv >= g.tips))
+    return fail(PLLGPU_EINVAL, "the subtree end references an index out of range");
+  for (unsigned k = 0; k < g.rate_cats; ++k)
+    if (freqs_indices[k] >= g.rate_matrices) return fail(PLLGPU_EINVAL, "freqs_indices[%u] = %u out of range", k, freqs_indices[k]);
+  for (unsigned i = 0; i < count; ++i)
+  {
+    if (int rc = check_insertion_end(c, cands[i].child1_clv, cands[i].child1_scaler, cands[i].child1_matrix, cands[i].child1_is_tip != 0, "child1", i)) return rc;
+    if (int rc = check_insertion_end(c, cands[i].child2_clv, cands[i].child2_scaler, cands[i].child2_matrix, cands[i].child2_is_tip != 0, "child2", i)) return rc;
+  }
+  for (unsigned n = 0; n < g.nodes; ++n)
+    if (c->ids[n] || c->clv_aos[n]) return fail(PLLGPU_EUNSUPPORTED, "insertion log-likelihoods over class-compressed CLVs");
+  // whatever pllgpu_update_partials holds back goes out as ordinary launches: a candidate may name what it produces
+  if (!c->deferred.empty() || c->chain_held)
+    if (int rc = flush_deferred(c)) return rc;
+
+  DevEdge e;
+  memset(&e, 0, sizeof e);
+  if (int rc = build_edge_child(c, subtree_clv, subtree_is_tip ? -1 : subtree_scaler, subtree_matrix, subtree_is_tip != 0, e)) return rc;
+  if (int rc = fill_edge_model(c, e, freqs_indices)) return rc;
+
+  const unsigned tiles = (g.sites + 63) / 64, max_blocks = 1024;
+  unsigned blocks;
+  if (c->dna_fast)
+  {
+    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
+    blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
+  }
+  else
+  {
+    const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
+    blocks = (tiles + tpb - 1) / tpb;
+  }
+  const unsigned per_launch = (unsigned)std::min<size_t>(std::min(count, kInsMaxCands), std::max<size_t>(1, kInsMaxSlots / blocks));
+  {
+    ScratchEpoch scratch_epoch_;
+    if (c->ins_partials.ensure((size_t)per_launch * blocks) || c->ins_results.ensure(count) || c->ins_cands.ensure((size_t)per_launch * sizeof(InsCand)))
+      return PLLGPU_ENOMEM;
+    if (c->ins_tickets.cap < per_launch)
+    {
+      if (c->ins_tickets.ensure(per_launch)) return PLLGPU_ENOMEM;
+      HIP_TRY(hipMemsetAsync(c->ins_tickets.p, 0, c->ins_tickets.cap * sizeof(unsigned), c->stream));
+    }
+  }
+  e.block_sums = c->ins_partials.p;
+  e.counter = c->ins_tickets.p;
+  for (unsigned first = 0; first < count; first += per_launch)
+    if (int rc = launch_insertions(c, e, cands, first, std::min(per_launch, count - first), subtree_is_tip != 0)) return rc;
+  // one copy back for all candidates, one wait
+  HIP_TRY(copy_down(c, host_out, c->ins_results.p, (size_t)count * sizeof(double)));
+  if (c->defer_down) HIP_TRY(stream_wait(c));
+  return 0;
 }
 
 // ---- marginal ancestral states (kernels_ancestral.h) -------------------------------------------------------

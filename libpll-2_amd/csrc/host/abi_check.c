@@ -94,5 +94,14 @@ AT(pll_pars_buildop_t, parent_score_index, 0);
 AT(pll_pars_buildop_t, child1_score_index, 4);
 AT(pll_pars_buildop_t, child2_score_index, 8);
 
+/* this library's own: one candidate edge of pll_gpu_insertion_loglikelihoods */
+_Static_assert(sizeof(pll_gpu_insertion_t) == 24, "pll_gpu_insertion_t size");
+AT(pll_gpu_insertion_t, child1_clv_index, 0);
+AT(pll_gpu_insertion_t, child1_scaler_index, 4);
+AT(pll_gpu_insertion_t, child1_matrix_index, 8);
+AT(pll_gpu_insertion_t, child2_clv_index, 12);
+AT(pll_gpu_insertion_t, child2_scaler_index, 16);
+AT(pll_gpu_insertion_t, child2_matrix_index, 20);
+
 /* the extension block must start 8-byte aligned directly behind the public struct */
 _Static_assert(sizeof(pll_partition_t) % 8 == 0, "extension block alignment");

@@ -135,6 +135,19 @@ class ParsBuildOp(C.Structure):
     _fields_ = [("parent_score_index", C.c_uint), ("child1_score_index", C.c_uint), ("child2_score_index", C.c_uint)]
 
 
+class Insertion(C.Structure):
+    """pll_gpu_insertion_t (include/pll_amd.h): one candidate edge of pll_gpu_insertion_loglikelihoods"""
+    _fields_ = [
+        ("child1_clv_index", C.c_uint),
+        ("child1_scaler_index", C.c_int),
+        ("child1_matrix_index", C.c_uint),
+        ("child2_clv_index", C.c_uint),
+        ("child2_scaler_index", C.c_int),
+        ("child2_matrix_index", C.c_uint),
+    ]
+
+
+assert C.sizeof(Insertion) == 24
 assert C.sizeof(Partition) == 232 and C.sizeof(Repeats) == 104 and C.sizeof(Operation) == 32
 assert C.sizeof(Parsimony) == 104 and C.sizeof(ParsBuildOp) == 12
 
@@ -215,6 +228,8 @@ _GPU_PROTOS = {
     "pll_gpu_sync_pmatrix": (C.c_int, [PartitionP, C.c_int]),
     "pll_gpu_edge_loglikelihood_async": (C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p, C.c_void_p]),
     "pll_gpu_node_ancestral_async": (C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p, C.c_void_p]),
+    "pll_gpu_insertion_loglikelihoods": (
+        C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.POINTER(Insertion), C.c_uint, c_uint_p, c_double_p]),
     "pll_gpu_last_algorithmic_bytes": (C.c_double, [PartitionP]),
     "pll_gpu_sync_repeats": (C.c_int, [PartitionP, C.c_int]),
     "pll_gpu_sync_all": (C.c_int, [PartitionP]),
@@ -311,6 +326,16 @@ def make_ops(rows):
     for o, r in zip(arr, rows):
         (o.parent_clv_index, o.parent_scaler_index, o.child1_clv_index, o.child1_matrix_index,
          o.child1_scaler_index, o.child2_clv_index, o.child2_matrix_index, o.child2_scaler_index) = [int(x) for x in r]
+    return arr
+
+
+def make_insertions(rows):
+    """rows: iterable of 6-tuples in pll_gpu_insertion_t field order."""
+    rows = list(rows)
+    arr = (Insertion * max(len(rows), 1))()
+    for o, r in zip(arr, rows):
+        (o.child1_clv_index, o.child1_scaler_index, o.child1_matrix_index,
+         o.child2_clv_index, o.child2_scaler_index, o.child2_matrix_index) = [int(x) for x in r]
     return arr
 
 

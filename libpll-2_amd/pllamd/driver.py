@@ -87,6 +87,31 @@ def states_padded_for(states, arch):
     return states
 
 
+def insertion_loglikelihoods(lib, partition, subtree, candidates, freqs_indices):
+    """pll_gpu_insertion_loglikelihoods: subtree = (clv, scaler, matrix) of the end that is inserted, candidates = rows
+    in pll_gpu_insertion_t field order (child1 clv, scaler, matrix, child2 clv, scaler, matrix); one log-likelihood
+    per candidate, all from one call. libpll_amd.so only."""
+    rows = list(candidates)
+    out = np.full(len(rows), np.nan)
+    fi = np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+    if not lib.pll_gpu_insertion_loglikelihoods(partition, int(subtree[0]), int(subtree[1]), int(subtree[2]),
+                                                api.make_insertions(rows), len(rows), api.uptr(fi), api.dptr(out)):
+        raise RuntimeError(f"pll_gpu_insertion_loglikelihoods: [{lib.errno()}] {lib.errmsg()}")
+    return out
+
+
+def insertion_loglikelihoods_per_edge(lib, partition, subtree, candidates, freqs_indices, tmp):
+    """the same values the way every libpll offers them: per candidate one pll_update_partials with a single operation
+    into the spare node tmp = (clv, scaler), then pll_compute_edge_loglikelihood between tmp and the subtree end"""
+    fi = np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+    out = np.empty(len(candidates))
+    for i, c in enumerate(candidates):
+        lib.pll_update_partials(partition, api.make_ops([(tmp[0], tmp[1], c[0], c[2], c[1], c[3], c[5], c[4])]), 1)
+        out[i] = lib.pll_compute_edge_loglikelihood(partition, tmp[0], tmp[1], int(subtree[0]), int(subtree[1]), int(subtree[2]),
+                                                    api.uptr(fi), None)
+    return out
+
+
 class Session:
     """A live partition built from a Case (kept open so benches can re-run the hot path)."""
 
@@ -185,6 +210,10 @@ class Session:
         if not ok:
             raise RuntimeError(f"pll_compute_node_ancestral: [{self.lib.errno()}] {self.lib.errmsg()}")
         return out
+
+    def insertion_lnls(self, subtree, candidates):
+        """log-likelihood of inserting subtree = (clv, scaler, matrix) into every candidate edge, one call"""
+        return insertion_loglikelihoods(self.lib, self.p, subtree, candidates, self._fi)
 
     def entries(self, clv_index):
         return self.lib.pll_get_sites_number(self.p, clv_index)
