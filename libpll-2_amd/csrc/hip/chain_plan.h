@@ -39,6 +39,12 @@ struct ChainPlan
   size_t held_from = 0;                // stages[held_from ..) = the last stage when it may be held for the edge evaluation
   unsigned launches = 0;
   double bytes = 0.0;
+  // The list is a balanced 64-taxon traversal (plan_tree below): eight seven-op groups under the two held chains, whose tops
+  // are complete 32-tip subtrees. While it is held NOTHING of it has been launched; the evaluation of the edge between the
+  // two tops takes all of it in one launch (kernels_dna.h: k_edge_dna_tree), anything else sends it out as the launches above.
+  bool tree = false;
+  TreeEnd tree_end[2];    // the subtree under the top of head 0 / head 1
+  double tree_bytes = 0.0; // of that one launch: codes in, every CLV and scaler out, nothing read back
 };
 
 static void drop_chain_plan(pllgpu_ctx *c)
@@ -95,6 +101,13 @@ static void launch_chain_heads(pllgpu_ctx *c, const ChainPlan &pl, unsigned firs
 // the next call shows whether it is the evaluation of the edge those chains end in
 static int launch_chain_plan(pllgpu_ctx *c, const ChainPlan &pl, bool hold)
 {
+  if (hold && pl.tree)
+  {
+    c->chain_held = c->tree_held = true;
+    c->last_launches = 0;
+    c->last_bytes = pl.tree_bytes;
+    return 0;
+  }
   for (const CC16Launch &l : pl.cc16)
     if (int rc = launch_cc16(c, l.pack, l.n, l.entries)) return rc;
   for (const CCLaunch &l : pl.cc)
@@ -107,11 +120,25 @@ static int launch_chain_plan(pllgpu_ctx *c, const ChainPlan &pl, bool hold)
   return launch_status();
 }
 
+// a held tree plan (ChainPlan::tree) goes the ordinary way after all: its stage 1, the seven-op groups, before the chains
+static int launch_held_tree_groups(pllgpu_ctx *c)
+{
+  if (!c->tree_held || !c->plan) return 0;
+  c->tree_held = false;
+  const ChainPlan &pl = *c->plan;
+  for (const CCLaunch &l : pl.cc)
+    if (int rc = launch_cc(c, l.pack, l.n, l.entries, l.lk, CK_FCC)) return rc;
+  c->last_launches += (unsigned)pl.cc.size();
+  c->last_bytes = pl.bytes;
+  return 0;
+}
+
 static int launch_held_chains(pllgpu_ctx *c)
 {
   if (!c->chain_held || !c->plan) return 0;
   c->chain_held = false;
   const ChainPlan &pl = *c->plan;
+  if (int rc = launch_held_tree_groups(c)) return rc;
   for (size_t i = pl.held_from; i < pl.stages.size(); ++i)
   {
     launch_chain_heads(c, pl, pl.stages[i].first_head, pl.stages[i].nchains, pl.stages[i].variant);
@@ -306,6 +333,23 @@ static bool use_cc16(const pllgpu_ctx *c, unsigned entries, unsigned count)
   return (size_t)entries * count >= (size_t)9000000;
 }
 
+// The whole-traversal launch (kernels_dna.h: k_edge_dna_tree) against the launches it replaces, same box, the switch forced
+// 0 / 1 alternating, three pairs of bench.py --steps 50 (profiles/dna_tree_c2.md). ms per step, the middle one of the three
+// runs' medians: 64 taxa x 20k sites 0.0520 -> 0.0476, 50k 0.0965 -> 0.0902, 100k (against the parent commit) 0.1630 ->
+// 0.1454, 200k (against fifteen-op groups) 0.2946 -> 0.2657. At 50k and 100k the new form's slowest block is below the
+// other's fastest in every pair; at 20k and 200k only its median is (its slowest block overlaps the other's fastest, and is
+// no slower than the other's slowest): the weaker criterion, on which the threshold sits at the smallest size measured.
+// 400k sites are beyond the held tail's 4096 tiles: today's plan either way. By size unless PLL_AMD_FUSE_TREE says 0 / 1:
+// entries of the list; only lists that plan_tree recognises are affected. Where fifteen-op groups qualify as well (200k)
+// the tree form goes first.
+constexpr unsigned kTreeMinEntries = 20000;
+static bool use_tree(const pllgpu_ctx *c, unsigned entries, unsigned count)
+{
+  if (count != 62u || !c->defer_tail) return false;
+  if (c->fuse_tree >= 0) return c->fuse_tree != 0;
+  return entries >= kTreeMinEntries;
+}
+
 // what a plan's descriptors are built from: the list, its partition, every chain op resolved
 struct ChainBuild
 {
@@ -452,8 +496,55 @@ static void choose_held_stage(const pllgpu_ctx *c, ChainPlan *pl)
   if (tail_heads && tail_steps + (2u - std::min(tail_heads, 2u)) > (unsigned)kChainPackSteps) pl->in_kernarg = false;
 }
 
+// Is the planned list a balanced 64-taxon traversal as k_edge_dna_tree evaluates it? Exactly eight complete 8-tip groups in
+// one launch and two held chains, each chain's top an op over two ops over four of the groups' parents: the two tops are
+// complete 32-tip subtrees, the ends of the edge the caller is expected to evaluate next. Fills the plan's tree fields.
+static void plan_tree(const pllgpu_ctx *c, const ChainBuild &b, unsigned count, ChainPlan *pl)
+{
+  const ChainPartition &part = b.part;
+  const pllgpu_op_t *ops = b.ops;
+  if (count != 62u || part.groups.size() != 8u || part.chains.size() != 2u || pl->heads.size() != 2u) return;
+  if (pl->cc.size() != 1u || pl->cc[0].n != 8u || pl->cc[0].lk != CK_FCC || !pl->cc16.empty()) return;
+  if (pl->held_from != 0 || pl->stages.empty()) return; // both chains wait for the evaluation
+  std::vector<int> group_of(count, -1);
+  for (size_t gi = 0; gi < 8u; ++gi)
+  {
+    const FusedGroup &g = part.groups[gi];
+    if (g.lk != CK_FCC || g.rk != CK_FCC || g.absorbed) return;
+    group_of[g.p] = (int)gi; // (build_cc_launches kept the list's order: pack.g[gi])
+  }
+  unsigned seen = 0;
+  for (unsigned k = 0; k < 2u; ++k)
+  {
+    const unsigned top = part.chains[k].ops[0];
+    unsigned h = 0;
+    while (h < 2u && (pl->head_top_clv[h] != ops[top].parent_clv || pl->head_top_scaler[h] != ops[top].parent_scaler)) ++h;
+    if (h == 2u) return;
+    TreeEnd &end = pl->tree_end[h];
+    memset(&end, 0, sizeof end);
+    to_top(b.dev[top], end.top);
+    for (int sd = 0; sd < 2; ++sd)
+    {
+      if (!part.is_chain_op(top, sd)) return;
+      const unsigned mid = (unsigned)part.pr_of[sd][top];
+      to_top(b.dev[mid], end.mid[sd]);
+      for (int sd2 = 0; sd2 < 2; ++sd2)
+      {
+        const int pr = part.pr_of[sd2][mid];
+        if (pr < 0 || group_of[pr] < 0) return;
+        seen |= 1u << group_of[pr];
+        end.g[sd * 2 + sd2] = pl->cc[0].pack.g[group_of[pr]];
+      }
+    }
+  }
+  if (seen != 0xffu) return; // 8 x 7 + 2 x 3 ops, every one placed
+  for (unsigned i = 0; i < count; ++i) pl->tree_bytes += op_traffic(c, ops[i], (ops[i].flags & PLLGPU_OP_LEFT_TIP) != 0, (ops[i].flags & PLLGPU_OP_RIGHT_TIP) != 0);
+  pl->tree = true;
+}
+
 // the plan of a partitioned list: cherry-cherry launches, then per (stage, fetch variant) one launch over its chains
-static int build_chain_plan(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count, unsigned entries, ChainPartition &part, ChainPlan *pl)
+static int build_chain_plan(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count, unsigned entries, ChainPartition &part, bool want_tree,
+                            ChainPlan *pl)
 {
   const std::vector<PChain> &chains = part.chains;
   ChainBuild b{ops, part, std::vector<DevOp>(count), entries, (unsigned)(clv_elems(c, entries) * sizeof(double)),
@@ -498,6 +589,7 @@ static int build_chain_plan(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned coun
   choose_held_stage(c, pl);
   pl->bytes += c->last_bytes; // the cherry-cherry groups (build_cc_launches counted them)
   pl->launches = (unsigned)(pl->cc.size() + pl->cc16.size() + pl->stages.size());
+  if (want_tree) plan_tree(c, b, count, pl);
   return 0;
 }
 
@@ -530,10 +622,23 @@ static int try_chain_plan(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigned count,
   }
   const unsigned entries = ops[0].parent_entries;
   if (entries == 0 || aos_entries(c, entries) || (size_t)entries * 128u >= ((size_t)1 << 31)) return 0; // 32-bit buffer offsets
-  ChainPartition part;
-  if (!partition_chains(ops, count, c->geo.nodes, c->geo.scale_buffers, entries, c->fuse_cc, use_cc16(c, entries, count), part)) return 0;
-  ChainPlan *pl = new ChainPlan();
-  int rc = build_chain_plan(c, ops, count, entries, part, pl);
+  // the tree form wants the seven-op groups; a list that turns out not to be one is planned again as it would have been
+  const bool cc16 = use_cc16(c, entries, count);
+  ChainPlan *pl = nullptr;
+  int rc = 0;
+  for (int want_tree = use_tree(c, entries, count) ? 1 : 0; want_tree >= 0; --want_tree)
+  {
+    ChainPartition part;
+    if (!partition_chains(ops, count, c->geo.nodes, c->geo.scale_buffers, entries, c->fuse_cc, cc16 && !want_tree, part))
+    {
+      delete pl;
+      return 0;
+    }
+    delete pl;
+    pl = new ChainPlan();
+    rc = build_chain_plan(c, ops, count, entries, part, want_tree != 0, pl);
+    if (rc || !want_tree || pl->tree || !cc16) break;
+  }
   if (!rc && !pl->in_kernarg) rc = upload_chain_plan(c, *pl);
   if (rc)
   {

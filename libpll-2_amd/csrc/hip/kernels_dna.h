@@ -1701,6 +1701,48 @@ __global__ __launch_bounds__(256) void k_partials_dna_chain(const ChainHead *hea
   chain_body<SM, C0, S1, C1>(src, entries);
 }
 
+// One sum per 64-site tile in e.block_sums -> the total, by the workgroup that arrived last: k_edge_dna's summation tree -
+// workgroups of four tiles (wave sums added in wave order), then the partials strided over 256 threads
+// (publish_block_sum). t = 0 .. 255: the caller's 256 threads (four whole waves), all of them call; ws: four doubles of LDS.
+__device__ __forceinline__ void dna_tile_sums_total(const DevEdge &e, unsigned t, double *ws)
+{
+  const unsigned lane = t & 63u, wave = t >> 6;
+  const unsigned site_tiles = (e.sites + 63u) / 64u, nblocks = (site_tiles + 3u) / 4u;
+  double a = 0.0;
+  for (unsigned base = 0; base < nblocks; base += 4u * 256u) // all requests of a batch first (sum_partials_strided)
+  {
+    double v[4][4];
+#pragma unroll
+    for (unsigned q = 0; q < 4u; ++q)
+    {
+      const unsigned i = base + q * 256u + t;
+#pragma unroll
+      for (unsigned w = 0; w < 4u; ++w) v[q][w] = (i < nblocks && 4u * i + w < site_tiles) ? partial_load(&e.block_sums[4u * i + w]) : 0.0;
+    }
+#pragma unroll
+    for (unsigned q = 0; q < 4u; ++q)
+      if (base + q * 256u + t < nblocks)
+      {
+        double sblk = v[q][0];
+#pragma unroll
+        for (unsigned w = 1; w < 4u; ++w) sblk += v[q][w];
+        a += sblk;
+      }
+  }
+  a = wave_sum(a);
+  if (lane == 0) ws[wave] = a;
+  __syncthreads();
+  if (t == 0)
+  {
+    double s = ws[0];
+    for (unsigned w = 1; w < 4u; ++w) s += ws[w];
+    __hip_atomic_store(e.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(e.result, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    handoff_before_sequence(e.fenced); // the value is in host memory before the sequence word follows
+    __hip_atomic_store(e.result + 1, e.sequence, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Chain tail: the chains that end in the two ends of the evaluated edge (the last stage of a
 // traversal, held back for one call like the ops of k_edge_dna_tail below) run inside the
@@ -1763,43 +1805,7 @@ __device__ __forceinline__ void chain_edge_body(const DevEdge &e, const SRC src,
   }
   __syncthreads();
   if (!last) return;
-  // k_edge_dna's summation tree: workgroups of four tiles (wave sums added in wave order), then the
-  // partials strided over 256 threads (publish_block_sum)
-  const unsigned wave = threadIdx.x >> 6;
-  const unsigned site_tiles = (e.sites + 63u) / 64u, nblocks = (site_tiles + 3u) / 4u;
-  double a = 0.0;
-  for (unsigned base = 0; base < nblocks; base += 4u * blockDim.x) // all requests of a batch first (sum_partials_strided)
-  {
-    double v[4][4];
-#pragma unroll
-    for (unsigned q = 0; q < 4u; ++q)
-    {
-      const unsigned i = base + q * blockDim.x + threadIdx.x;
-#pragma unroll
-      for (unsigned w = 0; w < 4u; ++w) v[q][w] = (i < nblocks && 4u * i + w < site_tiles) ? partial_load(&e.block_sums[4u * i + w]) : 0.0;
-    }
-#pragma unroll
-    for (unsigned q = 0; q < 4u; ++q)
-      if (base + q * blockDim.x + threadIdx.x < nblocks)
-      {
-        double sblk = v[q][0];
-#pragma unroll
-        for (unsigned w = 1; w < 4u; ++w) sblk += v[q][w];
-        a += sblk;
-      }
-  }
-  a = wave_sum(a);
-  if (lane == 0) ws[wave] = a;
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    double t = ws[0];
-    for (unsigned w = 1; w < 4u; ++w) t += ws[w];
-    __hip_atomic_store(e.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(e.result, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    handoff_before_sequence(e.fenced); // the value is in host memory before the sequence word follows
-    __hip_atomic_store(e.result + 1, e.sequence, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  dna_tile_sums_total(e, threadIdx.x, ws);
 }
 
 template <int SM, bool C0, bool S1, bool C1>
@@ -1869,4 +1875,163 @@ __global__ __launch_bounds__(256) void k_edge_dna_tail(const DevEdge e, const FG
     if (valid) acc += dna_site_finish(e, n, terma, terminv, scal, 0);
   }
   publish_block_sum(e, wave_sum(acc), 4u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The whole traversal of a balanced 64-taxon tree and the edge log-likelihood, per 64-site tile: k_partials_dna_cc16's
+// work split (a wave per complete 8-tip subtree, tops crossing through LDS) carried up to the evaluated edge. A workgroup
+// of EIGHT waves owns a tile: wave w forms 8-tip subtree w (dna_cc8's seven ops from eight code bytes), waves 0-3 under the
+// edge's parent end, waves 4-7 under its child end. Then three rounds, each "the right-hand wave leaves its top CLV and
+// scaler words in its LDS slot, barrier, the left-hand wave forms and stores the op above": level 4 (odd waves -> even
+// waves), level 5 (waves 2, 6 -> 0, 4: the two ends of the edge), the edge itself (wave 4 -> 0: k_edge_dna's site likelihood
+// from registers). A wave only ever writes its own slot, and only before others read it.
+// Nothing the step writes is read back: per site 64 code bytes in, 62 CLVs + scalers out. What this replaces is a second
+// launch (the chain tail) that re-read the eight group parents and whose time was mostly fixed cost - launch ramp, every
+// workgroup in the same phase, ticket and final sum (profiles/dna_tree_c2.md); here those overlap with other tiles' stores.
+// The arithmetic is dna_cherry / dna_combine's and k_edge_dna's, the tile sums are added in k_edge_dna's order: every
+// CLV, scaler and the value are bit-identical to the other routes (tests/test_gpu_dna_tree.py).
+struct TreeEnd // one end of the edge as a complete 32-tip subtree (1872 bytes)
+{
+  CCGroup g[4]; // the 8-tip subtrees, left to right
+  TOp mid[2];   // level 4: mid[0] over g[0], g[1] = the end's left child, mid[1] over g[2], g[3]; tip fields not read
+  TOp top;      // level 5: the end
+};
+
+struct TreePack // 3744 B of kernarg, + a DevEdge
+{
+  TreeEnd end[2]; // parent end, child end
+};
+static_assert(sizeof(TreePack) + sizeof(DevEdge) + 12 <= 4000, "k_edge_dna_tree's arguments must fit the kernarg segment");
+
+// a wave's CLV and scaler words of its lane's site into / out of a slot of the exchange buffer
+__device__ __forceinline__ void dna_tree_put(double (*xv)[64], uint4 *xs, unsigned lane, const double (&v)[4][4], uint4 sc)
+{
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xv[k * 4 + i][lane] = v[k][i];
+  xs[lane] = sc;
+}
+
+__device__ __forceinline__ void dna_tree_get(const double (*xv)[64], const uint4 *xs, unsigned lane, double (&v)[4][4], uint4 &sc)
+{
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[k][i] = xv[k * 4 + i][lane];
+  sc = xs[lane];
+}
+
+// dna_cc8 with the left half's top waiting in the wave's LDS slot, not in registers, while the right half is formed: with
+// dna_cc8 as it stands the kernel needs 154 registers (three waves per SIMD = ONE workgroup per CU) and spills under a bound
+// of 128; so it takes 115 (tools/kernel_resources.py) - four waves per SIMD, two workgroups per CU - without one. That figure
+// is how this compiler happens to schedule the code: check it again after a change of toolchain. The results do not depend
+// on it. The top stays in v / sc.
+__device__ __forceinline__ void dna_cc8_parked(const CCGroup &g, double (*xv)[64], uint4 *xs, unsigned lane, size_t off, unsigned n, bool valid,
+                                               int scale_mode, double (&v)[4][4], uint4 &sc)
+{
+  double vb[4][4], u[4][4];
+  uint4 scb, scu;
+  int mode;
+  dna_cc_child<CK_FCC>(g.p, true, g.a, g.aa, g.ab, off, n, valid, scale_mode, v, sc);
+  dna_tree_put(xv, xs, lane, v, sc);
+  asm volatile("" ::: "memory"); // (the reload below is not folded into the store above: in practice the values leave the registers)
+  dna_cc_child<CK_FCC>(g.p, false, g.b, g.ba, g.bb, off, n, valid, scale_mode, vb, scb);
+  asm volatile("" ::: "memory");
+  dna_tree_get(xv, xs, lane, v, sc);
+  dna_combine(g.p, scale_mode, v, sc, vb, scb, u, scu, mode);
+  dna_store<true>(g.p.parent, g.p.pscaler, off, n, valid, mode, u, scu);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[k][i] = u[k][i];
+  sc = scu;
+}
+
+// the op above two tops: this wave's (v, sc: the left child) and the one waiting in the slot; stored, left in v / sc
+__device__ __forceinline__ void dna_tree_up(const TOp &op, const double (*xv)[64], const uint4 *xs, unsigned lane, size_t off, unsigned n, bool valid,
+                                            int scale_mode, double (&v)[4][4], uint4 &sc)
+{
+  double vb[4][4], u[4][4];
+  uint4 scb, scu;
+  int mode;
+  dna_tree_get(xv, xs, lane, vb, scb);
+  dna_combine(op, scale_mode, v, sc, vb, scb, u, scu, mode);
+  dna_store<true>(op.parent, op.pscaler, off, n, valid, mode, u, scu);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[k][i] = u[k][i];
+  sc = scu;
+}
+
+// entries: of every CLV of the list - the sites, and behind them the per-state entries of an ascertainment-bias partition,
+// which are computed and stored like sites and enter no site likelihood (as in chain_edge_body)
+__global__ __launch_bounds__(512) void k_edge_dna_tree(const DevEdge e, const TreePack pack, unsigned entries, int scale_mode, unsigned xcd_order)
+{
+  // a slot of 9 KB per wave: 72 KB, two workgroups per CU
+  __shared__ double xv[8][16][64];
+  __shared__ uint4 xs[8][64];
+  __shared__ unsigned last;
+  __shared__ double ws[4];
+  const unsigned ntiles = (entries + 63u) / 64u;
+  const unsigned tile = xcd_linear(ntiles, xcd_order); // store traffic: every XCD on its own run of tiles (kernels_common.h)
+  if (tile == ~0u) return;                             // the grid's padding: whole workgroups
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned n0 = tile * 64u + lane;
+  const bool valid = n0 < entries;
+  const unsigned n = valid ? n0 : entries - 1;
+  const size_t off = (size_t)tile * kDnaTile + lane;
+  const TreeEnd &end = pack.end[wave >> 2];
+  double v[4][4];
+  uint4 sc;
+  dna_cc8_parked(end.g[wave & 3u], xv[wave], xs[wave], lane, off, n, valid, scale_mode, v, sc);
+  // every barrier below is met by all waves that have not left yet; they order LDS traffic only (lds_barrier: the stores
+  // to HBM stay in flight)
+  // round 1, level 4: odd waves -> even waves
+  if (wave & 1u) dna_tree_put(xv[wave], xs[wave], lane, v, sc);
+  lds_barrier();
+  if (wave & 1u) return;
+  dna_tree_up(end.mid[(wave >> 1) & 1u], xv[wave + 1u], xs[wave + 1u], lane, off, n, valid, scale_mode, v, sc);
+  // round 2, level 5: waves 2, 6 -> 0, 4
+  if (wave & 2u) dna_tree_put(xv[wave], xs[wave], lane, v, sc);
+  lds_barrier();
+  if (!(wave & 2u)) dna_tree_up(end.top, xv[wave + 2u], xs[wave + 2u], lane, off, n, valid, scale_mode, v, sc);
+  // round 3, the edge: wave 4 -> 0
+  if (wave == 4u) dna_tree_put(xv[4], xs[4], lane, v, sc);
+  lds_barrier();
+  if (wave == 0u)
+  {
+    double vc[4][4];
+    uint4 scc;
+    dna_tree_get(xv[4], xs[4], lane, vc, scc);
+    cdouble_p pm = as_const(e.mat);
+    unsigned rs[4];
+    const unsigned scal = dna_site_scalers(e, sc, scc, rs);
+    const bool is_site = n0 < e.sites;
+    const unsigned ns = is_site ? n0 : e.sites - 1;
+    const int inv = e.invariant ? e.invariant[ns] : -1;
+    double terma = 0.0, terminv = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+      double tb[4];
+      dna_matvec(tb, pm + k * 16, vc[k]);
+      dna_site_add(e, k, dna_rate_term(v[k], as_const(e.freqs) + (size_t)e.fidx[k] * 4, tb), rs, scal, inv, terma, terminv);
+    }
+    const double site = is_site ? dna_site_finish(e, ns, terma, terminv, scal, 0) : 0.0;
+    const double tile_sum = wave_sum(site);
+    if (lane == 0)
+    {
+      partial_store(&e.block_sums[tile], tile_sum); // (a tile of extra entries alone: 0, beyond what the sum reads) kernels_common.h: no fences in the hand-off by default
+      handoff_before_ticket(e.fenced);
+      const unsigned ticket = __hip_atomic_fetch_add(e.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      last = (ticket == ntiles - 1) ? 1u : 0u;
+      if (last) handoff_after_last_ticket(e.fenced);
+    }
+  }
+  __syncthreads();
+  if (!last) return;
+  dna_tile_sums_total(e, (wave >> 1) * 64u + lane, ws); // the four even waves stand in for k_edge_dna's 256 threads
 }

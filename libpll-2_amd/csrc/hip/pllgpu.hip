@@ -268,12 +268,15 @@ struct pllgpu_ctx
   bool fuse_cc = false;          // DNA: also two producer levels under a group parent (cherry-cherry children)
   int fuse_cc16 = -1;            // DNA, chain plans: also a parent over two complete 8-tip groups (fifteen ops, k_partials_dna_cc16):
                                  // -1 by size (chain_plan.h: use_cc16), 0 never, 1 always (PLL_AMD_FUSE_CC16)
+  int fuse_tree = -1;            // DNA, chain plans: a balanced 64-taxon traversal and its edge evaluation as one launch (k_edge_dna_tree):
+                                 // -1 by size (chain_plan.h: use_tree), 0 never, 1 always (PLL_AMD_FUSE_TREE)
   bool fuse_gg = true;           // DNA + site repeats: groups over two gathering producers (PLL_AMD_NO_FUSE_GG=1: off)
   bool fuse = false;             // DNA: evaluate producer + consumer ops in one kernel (kernels_dna.h)
   bool chains = false;           // DNA: chain plans (k_partials_dna_chain) for dependency-only op lists
   bool any_aos = false;          // a class-compressed CLV exists (site repeats): no chain plans
   struct ChainPlan *plan = nullptr; // the last chain plan, re-launched as is when the same list comes again
   bool chain_held = false;          // the plan's last stage has not been launched yet (chain tail, kernels_dna.h)
+  bool tree_held = false;           // ... and neither has its stage 1: the whole plan waits (ChainPlan::tree; implies chain_held)
   DevBuf<unsigned char> chain_dev;  // its descriptors
   // level-scheduled lists: the launches of a planned list are kept (descriptor packs by value) and replayed
   // as they are when the same list comes again while nothing they point at has moved (LevelPlan below)
@@ -463,6 +466,9 @@ static void derive_geometry(pllgpu_ctx *c)
   c->fuse_cc16 = -1;
   if (const char *v16 = getenv("PLL_AMD_FUSE_CC16"))
     if (*v16) c->fuse_cc16 = *v16 != '0' ? 1 : 0;
+  c->fuse_tree = -1;
+  if (const char *vt = getenv("PLL_AMD_FUSE_TREE"))
+    if (*vt) c->fuse_tree = *vt != '0' ? 1 : 0;
   if (const char *v = getenv("PLL_AMD_NO_FUSE_CC"))
     if (*v && *v != '0') c->fuse_cc = false;
   c->chains = c->fuse;
@@ -639,7 +645,7 @@ extern "C" void pllgpu_destroy(pllgpu_ctx_t *c)
   if (!c) return;
   DeviceScope device_scope_(c);
   c->deferred.clear(); // results nobody will ask for
-  c->chain_held = false;
+  c->chain_held = c->tree_held = false;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   drop_chain_plan(c);
   for (LevelPlan *lp : c->level_plans) delete lp;
@@ -708,6 +714,7 @@ extern "C" void pllgpu_destroy(pllgpu_ctx_t *c)
 // every entry point first launches what pllgpu_update_partials is holding back (tail fusion,
 // kernels_dna.h) - except the edge evaluation, which may consume it
 static int flush_deferred(pllgpu_ctx *c);
+static bool held_work_reads_matrices(const pllgpu_ctx *c, unsigned first, unsigned count);
 #define CHECK_CTX_KEEP(c)                    \
   if (!(c)) return fail(PLLGPU_EINVAL, "null context"); \
   DeviceScope device_scope_(c);              \
@@ -972,7 +979,11 @@ static int upload_matrices(pllgpu_ctx *c, unsigned first, unsigned count, const 
 
 extern "C" int pllgpu_pmatrix_upload(pllgpu_ctx_t *c, unsigned first, unsigned count, const double *host)
 {
-  CHECK_CTX(c);
+  // the matrix of the edge evaluated next is no input of the traversal before it and usually goes up between the two calls:
+  // what is held stays held unless it reads one of these matrices
+  CHECK_CTX_KEEP(c);
+  if (held_work_reads_matrices(c, first, count))
+    if (int rc = flush_deferred(c)) return rc;
   return upload_matrices(c, first, count, host, c->geo.prob_matrices);
 }
 
@@ -1661,6 +1672,17 @@ static int launch_partials(pllgpu_ctx *c, const OpPack &pack, unsigned nops, uns
 #include "chain_plan.h"
 #include "subtree_plan.h"
 
+static bool held_work_reads_matrices(const pllgpu_ctx *c, unsigned first, unsigned count)
+{
+  auto reads = [&](const pllgpu_op_t &o) { return o.left_matrix - first < count || o.right_matrix - first < count; };
+  for (const pllgpu_op_t &o : c->deferred)
+    if (reads(o)) return true;
+  if (c->chain_held && c->plan)
+    for (const pllgpu_op_t &o : c->plan->key)
+      if (reads(o)) return true;
+  return false;
+}
+
 // launch the held ops as ordinary updates (they are mutually independent: one level)
 static int flush_deferred(pllgpu_ctx *c)
 {
@@ -2079,13 +2101,16 @@ struct ChainTailCall
   unsigned variant;
   bool in_kernarg;
   ChainPack pack; // in_kernarg: heads[0] = hp, heads[1] = hc and their steps
+  const TreePack *tree = nullptr; // the held plan is a whole traversal (ChainPlan::tree): k_edge_dna_tree, nothing above is read
 };
 
 static void launch_edge_chain(pllgpu_ctx *c, const DevEdge &e, const ChainTailCall &t)
 {
   const ChainPlan &pl = *c->plan;
   dim3 grid((pl.entries + 63) / 64), block(256);
-  if (t.in_kernarg)
+  if (t.tree) // a workgroup of eight waves per tile, tiles in the XCD-aware order
+    hipLaunchKernelGGL(k_edge_dna_tree, xcd_grid(grid.x, 1), dim3(512), 0, c->stream, e, *t.tree, pl.entries, c->gg.scale_mode, c->xcd_order);
+  else if (t.in_kernarg)
     with_chain_variant(c->gg.scale_mode, t.variant, [&](auto SMV, auto C0, auto S1, auto C1) {
       hipLaunchKernelGGL((k_edge_dna_chain_pack<SMV(), C0(), S1(), C1()>), grid, block, 0, c->stream, e, t.pack, pl.entries);
     });
@@ -2251,6 +2276,7 @@ struct ClaimedWork
 {
   pllgpu_ctx *c;
   int heads[2] = {-1, -1};
+  bool tree = false; // the heads' whole plan was held (ChainPlan::tree): its groups first
   std::vector<pllgpu_op_t> ops;
   bool armed = false;
   explicit ClaimedWork(pllgpu_ctx *ctx) : c(ctx) {}
@@ -2260,6 +2286,11 @@ struct ClaimedWork
     if (!armed) return;
     char keep[sizeof g_err];
     memcpy(keep, g_err, sizeof keep); // the error that brought us here is the one to report
+    if (c->plan && tree)
+    {
+      c->tree_held = true;
+      (void)launch_held_tree_groups(c);
+    }
     if (c->plan)
       for (int h : heads)
         if (h >= 0)
@@ -2301,6 +2332,23 @@ static int claim_held_chains(pllgpu_ctx *c, const pllgpu_edge_t *ed, ClaimedWork
   held_p = held_c = -1;
   if (!c->chain_held) return 0;
   const ChainPlan &pl = *c->plan;
+  if (c->tree_held)
+  {
+    // a whole traversal is held: this evaluation takes it in one launch if it is of the edge between the two tops ...
+    for (int h = 0; h < 2 && !ed->gather && !ed->child_is_tip; ++h)
+      if (pl.head_top_clv[h] == ed->parent_clv && pl.head_top_scaler[h] == ed->parent_scaler && pl.head_top_clv[1 - h] == ed->child_clv &&
+          pl.head_top_scaler[1 - h] == ed->child_scaler)
+      {
+        if (int rc = c->block_sums.ensure((pl.entries + 63) / 64)) return rc; // before anything is claimed
+        c->chain_held = c->tree_held = false;
+        held_p = claimed.heads[0] = h;
+        held_c = claimed.heads[1] = 1 - h;
+        claimed.tree = claimed.armed = true;
+        return 0;
+      }
+    // ... any other edge meets today's plan: the groups go out, the chains stay held for the choice below
+    if (int rc = launch_held_tree_groups(c)) return rc;
+  }
   if (c->dna_fast && !ed->gather)
     for (size_t i = pl.held_from; i < pl.stages.size(); ++i)
       for (unsigned h = pl.stages[i].first_head; h < pl.stages[i].first_head + pl.stages[i].nchains; ++h)
@@ -2503,7 +2551,15 @@ extern "C" int pllgpu_edge_loglikelihood(pllgpu_ctx_t *c, const pllgpu_edge_t *e
   if (held_p >= 0 || held_c >= 0)
   {
     ChainTailCall ct;
-    if (int brc = build_chain_tail(c, ed, e, held_p, held_c, ct)) return brc;
+    TreePack tp;
+    if (claimed.tree)
+    {
+      tp.end[0] = c->plan->tree_end[held_p];
+      tp.end[1] = c->plan->tree_end[held_c];
+      ct.tree = &tp;
+    }
+    else if (int brc = build_chain_tail(c, ed, e, held_p, held_c, ct))
+      return brc;
     rc = run_lnl(c, e, ed->child_is_tip != 0, false, ed->freqs_indices, persite_host, lnl_out, ed->device_result, nullptr, &ct);
   }
   else if (use_tail)
