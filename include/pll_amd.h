@@ -545,6 +545,67 @@ int pll_compute_likelihood_derivatives(pll_partition_t *partition, int parent_sc
                                        const unsigned int *params_indices, const double *sumtable,
                                        double *d_f, double *dd_f);
 
+/* ---- Newton branch-length optimisation in one call (this library's own; the reference ships only the bare
+ * t -= d/dd loop of examples/newton/newton.c:55-92, one pll_compute_likelihood_derivatives per step). The whole
+ * iteration runs on the device: one launch per derivative evaluation, chained without a host wait; the host polls
+ * once per 8 evaluations. The first five arguments mean what they mean to pll_compute_likelihood_derivatives;
+ * `sumtable` is the handle pll_update_sumtable filled (a recycled handle fails, a table the library has never seen
+ * is uploaded). All arithmetic is binary64; d / dd are d_f / dd_f, the derivatives of -lnL:
+ *
+ *   t = clamp(t_start, t_min, t_max); lo = t_min; hi = t_max; lo_open = hi_open = true
+ *   repeat up to max_iters times:
+ *     (d, dd) = derivatives at t                          -- one row (t, d, dd) of the trace
+ *     if |d| < tolerance: CONVERGED, stop
+ *     if d > 0: if t == t_min: AT_MIN, stop;  hi = t; hi_open = false
+ *     else:     if t == t_max: AT_MAX, stop;  lo = t; lo_open = false
+ *     cand = dd > 0 ? t - d/dd : (d > 0 ? lo : 2*t)
+ *     if !(cand > lo): cand = lo_open ? lo : 0.5*(lo+hi)    -- also a NaN
+ *     else if !(cand < hi): cand = hi_open ? hi : 0.5*(lo+hi)
+ *     if cand == t: STALLED, stop
+ *     t = cand
+ *   otherwise: MAXITER                                      -- result.t stays the last point evaluated
+ *
+ * (d_f, dd_f) of every row are bit for bit what pll_compute_likelihood_derivatives returns at that t on the same
+ * table. |d| < tolerance is a statement about the slope, not about t: on a flat tail (a very long branch) it holds
+ * at once. With matrix_index >= 0 the transition matrix of result.t is left in that slot exactly as
+ * pll_update_prob_matrices(partition, params_indices, &matrix_index, &result.t, 1) would leave it (host mirror
+ * through pll_gpu_sync_pmatrix), for every status, so pll_update_partials can follow with no further call.
+ *
+ * Fails with PLL_ERROR_PARAM_INVALID - before anything is flushed or launched - for a NULL partition,
+ * params_indices, sumtable, options or result, !(0 <= t_min <= t_max) or non-finite t_min / t_max / t_start,
+ * !(tolerance > 0), max_iters outside 1..PLL_GPU_NEWTON_MAX_ITERS, matrix_index < -1 or >= prob_matrices,
+ * params_indices[k] >= rate_matrices; PLL_ERROR_GPU_UNAVAILABLE without a device; PLL_ERROR_GPU_UNSUPPORTED for the
+ * Lewis and Felsenstein ascertainment-bias corrections (their correction is host arithmetic on separate terms after
+ * every evaluation: use pll_compute_likelihood_derivatives; the Stamatakis correction is served, its extra entries
+ * are ordinary weighted sites). On any failure *result and trace are untouched. Synchronous;
+ * pll_gpu_last_launch_count reports the launches of the call. */
+#define PLL_GPU_NEWTON_MAX_ITERS 64
+#define PLL_GPU_NEWTON_CONVERGED 0   /* |d_f| < tolerance at result.t */
+#define PLL_GPU_NEWTON_AT_MIN    1   /* t == t_min and d_f > 0 there */
+#define PLL_GPU_NEWTON_AT_MAX    2   /* t == t_max and d_f < 0 there */
+#define PLL_GPU_NEWTON_STALLED   3   /* the next point equals the current one (bracket exhausted) */
+#define PLL_GPU_NEWTON_MAXITER   4   /* max_iters evaluations done, none of the above */
+
+typedef struct pll_gpu_newton
+{
+  double t_start, t_min, t_max, tolerance;
+  unsigned int max_iters;      /* 1 .. PLL_GPU_NEWTON_MAX_ITERS */
+  int matrix_index;            /* >= 0: leave P(result.t) in this prob-matrix slot; -1: none */
+} pll_gpu_newton_t;
+
+typedef struct pll_gpu_newton_result
+{
+  double t, d_f, dd_f;         /* the last point evaluated and its derivatives; t is the answer */
+  unsigned int iterations;     /* derivative evaluations performed */
+  unsigned int host_waits;     /* times the call blocked on the device */
+  int status;
+} pll_gpu_newton_result_t;
+
+int pll_gpu_optimize_branch_length(pll_partition_t *partition, int parent_scaler_index, int child_scaler_index,
+                                   const unsigned int *params_indices, const double *sumtable,
+                                   const pll_gpu_newton_t *options, pll_gpu_newton_result_t *result,
+                                   double *trace /* NULL, or 3 * max_iters doubles: (t, d_f, dd_f) per evaluation */);
+
 /* ---- site repeats bookkeeping (src/pll.h:682-742, src/repeats.c) --------------------------- */
 /* scaler vector of a parent whose children are class-compressed (src/pll.h:727-742,
  * src/repeats.c:392-540): parent[i] = left[lids[site]] + right[rids[site]] with site = psites[i]; a NULL

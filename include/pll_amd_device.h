@@ -255,6 +255,35 @@ int pllgpu_sumtable_release(pllgpu_ctx_t *ctx, unsigned int slot);
 int pllgpu_likelihood_derivatives(pllgpu_ctx_t *ctx, unsigned int slot, double branch_length,
                                   const unsigned int *params_indices, unsigned int eval_sites, double *d_f,
                                   double *dd_f);
+/* Safeguarded Newton iteration for the branch length of the slot's table, run on the device: one launch per
+ * evaluation chained on the context's stream (two where rate_cats * states > 1024: the diag table has its own), the
+ * step taken by the workgroup that finishes the sums, no host wait between the launches of a batch of 8; behind each
+ * batch a publish step and one poll of mapped memory (host_waits counts them). With matrix_index >= 0 the transition
+ * matrix of result.t is left in that slot by a k_pmatrix launch that reads t from the device (not waited for). The
+ * recipe, the statuses and the meaning of the fields: pll_gpu_optimize_branch_length (pll_amd.h), whose structs these
+ * mirror. Options out of range: PLLGPU_EINVAL before anything is launched. *result and trace (NULL, or 3 * max_iters
+ * doubles) are written only on success. Launches counted into pllgpu_last_launch_count. */
+#define PLLGPU_NEWTON_MAX_ITERS 64
+#define PLLGPU_NEWTON_CONVERGED 0
+#define PLLGPU_NEWTON_AT_MIN 1
+#define PLLGPU_NEWTON_AT_MAX 2
+#define PLLGPU_NEWTON_STALLED 3
+#define PLLGPU_NEWTON_MAXITER 4
+typedef struct pllgpu_newton
+{
+  double t_start, t_min, t_max, tolerance;
+  unsigned int max_iters;
+  int matrix_index;
+} pllgpu_newton_t;
+typedef struct pllgpu_newton_result
+{
+  double t, d_f, dd_f;
+  unsigned int iterations, host_waits;
+  int status;
+} pllgpu_newton_result_t;
+int pllgpu_optimize_branch_length(pllgpu_ctx_t *ctx, unsigned int slot, const unsigned int *params_indices,
+                                  unsigned int eval_sites, const pllgpu_newton_t *options, pllgpu_newton_result_t *result,
+                                  double *trace);
 /* (L, L', L'') of the per-state extra entries at the branch length of the LAST
  * pllgpu_likelihood_derivatives call on this context, and their scaling counts
  * (src/core_derivatives.c:864-891). Synchronises. */

@@ -46,14 +46,14 @@ struct DevDiag
   unsigned char fidx[kMaxRates];
 };
 
-// entry idx = k * S + j of the table: (e, l e, l^2 e, 0) into o
-__device__ __forceinline__ void diag_entry(const DevDiag &d, unsigned idx, double *o)
+// entry idx = k * S + j of the table at branch length t: (e, l e, l^2 e, 0) into o
+__device__ __forceinline__ void diag_entry(const DevDiag &d, double t, unsigned idx, double *o)
 {
   const unsigned k = idx / d.S, j = idx % d.S;
   const unsigned fi = d.fidx[k];
   const double ki = d.rates[k] / (1.0 - d.prop_invar[fi]);
   const double lam = d.eigenvals[(size_t)fi * d.SP + j];
-  const double e = exp(lam * ki * d.branch_length);
+  const double e = exp(lam * ki * t);
   o[0] = e;
   o[1] = lam * ki * e;
   o[2] = lam * ki * lam * ki * e;
@@ -62,14 +62,17 @@ __device__ __forceinline__ void diag_entry(const DevDiag &d, unsigned idx, doubl
 
 __global__ __launch_bounds__(256) void k_diagtable(const DevDiag d)
 {
-  for (unsigned idx = threadIdx.x; idx < d.R * d.S; idx += blockDim.x) diag_entry(d, idx, d.diag + (size_t)idx * 4);
+  for (unsigned idx = threadIdx.x; idx < d.R * d.S; idx += blockDim.x) diag_entry(d, d.branch_length, idx, d.diag + (size_t)idx * 4);
 }
 
+// One evaluation up to its two sums - the one copy of the per-site arithmetic, the block partials and the pairing of
+// additions that k_derivatives and k_derivatives_newton share. true in thread 0 of the workgroup that arrived last, with
+// (sum1, sum2) = (d_f, dd_f) and the ticket back at zero; false everywhere else.
 // local_diag: every workgroup forms the (small) diag table itself in LDS instead of waiting for a
 // k_diagtable launch - one launch per derivative evaluation, the call a Newton iteration repeats;
 // workgroup 0 also leaves the table in d.diag_out for k_asc_deriv_terms.
-__global__ __launch_bounds__(256) void k_derivatives(const DevDeriv d, const GenGeo g, unsigned tiles_per_wave, const DevDiag dg,
-                                                     unsigned local_diag)
+__device__ __forceinline__ bool derivative_sums(const DevDeriv &d, const GenGeo &g, unsigned tiles_per_wave, const DevDiag &dg,
+                                                double branch_length, unsigned local_diag, double &sum1, double &sum2)
 {
   __shared__ double ws[2][4];
   __shared__ unsigned last;
@@ -82,7 +85,7 @@ __global__ __launch_bounds__(256) void k_derivatives(const DevDeriv d, const Gen
     for (unsigned idx = threadIdx.x; idx < dg.R * dg.S; idx += blockDim.x)
     {
       double *o = ldiag + (size_t)idx * 4;
-      diag_entry(dg, idx, o);
+      diag_entry(dg, branch_length, idx, o);
       if (blockIdx.x == 0)
       {
         double *go = dg.diag + (size_t)idx * 4;
@@ -164,7 +167,7 @@ __global__ __launch_bounds__(256) void k_derivatives(const DevDeriv d, const Gen
     if (last) handoff_after_last_ticket(d.fenced);
   }
   __syncthreads();
-  if (!last) return;
+  if (!last) return false;
   double b1 = 0.0, b2 = 0.0;
   for (unsigned i = threadIdx.x; i < gridDim.x; i += 256)
   {
@@ -180,14 +183,163 @@ __global__ __launch_bounds__(256) void k_derivatives(const DevDeriv d, const Gen
     ws[1][wave] = b2;
   }
   __syncthreads();
-  if (threadIdx.x == 0)
+  if (threadIdx.x != 0) return false;
+  __hip_atomic_store(d.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  sum1 = (ws[0][0] + ws[0][1]) + (ws[0][2] + ws[0][3]);
+  sum2 = (ws[1][0] + ws[1][1]) + (ws[1][2] + ws[1][3]);
+  return true;
+}
+
+__global__ __launch_bounds__(256) void k_derivatives(const DevDeriv d, const GenGeo g, unsigned tiles_per_wave, const DevDiag dg,
+                                                     unsigned local_diag)
+{
+  double d_f, dd_f;
+  if (!derivative_sums(d, g, tiles_per_wave, dg, dg.branch_length, local_diag, d_f, dd_f)) return;
+  __hip_atomic_store(d.result, d_f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(d.result + 2, dd_f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  handoff_before_sequence(d.fenced); // the values are in host memory before the sequence word follows
+  __hip_atomic_store(d.result + 1, d.sequence, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---- Newton branch-length optimisation on the device (pllgpu_optimize_branch_length) ------------
+// One launch per evaluation, chained on the stream: every workgroup reads {t, status} from the state record, the
+// workgroup that arrives last takes the safeguarded step and stores the state the NEXT launch reads. Nothing waits
+// inside a launch: the kernel boundary carries the new t. A launch that finds a terminal status returns at once, so
+// the host enqueues launches in batches without knowing where the run ends.
+constexpr int kNewtonRunning = -1; // any other status is one of PLLGPU_NEWTON_* (terminal)
+
+struct NewtonState
+{
+  double t;               // where the next launch evaluates; once the status is terminal: the last point evaluated
+  double lo, hi;          // the bracket: d_f < 0 at lo and d_f > 0 at hi, unless still open (= t_min / t_max, not evaluated)
+  double d_f, dd_f;       // at the last point evaluated
+  unsigned matrix;        // DevPmat.mindex of the k_pmatrix launch behind the chain reads this word
+  int status;
+  unsigned iterations;    // evaluations so far = rows of the trace
+  unsigned lo_open, hi_open;
+};
+
+struct DevNewton
+{
+  NewtonState *state;
+  double *trace;          // [max_iters][3] (t, d_f, dd_f), device memory
+  double t_first;         // clamp(t_start, t_min, t_max)
+  double t_min, t_max, tolerance;
+  unsigned max_iters;
+  unsigned matrix;
+  unsigned first;         // the launch that starts a run: the state record is written, never read
+};
+
+// what the launch evaluates: false when the run has ended
+__device__ __forceinline__ bool newton_point(const DevNewton &n, double &t)
+{
+  if (n.first)
   {
-    __hip_atomic_store(d.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(d.result, (ws[0][0] + ws[0][1]) + (ws[0][2] + ws[0][3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(d.result + 2, (ws[1][0] + ws[1][1]) + (ws[1][2] + ws[1][3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    handoff_before_sequence(d.fenced); // the values are in host memory before the sequence word follows
-    __hip_atomic_store(d.result + 1, d.sequence, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    t = n.t_first;
+    return true;
   }
+  t = n.state->t;
+  return n.state->status == kNewtonRunning;
+}
+
+// The step, by thread 0 of the workgroup that arrived last: binary64 in exactly the operations written here (no
+// contraction, correctly rounded division), plain stores - the next launch starts behind the kernel boundary.
+__device__ __forceinline__ void newton_advance(const DevNewton &n, double t, double d, double dd)
+{
+#pragma clang fp contract(off)
+  NewtonState s;
+  if (n.first)
+  {
+    s.lo = n.t_min;
+    s.hi = n.t_max;
+    s.iterations = 0;
+    s.lo_open = s.hi_open = 1u;
+  }
+  else
+    s = *n.state;
+  if (s.iterations < PLLGPU_NEWTON_MAX_ITERS) // always: a run ends at max_iters <= PLLGPU_NEWTON_MAX_ITERS evaluations
+  {
+    double *row = n.trace + (size_t)3 * s.iterations;
+    row[0] = t;
+    row[1] = d;
+    row[2] = dd;
+  }
+  s.iterations += 1;
+  s.t = t;
+  s.d_f = d;
+  s.dd_f = dd;
+  s.matrix = n.matrix;
+  s.status = kNewtonRunning;
+  if (fabs(d) < n.tolerance)
+    s.status = PLLGPU_NEWTON_CONVERGED;
+  else if (d > 0.0 && t == n.t_min)
+    s.status = PLLGPU_NEWTON_AT_MIN;
+  else if (!(d > 0.0) && t == n.t_max)
+    s.status = PLLGPU_NEWTON_AT_MAX;
+  else
+  {
+    if (d > 0.0)
+    {
+      s.hi = t;
+      s.hi_open = 0u;
+    }
+    else
+    {
+      s.lo = t;
+      s.lo_open = 0u;
+    }
+    double cand = dd > 0.0 ? t - d / dd : (d > 0.0 ? s.lo : 2.0 * t);
+    if (!(cand > s.lo)) // also a NaN
+      cand = s.lo_open ? s.lo : 0.5 * (s.lo + s.hi);
+    else if (!(cand < s.hi))
+      cand = s.hi_open ? s.hi : 0.5 * (s.lo + s.hi);
+    if (cand == t)
+      s.status = PLLGPU_NEWTON_STALLED;
+    else if (s.iterations == n.max_iters)
+      s.status = PLLGPU_NEWTON_MAXITER; // t stays the last point evaluated
+    else
+      s.t = cand;
+  }
+  *n.state = s;
+}
+
+// large diag tables (k_diagtable's case): the table of the state record's t
+__global__ __launch_bounds__(256) void k_diagtable_newton(const DevDiag d, const DevNewton n)
+{
+  double t;
+  if (!newton_point(n, t)) return;
+  for (unsigned idx = threadIdx.x; idx < d.R * d.S; idx += blockDim.x) diag_entry(d, t, idx, d.diag + (size_t)idx * 4);
+}
+
+__global__ __launch_bounds__(256) void k_derivatives_newton(const DevDeriv d, const GenGeo g, unsigned tiles_per_wave, const DevDiag dg,
+                                                            unsigned local_diag, const DevNewton n)
+{
+  double t, d_f, dd_f;
+  if (!newton_point(n, t)) return; // the same answer in every workgroup: nobody has taken a ticket
+  if (!derivative_sums(d, g, tiles_per_wave, dg, t, local_diag, d_f, dd_f)) return;
+  newton_advance(n, t, d_f, dd_f);
+}
+
+// the publish step behind a batch of launches: state and trace into mapped host memory, then the sequence word the
+// host polls. One wave, so the wait in front of the sequence word covers every lane's stores.
+constexpr unsigned kNewtonOut = 8;       // result[kNewtonOut + 0..4] = t, d_f, dd_f, status, iterations (as doubles)
+constexpr unsigned kNewtonTraceOut = 16; // result[kNewtonTraceOut + 3 * i + 0..2] = row i of the trace
+
+__global__ __launch_bounds__(64) void k_newton_publish(const NewtonState *state, const double *trace, double *result, double sequence,
+                                                       int fenced)
+{
+  const NewtonState s = *state;
+  const unsigned rows = s.iterations < PLLGPU_NEWTON_MAX_ITERS ? s.iterations : PLLGPU_NEWTON_MAX_ITERS;
+  for (unsigned i = threadIdx.x; i < 3u * rows; i += 64u)
+    __hip_atomic_store(result + kNewtonTraceOut + i, trace[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (threadIdx.x < 5u)
+  {
+    const unsigned i = threadIdx.x;
+    const double v = i == 0u ? s.t : i == 1u ? s.d_f : i == 2u ? s.dd_f : i == 3u ? (double)s.status : (double)s.iterations;
+    __hip_atomic_store(result + kNewtonOut + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  handoff_before_sequence(fenced);
+  if (threadIdx.x == 0) __hip_atomic_store(result + 1, sequence, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // per-rate scalers only: multiply column k of every site by 2^(-256 * min(rs_k - min_k rs, 4))

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <thread>
 #include <cstdarg>
 #include <cstdio>
@@ -224,6 +225,8 @@ struct pllgpu_ctx
   DevBuf<unsigned char> ins_cands;
   DevBuf<unsigned char> mfma_flags;      // [op in launch][rate][entry] scaling decisions (kernels_mfma.h)
   DevBuf<double> eigenvals, rates, diag; // derivatives: [rate_matrices][SP], [R], [R][S][4]
+  DevBuf<double> newton;                 // pllgpu_optimize_branch_length: the state record (NewtonState), then the trace
+  unsigned newton_batch = 8;             // ... and how many evaluations it enqueues between two polls (tools/newton_device_latency.py)
   DevBuf<double> evecs, ievecs, brlen;   // device P-matrices: [rate_matrices][S][SP] x 2, staged branch lengths
   DevBuf<unsigned> mindex;               // staged matrix indices
   DevBuf<unsigned> rep_table, rep_blocksum, rep_counts; // site-repeats class computation (kernels_repeats.h): arena, bitmaps, counts per op of a call
@@ -480,6 +483,8 @@ static void derive_geometry(pllgpu_ctx *c)
     if (*v && *v != '0') c->fenced = 1;
   if (const char *v = getenv("PLL_AMD_NO_PLAN_CACHE"))
     if (*v && *v != '0') c->plan_cache = false;
+  if (const char *v = getenv("PLL_AMD_NEWTON_BATCH")) // A/B (tools/newton_device_latency.py): evaluations enqueued per host wait
+    if (atoi(v) >= 1) c->newton_batch = (unsigned)std::min(atoi(v), PLLGPU_NEWTON_MAX_ITERS);
   if (const char *v = getenv("PLL_AMD_NO_FUSE_GG"))
     if (*v && *v != '0') c->fuse_gg = false;
   c->subtrees = c->dna_fast;
@@ -695,6 +700,7 @@ extern "C" void pllgpu_destroy(pllgpu_ctx_t *c)
   c->rep_final.release();
   c->rates.release();
   c->diag.release();
+  c->newton.release();
   for (auto &b : c->sumtable) b.release();
   c->pattern_weights.release();
   c->invariant.release();
@@ -3122,17 +3128,24 @@ extern "C" int pllgpu_sumtable_release(pllgpu_ctx_t *c, unsigned slot)
   return 0;
 }
 
-extern "C" int pllgpu_likelihood_derivatives(pllgpu_ctx_t *c, unsigned slot, double branch_length,
-                                             const unsigned *params_indices, unsigned eval_sites, double *d_f, double *dd_f)
+// what one derivative evaluation launches with, for the per-call path and the Newton chain alike
+struct DerivLaunch
 {
-  CHECK_CTX(c);
+  DevDiag dg;
+  DevDeriv dv;
+  size_t diag_bytes;
+  unsigned local_diag, tpw, blocks;
+};
+
+static int deriv_launch_setup(pllgpu_ctx *c, unsigned slot, const unsigned *params_indices, unsigned eval_sites, DerivLaunch &l)
+{
   const pllgpu_geometry_t &g = c->geo;
   if (slot >= PLLGPU_SUMTABLE_SLOTS || !c->sumtable[slot].p) return fail(PLLGPU_EINVAL, "sumtable slot %u is empty", slot);
   if (eval_sites == 0 || eval_sites > g.sites_alloc) return fail(PLLGPU_EINVAL, "eval_sites %u out of range", eval_sites);
   if (!c->eigenvals.p || !c->rates.p) return fail(PLLGPU_EINVAL, "eigenvalues / category rates were not uploaded");
   if (int rc = c->diag.ensure((size_t)g.rate_cats * g.states * 4)) return rc;
-  DevDiag dg;
-  DevDeriv dv;
+  DevDiag &dg = l.dg;
+  DevDeriv &dv = l.dv;
   memset(&dg, 0, sizeof dg);
   memset(&dv, 0, sizeof dv);
   for (unsigned k = 0; k < g.rate_cats; ++k)
@@ -3144,14 +3157,12 @@ extern "C" int pllgpu_likelihood_derivatives(pllgpu_ctx_t *c, unsigned slot, dou
   dg.eigenvals = c->eigenvals.p;
   dg.rates = c->rates.p;
   dg.prop_invar = c->prop_invar.p;
-  dg.branch_length = branch_length;
   dg.S = g.states;
   dg.SP = g.states_padded;
   dg.R = g.rate_cats;
   // small tables are formed inside k_derivatives (one launch per evaluation); large ones keep the pre-kernel
-  const size_t diag_bytes = (size_t)g.rate_cats * g.states * 4 * sizeof(double);
-  const unsigned local_diag = diag_bytes <= 32768 ? 1u : 0u;
-  if (!local_diag) hipLaunchKernelGGL(k_diagtable, dim3(1), dim3(256), 0, c->stream, dg);
+  l.diag_bytes = (size_t)g.rate_cats * g.states * 4 * sizeof(double);
+  l.local_diag = l.diag_bytes <= 32768 ? 1u : 0u;
 
   dv.table = c->sumtable[slot].p;
   dv.diag = c->diag.p;
@@ -3163,17 +3174,26 @@ extern "C" int pllgpu_likelihood_derivatives(pllgpu_ctx_t *c, unsigned slot, dou
   dv.block_sums = c->block_sums.p;
   dv.counter = c->counter.p;
   dv.result = c->result_dev;
-  c->seq += 1.0;
-  dv.sequence = c->seq;
   dv.sites = eval_sites;
   dv.fenced = c->fenced;
-  unsigned long long seq_bits;
-  memcpy(&seq_bits, &c->seq, sizeof seq_bits);
   const unsigned tiles = (eval_sites + 63) / 64;
-  const unsigned tpw = (tiles + 4 * 1024 - 1) / (4 * 1024);
-  const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
-  hipLaunchKernelGGL(k_derivatives, dim3(blocks), dim3(256), local_diag ? diag_bytes : 0, c->stream, dv, c->gg, tpw, dg, local_diag);
-  HIP_TRY(hipGetLastError());
+  l.tpw = (tiles + 4 * 1024 - 1) / (4 * 1024);
+  l.blocks = (tiles + 4 * l.tpw - 1) / (4 * l.tpw);
+  return 0;
+}
+
+// the next sequence word, for a kernel to leave in result[1]
+static double next_sequence(pllgpu_ctx *c)
+{
+  c->seq += 1.0;
+  return c->seq;
+}
+
+// wait until result[1] carries `sequence`: a poll of mapped memory, a stream synchronise once that has taken 20 ms
+static int wait_for_sequence(pllgpu_ctx *c, double sequence)
+{
+  unsigned long long seq_bits;
+  memcpy(&seq_bits, &sequence, sizeof seq_bits);
   volatile double *res = c->result_host;
   const auto t0 = std::chrono::steady_clock::now();
   unsigned spins = 0;
@@ -3185,8 +3205,119 @@ extern "C" int pllgpu_likelihood_derivatives(pllgpu_ctx_t *c, unsigned slot, dou
       break;
     }
   }
+  return 0;
+}
+
+extern "C" int pllgpu_likelihood_derivatives(pllgpu_ctx_t *c, unsigned slot, double branch_length,
+                                             const unsigned *params_indices, unsigned eval_sites, double *d_f, double *dd_f)
+{
+  CHECK_CTX(c);
+  DerivLaunch l;
+  if (int rc = deriv_launch_setup(c, slot, params_indices, eval_sites, l)) return rc;
+  l.dg.branch_length = branch_length;
+  if (!l.local_diag) hipLaunchKernelGGL(k_diagtable, dim3(1), dim3(256), 0, c->stream, l.dg);
+  l.dv.sequence = next_sequence(c);
+  hipLaunchKernelGGL(k_derivatives, dim3(l.blocks), dim3(256), l.local_diag ? l.diag_bytes : 0, c->stream, l.dv, c->gg, l.tpw, l.dg,
+                     l.local_diag);
+  HIP_TRY(hipGetLastError());
+  if (int rc = wait_for_sequence(c, l.dv.sequence)) return rc;
   *d_f = c->result_host[0];
   *dd_f = c->result_host[2];
+  return 0;
+}
+
+// Newton's iteration on the device (kernels_deriv.h): one k_derivatives_newton launch per evaluation (behind a
+// k_diagtable_newton where the diag table is large), newton_batch = 8 evaluations enqueued at a time with no wait between
+// them; behind each batch k_newton_publish and ONE poll. Launches behind the terminal one return at once.
+static_assert(kNewtonTraceOut + 3 * PLLGPU_NEWTON_MAX_ITERS <= kResultBytes / sizeof(double), "the trace fits the mapped result block");
+static_assert(sizeof(NewtonState) == 8 * sizeof(double), "the state record: eight words in front of the trace");
+
+extern "C" int pllgpu_optimize_branch_length(pllgpu_ctx_t *c, unsigned slot, const unsigned *params_indices, unsigned eval_sites,
+                                             const pllgpu_newton_t *opt, pllgpu_newton_result_t *result, double *trace)
+{
+  CHECK_CTX(c);
+  const pllgpu_geometry_t &g = c->geo;
+  if (!opt || !result) return fail(PLLGPU_EINVAL, "null options / result");
+  if (!(opt->t_min >= 0) || !(opt->t_min <= opt->t_max) || !std::isfinite(opt->t_max) || !std::isfinite(opt->t_start) ||
+      !(opt->tolerance > 0) || opt->max_iters < 1 || opt->max_iters > PLLGPU_NEWTON_MAX_ITERS || opt->matrix_index < -1 ||
+      opt->matrix_index >= (int)g.prob_matrices)
+    return fail(PLLGPU_EINVAL, "Newton options out of range");
+  const bool with_matrix = opt->matrix_index >= 0;
+  if (with_matrix && (!c->evecs.p || !c->ievecs.p)) return fail(PLLGPU_EINVAL, "eigensystem was not uploaded");
+  DerivLaunch l;
+  if (int rc = deriv_launch_setup(c, slot, params_indices, eval_sites, l)) return rc;
+  if (int rc = c->newton.ensure(8 + 3 * PLLGPU_NEWTON_MAX_ITERS)) return rc;
+  DevNewton n;
+  memset(&n, 0, sizeof n);
+  n.state = reinterpret_cast<NewtonState *>(c->newton.p);
+  n.trace = c->newton.p + 8;
+  n.t_first = std::min(std::max(opt->t_start, opt->t_min), opt->t_max);
+  n.t_min = opt->t_min;
+  n.t_max = opt->t_max;
+  n.tolerance = opt->tolerance;
+  n.max_iters = opt->max_iters;
+  n.matrix = with_matrix ? (unsigned)opt->matrix_index : 0u;
+  c->last_launches = 0;
+  unsigned waits = 0;
+  int status = kNewtonRunning;
+  for (unsigned done = 0; done < opt->max_iters && status == kNewtonRunning;)
+  {
+    const unsigned batch = std::min(c->newton_batch, opt->max_iters - done);
+    for (unsigned i = 0; i < batch; ++i, ++done)
+    {
+      n.first = done == 0 ? 1u : 0u;
+      if (!l.local_diag)
+      {
+        hipLaunchKernelGGL(k_diagtable_newton, dim3(1), dim3(256), 0, c->stream, l.dg, n);
+        ++c->last_launches;
+      }
+      hipLaunchKernelGGL(k_derivatives_newton, dim3(l.blocks), dim3(256), l.local_diag ? l.diag_bytes : 0, c->stream, l.dv, c->gg, l.tpw,
+                         l.dg, l.local_diag, n);
+      ++c->last_launches;
+    }
+    const double sequence = next_sequence(c);
+    hipLaunchKernelGGL(k_newton_publish, dim3(1), dim3(64), 0, c->stream, n.state, n.trace, c->result_dev, sequence, c->fenced);
+    ++c->last_launches;
+    HIP_TRY(hipGetLastError());
+    if (int rc = wait_for_sequence(c, sequence)) return rc;
+    ++waits;
+    status = (int)c->result_host[kNewtonOut + 3];
+  }
+  const unsigned iterations = (unsigned)c->result_host[kNewtonOut + 4];
+  if (status == kNewtonRunning || iterations < 1 || iterations > opt->max_iters)
+    return fail(PLLGPU_ERUNTIME, "the Newton chain ended without a terminal status (status %d after %u evaluations)", status, iterations);
+  if (with_matrix)
+  {
+    // P(result.t) straight from the state record: no value of t crosses to the host and back
+    DevPmat d;
+    memset(&d, 0, sizeof d);
+    memcpy(d.fidx, l.dg.fidx, sizeof d.fidx);
+    d.pmat = c->pmat.p;
+    d.evecs = c->evecs.p;
+    d.ievecs = c->ievecs.p;
+    d.evals = c->eigenvals.p;
+    d.rates = c->rates.p;
+    d.prop_invar = c->prop_invar.p;
+    d.mindex = &n.state->matrix;
+    d.brlen = &n.state->t;
+    d.pm_stride = c->pm_stride;
+    d.S = g.states;
+    d.SP = g.states_padded;
+    d.SPT = c->gg.SPT;
+    const size_t lds = (size_t)2 * g.states * (g.states | 1u) * sizeof(double);
+    raise_lds_limit((const void *)k_pmatrix, c->device, lds);
+    ++c->pm_version[opt->matrix_index];
+    hipLaunchKernelGGL(k_pmatrix, dim3(1, g.rate_cats), dim3(256), lds, c->stream, d);
+    ++c->last_launches;
+    HIP_TRY(hipGetLastError());
+  }
+  result->t = c->result_host[kNewtonOut + 0];
+  result->d_f = c->result_host[kNewtonOut + 1];
+  result->dd_f = c->result_host[kNewtonOut + 2];
+  result->iterations = iterations;
+  result->host_waits = waits;
+  result->status = status;
+  if (trace) memcpy(trace, c->result_host + kNewtonTraceOut, sizeof(double) * 3 * iterations);
   return 0;
 }
 

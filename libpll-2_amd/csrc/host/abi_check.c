@@ -105,3 +105,15 @@ AT(pll_gpu_insertion_t, child2_matrix_index, 20);
 
 /* the extension block must start 8-byte aligned directly behind the public struct */
 _Static_assert(sizeof(pll_partition_t) % 8 == 0, "extension block alignment");
+
+/* options and result of pll_gpu_optimize_branch_length, mirrored field for field by the device layer */
+_Static_assert(sizeof(pll_gpu_newton_t) == 40 && sizeof(pllgpu_newton_t) == 40, "pll_gpu_newton_t size");
+AT(pll_gpu_newton_t, tolerance, 24);
+AT(pll_gpu_newton_t, max_iters, 32);
+AT(pll_gpu_newton_t, matrix_index, 36);
+_Static_assert(sizeof(pll_gpu_newton_result_t) == 40 && sizeof(pllgpu_newton_result_t) == 40, "pll_gpu_newton_result_t size");
+AT(pll_gpu_newton_result_t, dd_f, 16);
+AT(pll_gpu_newton_result_t, iterations, 24);
+AT(pll_gpu_newton_result_t, host_waits, 28);
+AT(pll_gpu_newton_result_t, status, 32);
+_Static_assert(PLL_GPU_NEWTON_MAX_ITERS == PLLGPU_NEWTON_MAX_ITERS && PLL_GPU_NEWTON_MAXITER == PLLGPU_NEWTON_MAXITER, "Newton constants");

@@ -218,6 +218,30 @@ int pll_gpu_release_sumtable(pll_partition_t *p, const double *sumtable)
   return PLL_SUCCESS;
 }
 
+/* the device slot an evaluation on this handle reads, or -1 with the error set: a recycled handle fails, a table the
+ * library has never seen is uploaded */
+static int resident_slot(pll_amd_ext_t *x, const double *sumtable, const char *who)
+{
+  int slot = slot_of(x, sumtable, 0);
+  if (slot >= 0) return slot;
+  if (was_evicted(x, sumtable))
+  {
+    pll_set_error(PLL_ERROR_GPU_RUNTIME, "%s: the device table of this sumtable was recycled "
+                  "(more than %d live sumtables in one partition); call pll_update_sumtable again", who, PLLGPU_SUMTABLE_SLOTS);
+    fail_loudly(who);
+    return -1;
+  }
+  /* a table this library did not produce: the caller's buffer is the truth */
+  slot = slot_of(x, sumtable, 1);
+  if (pllgpu_sumtable_upload(x->ctx, (unsigned)slot, sumtable) != 0)
+  {
+    x->sumtable_key[slot] = NULL;
+    pll_set_gpu_error(who);
+    return -1;
+  }
+  return slot;
+}
+
 int pll_compute_likelihood_derivatives(pll_partition_t *p, int parent_scaler_index, int child_scaler_index,
                                        double branch_length, const unsigned int *params_indices,
                                        const double *sumtable, double *d_f, double *dd_f)
@@ -235,24 +259,8 @@ int pll_compute_likelihood_derivatives(pll_partition_t *p, int parent_scaler_ind
     return fail_loudly("pll_compute_likelihood_derivatives");
   }
   if (!flush_deriv_model(p, x)) return fail_loudly("pll_compute_likelihood_derivatives");
-  int slot = slot_of(x, sumtable, 0);
-  if (slot < 0)
-  {
-    if (was_evicted(x, sumtable))
-    {
-      pll_set_error(PLL_ERROR_GPU_RUNTIME, "pll_compute_likelihood_derivatives: the device table of this sumtable was recycled "
-                    "(more than %d live sumtables in one partition); call pll_update_sumtable again", PLLGPU_SUMTABLE_SLOTS);
-      return fail_loudly("pll_compute_likelihood_derivatives");
-    }
-    /* a table this library did not produce: the caller's buffer is the truth */
-    slot = slot_of(x, sumtable, 1);
-    if (pllgpu_sumtable_upload(x->ctx, (unsigned)slot, sumtable) != 0)
-    {
-      x->sumtable_key[slot] = NULL;
-      pll_set_gpu_error("pll_compute_likelihood_derivatives (table upload)");
-      return PLL_FAILURE;
-    }
-  }
+  const int slot = resident_slot(x, sumtable, "pll_compute_likelihood_derivatives");
+  if (slot < 0) return PLL_FAILURE;
   /* Stamatakis: the per-state extra entries are ordinary weighted sites (src/core_derivatives.c:733-742) */
   const unsigned int eval_sites = p->sites + (asc_type == PLL_ATTRIB_AB_STAMATAKIS ? p->states : 0);
   if (pllgpu_likelihood_derivatives(x->ctx, (unsigned)slot, branch_length, params_indices, eval_sites, d_f, dd_f) != 0)
@@ -301,5 +309,87 @@ int pll_compute_likelihood_derivatives(pll_partition_t *p, int parent_scaler_ind
       return PLL_FAILURE;
     }
   }
+  return PLL_SUCCESS;
+}
+
+/* Newton's iteration for one branch length, on the device (include/pll_amd.h; kernels_deriv.h: k_derivatives_newton) */
+int pll_gpu_optimize_branch_length(pll_partition_t *p, int parent_scaler_index, int child_scaler_index,
+                                   const unsigned int *params_indices, const double *sumtable,
+                                   const pll_gpu_newton_t *options, pll_gpu_newton_result_t *result, double *trace)
+{
+  static const char who[] = "pll_gpu_optimize_branch_length";
+  unsigned int k;
+  (void)parent_scaler_index; /* the scalers enter through the Lewis / Felsenstein terms alone, which are refused */
+  (void)child_scaler_index;
+  if (!p)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: NULL partition", who);
+    return fail_loudly(who);
+  }
+  pll_amd_ext_t *x = pll_ext(p);
+  if (!x || !x->ctx)
+  {
+    pll_set_error(PLL_ERROR_GPU_UNAVAILABLE, "%s: no MI355X context behind this partition; this library has no CPU path", who);
+    return fail_loudly(who);
+  }
+  if (!params_indices || !sumtable || !options || !result)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: NULL argument", who);
+    return fail_loudly(who);
+  }
+  if (!(options->t_min >= 0) || !(options->t_min <= options->t_max) || !isfinite(options->t_max) || !isfinite(options->t_start) ||
+      !(options->tolerance > 0) || options->max_iters < 1 || options->max_iters > PLL_GPU_NEWTON_MAX_ITERS ||
+      options->matrix_index < -1 || options->matrix_index >= (int)p->prob_matrices)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: options out of range (t_start %g, bounds [%g, %g], tolerance %g, max_iters %u, matrix_index %d)",
+                  who, options->t_start, options->t_min, options->t_max, options->tolerance, options->max_iters, options->matrix_index);
+    return fail_loudly(who);
+  }
+  for (k = 0; k < p->rate_cats; ++k)
+    if (params_indices[k] >= p->rate_matrices)
+    {
+      pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: params_indices[%u] out of range", who, k);
+      return fail_loudly(who);
+    }
+  const int asc_type = (int)(p->attributes & PLL_ATTRIB_AB_MASK);
+  if (asc_type && asc_type != PLL_ATTRIB_AB_STAMATAKIS)
+  {
+    pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: the Lewis / Felsenstein correction is host arithmetic after every evaluation; "
+                  "iterate over pll_compute_likelihood_derivatives", who);
+    return fail_loudly(who);
+  }
+  for (k = 0; k < p->rate_cats; ++k)
+    if (!p->eigen_decomp_valid[params_indices[k]] && !pll_update_eigen(p, params_indices[k])) return PLL_FAILURE;
+  if (!flush_deriv_model(p, x)) return fail_loudly(who);
+  const int slot = resident_slot(x, sumtable, who);
+  if (slot < 0) return PLL_FAILURE;
+
+  pllgpu_newton_t opt;
+  pllgpu_newton_result_t res;
+  opt.t_start = options->t_start;
+  opt.t_min = options->t_min;
+  opt.t_max = options->t_max;
+  opt.tolerance = options->tolerance;
+  opt.max_iters = options->max_iters;
+  opt.matrix_index = options->matrix_index;
+  /* Stamatakis: the per-state extra entries are ordinary weighted sites (src/core_derivatives.c:733-742) */
+  const unsigned int eval_sites = p->sites + (asc_type == PLL_ATTRIB_AB_STAMATAKIS ? p->states : 0);
+  /* (a caller of `trace` gets its rows only once the whole call has succeeded: the device layer writes last) */
+  if (pllgpu_optimize_branch_length(x->ctx, (unsigned)slot, params_indices, eval_sites, &opt, &res, trace) != 0)
+  {
+    pll_set_gpu_error(who);
+    return PLL_FAILURE;
+  }
+  if (options->matrix_index >= 0)
+  {
+    pll_pmatrix_formed_on_device(p, x, params_indices, (unsigned int)options->matrix_index);
+    if (x->eager_mirror && !pll_gpu_sync_pmatrix(p, options->matrix_index)) return PLL_FAILURE;
+  }
+  result->t = res.t;
+  result->d_f = res.d_f;
+  result->dd_f = res.dd_f;
+  result->iterations = res.iterations;
+  result->host_waits = res.host_waits;
+  result->status = res.status;
   return PLL_SUCCESS;
 }

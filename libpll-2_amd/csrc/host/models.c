@@ -240,6 +240,20 @@ int pll_update_eigen(pll_partition_t *p, unsigned int idx)
   return PLL_SUCCESS;
 }
 
+void pll_pmatrix_formed_on_device(const pll_partition_t *p, pll_amd_ext_t *x, const unsigned int *params_indices,
+                                  unsigned int matrix_index)
+{
+  unsigned int n;
+  x->pmatrix_dirty[matrix_index] = 0;
+  x->pmatrix_stale[matrix_index] = 1;
+  for (n = 0; n < p->rate_cats; ++n)
+  {
+    const size_t at = (size_t)matrix_index * p->rate_cats + n;
+    x->pmatrix_params[at] = (params_indices[n] < 0xFFu && !x->model_foreign[params_indices[n]]) ? (unsigned char)params_indices[n] : 0xFFu;
+    x->pmatrix_version[at] = x->model_version[params_indices[n]];
+  }
+}
+
 int pll_update_prob_matrices(pll_partition_t *p, const unsigned int *params_indices,
                              const unsigned int *matrix_indices, const double *branch_lengths,
                              unsigned int count)
@@ -325,17 +339,7 @@ int pll_update_prob_matrices(pll_partition_t *p, const unsigned int *params_indi
     pll_set_gpu_error("pll_update_prob_matrices");
     return PLL_FAILURE;
   }
-  for (b = 0; b < count; ++b)
-  {
-    x->pmatrix_dirty[matrix_indices[b]] = 0;
-    x->pmatrix_stale[matrix_indices[b]] = 1;
-    for (n = 0; n < p->rate_cats; ++n)
-    {
-      const size_t at = (size_t)matrix_indices[b] * p->rate_cats + n;
-      x->pmatrix_params[at] = (params_indices[n] < 0xFFu && !x->model_foreign[params_indices[n]]) ? (unsigned char)params_indices[n] : 0xFFu;
-      x->pmatrix_version[at] = x->model_version[params_indices[n]];
-    }
-  }
+  for (b = 0; b < count; ++b) pll_pmatrix_formed_on_device(p, x, params_indices, matrix_indices[b]);
   if (x->eager_mirror) return pll_gpu_sync_pmatrix(p, -1);
   return PLL_SUCCESS;
 }

@@ -135,6 +135,10 @@ int pll_update_repeats_device(pll_partition_t *p, pll_amd_ext_t *x, const pll_op
                               unsigned int count, const unsigned int *level, unsigned int nlevels);
 int pll_flush_pmatrix(pll_partition_t *p, pll_amd_ext_t *x, unsigned int first, unsigned int last);
 int pll_flush_repeats(pll_partition_t *p, pll_amd_ext_t *x, unsigned int node);
+/* a kernel has just formed this transition matrix on the device with these params_indices: the device copy is the
+ * truth, the host mirror waits for pll_gpu_sync_pmatrix (models.c) */
+void pll_pmatrix_formed_on_device(const pll_partition_t *p, pll_amd_ext_t *x, const unsigned int *params_indices,
+                                  unsigned int matrix_index);
 /* one end of an edge evaluation: its CLV (or tip codes), its scaler vector and its class map (likelihood.c) */
 int pll_prepare_end(pll_partition_t *p, pll_amd_ext_t *x, unsigned int clv, int scaler);
 /* the class map of `node` (all nodes: node < 0) was written by something other than the class kernels, or must be

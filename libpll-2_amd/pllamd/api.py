@@ -147,7 +147,35 @@ class Insertion(C.Structure):
     ]
 
 
+class Newton(C.Structure):
+    """pll_gpu_newton_t (include/pll_amd.h): options of pll_gpu_optimize_branch_length"""
+    _fields_ = [
+        ("t_start", C.c_double),
+        ("t_min", C.c_double),
+        ("t_max", C.c_double),
+        ("tolerance", C.c_double),
+        ("max_iters", C.c_uint),
+        ("matrix_index", C.c_int),
+    ]
+
+
+class NewtonResult(C.Structure):
+    """pll_gpu_newton_result_t (include/pll_amd.h)"""
+    _fields_ = [
+        ("t", C.c_double),
+        ("d_f", C.c_double),
+        ("dd_f", C.c_double),
+        ("iterations", C.c_uint),
+        ("host_waits", C.c_uint),
+        ("status", C.c_int),
+    ]
+
+
+NEWTON_MAX_ITERS = 64
+NEWTON_CONVERGED, NEWTON_AT_MIN, NEWTON_AT_MAX, NEWTON_STALLED, NEWTON_MAXITER = 0, 1, 2, 3, 4
+
 assert C.sizeof(Insertion) == 24
+assert C.sizeof(Newton) == 40 and C.sizeof(NewtonResult) == 40
 assert C.sizeof(Partition) == 232 and C.sizeof(Repeats) == 104 and C.sizeof(Operation) == 32
 assert C.sizeof(Parsimony) == 104 and C.sizeof(ParsBuildOp) == 12
 
@@ -230,6 +258,8 @@ _GPU_PROTOS = {
     "pll_gpu_node_ancestral_async": (C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p, C.c_void_p]),
     "pll_gpu_insertion_loglikelihoods": (
         C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.POINTER(Insertion), C.c_uint, c_uint_p, c_double_p]),
+    "pll_gpu_optimize_branch_length": (
+        C.c_int, [PartitionP, C.c_int, C.c_int, c_uint_p, c_double_p, C.POINTER(Newton), C.POINTER(NewtonResult), c_double_p]),
     "pll_gpu_last_algorithmic_bytes": (C.c_double, [PartitionP]),
     "pll_gpu_sync_repeats": (C.c_int, [PartitionP, C.c_int]),
     "pll_gpu_sync_all": (C.c_int, [PartitionP]),

@@ -326,6 +326,19 @@ class Session:
             raise RuntimeError(f"pll_compute_likelihood_derivatives: [{self.lib.errno()}] {self.lib.errmsg()}")
         return d1.value, d2.value
 
+    def optimize_branch(self, edge, sumtable, t_start, t_min, t_max, tolerance, max_iters=api.NEWTON_MAX_ITERS,
+                        matrix_index=-1):
+        """pll_gpu_optimize_branch_length (libpll_amd.so only): the whole safeguarded Newton iteration of pllamd.newton
+        in one call. Returns (result, trace): the api.NewtonResult and the evaluations as rows (t, d_f, dd_f)."""
+        opt = api.Newton(float(t_start), float(t_min), float(t_max), float(tolerance), int(max_iters), int(matrix_index))
+        res = api.NewtonResult()
+        trace = np.full((max(int(max_iters), 1), 3), np.nan)
+        ok = self.lib.pll_gpu_optimize_branch_length(self.p, edge[1], edge[3], api.uptr(self._fi), api.dptr(sumtable),
+                                                     C.byref(opt), C.byref(res), api.dptr(trace))
+        if not ok:
+            raise RuntimeError(f"pll_gpu_optimize_branch_length: [{self.lib.errno()}] {self.lib.errmsg()}")
+        return res, trace[:res.iterations].copy()
+
     def close(self):
         if self.p:
             self.lib.pll_partition_destroy(self.p)
