@@ -439,6 +439,14 @@ int pll_update_repeats_device(pll_partition_t *p, pll_amd_ext_t *x, const pll_op
     if (!failed) ok = classes_call(p, x, ops, rop, idx, kept, counts, &changed);
     for (i = 0; i < count && ok; ++i)
       if (keep[i] == 2) ok = follow_count(p, x, &ops[i], 0u, &changed);
+    /* every op names the scaler slot its parent's classes go with, the later op of the list last as in the reference
+     * (src/repeats.c:328-369 sets the field on every call): an op whose map stands - it was skipped above - may come
+     * back with another slot than last time, or another op may have used its slot in between */
+    for (i = 0; i < count && ok; ++i)
+    {
+      const int slot = ops[i].parent_scaler_index;
+      if (slot != PLL_SCALE_BUFFER_NONE) r->perscale_ids[slot] = r->pernode_ids[ops[i].parent_clv_index];
+    }
     if (!ok) /* whatever the device left of these maps is not what their stamps say */
       for (i = 0; i < count; ++i)
         if (keep[i]) pll_maps_touched(x, p, (int)ops[i].parent_clv_index);

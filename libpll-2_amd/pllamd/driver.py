@@ -253,6 +253,17 @@ class Session:
                 a = a[api.as_np(sid, c.sites, np.uint32)]
         return a
 
+    def write_scaler(self, scaler_index, clv_index, counts):
+        """the caller's own scaling counts into partition->scale_buffer[scaler_index] - [entries] or [entries][rates] with
+        PLL_ATTRIB_RATE_SCALERS, entries = pll_get_sites_number of the node the buffer belongs to. read_scaler first
+        settles the device side (whatever pll_update_partials holds back is launched, the host copy becomes current);
+        afterwards libpll_amd.so is told that the host copy is the newer one"""
+        cur = self.read_scaler(scaler_index, clv_index, expand=False)
+        new = np.ascontiguousarray(counts, dtype=np.uint32).reshape(cur.shape)
+        api.as_np(self.part.scale_buffer[scaler_index], new.size, np.uint32)[:] = new.ravel()
+        if self.lib.is_amd:
+            self.lib.pll_gpu_invalidate(self.p, api.DIRTY_SCALER, scaler_index)
+
     # ---- branch-length derivatives (SURVEY section 8 row f1) ---------------------------------
     def set_model(self, exch, freqs, rates):
         """substitution parameters, frequencies and category rates through the model setters; the

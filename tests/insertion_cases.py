@@ -201,6 +201,14 @@ class Bed:
         per = self.rate_cats if (self.attrs & api.RATE_SCALERS) else 1
         return api.as_np(self.part.scale_buffer[index], self.sites * per, np.uint32).copy()
 
+    def write_scaler(self, index, counts):
+        """the caller's own counts into scale_buffer[index], as driver.Session.write_scaler does it"""
+        old = self.scaler(index)  # (settles the device side)
+        new = np.ascontiguousarray(counts, dtype=np.uint32).reshape(old.shape)
+        api.as_np(self.part.scale_buffer[index], new.size, np.uint32)[:] = new
+        if self.lib.is_amd:
+            self.lib.pll_gpu_invalidate(self.p, api.DIRTY_SCALER, index)
+
     def clv_bytes(self, index):
         assert self.lib.pll_gpu_sync_clv(self.p, index)
         n = self.sites * self.rate_cats * self.part.states_padded

@@ -20,14 +20,13 @@ import os
 import numpy as np
 import pytest
 
-from compare import RTOL
+from ancestral_common import SUMTOL, _part_arrays, assert_table, restated
 from pllamd import api, driver, fixtures, workload as W
 from utree import UTree
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SUMTOL = 1e-12
 
 
 def _golden_cases():
@@ -48,67 +47,6 @@ def _case_edges(case, extra):
     """(node, node scaler, other, other scaler, matrix): the case's edges; a derivative fixture names (parent, scaler,
     child, scaler) and forms its own matrices per branch length - here its edge goes with the case's matrix 0"""
     return [tuple(e) for e in case.edges] or [tuple(de[0]) + (0,) for de in extra["deriv_edges"]]
-
-
-# ---- the expected values -------------------------------------------------------------------------------------------
-def assert_table(got, exp, what):
-    """got against exp under the tolerance of this file; returns the worst relative error"""
-    assert got.shape == exp.shape, (what, got.shape, exp.shape)
-    assert np.isfinite(exp).all(), (what, "the expected table has non-finite rows", np.argwhere(~np.isfinite(exp).all(1))[:5])
-    assert np.isfinite(got).all(), (what, "non-finite rows", np.argwhere(~np.isfinite(got).all(1))[:5])
-    zero = exp == 0
-    assert (got[zero] == 0).all(), (what, "an entry expected as exactly 0 is not")
-    rel = np.zeros_like(exp)
-    rel[~zero] = np.abs(got[~zero] - exp[~zero]) / exp[~zero]
-    worst = float(rel.max()) if rel.size else 0.0
-    assert worst <= RTOL, (what, worst, np.unravel_index(int(rel.argmax()), rel.shape))
-    rows = np.abs(got.sum(1) - 1.0)
-    assert rows.max() <= SUMTOL, (what, "row sum", float(rows.max()))
-    return worst
-
-
-def _part_arrays(lib, p, node, nscaler, other, oscaler, matrix):
-    """what the formula reads, from the HOST memory of partition p (the reference's): x, y [sites][rates][states],
-    P [rates][states][states], and the per-rate counts of both ends summed [sites][rates] (None without RATE_SCALERS)"""
-    part = p.contents
-    s, sp, r, n = part.states, part.states_padded, part.rate_cats, part.sites
-    per_rate = bool(part.attributes & api.RATE_SCALERS)
-
-    def clv(idx):
-        if idx < part.tips and (part.attributes & api.PATTERN_TIP):
-            codes = api.as_np(part.tipchars[idx], n, np.uint8)
-            if s == 4:
-                masks = codes.astype(np.uint64)
-            else:
-                masks = api.as_np(part.tipmap, part.maxstates, np.uint64)[codes]
-            y = ((masks[:, None] >> np.arange(s, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.float64)
-            return np.repeat(y[:, None, :], r, axis=1)
-        return api.as_np(part.clv[idx], n * r * sp, np.float64).reshape(n, r, sp)[:, :, :s].copy()
-
-    def counts(idx):
-        if idx < 0:
-            return np.zeros((n, r if per_rate else 1), dtype=np.int64)
-        return api.as_np(part.scale_buffer[idx], n * (r if per_rate else 1), np.uint32).reshape(n, -1).astype(np.int64)
-
-    pm = api.as_np(part.pmatrix[matrix], r * s * sp, np.float64).reshape(r, s, sp)[:, :, :s].copy()
-    other_is_codes = other < part.tips and bool(part.attributes & api.PATTERN_TIP)
-    cn, co = counts(nscaler), (counts(-1) if other_is_codes else counts(oscaler))
-    return clv(node), clv(other), pm, (cn + co) if per_rate else None, (cn, co)
-
-
-def restated(lib, p, edge, fi):
-    """the formula of the module docstring on partition p's host arrays"""
-    part = p.contents
-    x, y, pm, rs, _ = _part_arrays(lib, p, *edge)
-    s, sp, r = part.states, part.states_padded, part.rate_cats
-    v = x * np.einsum("kij,nkj->nki", pm, y)
-    if rs is not None:
-        ex = np.minimum(rs - rs.min(1, keepdims=True), 4)
-        v = v * np.ldexp(1.0, (-256 * ex).astype(np.int64))[:, :, None]
-    w = api.as_np(part.rate_weights, r, np.float64)
-    pi = np.stack([api.as_np(part.frequencies[int(f)], sp, np.float64)[:s] for f in fi])
-    a = np.einsum("k,kj,nkj->nj", w, pi, v)
-    return a / a.sum(1, keepdims=True)
 
 
 def _call(lib, p, edge, fi, sites, states):

@@ -6,6 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import scaler_cases as SC
+from compare import RTOL
 from pllamd import api, driver, workload as W
 
 pytestmark = pytest.mark.gpu
@@ -376,3 +378,67 @@ def test_the_same_list_again_goes_straight_to_the_launches(amd_lib, attributes):
         s.update_partials()
         assert amd_lib.pll_gpu_last_update_replayed(s.p) == 1
         assert s.edge_lnl(case.edges[0], persite=False)[0] == first
+
+
+def test_a_standing_class_map_still_names_its_scaler_slot(amd_lib, ref_lib):
+    """perscale_ids[op->parent_scaler_index] = pernode_ids[parent] on every call (src/repeats.c:328-369; read by the
+    reference's pll_update_sumtable, src/derivatives.c:385-389): an op whose class map stands - same children, same
+    versions, nothing to compute - may still arrive with ANOTHER scaler slot than last time, or find that another op has
+    used its slot in between.
+    With site repeats both libraries give a scale buffer its host memory only when its parent's class count changes
+    (src/pll.c:838-839, src/repeats.c:262-263), so the slot that changes hands must have been some node's FIRST slot:
+    here the spare buffer is first the slot of the larger of the two top nodes, then the smaller one borrows it (its
+    classes fit the buffer), the larger takes it back, the smaller borrows it again. The borrower's children carry
+    written counts, so what it leaves in the slot through the class maps is not zero. After every step perscale_ids
+    equals the reference's as integers, so do the borrower's entries of the slot, and the log-likelihood across the
+    root edge, read through the slot, is within RTOL"""
+    case = W.make_case("slot", 4, 16, 130, attributes=api.SITE_REPEATS, mutate_pct=5, seed=SC.REPEAT_SEEDS["dna"])
+    spare = case.scale_buffers
+    case.scale_buffers += 1
+    ops = list(case.op_batches[0])
+    owner_op, borrower_op = ops[-2], ops[-1]
+    e = case.edges[0]
+    assert (e[0], e[2]) == (owner_op[0], borrower_op[0])
+    first = ops[:-2] + [(owner_op[0], spare) + tuple(owner_op[2:]), borrower_op]
+    moved = [owner_op, (borrower_op[0], spare) + tuple(borrower_op[2:])]  # (the ops below would write their own counts again)
+    taken_back = [(owner_op[0], spare) + tuple(owner_op[2:])]
+    through_slot = (e[0], api.SCALE_BUFFER_NONE, e[2], spare, e[4])
+    sessions = [driver.Session(lib, case, api.ARCH_AVX2) for lib in (amd_lib, ref_lib)]
+    try:
+        def both(fn):
+            return [fn(s) for s in sessions]
+
+        def run(rows):
+            both(lambda s: s.lib.pll_update_partials(s.p, api.make_ops(rows), len(rows)))
+
+        def slot_ids():
+            a, r = both(lambda s: api.as_np(s.part.repeats.contents.perscale_ids, case.scale_buffers, np.uint32).copy())
+            assert np.array_equal(a, r), (a, r)
+            return int(r[spare])
+
+        def check(step):
+            assert slot_ids() == n_borrower, step
+            (sc_a, v_a), (sc_r, v_r) = both(lambda s: (s.read_scaler(spare, borrower_op[0], expand=False),
+                                                        s.edge_lnl(through_slot, persite=False)[0]))
+            assert sc_r.shape[0] == n_borrower and sc_r.any(), (step, "the slot holds no counts: the case shows nothing")
+            assert np.array_equal(sc_a, sc_r), (step, np.argwhere(sc_a != sc_r)[:5])
+            assert np.isfinite(v_r) and abs(v_a - v_r) <= RTOL * abs(v_r), (step, v_a, v_r)
+
+        run(first)
+        n_owner, n_borrower = both(lambda s: (s.entries(owner_op[0]), s.entries(borrower_op[0])))[1]
+        assert both(lambda s: (s.entries(owner_op[0]), s.entries(borrower_op[0]))) == [(n_owner, n_borrower)] * 2
+        assert n_borrower < n_owner < case.sites, (n_owner, n_borrower)
+        assert all(s.part.scale_buffer[spare] for s in sessions), "the spare slot has no host buffer"
+        assert slot_ids() == n_owner
+        for s in sessions:
+            for second, (clv, scaler) in enumerate(((borrower_op[2], borrower_op[4]), (borrower_op[5], borrower_op[7]))):
+                SC.write_scaler(s, scaler, clv, SC.table(s.entries(clv), shift=SC.SECOND_END_SHIFT * second))
+        run(moved)        # the same parents and children come back, the smaller one with the spare slot: every map stands
+        check("another slot")
+        run(taken_back)   # another op uses the slot for a different parent ...
+        assert slot_ids() == n_owner
+        run(moved)        # ... and the list comes back
+        check("the slot was borrowed in between")
+    finally:
+        for s in sessions:
+            s.close()
