@@ -834,6 +834,12 @@ int pll_gpu_last_update_replayed(const pll_partition_t *partition);
  * reads + parent and scaler writes of every launch AS IT WAS GROUPED (an op evaluated together with
  * the producers of its children does not read those children back) - bench.py's roofline numerator */
 double pll_gpu_last_algorithmic_bytes(const pll_partition_t *partition);
+/* CLVs (with their scalers) that the last step computed and has not stored on the device: the 32 tip x tip parents of a
+ * balanced 64-taxon DNA traversal evaluated together with its root edge as one launch (PLL_AMD_LAZY_CHERRIES=0: always 0).
+ * Every call that reads one of them, overwrites it or changes its tip codes stores them first, in one launch; the same
+ * traversal again simply recomputes them, and a change of a matrix they read leaves them pending (they keep the old one).
+ * Nothing a caller has to do - the number says why a read launched something */
+unsigned int pll_gpu_pending_clvs(const pll_partition_t *partition);
 int pll_gpu_device_count(void);
 /* 1 if a usable gfx950 device is present, 0 otherwise (the analogue of src/hardware.c's probe) */
 int pll_gpu_available(void);

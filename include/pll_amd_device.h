@@ -374,6 +374,8 @@ unsigned int pllgpu_last_launch_count(const pllgpu_ctx_t *ctx);
 /* HBM bytes the kernels of the last pllgpu_update_partials call had to move by construction
  * (child reads + parent and scaler writes of every launch as it was grouped) */
 double pllgpu_last_algorithmic_bytes(const pllgpu_ctx_t *ctx);
+/* CLVs the last whole-traversal launch formed and did not store (stored on demand by whatever may read them) */
+unsigned pllgpu_pending_clvs(const pllgpu_ctx_t *ctx);
 
 /* Test hook, host logic only (no device is touched): how pllgpu_update_partials partitions a
  * 4-state x 4-rate op list - classified and level-sorted like the ones the host layer hands over -

@@ -44,11 +44,14 @@ struct ChainPlan
   // two tops takes all of it in one launch (kernels_dna.h: k_edge_dna_tree), anything else sends it out as the launches above.
   bool tree = false;
   TreeEnd tree_end[2];    // the subtree under the top of head 0 / head 1
-  double tree_bytes = 0.0; // of that one launch: codes in, every CLV and scaler out, nothing read back
+  double tree_bytes = 0.0; // of that one launch: codes in, every CLV and scaler it stores out, nothing read back
+  // the list's 32 tip x tip ops as planned: what the lean form of the launch leaves unstored (pllgpu_ctx::pending)
+  std::vector<pllgpu_op_t> cherries;
 };
 
 static void drop_chain_plan(pllgpu_ctx *c)
 {
+  if (c->pending_plan == c->plan) c->pending_plan = nullptr; // (the pending ops are kept by value: they can still be stored)
   delete c->plan;
   c->plan = nullptr;
 }
@@ -121,29 +124,38 @@ static int launch_chain_plan(pllgpu_ctx *c, const ChainPlan &pl, bool hold)
 }
 
 // a held tree plan (ChainPlan::tree) goes the ordinary way after all: its stage 1, the seven-op groups, before the chains
-static int launch_held_tree_groups(pllgpu_ctx *c)
+// lean: without the stores of the 32 tip x tip parents (the caller marks them pending once everything is issued)
+static int launch_held_tree_groups(pllgpu_ctx *c, bool lean = false)
 {
   if (!c->tree_held || !c->plan) return 0;
   c->tree_held = false;
   const ChainPlan &pl = *c->plan;
   for (const CCLaunch &l : pl.cc)
-    if (int rc = launch_cc(c, l.pack, l.n, l.entries, l.lk, CK_FCC)) return rc;
+    if (int rc = launch_cc(c, l.pack, l.n, l.entries, l.lk, CK_FCC, lean)) return rc;
   c->last_launches += (unsigned)pl.cc.size();
   c->last_bytes = pl.bytes;
+  if (lean)
+    for (const pllgpu_op_t &o : pl.cherries) c->last_bytes -= op_traffic(c, o, false, false); // their CLV and scaler stores
   return 0;
 }
 
-static int launch_held_chains(pllgpu_ctx *c)
+// keep_pending: for a call that reads no CLV (a wait for the stream, the timer, an upload that is no input of one)
+static int launch_held_chains(pllgpu_ctx *c, bool keep_pending = false)
 {
   if (!c->chain_held || !c->plan) return 0;
   c->chain_held = false;
   const ChainPlan &pl = *c->plan;
-  if (int rc = launch_held_tree_groups(c)) return rc;
+  // a whole traversal sent out by such a call: the ordinary launches, and the tip x tip parents stay unstored as they would
+  // after the one-launch form (pllgpu_ctx::pending)
+  const bool lean = keep_pending && c->tree_held && c->lazy_cherries && pl.tree && c->pending.empty();
+  if (int rc = launch_held_tree_groups(c, lean)) return rc;
   for (size_t i = pl.held_from; i < pl.stages.size(); ++i)
   {
     launch_chain_heads(c, pl, pl.stages[i].first_head, pl.stages[i].nchains, pl.stages[i].variant);
     ++c->last_launches;
   }
+  // (pending whatever launch_status says: not stored by these launches, and what stores them forms them from their inputs)
+  if (lean) set_pending(c, c->plan);
   return launch_status();
 }
 
@@ -341,7 +353,9 @@ static bool use_cc16(const pllgpu_ctx *c, unsigned entries, unsigned count)
 // no slower than the other's slowest): the weaker criterion, on which the threshold sits at the smallest size measured.
 // 400k sites are beyond the held tail's 4096 tiles: today's plan either way. By size unless PLL_AMD_FUSE_TREE says 0 / 1:
 // entries of the list; only lists that plan_tree recognises are affected. Where fifteen-op groups qualify as well (200k)
-// the tree form goes first.
+// the tree form goes first. The launch leaves the list's 32 tip x tip parents unstored unless PLL_AMD_LAZY_CHERRIES=0
+// (pllgpu_ctx::pending; profiles/dna_tree_lazy_cherries.md). The threshold stays where it was: at 20k sites the lean form
+// is ahead by the medians only, as the storing form was when the threshold was set.
 constexpr unsigned kTreeMinEntries = 20000;
 static bool use_tree(const pllgpu_ctx *c, unsigned entries, unsigned count)
 {
@@ -538,7 +552,15 @@ static void plan_tree(const pllgpu_ctx *c, const ChainBuild &b, unsigned count, 
     }
   }
   if (seen != 0xffu) return; // 8 x 7 + 2 x 3 ops, every one placed
-  for (unsigned i = 0; i < count; ++i) pl->tree_bytes += op_traffic(c, ops[i], (ops[i].flags & PLLGPU_OP_LEFT_TIP) != 0, (ops[i].flags & PLLGPU_OP_RIGHT_TIP) != 0);
+  for (unsigned i = 0; i < count; ++i)
+    if ((ops[i].flags & PLLGPU_OP_LEFT_TIP) && (ops[i].flags & PLLGPU_OP_RIGHT_TIP)) pl->cherries.push_back(ops[i]);
+  if (pl->cherries.size() != 32u) return; // (eight complete groups: cannot happen)
+  for (unsigned i = 0; i < count; ++i)
+  {
+    const bool lt = (ops[i].flags & PLLGPU_OP_LEFT_TIP) != 0, rt = (ops[i].flags & PLLGPU_OP_RIGHT_TIP) != 0;
+    // the lean form reads a cherry's two codes and stores nothing of it
+    pl->tree_bytes += (c->lazy_cherries && lt && rt) ? 2.0 * ops[i].parent_entries : op_traffic(c, ops[i], lt, rt);
+  }
   pl->tree = true;
 }
 

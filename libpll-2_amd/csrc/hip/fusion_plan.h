@@ -229,14 +229,14 @@ static void to_top(const DevOp &d, TOp &t)
   t.rmat = d.rmat;
 }
 
-template <int LK, int RK>
+template <int LK, int RK, bool STORE_CHERRIES = true>
 static void launch_cc_t(pllgpu_ctx *c, const CCPack &pack, unsigned ngroups, unsigned entries)
 {
   const unsigned tiles = (entries + 63) / 64;
   const unsigned tpw = kDnaTilesPerWave;
   const unsigned nx = (tiles + 4 * tpw - 1) / (4 * tpw);
   unsigned stream_parent = ((size_t)ngroups * entries * 128u > c->stream_parent_bytes) ? 1u : 0u;
-  hipLaunchKernelGGL((k_partials_dna_cc<LK, RK>), xcd_grid(nx, ngroups), dim3(256), 0, c->stream, pack, entries, c->gg.scale_mode, tpw, stream_parent,
+  hipLaunchKernelGGL((k_partials_dna_cc<LK, RK, STORE_CHERRIES>), xcd_grid(nx, ngroups), dim3(256), 0, c->stream, pack, entries, c->gg.scale_mode, tpw, stream_parent,
                      nx, ngroups, c->xcd_order);
 }
 
@@ -250,8 +250,16 @@ static int launch_cc16(pllgpu_ctx *c, const CC16Pack &pack, unsigned ngroups, un
   return 0;
 }
 
-static int launch_cc(pllgpu_ctx *c, const CCPack &pack, unsigned ngroups, unsigned entries, int lk, int rk)
+// lean: complete (CK_FCC, CK_FCC) groups without the stores of their four tip x tip parents (a held whole-traversal plan
+// sent out by a call that reads none of them: chain_plan.h, launch_held_chains)
+static int launch_cc(pllgpu_ctx *c, const CCPack &pack, unsigned ngroups, unsigned entries, int lk, int rk, bool lean = false)
 {
+  if (lean)
+  {
+    if (lk != CK_FCC || rk != CK_FCC) return fail(PLLGPU_EINVAL, "the lean cherry-cherry launch is for complete groups only");
+    launch_cc_t<CK_FCC, CK_FCC, false>(c, pack, ngroups, entries);
+    return 0;
+  }
   const bool known = with_kind_pair(
       lk, rk, [&](auto LK, auto RK) { launch_cc_t<LK(), RK()>(c, pack, ngroups, entries); },
       KindPair<CK_INNER, CK_FCC>(), KindPair<CK_TIP, CK_FCC>(), KindPair<CK_FCC, CK_FCC>());

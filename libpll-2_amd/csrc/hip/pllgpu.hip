@@ -280,6 +280,19 @@ struct pllgpu_ctx
   struct ChainPlan *plan = nullptr; // the last chain plan, re-launched as is when the same list comes again
   bool chain_held = false;          // the plan's last stage has not been launched yet (chain tail, kernels_dna.h)
   bool tree_held = false;           // ... and neither has its stage 1: the whole plan waits (ChainPlan::tree; implies chain_held)
+  // Lazy cherries: the whole-traversal launch ran in its lean form (k_edge_dna_tree<false>) and did not store the list's 32
+  // tip x tip parents. They are PENDING: a representation, not work in flight - each is a function of two tip code vectors
+  // and two matrices that are on the device and have not changed since (every entry point that could read a pending CLV or
+  // scaler, overwrite it or change one of its inputs stores them first: materialise_pending). Never non-empty while
+  // anything is held: the launch that leaves them consumed the held plan, and the next update call resolves them.
+  // A matrix one of them reads may change all the same (the model-parameter loop rewrites every matrix between two steps,
+  // a branch-length pass the evaluated edge's): the 64 matrices of the step are copied aside first, device to device in
+  // one small launch (keep_pending_matrices), and the pending ops are stored from the copies if they are stored at all.
+  bool lazy_cherries = true;          // PLL_AMD_LAZY_CHERRIES=0: the launch stores everything
+  std::vector<pllgpu_op_t> pending;   // the ops as planned: parent CLV, scaler, tip and matrix indices
+  const struct ChainPlan *pending_plan = nullptr; // the plan they belong to: its own list again recomputes them all
+  DevBuf<double> pending_mats;        // op i's left and right matrix as they were at the step: slots 2i, 2i + 1 ...
+  bool pending_mats_kept = false;     // ... once one of them was about to change (else the ops read c->pmat)
   DevBuf<unsigned char> chain_dev;  // its descriptors
   // level-scheduled lists: the launches of a planned list are kept (descriptor packs by value) and replayed
   // as they are when the same list comes again while nothing they point at has moved (LevelPlan below)
@@ -472,6 +485,9 @@ static void derive_geometry(pllgpu_ctx *c)
   c->fuse_tree = -1;
   if (const char *vt = getenv("PLL_AMD_FUSE_TREE"))
     if (*vt) c->fuse_tree = *vt != '0' ? 1 : 0;
+  c->lazy_cherries = true;
+  if (const char *v = getenv("PLL_AMD_LAZY_CHERRIES"))
+    if (*v) c->lazy_cherries = *v != '0';
   if (const char *v = getenv("PLL_AMD_NO_FUSE_CC"))
     if (*v && *v != '0') c->fuse_cc = false;
   c->chains = c->fuse;
@@ -622,7 +638,7 @@ extern "C" pllgpu_ctx_t *pllgpu_create(const pllgpu_geometry_t *geo, int device)
   if (c->pmat.ensure(c->pm_stride * (geo->prob_matrices + 2)) || c->freqs.ensure((size_t)geo->rate_matrices * geo->states_padded) ||
       c->rate_weights.ensure(geo->rate_cats) || c->prop_invar.ensure(geo->rate_matrices) ||
       c->pattern_weights.ensure(geo->sites_alloc) || c->persite.ensure(geo->sites_alloc) ||
-      c->block_sums.ensure(4096) || c->counter.ensure(4) || c->rep_sync.ensure((size_t)kRepOps + 1) || c->rep_changed.ensure(1))
+      c->block_sums.ensure(4096) || c->counter.ensure(4) || (c->dna_fast && c->lazy_cherries && c->pending_mats.ensure(c->pm_stride * 64u)) || c->rep_sync.ensure((size_t)kRepOps + 1) || c->rep_changed.ensure(1))
   {
     pllgpu_destroy(c);
     return nullptr;
@@ -659,6 +675,7 @@ extern "C" void pllgpu_destroy(pllgpu_ctx_t *c)
   c->sub_dev.release();
   c->sub_packed.release();
   c->cherry_bits.release();
+  c->pending_mats.release();
   for (auto &b : c->clv) b.release();
   for (auto &b : c->scaler) b.release();
   for (auto &b : c->tipchars) b.release();
@@ -719,16 +736,27 @@ extern "C" void pllgpu_destroy(pllgpu_ctx_t *c)
 // returns, so the caller may reuse its buffer; ordering with kernels is by the stream.
 // every entry point first launches what pllgpu_update_partials is holding back (tail fusion,
 // kernels_dna.h) - except the edge evaluation, which may consume it
-static int flush_deferred(pllgpu_ctx *c);
-static bool held_work_reads_matrices(const pllgpu_ctx *c, unsigned first, unsigned count);
+static int flush_deferred(pllgpu_ctx *c, bool keep_pending = false);
+static int matrices_change(pllgpu_ctx *c, const unsigned *indices, unsigned first, unsigned count);
+static int materialise_pending(pllgpu_ctx *c);
+static void set_pending(pllgpu_ctx *c, const struct ChainPlan *pl);
 #define CHECK_CTX_KEEP(c)                    \
   if (!(c)) return fail(PLLGPU_EINVAL, "null context"); \
   DeviceScope device_scope_(c);              \
   if (device_scope_.rc) return device_scope_.rc
+#define HOLDS_WORK(c) (!(c)->deferred.empty() || (c)->chain_held)
+// ... and stores what the lean tree launch left unstored (pllgpu_ctx::pending): whoever comes through here may read it,
+// overwrite it or change what it is a function of
 #define CHECK_CTX(c)                                   \
   CHECK_CTX_KEEP(c);                                   \
-  if (!(c)->deferred.empty() || (c)->chain_held)       \
+  if (HOLDS_WORK(c) || !(c)->pending.empty())          \
     if (int rc_ = flush_deferred(c)) return rc_
+// held work goes out, pending CLVs stay as they are: for calls that touch neither them nor their inputs (a held whole
+// traversal goes out without the tip x tip stores too: chain_plan.h, launch_held_chains)
+#define CHECK_CTX_KEEP_PENDING(c)                      \
+  CHECK_CTX_KEEP(c);                                   \
+  if (HOLDS_WORK(c))                                   \
+    if (int rc_ = flush_deferred(c, true)) return rc_
 
 // Small transfers. hipMemcpyAsync from or to pageable memory is a blocking trip through the runtime's own staging (10-25 us
 // whatever the size; the flat pll_core_* seam made six of them per call): a transfer of up to kRingMax bytes goes through
@@ -988,21 +1016,20 @@ extern "C" int pllgpu_pmatrix_upload(pllgpu_ctx_t *c, unsigned first, unsigned c
   // the matrix of the edge evaluated next is no input of the traversal before it and usually goes up between the two calls:
   // what is held stays held unless it reads one of these matrices
   CHECK_CTX_KEEP(c);
-  if (held_work_reads_matrices(c, first, count))
-    if (int rc = flush_deferred(c)) return rc;
+  if (int rc = matrices_change(c, nullptr, first, count)) return rc;
   return upload_matrices(c, first, count, host, c->geo.prob_matrices);
 }
 
 extern "C" int pllgpu_aux_matrix_upload(pllgpu_ctx_t *c, unsigned slot, const double *host)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   if (slot > 1) return fail(PLLGPU_EINVAL, "aux matrix slot %u out of range", slot);
   return upload_matrices(c, c->geo.prob_matrices + slot, 1, host, c->geo.prob_matrices + 2);
 }
 
 extern "C" int pllgpu_frequencies_upload(pllgpu_ctx_t *c, unsigned index, const double *host)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   if (index >= c->geo.rate_matrices) return fail(PLLGPU_EINVAL, "frequency set %u out of range", index);
   HIP_TRY(hipMemcpyAsync(c->freqs.p + (size_t)index * c->geo.states_padded, host,
                          c->geo.states_padded * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -1011,21 +1038,21 @@ extern "C" int pllgpu_frequencies_upload(pllgpu_ctx_t *c, unsigned index, const 
 
 extern "C" int pllgpu_rate_weights_upload(pllgpu_ctx_t *c, const double *host)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   HIP_TRY(hipMemcpyAsync(c->rate_weights.p, host, c->geo.rate_cats * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return 0;
 }
 
 extern "C" int pllgpu_prop_invar_upload(pllgpu_ctx_t *c, const double *host)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   HIP_TRY(hipMemcpyAsync(c->prop_invar.p, host, c->geo.rate_matrices * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return 0;
 }
 
 extern "C" int pllgpu_pattern_weights_upload(pllgpu_ctx_t *c, const unsigned *host, unsigned count)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   if (count > c->geo.sites_alloc) return fail(PLLGPU_EINVAL, "pattern weight count %u > %u", count, c->geo.sites_alloc);
   HIP_TRY(hipMemcpyAsync(c->pattern_weights.p, host, count * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
   return 0;
@@ -1033,7 +1060,7 @@ extern "C" int pllgpu_pattern_weights_upload(pllgpu_ctx_t *c, const unsigned *ho
 
 extern "C" int pllgpu_invariant_upload(pllgpu_ctx_t *c, const int *host, unsigned count)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   if (!host)
   {
     c->invariant_set = false;
@@ -1678,21 +1705,152 @@ static int launch_partials(pllgpu_ctx *c, const OpPack &pack, unsigned nops, uns
 #include "chain_plan.h"
 #include "subtree_plan.h"
 
-static bool held_work_reads_matrices(const pllgpu_ctx *c, unsigned first, unsigned count)
+// matrices about to change: indices[0..count) if given, else [first, first + count)
+struct MatrixSet
 {
-  auto reads = [&](const pllgpu_op_t &o) { return o.left_matrix - first < count || o.right_matrix - first < count; };
+  const unsigned *indices;
+  unsigned first, count;
+  bool has(unsigned m) const
+  {
+    if (!indices) return m - first < count;
+    for (unsigned i = 0; i < count; ++i)
+      if (indices[i] == m) return true;
+    return false;
+  }
+  bool read_by(const pllgpu_op_t &o) const { return has(o.left_matrix) || has(o.right_matrix); }
+};
+
+static bool held_work_reads_matrices(const pllgpu_ctx *c, const MatrixSet &ms)
+{
   for (const pllgpu_op_t &o : c->deferred)
-    if (reads(o)) return true;
+    if (ms.read_by(o)) return true;
   if (c->chain_held && c->plan)
     for (const pllgpu_op_t &o : c->plan->key)
-      if (reads(o)) return true;
+      if (ms.read_by(o)) return true;
   return false;
 }
 
-// launch the held ops as ordinary updates (they are mutually independent: one level)
-static int flush_deferred(pllgpu_ctx *c)
+static void set_pending(pllgpu_ctx *c, const ChainPlan *pl)
 {
-  if (int rc = launch_held_chains(c)) return rc;
+  c->pending = pl->cherries;
+  c->pending_plan = pl;
+  c->pending_mats_kept = false;
+}
+
+static void drop_pending(pllgpu_ctx *c)
+{
+  c->pending.clear();
+  c->pending_plan = nullptr;
+  c->pending_mats_kept = false;
+}
+
+// is this CLV one that the lean tree launch left unstored
+static bool clv_is_pending(const pllgpu_ctx *c, unsigned clv)
+{
+  for (const pllgpu_op_t &o : c->pending)
+    if (o.parent_clv == clv) return true;
+  return false;
+}
+
+// The matrices the pending ops read, as they are now, into slots of their own: one launch of 2 x 32 blocks, 32 KB for
+// 4 states x 4 rates. Once per step at the most - from then on no change of a matrix concerns what is pending.
+struct MatrixCopies
+{
+  unsigned short src[2 * 32];
+};
+__global__ void k_keep_matrices(const double *__restrict__ pmat, double *__restrict__ kept, MatrixCopies mc, unsigned stride)
+{
+  const double *s = pmat + (size_t)mc.src[blockIdx.x] * stride;
+  double *d = kept + (size_t)blockIdx.x * stride;
+  for (unsigned i = threadIdx.x; i < stride; i += blockDim.x) d[i] = s[i];
+}
+
+static int keep_pending_matrices(pllgpu_ctx *c)
+{
+  if (c->pending.empty() || c->pending_mats_kept) return 0;
+  const unsigned n = (unsigned)c->pending.size();
+  MatrixCopies mc;
+  if (2u * n > sizeof mc.src / sizeof mc.src[0] || c->geo.prob_matrices > 65535u) return materialise_pending(c); // (cannot happen: 32 ops)
+  for (unsigned i = 0; i < n; ++i)
+  {
+    mc.src[2 * i] = (unsigned short)c->pending[i].left_matrix;
+    mc.src[2 * i + 1] = (unsigned short)c->pending[i].right_matrix;
+  }
+  if (int rc = c->pending_mats.ensure(c->pm_stride * 2u * n)) return rc;
+  hipLaunchKernelGGL(k_keep_matrices, dim3(2u * n), dim3(64), 0, c->stream, c->pmat.p, c->pending_mats.p, mc, (unsigned)c->pm_stride);
+  if (int rc = launch_status()) return rc;
+  c->pending_mats_kept = true;
+  return 0;
+}
+
+// Matrices are about to be overwritten, in stream order behind everything launched so far. Held work that reads one of
+// them goes out first, with the old matrix. Pending CLVs that read one are NOT stored for it: the usual next call is the
+// plan's own list again, which drops them - they keep copies of their matrices instead.
+static int matrices_change(pllgpu_ctx *c, const unsigned *indices, unsigned first, unsigned count)
+{
+  if (!HOLDS_WORK(c) && c->pending.empty()) return 0;
+  const MatrixSet ms{indices, first, count};
+  if (HOLDS_WORK(c) && held_work_reads_matrices(c, ms))
+    if (int rc = flush_deferred(c, true)) return rc;
+  if (!c->pending.empty() && !c->pending_mats_kept)
+    for (const pllgpu_op_t &o : c->pending)
+      if (ms.read_by(o)) return keep_pending_matrices(c);
+  return 0;
+}
+
+// Store the pending tip x tip parents: ordinary updates through the level path (k_partials_dna<tip, tip>, the arithmetic
+// of dna_cherry: the bits the full launch stores), on the context's stream, from the codes as they are on the device and
+// the matrices as they are there or as they were kept - those of the step, since nothing that changes them gets past
+// matrices_change or this. The kept plan is not touched; the counters of the last update call stay what they were, the
+// launch is counted. On an error they stay pending.
+static int materialise_pending(pllgpu_ctx *c)
+{
+  if (c->pending.empty()) return 0;
+  OpPack pack;
+  unsigned nops = 0, maxent = 0;
+  auto launch = [&]() -> int {
+    if (!nops) return 0;
+    if (int rc = launch_partials(c, pack, nops, maxent, 2, false)) return rc;
+    ++c->last_launches;
+    nops = maxent = 0;
+    return 0;
+  };
+  for (size_t i = 0; i < c->pending.size(); ++i)
+  {
+    const pllgpu_op_t &o = c->pending[i];
+    DevOp &d = pack.ops[nops];
+    if (int rc = resolve_op(c, o, d)) return rc; // (the buffers exist: the plan resolved them)
+    if (c->pending_mats_kept)
+    {
+      d.lmat = c->pending_mats.p + (2 * i) * c->pm_stride;
+      d.rmat = c->pending_mats.p + (2 * i + 1) * c->pm_stride;
+    }
+    maxent = std::max(maxent, o.parent_entries);
+    if (++nops == (unsigned)kMaxOpsPerLaunch)
+      if (int rc = launch()) return rc;
+  }
+  if (int rc = launch()) return rc;
+  if (int rc = launch_status()) return rc;
+  drop_pending(c);
+  return 0;
+}
+
+// for calls that read the two ends of an edge (or the one end of a root) and nothing else
+static int materialise_if_an_end_is_pending(pllgpu_ctx *c, const pllgpu_edge_t *ed, bool is_root)
+{
+  if (c->pending.empty()) return 0;
+  if (clv_is_pending(c, ed->parent_clv) || (!is_root && !ed->child_is_tip && clv_is_pending(c, ed->child_clv))) return materialise_pending(c);
+  return 0;
+}
+
+// launch the held ops as ordinary updates (they are mutually independent: one level)
+// keep_pending: for a caller that neither reads a CLV nor changes an input of one - what is pending stays, and a held whole
+// traversal leaves its tip x tip parents pending as well
+static int flush_deferred(pllgpu_ctx *c, bool keep_pending)
+{
+  if (!keep_pending)
+    if (int rc = materialise_pending(c)) return rc;
+  if (int rc = launch_held_chains(c, keep_pending)) return rc;
   std::vector<pllgpu_op_t> ops;
   ops.swap(c->deferred);
   for (unsigned kind = 0; kind < 3; ++kind)
@@ -2002,7 +2160,18 @@ static int plan_and_launch_levels(pllgpu_ctx *c, const pllgpu_op_t *ops, unsigne
 
 extern "C" int pllgpu_update_partials(pllgpu_ctx_t *c, const pllgpu_op_t *ops, unsigned count)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP(c);
+  // the kept plan's own list again (what try_chain_plan will replay) recomputes every pending CLV: they are dropped, not
+  // stored. However the held plan is resolved later, it stores them or leaves them pending again. Any other list may read
+  // or overwrite them: stored first. Compared BEFORE anything is flushed.
+  const bool replay = c->plan && c->chains && c->fuse && !c->any_aos && c->plan->epoch == c->alloc_epoch && c->plan->key.size() == count &&
+                      memcmp(c->plan->key.data(), ops, count * sizeof(pllgpu_op_t)) == 0;
+  if (replay && c->pending_plan == c->plan) drop_pending(c);
+  // (the same list while it is still held: the traversal goes out, and what it would store only to be recomputed below
+  // stays unstored)
+  if (HOLDS_WORK(c) || !c->pending.empty())
+    if (int rc = flush_deferred(c, replay && c->pending.empty())) return rc;
+  if (replay && c->pending_plan == c->plan) drop_pending(c);
   c->last_launches = 0;
   c->last_bytes = 0.0;
   {
@@ -2065,6 +2234,7 @@ extern "C" int pllgpu_update_partials(pllgpu_ctx_t *c, const pllgpu_op_t *ops, u
 }
 
 extern "C" double pllgpu_last_algorithmic_bytes(const pllgpu_ctx_t *c) { return c ? c->last_bytes : 0.0; }
+extern "C" unsigned pllgpu_pending_clvs(const pllgpu_ctx_t *c) { return c ? (unsigned)c->pending.size() : 0u; }
 
 // ---- log-likelihood ----------------------------------------------------------------------------
 template <int ICH>
@@ -2108,6 +2278,7 @@ struct ChainTailCall
   bool in_kernarg;
   ChainPack pack; // in_kernarg: heads[0] = hp, heads[1] = hc and their steps
   const TreePack *tree = nullptr; // the held plan is a whole traversal (ChainPlan::tree): k_edge_dna_tree, nothing above is read
+  bool lean = false;              // ... in the form that leaves the 32 tip x tip parents unstored (pllgpu_ctx::pending)
 };
 
 static void launch_edge_chain(pllgpu_ctx *c, const DevEdge &e, const ChainTailCall &t)
@@ -2115,7 +2286,9 @@ static void launch_edge_chain(pllgpu_ctx *c, const DevEdge &e, const ChainTailCa
   const ChainPlan &pl = *c->plan;
   dim3 grid((pl.entries + 63) / 64), block(256);
   if (t.tree) // a workgroup of eight waves per tile, tiles in the XCD-aware order
-    hipLaunchKernelGGL(k_edge_dna_tree, xcd_grid(grid.x, 1), dim3(512), 0, c->stream, e, *t.tree, pl.entries, c->gg.scale_mode, c->xcd_order);
+    with_bools(!t.lean, false, [&](auto STORE, auto) {
+      hipLaunchKernelGGL(k_edge_dna_tree<STORE()>, xcd_grid(grid.x, 1), dim3(512), 0, c->stream, e, *t.tree, pl.entries, c->gg.scale_mode, c->xcd_order);
+    });
   else if (t.in_kernarg)
     with_chain_variant(c->gg.scale_mode, t.variant, [&](auto SMV, auto C0, auto S1, auto C1) {
       hipLaunchKernelGGL((k_edge_dna_chain_pack<SMV(), C0(), S1(), C1()>), grid, block, 0, c->stream, e, t.pack, pl.entries);
@@ -2545,6 +2718,10 @@ extern "C" int pllgpu_edge_loglikelihood(pllgpu_ctx_t *c, const pllgpu_edge_t *e
     ~SeqScope() { c->seq_override = 0.0; }
   } seq_scope_{c};
   c->seq_override = ed->sequence;
+  // an end that the lean tree launch left unstored is stored first; any other edge reads nothing that is pending (the
+  // evaluated edge's own matrix, new or not, is no concern of theirs: a cherry that read it kept the old one aside when it
+  // changed - matrices_change)
+  if (int rc = materialise_if_an_end_is_pending(c, ed, false)) return rc;
   ClaimedWork claimed(c);
   TailCall tail;
   bool use_tail = false;
@@ -2563,10 +2740,17 @@ extern "C" int pllgpu_edge_loglikelihood(pllgpu_ctx_t *c, const pllgpu_edge_t *e
       tp.end[0] = c->plan->tree_end[held_p];
       tp.end[1] = c->plan->tree_end[held_c];
       ct.tree = &tp;
+      ct.lean = c->lazy_cherries;
     }
     else if (int brc = build_chain_tail(c, ed, e, held_p, held_c, ct))
       return brc;
     rc = run_lnl(c, e, ed->child_is_tip != 0, false, ed->freqs_indices, persite_host, lnl_out, ed->device_result, nullptr, &ct);
+    if (rc == 0 && ct.lean)
+    {
+      // issued: from here on the cherries are pending (on a failure ClaimedWork sends the plan out the ordinary way, which
+      // stores everything: nothing pending)
+      set_pending(c, c->plan);
+    }
   }
   else if (use_tail)
   {
@@ -2703,7 +2887,7 @@ extern "C" int pllgpu_insertion_loglikelihoods(pllgpu_ctx_t *c, unsigned subtree
   for (unsigned n = 0; n < g.nodes; ++n)
     if (c->ids[n] || c->clv_aos[n]) return fail(PLLGPU_EUNSUPPORTED, "insertion log-likelihoods over class-compressed CLVs");
   // whatever pllgpu_update_partials holds back goes out as ordinary launches: a candidate may name what it produces
-  if (!c->deferred.empty() || c->chain_held)
+  if (HOLDS_WORK(c) || !c->pending.empty())
     if (int rc = flush_deferred(c)) return rc;
 
   DevEdge e;
@@ -2904,7 +3088,7 @@ __global__ void k_set_pair(double *__restrict__ pair, double value, double seque
 
 extern "C" int pllgpu_reduce_poison(pllgpu_ctx_t *c, double sequence)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   if (!c->reduce.p) return fail(PLLGPU_EINVAL, "no reduce buffer");
   hipLaunchKernelGGL(k_set_pair, dim3(1), dim3(1), 0, c->stream, c->reduce.p, -HUGE_VAL, sequence);
   HIP_TRY(hipGetLastError());
@@ -2922,7 +3106,7 @@ __global__ void k_publish_pair(const double *__restrict__ pair, double *__restri
 
 extern "C" int pllgpu_reduce_fetch(pllgpu_ctx_t *c, double expected_sequence, double *value_out, int timeout_ms)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   if (!c->reduce.p) return fail(PLLGPU_EINVAL, "no reduce buffer");
   // words 4 and 5 of the mapped result block (0..2 belong to the synchronous evaluations and the derivatives)
   hipLaunchKernelGGL(k_publish_pair, dim3(1), dim3(1), 0, c->stream, c->reduce.p, c->result_dev + 4);
@@ -2974,7 +3158,7 @@ extern "C" void *pllgpu_get_stream(const pllgpu_ctx_t *cc)
 {
   // a caller who asks for the stream is about to order its own work against ours: nothing may be held back
   pllgpu_ctx *c = const_cast<pllgpu_ctx *>(cc);
-  if (c && (!c->deferred.empty() || c->chain_held))
+  if (c && (HOLDS_WORK(c) || !c->pending.empty()))
   {
     DeviceScope device_scope_(c);
     if (device_scope_.rc == 0) (void)flush_deferred(c);
@@ -2984,14 +3168,14 @@ extern "C" void *pllgpu_get_stream(const pllgpu_ctx_t *cc)
 
 extern "C" int pllgpu_synchronize(pllgpu_ctx_t *c)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // pending CLVs are a representation, not work in flight
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
 
 extern "C" int pllgpu_timer_start(pllgpu_ctx_t *c)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   return 0;
 }
@@ -3001,7 +3185,7 @@ extern "C" double pllgpu_timer_stop(pllgpu_ctx_t *c)
   if (!c) return -1.0;
   DeviceScope device_scope_(c);
   if (device_scope_.rc) return -1.0;
-  if ((!c->deferred.empty() || c->chain_held) && flush_deferred(c)) return -1.0;
+  if (HOLDS_WORK(c) && flush_deferred(c, true)) return -1.0; // the timer reads no CLV
   float ms = 0;
   if (hipEventRecord(c->ev1, c->stream) != hipSuccess || hipEventSynchronize(c->ev1) != hipSuccess ||
       hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess)
@@ -3019,7 +3203,7 @@ extern "C" unsigned long long pllgpu_class_map_work(const pllgpu_ctx_t *c, int l
 // ---- branch-length derivatives ------------------------------------------------------------------
 extern "C" int pllgpu_eigenvals_upload(pllgpu_ctx_t *c, unsigned index, const double *host)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   if (index >= c->geo.rate_matrices) return fail(PLLGPU_EINVAL, "eigenvalue set %u out of range", index);
   if (int rc = c->eigenvals.ensure((size_t)c->geo.rate_matrices * c->geo.states_padded)) return rc;
   HIP_TRY(hipMemcpyAsync(c->eigenvals.p + (size_t)index * c->geo.states_padded, host,
@@ -3029,7 +3213,7 @@ extern "C" int pllgpu_eigenvals_upload(pllgpu_ctx_t *c, unsigned index, const do
 
 extern "C" int pllgpu_rates_upload(pllgpu_ctx_t *c, const double *host)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   if (int rc = c->rates.ensure(c->geo.rate_cats)) return rc;
   HIP_TRY(hipMemcpyAsync(c->rates.p, host, c->geo.rate_cats * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return 0;
@@ -3043,10 +3227,14 @@ static int sumtable_slot(pllgpu_ctx *c, unsigned slot)
 
 extern "C" int pllgpu_update_sumtable(pllgpu_ctx_t *c, const pllgpu_sumtable_t *st, unsigned slot)
 {
-  CHECK_CTX(c);
-  if (int rc = sumtable_slot(c, slot)) return rc;
+  // reads the two ends of its edge: pending CLVs are stored first only if an end is one (a Newton pass on the root edge
+  // after a step leaves them as they are)
+  CHECK_CTX_KEEP_PENDING(c);
   const pllgpu_geometry_t &g = c->geo;
   if (st->left_clv >= g.nodes || st->right_clv >= g.nodes) return fail(PLLGPU_EINVAL, "sumtable references a CLV out of range");
+  if (!c->pending.empty() && (clv_is_pending(c, st->right_clv) || (!st->left_is_tip && clv_is_pending(c, st->left_clv))))
+    if (int rc = materialise_pending(c)) return rc;
+  if (int rc = sumtable_slot(c, slot)) return rc;
   OpPack pack;
   DevOp &d = pack.ops[0];
   memset(&d, 0, sizeof d);
@@ -3211,7 +3399,7 @@ static int wait_for_sequence(pllgpu_ctx *c, double sequence)
 extern "C" int pllgpu_likelihood_derivatives(pllgpu_ctx_t *c, unsigned slot, double branch_length,
                                              const unsigned *params_indices, unsigned eval_sites, double *d_f, double *dd_f)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (reads the sumtable, no CLV)
   DerivLaunch l;
   if (int rc = deriv_launch_setup(c, slot, params_indices, eval_sites, l)) return rc;
   l.dg.branch_length = branch_length;
@@ -3235,7 +3423,7 @@ static_assert(sizeof(NewtonState) == 8 * sizeof(double), "the state record: eigh
 extern "C" int pllgpu_optimize_branch_length(pllgpu_ctx_t *c, unsigned slot, const unsigned *params_indices, unsigned eval_sites,
                                              const pllgpu_newton_t *opt, pllgpu_newton_result_t *result, double *trace)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (reads the sumtable, no CLV; the matrix it may write: below)
   const pllgpu_geometry_t &g = c->geo;
   if (!opt || !result) return fail(PLLGPU_EINVAL, "null options / result");
   if (!(opt->t_min >= 0) || !(opt->t_min <= opt->t_max) || !std::isfinite(opt->t_max) || !std::isfinite(opt->t_start) ||
@@ -3244,6 +3432,12 @@ extern "C" int pllgpu_optimize_branch_length(pllgpu_ctx_t *c, unsigned slot, con
     return fail(PLLGPU_EINVAL, "Newton options out of range");
   const bool with_matrix = opt->matrix_index >= 0;
   if (with_matrix && (!c->evecs.p || !c->ievecs.p)) return fail(PLLGPU_EINVAL, "eigensystem was not uploaded");
+  if (with_matrix)
+  {
+    // the matrix formed at the end is a change like any other: pending CLVs that read it keep the old one aside first
+    const unsigned m = (unsigned)opt->matrix_index;
+    if (int rc = matrices_change(c, &m, 0, 1)) return rc;
+  }
   DerivLaunch l;
   if (int rc = deriv_launch_setup(c, slot, params_indices, eval_sites, l)) return rc;
   if (int rc = c->newton.ensure(8 + 3 * PLLGPU_NEWTON_MAX_ITERS)) return rc;
@@ -3324,7 +3518,10 @@ extern "C" int pllgpu_optimize_branch_length(pllgpu_ctx_t *c, unsigned slot, con
 // ---- ascertainment-bias terms --------------------------------------------------------------------
 extern "C" int pllgpu_asc_terms(pllgpu_ctx_t *c, const pllgpu_edge_t *ed, int is_root, double *terms, unsigned *scalings)
 {
-  CHECK_CTX(c);
+  // reads the per-state entries of the edge's two ends and nothing else: pending CLVs are stored first only if an end is one
+  // (the correction of the root edge follows every evaluation of an ascertainment-bias partition)
+  CHECK_CTX_KEEP_PENDING(c);
+  if (int rc = materialise_if_an_end_is_pending(c, ed, is_root != 0)) return rc;
   const pllgpu_geometry_t &g = c->geo;
   if (g.sites_alloc < g.sites + g.states) return fail(PLLGPU_EINVAL, "the partition has no per-state extra entries");
   if (ed->parent_clv >= g.nodes || !c->clv[ed->parent_clv].p) return fail(PLLGPU_EINVAL, "CLV %u unavailable on the device", ed->parent_clv);
@@ -3406,7 +3603,7 @@ extern "C" int pllgpu_asc_derivative_terms(pllgpu_ctx_t *c, unsigned slot, int p
 extern "C" int pllgpu_eigen_upload(pllgpu_ctx_t *c, unsigned index, const double *eigenvecs, const double *inv_eigenvecs,
                                    const double *eigenvals)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (an input of the matrices formed from here on, of no CLV)
   const pllgpu_geometry_t &g = c->geo;
   if (index >= g.rate_matrices) return fail(PLLGPU_EINVAL, "eigensystem %u out of range", index);
   const size_t n = (size_t)g.states * g.states_padded;
@@ -3420,7 +3617,8 @@ extern "C" int pllgpu_eigen_upload(pllgpu_ctx_t *c, unsigned index, const double
 extern "C" int pllgpu_update_pmatrices(pllgpu_ctx_t *c, const unsigned *params_indices, const unsigned *matrix_indices,
                                        const double *branch_lengths, unsigned count)
 {
-  CHECK_CTX(c);
+  // like an upload: held work that reads one of these matrices goes out first, pending CLVs that do keep their own copy
+  CHECK_CTX_KEEP(c);
   const pllgpu_geometry_t &g = c->geo;
   if (!count) return 0;
   if (!c->evecs.p || !c->ievecs.p || !c->eigenvals.p || !c->rates.p)
@@ -3435,6 +3633,7 @@ extern "C" int pllgpu_update_pmatrices(pllgpu_ctx_t *c, const unsigned *params_i
   for (unsigned i = 0; i < count; ++i)
     if (matrix_indices[i] >= g.prob_matrices || !(branch_lengths[i] >= 0))
       return fail(PLLGPU_EINVAL, "matrix index %u / branch length %g invalid", matrix_indices[i], branch_lengths[i]);
+  if (int rc = matrices_change(c, matrix_indices, 0, count)) return rc;
   for (unsigned i = 0; i < count; ++i) ++c->pm_version[matrix_indices[i]];
   const bool few = count <= kPmatInline;
   if (!few)
@@ -3487,7 +3686,7 @@ extern "C" int pllgpu_update_pmatrices(pllgpu_ctx_t *c, const unsigned *params_i
 
 extern "C" int pllgpu_pmatrix_download(pllgpu_ctx_t *c, unsigned index, double *host)
 {
-  CHECK_CTX(c);
+  CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   const pllgpu_geometry_t &g = c->geo;
   if (index >= g.prob_matrices) return fail(PLLGPU_EINVAL, "matrix %u out of range", index);
   HIP_TRY(hipStreamSynchronize(c->stream)); // an earlier upload may still read the staging vector

@@ -117,3 +117,7 @@ AT(pll_gpu_newton_result_t, iterations, 24);
 AT(pll_gpu_newton_result_t, host_waits, 28);
 AT(pll_gpu_newton_result_t, status, 32);
 _Static_assert(PLL_GPU_NEWTON_MAX_ITERS == PLLGPU_NEWTON_MAX_ITERS && PLL_GPU_NEWTON_MAXITER == PLLGPU_NEWTON_MAXITER, "Newton constants");
+
+/* queries the Python binding declares by hand (pllamd/api.py): the prototypes it assumes */
+_Static_assert(_Generic(&pll_gpu_pending_clvs, unsigned int (*)(const pll_partition_t *): 1, default: 0) &&
+               _Generic(&pllgpu_pending_clvs, unsigned (*)(const pllgpu_ctx_t *): 1, default: 0), "pll_gpu_pending_clvs prototype");

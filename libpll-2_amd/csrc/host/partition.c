@@ -932,6 +932,12 @@ int pll_gpu_last_update_replayed(const pll_partition_t *p)
   return x ? x->fast_taken : 0;
 }
 
+unsigned int pll_gpu_pending_clvs(const pll_partition_t *p)
+{
+  const pll_amd_ext_t *x = p ? pll_ext(p) : NULL;
+  return (x && x->ctx) ? pllgpu_pending_clvs(x->ctx) : 0u;
+}
+
 unsigned long long pll_gpu_plan_replays(const pll_partition_t *p)
 {
   pll_amd_ext_t *x = p ? pll_ext(p) : NULL;

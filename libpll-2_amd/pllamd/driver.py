@@ -200,6 +200,10 @@ class Session:
             self.p, root[0], root[1], api.uptr(self._fi), api.dptr(ps) if persite else None)
         return v, ps
 
+    def pending_clvs(self):
+        """pll_gpu_pending_clvs (libpll_amd.so only): CLVs the last step formed and has not stored on the device"""
+        return int(self.lib.pll_gpu_pending_clvs(self.p)) if self.lib.is_amd else 0
+
     def node_ancestral(self, edge):
         """marginal state probabilities [sites, states] of the node edge[0] (scaler edge[1]) towards the other
         end edge[2] (scaler edge[3]) across matrix edge[4]"""
