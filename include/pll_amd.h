@@ -739,6 +739,41 @@ typedef struct pll_gpu_insertion
 int pll_gpu_insertion_loglikelihoods(pll_partition_t *partition, unsigned int subtree_clv_index, int subtree_scaler_index,
                                      unsigned int subtree_matrix_index, const pll_gpu_insertion_t *candidates,
                                      unsigned int count, const unsigned int *freqs_indices, double *lnl);
+/* ---- batched placement log-likelihoods ---------------------------------
+ * Every query x every candidate edge in one call: the pre-scoring pass of a phylogenetic placement, the first pass of
+ * a stepwise addition by likelihood. lnl is [query_count][count], query-major, and lnl[q * count + i] is BY DEFINITION
+ * what pll_gpu_insertion_loglikelihoods(partition, query_tip_indices[q], PLL_SCALE_BUFFER_NONE, pendant_matrix_index,
+ * &candidates[i], 1, freqs_indices, ...) returns, bit for bit: the reference's pll_update_partials with the one
+ * operation {tmp, tmp_scaler, child1..., child2...} of candidate i (src/partials.c:237-291) followed by
+ * pll_compute_edge_loglikelihood(partition, tmp, tmp_scaler, query_tip_indices[q], PLL_SCALE_BUFFER_NONE,
+ * pendant_matrix_index, freqs_indices, NULL) (src/likelihood.c:586-636). A caller may pre-score with this call and
+ * score the best edges again with the other: the ranking does not move. The tree, its CLVs and the candidates are read
+ * once per chunk of queries instead of once per query (a 4 x 4 candidate: about 264 + Q bytes per site, not 265 Q).
+ * Queries are tips of the partition set through pll_set_tip_states, with or without PLL_ATTRIB_PATTERN_TIP; a caller
+ * with more queries than spare tips sets the spare tips again chunk by chunk ("Scoring many queries at
+ * once"). A tip may be named twice (two equal rows) and may also be an end of a candidate. Candidates are exactly those
+ * of pll_gpu_insertion_loglikelihoods. Nothing in the partition is written - no CLV, scaler, matrix, class map or
+ * cached launch plan; what the previous pll_update_partials still holds back is launched first. Synchronous: one copy
+ * back of the whole matrix and one wait. Every lnl[q][i] has the same bits whatever else the two lists hold, in
+ * whatever order, and from run to run.
+ * PLL_SUCCESS, or PLL_FAILURE with pll_errno, the usual line on stderr and lnl untouched. Both lists are checked whole
+ * before anything is flushed or launched, in this order: PLL_ERROR_PARAM_INVALID for a NULL partition, for a NULL
+ * query_tip_indices, candidates, lnl or freqs_indices with both counts > 0, for a query index >= partition->tips, for a
+ * pendant matrix, a candidate field or a freqs_indices[k] out of range; PLL_ERROR_GPU_UNSUPPORTED for a
+ * PLL_ATTRIB_SITE_REPEATS partition, for a partition with an ascertainment-bias correction, and for a query tip the
+ * device does not hold as codes (set with pll_set_tip_clv to anything but indicator vectors, made dense by an earlier
+ * call, or PLL_AMD_NO_TIP_CODES on a partition without PLL_ATTRIB_PATTERN_TIP: set it again with pll_set_tip_states);
+ * PLL_ERROR_GPU_UNAVAILABLE without a
+ * device. query_count == 0 or count == 0 succeeds without a launch and without touching lnl.
+ * pll_gpu_last_launch_count reports the launches of the call; long lists are cut internally by candidates and by
+ * chunks of queries (the rule: include/pll_amd_device.h, pllgpu_placement_loglikelihoods).
+ * Not offered: a pendant length per query (one matrix serves all), inner subtree ends as queries (the call above serves
+ * one), site repeats and the ascertainment-bias correction (refused), the best k edges chosen on the device, and an
+ * optimised pendant branch per placement (absent). */
+int pll_gpu_placement_loglikelihoods(pll_partition_t *partition, const unsigned int *query_tip_indices,
+                                     unsigned int query_count, unsigned int pendant_matrix_index,
+                                     const pll_gpu_insertion_t *candidates, unsigned int count,
+                                     const unsigned int *freqs_indices, double *lnl);
 /* pll_compute_node_ancestral (src/pll.h:799-806) without the host round trip: the kernel is enqueued on the
  * partition's stream (pll_gpu_set_stream / pll_gpu_get_stream apply) and leaves the table in the sites * states
  * doubles of DEVICE memory at device_ancestral; nothing is copied back and the call does not wait. A caller that
@@ -819,7 +854,8 @@ int pll_gpu_rccl_available(void);
  * brackets whatever was enqueued in between; returns elapsed milliseconds from stop(). */
 int pll_gpu_timer_start(pll_partition_t *partition);
 double pll_gpu_timer_stop(pll_partition_t *partition);
-/* number of kernel launches issued by the last pll_update_partials or pll_gpu_insertion_loglikelihoods call */
+/* number of kernel launches issued by the last pll_update_partials, pll_gpu_insertion_loglikelihoods or
+ * pll_gpu_placement_loglikelihoods call */
 unsigned int pll_gpu_last_launch_count(const pll_partition_t *partition);
 /* site repeats: class-map operations computed on the device (launches = 0) / class kernels launched (launches != 0)
  * since the partition was created. An unchanged tree adds nothing, a topology move the ops of its partial traversal */

@@ -194,6 +194,31 @@ int pllgpu_insertion_loglikelihoods(pllgpu_ctx_t *ctx, unsigned int subtree_clv,
                                     unsigned int subtree_is_tip, const pllgpu_insertion_t *cands, unsigned int count,
                                     const unsigned int *freqs_indices, double *host_out);
 
+/* The same question for `queries` query tips at once: host_out[q * count + i] = what pllgpu_insertion_loglikelihoods gives
+ * for the subtree end (query_tips[q], no scaler, pendant_matrix, a tip given by codes) and candidate i, bit for bit. The
+ * inserted node of a candidate is formed once per site tile and a chunk of queries is scored against it
+ * (kernels_placement.h). Every query must be a tip whose codes the context holds (PLLGPU_EINVAL otherwise). Every index
+ * of both lists is checked before held work is launched or anything else happens; class-compressed CLVs anywhere in the
+ * context and ascertainment-bias entries are PLLGPU_EUNSUPPORTED. Nothing the context holds is written.
+ * The cutting rule. B = the workgroups per (query, candidate), launch_insertions' cut of the site tiles: with
+ * T = ceil(sites / 64), 4 x 4: w = ceil(T / 4096), B = ceil(T / (4 w)); every other shape: w = ceil(T / 1024),
+ * B = ceil(T / w). QCH = PLLGPU_PLACEMENT_CHUNK_DNA (4 x 4) or PLLGPU_PLACEMENT_CHUNK_TILED queries per workgroup.
+ * A launch carries at most PLLGPU_INSERTION_MAX_CANDS descriptors and PLLGPU_INSERTION_MAX_SLOTS partial slots
+ * (queries x candidates x B):
+ *   C = min(count, MAX_CANDS, max(1, floor(MAX_SLOTS / (B QCH))))                 candidates per launch,
+ *   Q = min(queries, QCH min(65535, max(1, floor(floor(MAX_SLOTS / (B C)) / QCH)))) queries per launch,
+ * grid (B, C, ceil(Q / QCH)), and the call is ceil(count / C) * ceil(queries / Q) launches (counted into
+ * pllgpu_last_launch_count), candidates outermost; one copy back of the whole matrix, one wait. queries == 1 is handed to
+ * pllgpu_insertion_loglikelihoods (no node to share; its launches: C = min(count, MAX_CANDS, max(1, floor(MAX_SLOTS / B)))).
+ * host_out is written only on success; queries == 0 or count == 0 succeeds without a launch. */
+#define PLLGPU_PLACEMENT_CHUNK_DNA 16
+#define PLLGPU_PLACEMENT_CHUNK_TILED 4
+#define PLLGPU_INSERTION_MAX_CANDS 16384
+#define PLLGPU_INSERTION_MAX_SLOTS (4u << 20)
+int pllgpu_placement_loglikelihoods(pllgpu_ctx_t *ctx, const unsigned int *query_tips, unsigned int queries,
+                                    unsigned int pendant_matrix, const pllgpu_insertion_t *cands, unsigned int count,
+                                    const unsigned int *freqs_indices, double *host_out);
+
 /* replaces pll_compute_node_ancestral[_extbuf] (src/likelihood.c:639-823): the marginal state probabilities of
  * the node at edge->parent_clv, [sites][states] unpadded, given the other end edge->child_clv (a CLV, or tip codes
  * with child_is_tip) across edge->matrix. Of `edge`, gather must be 0 and want_persite / device_result / sequence

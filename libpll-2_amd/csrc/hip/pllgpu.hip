@@ -31,6 +31,7 @@
 #include "kernels_ancestral.h"
 #include "kernels_parsimony.h"
 #include "kernels_insertion.h"
+#include "kernels_placement.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
@@ -223,6 +224,9 @@ struct pllgpu_ctx
   DevBuf<double> ins_partials, ins_results;
   DevBuf<unsigned> ins_tickets;
   DevBuf<unsigned char> ins_cands;
+  // pllgpu_placement_loglikelihoods (kernels_placement.h) uses the four above - slots and tickets per (query, candidate)
+  // of a launch, the [query][candidate] results of a call - and the code rows of the call's queries
+  DevBuf<unsigned char> plc_rows;
   DevBuf<unsigned char> mfma_flags;      // [op in launch][rate][entry] scaling decisions (kernels_mfma.h)
   DevBuf<double> eigenvals, rates, diag; // derivatives: [rate_matrices][SP], [R], [R][S][4]
   DevBuf<double> newton;                 // pllgpu_optimize_branch_length: the state record (NewtonState), then the trace
@@ -2789,6 +2793,7 @@ extern "C" int pllgpu_root_loglikelihood(pllgpu_ctx_t *c, unsigned clv, int scal
 constexpr unsigned kInsMaxCands = 16384;          // 1 MB of descriptors, well below the grid's y limit
 constexpr size_t kInsMaxSlots = (size_t)4 << 20;  // 32 MB of partial sums per launch
 constexpr size_t kInsLdsMax = 144 * 1024;         // the inserted node's tile in LDS, beside the kernel's static 8 KB
+constexpr size_t kPlcLdsMax = 126 * 1024;         // ... beside k_placement_tiled's static 32 KB (the flags, 7 KB per query of the chunk, the hand-off's words)
 
 // Scratch that no kept plan points at: (re)allocating it must not move the context's allocation epoch, or the first
 // batched call would drop every cached launch plan of the partition.
@@ -2924,6 +2929,168 @@ extern "C" int pllgpu_insertion_loglikelihoods(pllgpu_ctx_t *c, unsigned subtree
     if (int rc = launch_insertions(c, e, cands, first, std::min(per_launch, count - first), subtree_is_tip != 0)) return rc;
   // one copy back for all candidates, one wait
   HIP_TRY(copy_down(c, host_out, c->ins_results.p, (size_t)count * sizeof(double)));
+  if (c->defer_down) HIP_TRY(stream_wait(c));
+  return 0;
+}
+
+// ---- batched placement log-likelihoods (kernels_placement.h) -------------------------------------------------
+// the candidates' descriptors of launches [first, first + n) on the device (launch_insertions' own, for several launches)
+static int upload_candidates(pllgpu_ctx *c, const pllgpu_insertion_t *cands, unsigned first, unsigned n)
+{
+  const size_t bytes = (size_t)n * sizeof(InsCand);
+  unsigned char *dev = nullptr;
+  InsCand *host = reinterpret_cast<InsCand *>(stage_take(c, bytes, &dev));
+  std::vector<InsCand> pageable;
+  if (!host)
+  {
+    pageable.resize(n);
+    host = pageable.data();
+  }
+  for (unsigned i = 0; i < n; ++i)
+  {
+    const pllgpu_insertion_t &q = cands[first + i];
+    InsCand &d = host[i];
+    if (int rc = end_in_hbm(c, q.child1_clv, q.child1_is_tip ? -1 : q.child1_scaler, q.child1_is_tip != 0, d.left, d.ltip, d.lscaler)) return rc;
+    if (int rc = end_in_hbm(c, q.child2_clv, q.child2_is_tip ? -1 : q.child2_scaler, q.child2_is_tip != 0, d.right, d.rtip, d.rscaler)) return rc;
+    d.lmat = c->pmat.p + (size_t)q.child1_matrix * c->pm_stride;
+    d.rmat = c->pmat.p + (size_t)q.child2_matrix * c->pm_stride;
+  }
+  HIP_TRY(hipMemcpyAsync(c->ins_cands.p, host, bytes, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+// The cutting rule of pllgpu_placement_loglikelihoods (include/pll_amd_device.h states it): candidates per launch, queries
+// per launch (whole chunks), the chunk of the shape.
+struct PlacementCut
+{
+  unsigned blocks, tiles_per, chunk, cands, queries;
+};
+
+static_assert(kPlcDnaChunk == PLLGPU_PLACEMENT_CHUNK_DNA && kPlcTiledChunk == PLLGPU_PLACEMENT_CHUNK_TILED &&
+                  kInsMaxCands == PLLGPU_INSERTION_MAX_CANDS && kInsMaxSlots == PLLGPU_INSERTION_MAX_SLOTS,
+              "the cutting rule as include/pll_amd_device.h states it");
+
+static PlacementCut placement_cut(const pllgpu_ctx *c, unsigned queries, unsigned count)
+{
+  PlacementCut k;
+  const unsigned tiles = (c->geo.sites + 63) / 64, max_blocks = 1024;
+  if (c->dna_fast)
+  {
+    k.tiles_per = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
+    k.blocks = (tiles + 4 * k.tiles_per - 1) / (4 * k.tiles_per);
+    k.chunk = kPlcDnaChunk;
+  }
+  else
+  {
+    k.tiles_per = (tiles + max_blocks - 1) / max_blocks;
+    k.blocks = (tiles + k.tiles_per - 1) / k.tiles_per;
+    k.chunk = kPlcTiledChunk;
+  }
+  k.cands = (unsigned)std::min<size_t>(std::min(count, kInsMaxCands), std::max<size_t>(1, kInsMaxSlots / ((size_t)k.blocks * k.chunk)));
+  const size_t chunks = std::min<size_t>(std::max<size_t>(1, kInsMaxSlots / ((size_t)k.blocks * k.cands) / k.chunk), 65535u);
+  k.queries = (unsigned)std::min<size_t>(queries, chunks * k.chunk);
+  return k;
+}
+
+// one launch: queries [q0, q0 + nq) of the call x the n candidates whose descriptors stand in ins_cands
+static int launch_placements(pllgpu_ctx *c, DevEdge e, const PlacementCut &k, unsigned q0, unsigned nq, unsigned first, unsigned n, unsigned count)
+{
+  const InsCand *dc = reinterpret_cast<const InsCand *>(c->ins_cands.p);
+  const unsigned char *const *rows = reinterpret_cast<const unsigned char *const *>(c->plc_rows.p) + q0;
+  e.result = c->ins_results.p + (size_t)q0 * count + first;
+  const dim3 grid(k.blocks, n, (nq + k.chunk - 1) / k.chunk);
+  if (c->dna_fast)
+    hipLaunchKernelGGL((k_placement_dna<kPlcDnaChunk>), grid, dim3(256), 0, c->stream, e, dc, rows, nq, count, c->gg.scale_mode, k.tiles_per);
+  else
+  {
+    const unsigned threads = 64u * std::min(c->gg.R, 4u);
+    size_t lds = (size_t)c->gg.tile_sz * sizeof(double);
+    const unsigned keep = lds <= kPlcLdsMax ? 1u : 0u;
+    if (!keep) lds = 0;
+    const unsigned long long *tm = tipmap_ptr(c);
+    with_ich(c->ich, [&](auto ICH) {
+      raise_lds_limit(reinterpret_cast<const void *>(&k_placement_tiled<ICH(), kPlcTiledChunk>), c->device, lds);
+      hipLaunchKernelGGL((k_placement_tiled<ICH(), kPlcTiledChunk>), grid, dim3(threads), lds, c->stream, e, dc, rows, nq, count, c->gg, tm,
+                         k.tiles_per, keep);
+    });
+  }
+  ++c->last_launches;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pllgpu_placement_loglikelihoods(pllgpu_ctx_t *c, const unsigned *query_tips, unsigned queries, unsigned pendant_matrix,
+                                               const pllgpu_insertion_t *cands, unsigned count, const unsigned *freqs_indices, double *host_out)
+{
+  CHECK_CTX_KEEP(c);
+  const pllgpu_geometry_t &g = c->geo;
+  c->last_launches = 0;
+  if (!queries || !count) return 0;
+  // everything that needs no device state, for both lists, before held work is touched
+  if (!query_tips || !cands || !host_out || !freqs_indices) return fail(PLLGPU_EINVAL, "placement log-likelihoods: null argument");
+  // one query is what the insertion call serves, with the same checks and the same bits: there is no node to share
+  if (queries == 1 && query_tips[0] < g.tips)
+    return pllgpu_insertion_loglikelihoods(c, query_tips[0], -1, pendant_matrix, 1u, cands, count, freqs_indices, host_out);
+  if (g.sites == 0 || g.sites != g.sites_alloc) return fail(PLLGPU_EUNSUPPORTED, "placement log-likelihoods with ascertainment-bias entries");
+  for (unsigned q = 0; q < queries; ++q)
+    if (query_tips[q] >= g.tips) return fail(PLLGPU_EINVAL, "query %u: %u is no tip", q, query_tips[q]);
+  if (pendant_matrix >= g.prob_matrices) return fail(PLLGPU_EINVAL, "the pendant matrix index is out of range");
+  for (unsigned k = 0; k < g.rate_cats; ++k)
+    if (freqs_indices[k] >= g.rate_matrices) return fail(PLLGPU_EINVAL, "freqs_indices[%u] = %u out of range", k, freqs_indices[k]);
+  for (unsigned i = 0; i < count; ++i)
+  {
+    if (int rc = check_insertion_end(c, cands[i].child1_clv, cands[i].child1_scaler, cands[i].child1_matrix, cands[i].child1_is_tip != 0, "child1", i)) return rc;
+    if (int rc = check_insertion_end(c, cands[i].child2_clv, cands[i].child2_scaler, cands[i].child2_matrix, cands[i].child2_is_tip != 0, "child2", i)) return rc;
+  }
+  for (unsigned n = 0; n < g.nodes; ++n)
+    if (c->ids[n] || c->clv_aos[n]) return fail(PLLGPU_EUNSUPPORTED, "placement log-likelihoods over class-compressed CLVs");
+  for (unsigned q = 0; q < queries; ++q)
+    if (!c->tipchars[query_tips[q]].p) return fail(PLLGPU_EINVAL, "query %u: tip %u has no codes on the device", q, query_tips[q]);
+  // whatever pllgpu_update_partials holds back goes out as ordinary launches: a candidate may name what it produces
+  if (HOLDS_WORK(c) || !c->pending.empty())
+    if (int rc = flush_deferred(c)) return rc;
+
+  DevEdge e;
+  memset(&e, 0, sizeof e);
+  e.mat = c->pmat.p + (size_t)pendant_matrix * c->pm_stride;
+  if (int rc = fill_edge_model(c, e, freqs_indices)) return rc;
+
+  const PlacementCut k = placement_cut(c, queries, count);
+  const size_t pairs = (size_t)k.queries * k.cands, row_bytes = (size_t)queries * sizeof(const unsigned char *);
+  {
+    ScratchEpoch scratch_epoch_;
+    if (c->ins_partials.ensure(pairs * k.blocks) || c->ins_results.ensure((size_t)queries * count) ||
+        c->ins_cands.ensure((size_t)k.cands * sizeof(InsCand)) || c->plc_rows.ensure(row_bytes))
+      return PLLGPU_ENOMEM;
+    if (c->ins_tickets.cap < pairs)
+    {
+      if (c->ins_tickets.ensure(pairs)) return PLLGPU_ENOMEM;
+      HIP_TRY(hipMemsetAsync(c->ins_tickets.p, 0, c->ins_tickets.cap * sizeof(unsigned), c->stream));
+    }
+  }
+  {
+    unsigned char *dev = nullptr;
+    const unsigned char **host = reinterpret_cast<const unsigned char **>(stage_take(c, row_bytes, &dev));
+    std::vector<const unsigned char *> pageable;
+    if (!host)
+    {
+      pageable.resize(queries);
+      host = pageable.data();
+    }
+    for (unsigned q = 0; q < queries; ++q) host[q] = c->tipchars[query_tips[q]].p;
+    HIP_TRY(hipMemcpyAsync(c->plc_rows.p, host, row_bytes, hipMemcpyHostToDevice, c->stream));
+  }
+  e.block_sums = c->ins_partials.p;
+  e.counter = c->ins_tickets.p;
+  for (unsigned first = 0; first < count; first += k.cands)
+  {
+    const unsigned n = std::min(k.cands, count - first);
+    if (int rc = upload_candidates(c, cands, first, n)) return rc;
+    for (unsigned q0 = 0; q0 < queries; q0 += k.queries)
+      if (int rc = launch_placements(c, e, k, q0, std::min(k.queries, queries - q0), first, n, count)) return rc;
+  }
+  // one copy back for the whole matrix, one wait
+  HIP_TRY(copy_down(c, host_out, c->ins_results.p, (size_t)queries * count * sizeof(double)));
   if (c->defer_down) HIP_TRY(stream_wait(c));
   return 0;
 }

@@ -258,6 +258,8 @@ _GPU_PROTOS = {
     "pll_gpu_node_ancestral_async": (C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p, C.c_void_p]),
     "pll_gpu_insertion_loglikelihoods": (
         C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.POINTER(Insertion), C.c_uint, c_uint_p, c_double_p]),
+    "pll_gpu_placement_loglikelihoods": (
+        C.c_int, [PartitionP, c_uint_p, C.c_uint, C.c_uint, C.POINTER(Insertion), C.c_uint, c_uint_p, c_double_p]),
     "pll_gpu_optimize_branch_length": (
         C.c_int, [PartitionP, C.c_int, C.c_int, c_uint_p, c_double_p, C.POINTER(Newton), C.POINTER(NewtonResult), c_double_p]),
     "pll_gpu_last_algorithmic_bytes": (C.c_double, [PartitionP]),

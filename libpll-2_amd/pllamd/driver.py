@@ -100,6 +100,19 @@ def insertion_loglikelihoods(lib, partition, subtree, candidates, freqs_indices)
     return out
 
 
+def placement_loglikelihoods(lib, partition, query_tips, pendant_matrix, candidates, freqs_indices):
+    """pll_gpu_placement_loglikelihoods: every query tip of query_tips inserted into every candidate (rows in
+    pll_gpu_insertion_t field order) across the one pendant matrix; a [Q, E] array from one call. libpll_amd.so only."""
+    rows = list(candidates)
+    tips = np.ascontiguousarray(query_tips, dtype=np.uint32)
+    out = np.full((len(tips), len(rows)), np.nan)
+    fi = np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+    if not lib.pll_gpu_placement_loglikelihoods(partition, api.uptr(tips), len(tips), int(pendant_matrix), api.make_insertions(rows),
+                                                len(rows), api.uptr(fi), api.dptr(out)):
+        raise RuntimeError(f"pll_gpu_placement_loglikelihoods: [{lib.errno()}] {lib.errmsg()}")
+    return out
+
+
 def insertion_loglikelihoods_per_edge(lib, partition, subtree, candidates, freqs_indices, tmp):
     """the same values the way every libpll offers them: per candidate one pll_update_partials with a single operation
     into the spare node tmp = (clv, scaler), then pll_compute_edge_loglikelihood between tmp and the subtree end"""
