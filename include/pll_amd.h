@@ -739,6 +739,49 @@ typedef struct pll_gpu_insertion
 int pll_gpu_insertion_loglikelihoods(pll_partition_t *partition, unsigned int subtree_clv_index, int subtree_scaler_index,
                                      unsigned int subtree_matrix_index, const pll_gpu_insertion_t *candidates,
                                      unsigned int count, const unsigned int *freqs_indices, double *lnl);
+/* ---- batched NNI scores -------------------------------------------------
+ * "What is the log-likelihood if the four subtrees around this inner edge are paired the other two ways?" for `count`
+ * quartets in one call: the question a search that ranks the NNI neighbourhood of a tree asks of each of its T - 3 inner
+ * edges. A quartet names its four ends e0..e3, each oriented towards the quartet's inner edge, with the matrix of each
+ * end's own branch (it travels with the end) and the matrix of the inner edge. For quartet i the call returns
+ *   lnl[3 i + 0] for ((e0,e1),(e2,e3)),  lnl[3 i + 1] for ((e0,e2),(e1,e3)),  lnl[3 i + 2] for ((e0,e3),(e1,e2)).
+ * Arrangement ((x,y),(z,w)) is BY DEFINITION what the reference returns for pll_update_partials with the two operations
+ * {tmp1, s1, x, matrix[x], scaler[x], y, matrix[y], scaler[y]} and {tmp2, s2, z, matrix[z], scaler[z], w, matrix[w],
+ * scaler[w]} (src/partials.c:237-291), tmp1 / tmp2 spare inner CLVs with scalers s1 / s2, followed by
+ * pll_compute_edge_loglikelihood(partition, tmp1, s1, tmp2, s2, inner_matrix_index, freqs_indices, NULL)
+ * (src/likelihood.c:586-636): the child order inside a pair is the order written, the pair that holds e0 is the edge's
+ * parent end, both nodes always scale, a pair of two tips follows the reference's tip-tip rule. No spare slot is
+ * needed: both nodes and their scaling counts exist inside the kernel only, and nothing in the partition is written - no
+ * CLV, scaler, matrix, class map or cached launch plan.
+ * Any end may be an inner CLV (with or without a scaler), a PLL_ATTRIB_PATTERN_TIP tip or a tip set through
+ * pll_set_tip_states; a scaler index named for a tip is ignored, as the reference's tip kernels do.
+ * All four ends of every quartet are read in one launch, so each must hold the named orientation AT THE SAME TIME: a
+ * caller computes the "upward" CLVs into spare clv_buffers slots first, exactly as for the insertion call
+ * ("Scoring every NNI at once"). What the previous pll_update_partials still holds back is launched
+ * first. For an inner edge p of a pll_utree, e0 = p->next->back, e1 = p->next->next->back, e2 = p->back->next->back,
+ * e3 = p->back->next->next->back make arrangement 0 the tree itself, arrangement 2 the tree after the NNI that swaps
+ * p->next with p->back->next and arrangement 1 the tree after the one that swaps p->next with p->back->next->next
+ * ("Scoring every NNI at once", has the table).
+ * Synchronous: one copy back and one wait. Each value is formed in an order that depends on the site count alone: it has
+ * the same bits alone, among others, in any list order, and from run to run.
+ * PLL_SUCCESS, or PLL_FAILURE with pll_errno, the usual line on stderr and lnl untouched. The whole list is checked
+ * before anything is flushed or launched, in this order: PLL_ERROR_PARAM_INVALID for a NULL partition, for a NULL
+ * quartets, lnl or freqs_indices with count > 0, for any index of any quartet or a freqs_indices[k] out of range;
+ * PLL_ERROR_GPU_UNSUPPORTED for a PLL_ATTRIB_SITE_REPEATS partition and for a partition with an ascertainment-bias
+ * correction; PLL_ERROR_GPU_UNAVAILABLE without a device. count == 0 succeeds without a launch and without touching
+ * lnl. pll_gpu_last_launch_count reports the launches of the call; long lists are cut internally (the rule:
+ * include/pll_amd_device.h, pllgpu_quartet_loglikelihoods).
+ * Not offered: a choice of fewer than three arrangements, optimised branch lengths per arrangement, site repeats and the
+ * ascertainment-bias correction (refused). */
+typedef struct pll_gpu_quartet
+{
+  unsigned int clv_index[4];      /* the four ends e0..e3, each oriented towards the quartet's inner edge */
+  int scaler_index[4];            /* PLL_SCALE_BUFFER_NONE or a scale buffer; ignored for a tip */
+  unsigned int matrix_index[4];   /* the matrix of each end's own branch */
+  unsigned int inner_matrix_index;
+} pll_gpu_quartet_t;
+int pll_gpu_quartet_loglikelihoods(pll_partition_t *partition, const pll_gpu_quartet_t *quartets, unsigned int count,
+                                   const unsigned int *freqs_indices, double *lnl /* [count][3] */);
 /* ---- batched placement log-likelihoods ---------------------------------
  * Every query x every candidate edge in one call: the pre-scoring pass of a phylogenetic placement, the first pass of
  * a stepwise addition by likelihood. lnl is [query_count][count], query-major, and lnl[q * count + i] is BY DEFINITION
@@ -854,8 +897,8 @@ int pll_gpu_rccl_available(void);
  * brackets whatever was enqueued in between; returns elapsed milliseconds from stop(). */
 int pll_gpu_timer_start(pll_partition_t *partition);
 double pll_gpu_timer_stop(pll_partition_t *partition);
-/* number of kernel launches issued by the last pll_update_partials, pll_gpu_insertion_loglikelihoods or
- * pll_gpu_placement_loglikelihoods call */
+/* number of kernel launches issued by the last pll_update_partials, pll_gpu_insertion_loglikelihoods,
+ * pll_gpu_placement_loglikelihoods or pll_gpu_quartet_loglikelihoods call */
 unsigned int pll_gpu_last_launch_count(const pll_partition_t *partition);
 /* site repeats: class-map operations computed on the device (launches = 0) / class kernels launched (launches != 0)
  * since the partition was created. An unchanged tree adds nothing, a topology move the ops of its partial traversal */

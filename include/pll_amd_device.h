@@ -219,6 +219,38 @@ int pllgpu_placement_loglikelihoods(pllgpu_ctx_t *ctx, const unsigned int *query
                                     unsigned int pendant_matrix, const pllgpu_insertion_t *cands, unsigned int count,
                                     const unsigned int *freqs_indices, double *host_out);
 
+/* All three pairings of the four ends around an inner edge, for `count` quartets at once (kernels_quartet.h):
+ * host_out[3 i + a] replaces pll_update_partials with two ops into two spare nodes (src/partials.c:237-291) +
+ * pll_compute_edge_loglikelihood between them over `inner_matrix` (src/likelihood.c:586-636), for a = 0: ((e0,e1),(e2,e3)),
+ * 1: ((e0,e2),(e1,e3)), 2: ((e0,e3),(e1,e2)); the pair that holds e0 is the edge's parent end, the children of a pair stand
+ * in the order written. Both nodes exist in registers / LDS only; nothing the context holds is written. is_tip of an end:
+ * PLLGPU_QUARTET_TIP_CODES - the end is read as tip codes (its scaler index is not read); PLLGPU_QUARTET_TIP_PATTERN in
+ * addition - the reference reads it with its tip kernels (PLL_ATTRIB_PATTERN_TIP), and a pair of two such ends takes no
+ * scaling decision, as the reference's tip-tip kernels take none. Every index of the whole list and every tip mark is
+ * checked before held work is launched or anything else happens; class-compressed CLVs anywhere in the context and
+ * ascertainment-bias entries are PLLGPU_EUNSUPPORTED.
+ * The cutting rule. B = the workgroups per quartet, launch_insertions' cut of the site tiles (T = ceil(sites / 64); 4 x 4:
+ * w = ceil(T / 4096), B = ceil(T / (4 w)); every other shape: w = ceil(T / 1024), B = ceil(T / w)). A workgroup leaves three
+ * partial sums, one per arrangement, and a launch carries at most PLLGPU_QUARTET_MAX descriptors (144 bytes each: one
+ * piece of the pinned block) and PLLGPU_INSERTION_MAX_SLOTS partial slots:
+ *   Q = min(count, PLLGPU_QUARTET_MAX, max(1, floor(PLLGPU_INSERTION_MAX_SLOTS / (3 B))))   quartets per launch,
+ * grid (B, Q), ceil(count / Q) launches (counted into pllgpu_last_launch_count); one copy back of all 3 count values, one
+ * wait. Value 3 i + a owns B slots and a ticket of its own: its bits depend on the site count and its own ends alone.
+ * host_out is written only on success; count == 0 succeeds without a launch. */
+#define PLLGPU_QUARTET_TIP_CODES 1u
+#define PLLGPU_QUARTET_TIP_PATTERN 2u
+#define PLLGPU_QUARTET_MAX 8192
+typedef struct pllgpu_quartet
+{
+  unsigned int clv[4];
+  int scaler[4];
+  unsigned int matrix[4];
+  unsigned int is_tip[4];
+  unsigned int inner_matrix;
+} pllgpu_quartet_t;
+int pllgpu_quartet_loglikelihoods(pllgpu_ctx_t *ctx, const pllgpu_quartet_t *quartets, unsigned int count,
+                                  const unsigned int *freqs_indices, double *host_out);
+
 /* replaces pll_compute_node_ancestral[_extbuf] (src/likelihood.c:639-823): the marginal state probabilities of
  * the node at edge->parent_clv, [sites][states] unpadded, given the other end edge->child_clv (a CLV, or tip codes
  * with child_is_tip) across edge->matrix. Of `edge`, gather must be 0 and want_persite / device_result / sequence

@@ -603,6 +603,23 @@ __device__ __forceinline__ void dna_combine(const OP &op, int scale_mode, const 
   dna_scale(v, small, mode, sca, scb, sc);
 }
 
+// dna_combine's step from vectors whose matrices have been applied already (a = P_l x_l, b = P_r x_r): the same products
+// (dna_product), the same decision, rescaling and scaler words (dna_scale) - what a caller that pairs the same applied
+// vectors several ways needs (kernels_quartet.h). dna_combine keeps its own loop, matrix and product rate by rate: its
+// callers' register counts were tuned around that interleaving.
+// [K0, K1): the rates to form; the other rows of v are left alone and count as "not small". Anything narrower than all
+// four is meaningful only where rates decide on their own - per-rate scaling (mode 2) or no scaling (mode 0): there the
+// words of the windows add up to the words of the whole, and a caller can finish one rate before it forms the next.
+template <int K0 = 0, int K1 = 4>
+__device__ __forceinline__ void dna_join(int mode, const double (&a)[4][4], uint4 sca, const double (&b)[4][4], uint4 scb, double (&v)[4][4],
+                                         uint4 &sc)
+{
+  bool small[4] = {false, false, false, false};
+#pragma unroll
+  for (int k = K0; k < K1; ++k) small[k] = dna_product(v[k], a[k], b[k]);
+  dna_scale(v, small, mode, sca, scb, sc);
+}
+
 // the 0/1 rows of a tip child (the same for every rate)
 __device__ __forceinline__ void dna_tip_rows(double (&x)[4][4], unsigned code)
 {

@@ -32,6 +32,7 @@
 #include "kernels_parsimony.h"
 #include "kernels_insertion.h"
 #include "kernels_placement.h"
+#include "kernels_quartet.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
@@ -3092,6 +3093,143 @@ extern "C" int pllgpu_placement_loglikelihoods(pllgpu_ctx_t *c, const unsigned *
   // one copy back for the whole matrix, one wait
   HIP_TRY(copy_down(c, host_out, c->ins_results.p, (size_t)queries * count * sizeof(double)));
   if (c->defer_down) HIP_TRY(stream_wait(c));
+  return 0;
+}
+
+// ---- batched NNI scores (kernels_quartet.h) ------------------------------------------------------------------
+// The cutting rule of pllgpu_quartet_loglikelihoods (include/pll_amd_device.h states it)
+constexpr unsigned kQuartetMax = 8192; // 1.1 MB of descriptors: one piece of the pinned block
+static_assert(kQuartetMax == PLLGPU_QUARTET_MAX && kQuartetMax * sizeof(QuartetDesc) <= kRingMax, "include/pll_amd_device.h states the cutting rule");
+
+// one launch for quartets [first, first + n): descriptors up through the pinned block, the kernel of the shape
+static int launch_quartets(pllgpu_ctx *c, DevEdge e, const pllgpu_quartet_t *quartets, unsigned first, unsigned n, unsigned count)
+{
+  const size_t bytes = (size_t)n * sizeof(QuartetDesc);
+  unsigned char *dev = nullptr;
+  QuartetDesc *host = reinterpret_cast<QuartetDesc *>(stage_take(c, bytes, &dev));
+  std::vector<QuartetDesc> pageable;
+  if (!host)
+  {
+    pageable.resize(n);
+    host = pageable.data();
+  }
+  for (unsigned i = 0; i < n; ++i)
+  {
+    const pllgpu_quartet_t &q = quartets[first + i];
+    QuartetDesc &d = host[i];
+    d.tt_rule = 0u;
+    d.pad_ = 0u;
+    for (unsigned x = 0; x < 4; ++x)
+    {
+      const bool tip = (q.is_tip[x] & PLLGPU_QUARTET_TIP_CODES) != 0;
+      if (int rc = end_in_hbm(c, q.clv[x], tip ? -1 : q.scaler[x], tip, d.end[x].clv, d.end[x].tip, d.end[x].scaler)) return rc;
+      d.end[x].mat = c->pmat.p + (size_t)q.matrix[x] * c->pm_stride;
+      if (tip && (q.is_tip[x] & PLLGPU_QUARTET_TIP_PATTERN)) d.tt_rule |= 1u << x;
+    }
+    d.inner = c->pmat.p + (size_t)q.inner_matrix * c->pm_stride;
+  }
+  HIP_TRY(hipMemcpyAsync(c->ins_cands.p, host, bytes, hipMemcpyHostToDevice, c->stream));
+  const QuartetDesc *dq = reinterpret_cast<const QuartetDesc *>(c->ins_cands.p);
+  e.result = c->ins_results.p + first; // [arrangement][quartet of the call]
+  // launch_insertions' tile walk, unchanged: the order of every sum follows from the site count alone
+  const unsigned tiles = (c->geo.sites + 63) / 64, max_blocks = 1024;
+  if (c->dna_fast)
+  {
+    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
+    const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
+    if (c->gg.scale_mode == 2)
+      hipLaunchKernelGGL((k_quartet_dna<2>), dim3(blocks, n), dim3(256), 0, c->stream, e, dq, count, tpw);
+    else
+      hipLaunchKernelGGL((k_quartet_dna<1>), dim3(blocks, n), dim3(256), 0, c->stream, e, dq, count, tpw);
+  }
+  else
+  {
+    const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
+    const unsigned blocks = (tiles + tpb - 1) / tpb;
+    const unsigned nw = std::min(c->gg.R, 4u);
+    const size_t node_bytes = (size_t)c->gg.R * c->gg.S * 64u * sizeof(double);
+    // both nodes of an arrangement in LDS, or (recompute path) one rate of the second node per wave
+    const unsigned keep = 2 * node_bytes <= kInsLdsMax ? 1u : 0u;
+    const size_t lds = keep ? 2 * node_bytes : (size_t)nw * c->gg.S * 64u * sizeof(double);
+    const unsigned long long *tm = tipmap_ptr(c);
+    with_ich(c->ich, [&](auto ICH) {
+      raise_lds_limit(reinterpret_cast<const void *>(&k_quartet_tiled<ICH()>), c->device, lds);
+      hipLaunchKernelGGL((k_quartet_tiled<ICH()>), dim3(blocks, n), dim3(64u * nw), lds, c->stream, e, dq, c->gg, tm, count, tpb, keep);
+    });
+  }
+  ++c->last_launches;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pllgpu_quartet_loglikelihoods(pllgpu_ctx_t *c, const pllgpu_quartet_t *quartets, unsigned count, const unsigned *freqs_indices,
+                                             double *host_out)
+{
+  CHECK_CTX_KEEP(c);
+  const pllgpu_geometry_t &g = c->geo;
+  c->last_launches = 0;
+  if (!count) return 0;
+  // everything that needs no device state, for the whole list, before held work is touched
+  if (!quartets || !host_out || !freqs_indices) return fail(PLLGPU_EINVAL, "quartet log-likelihoods: null argument");
+  if (g.sites == 0 || g.sites != g.sites_alloc) return fail(PLLGPU_EUNSUPPORTED, "quartet log-likelihoods with ascertainment-bias entries");
+  for (unsigned k = 0; k < g.rate_cats; ++k)
+    if (freqs_indices[k] >= g.rate_matrices) return fail(PLLGPU_EINVAL, "freqs_indices[%u] = %u out of range", k, freqs_indices[k]);
+  for (unsigned i = 0; i < count; ++i)
+  {
+    const pllgpu_quartet_t &q = quartets[i];
+    for (unsigned x = 0; x < 4; ++x)
+    {
+      if (q.clv[x] >= g.nodes || q.matrix[x] >= g.prob_matrices || q.scaler[x] >= (int)g.scale_buffers)
+        return fail(PLLGPU_EINVAL, "quartet %u: end %u references an index out of range", i, x);
+      if (q.is_tip[x] && (!(q.is_tip[x] & PLLGPU_QUARTET_TIP_CODES) || q.clv[x] >= g.tips))
+        return fail(PLLGPU_EINVAL, "quartet %u: end %u is marked as a tip and is none", i, x);
+    }
+    if (q.inner_matrix >= g.prob_matrices) return fail(PLLGPU_EINVAL, "quartet %u: the inner matrix index is out of range", i);
+  }
+  for (unsigned n = 0; n < g.nodes; ++n)
+    if (c->ids[n] || c->clv_aos[n]) return fail(PLLGPU_EUNSUPPORTED, "quartet log-likelihoods over class-compressed CLVs");
+  // whatever pllgpu_update_partials holds back goes out as ordinary launches: a quartet may name what it produces
+  if (HOLDS_WORK(c) || !c->pending.empty())
+    if (int rc = flush_deferred(c)) return rc;
+
+  DevEdge e;
+  memset(&e, 0, sizeof e);
+  if (int rc = fill_edge_model(c, e, freqs_indices)) return rc;
+
+  const unsigned tiles = (g.sites + 63) / 64, max_blocks = 1024;
+  unsigned blocks;
+  if (c->dna_fast)
+  {
+    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
+    blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
+  }
+  else
+  {
+    const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
+    blocks = (tiles + tpb - 1) / tpb;
+  }
+  const unsigned per_launch = (unsigned)std::min<size_t>(std::min(count, kQuartetMax), std::max<size_t>(1, kInsMaxSlots / ((size_t)3 * blocks)));
+  {
+    ScratchEpoch scratch_epoch_;
+    if (c->ins_partials.ensure((size_t)3 * per_launch * blocks) || c->ins_results.ensure((size_t)3 * count) ||
+        c->ins_cands.ensure((size_t)per_launch * sizeof(QuartetDesc)))
+      return PLLGPU_ENOMEM;
+    if (c->ins_tickets.cap < (size_t)3 * per_launch)
+    {
+      if (c->ins_tickets.ensure((size_t)3 * per_launch)) return PLLGPU_ENOMEM;
+      HIP_TRY(hipMemsetAsync(c->ins_tickets.p, 0, c->ins_tickets.cap * sizeof(unsigned), c->stream));
+    }
+  }
+  e.block_sums = c->ins_partials.p;
+  e.counter = c->ins_tickets.p;
+  for (unsigned first = 0; first < count; first += per_launch)
+    if (int rc = launch_quartets(c, e, quartets, first, std::min(per_launch, count - first), count)) return rc;
+  // one copy back for all values, one wait; the kernels leave [arrangement][quartet], the caller gets [quartet][3]
+  std::vector<double> rows((size_t)3 * count);
+  HIP_TRY(copy_down(c, rows.data(), c->ins_results.p, rows.size() * sizeof(double)));
+  if (c->defer_down) HIP_TRY(stream_wait(c));
+  for (unsigned i = 0; i < count; ++i)
+    for (unsigned a = 0; a < 3; ++a) host_out[(size_t)3 * i + a] = rows[(size_t)a * count + i];
   return 0;
 }
 

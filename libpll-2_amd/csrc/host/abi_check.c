@@ -102,6 +102,12 @@ AT(pll_gpu_insertion_t, child1_matrix_index, 8);
 AT(pll_gpu_insertion_t, child2_clv_index, 12);
 AT(pll_gpu_insertion_t, child2_scaler_index, 16);
 AT(pll_gpu_insertion_t, child2_matrix_index, 20);
+/* ... and one quartet of pll_gpu_quartet_loglikelihoods */
+_Static_assert(sizeof(pll_gpu_quartet_t) == 52, "pll_gpu_quartet_t size");
+AT(pll_gpu_quartet_t, clv_index, 0);
+AT(pll_gpu_quartet_t, scaler_index, 16);
+AT(pll_gpu_quartet_t, matrix_index, 32);
+AT(pll_gpu_quartet_t, inner_matrix_index, 48);
 
 /* the extension block must start 8-byte aligned directly behind the public struct */
 _Static_assert(sizeof(pll_partition_t) % 8 == 0, "extension block alignment");

@@ -1,0 +1,137 @@
+/* quartet.c - pll_gpu_quartet_loglikelihoods: the log-likelihoods of all three pairings of the four subtrees around an
+ * inner edge, for `count` quartets in one call: what ranking the NNI neighbourhood of a tree asks.
+ *
+ * lnl[3 i + a] is what the reference returns for pll_update_partials with the two operations {tmp1, s1, x, y} and
+ * {tmp2, s2, z, w} of arrangement a (src/partials.c:237-291) followed by pll_compute_edge_loglikelihood(tmp1, s1, tmp2,
+ * s2, inner_matrix_index, ...) (src/likelihood.c:586-636) - but neither tmp exists: both nodes live in the kernel's
+ * registers or LDS (csrc/hip/kernels_quartet.h) and nothing in the partition is written.
+ *
+ * This file, as insertion.c for its call: validation of the whole list before anything is flushed or launched, the
+ * refusals, which ends the device reads as tip codes, the flushes (model, one matrix span, every named CLV and scaler
+ * once), the error convention. */
+#include "pll_internal.h"
+
+static const char *const who = "pll_gpu_quartet_loglikelihoods";
+
+static int fail_quartet(void)
+{
+  fprintf(stderr, "libpll_amd: %s: [%d] %s\n", who, pll_errno, pll_errmsg);
+  return PLL_FAILURE;
+}
+
+static int end_in_range(const pll_partition_t *p, unsigned int clv, int scaler, unsigned int matrix)
+{
+  return clv < p->nodes && matrix < p->prob_matrices && scaler >= PLL_SCALE_BUFFER_NONE && scaler < (int)p->scale_buffers;
+}
+
+/* the CLV (or tip codes) and scaler of one end on the device, each index once per call */
+static int prepare_once(pll_partition_t *p, pll_amd_ext_t *x, unsigned char *seen_clv, unsigned char *seen_scaler, unsigned int clv, int scaler)
+{
+  const int wants_scaler = scaler >= 0 && !pll_tip_by_codes(p, clv);
+  if (seen_clv[clv] && !(wants_scaler && !seen_scaler[scaler])) return 1;
+  seen_clv[clv] = 1;
+  if (wants_scaler) seen_scaler[scaler] = 1;
+  return pll_prepare_end(p, x, clv, scaler);
+}
+
+int pll_gpu_quartet_loglikelihoods(pll_partition_t *p, const pll_gpu_quartet_t *quartets, unsigned int count,
+                                   const unsigned int *freqs_indices, double *lnl)
+{
+  unsigned int i, k, e;
+  if (!p)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
+    return fail_quartet();
+  }
+  if (!count) return PLL_SUCCESS;
+  if (!quartets || !lnl || !freqs_indices)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: quartets, lnl or freqs_indices is NULL", who);
+    return fail_quartet();
+  }
+  for (i = 0; i < count; ++i)
+  {
+    const pll_gpu_quartet_t *q = &quartets[i];
+    int ok = q->inner_matrix_index < p->prob_matrices;
+    for (e = 0; e < 4; ++e) ok = ok && end_in_range(p, q->clv_index[e], q->scaler_index[e], q->matrix_index[e]);
+    if (!ok)
+    {
+      pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: quartet %u has an index out of range", who, i);
+      return fail_quartet();
+    }
+  }
+  for (k = 0; k < p->rate_cats; ++k)
+    if (freqs_indices[k] >= p->rate_matrices)
+    {
+      pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: freqs_indices[%u] out of range", who, k);
+      return fail_quartet();
+    }
+  if (pll_repeats_enabled(p))
+  {
+    /* the two nodes have no class map */
+    pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: PLL_ATTRIB_SITE_REPEATS partitions are not supported", who);
+    return fail_quartet();
+  }
+  if (p->attributes & PLL_ATTRIB_AB_MASK)
+  {
+    pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: the ascertainment-bias correction needs pll_compute_edge_loglikelihood", who);
+    return fail_quartet();
+  }
+  pll_amd_ext_t *x = pll_ext(p);
+  if (!x || !x->ctx)
+  {
+    pll_set_error(PLL_ERROR_GPU_UNAVAILABLE, "%s: no MI355X context behind this partition; this library has no CPU path", who);
+    return fail_quartet();
+  }
+
+  /* inputs current on the device: the model, one span over every named matrix, every named end once */
+  unsigned int lo = quartets[0].inner_matrix_index, hi = lo;
+  for (i = 0; i < count; ++i)
+    for (e = 0; e < 5; ++e)
+    {
+      const unsigned int m = e < 4 ? quartets[i].matrix_index[e] : quartets[i].inner_matrix_index;
+      if (m < lo) lo = m;
+      if (m > hi) hi = m;
+    }
+  unsigned char *seen = (unsigned char *)calloc((size_t)p->nodes + p->scale_buffers + 1, 1);
+  pllgpu_quartet_t *dev = (pllgpu_quartet_t *)malloc(sizeof(pllgpu_quartet_t) * count);
+  if (!seen || !dev)
+  {
+    free(seen);
+    free(dev);
+    pll_set_error(PLL_ERROR_MEM_ALLOC, "%s: out of memory", who);
+    return fail_quartet();
+  }
+  unsigned char *seen_scaler = seen + p->nodes;
+  /* a pair of two tips takes no scaling decision where the reference reads both with its tip kernels */
+  const unsigned int tip_mark = PLLGPU_QUARTET_TIP_CODES | ((p->attributes & PLL_ATTRIB_PATTERN_TIP) ? PLLGPU_QUARTET_TIP_PATTERN : 0u);
+  int ok = pll_flush_model(p, x) && pll_flush_pmatrix(p, x, lo, hi);
+  for (i = 0; ok && i < count; ++i)
+  {
+    const pll_gpu_quartet_t *q = &quartets[i];
+    pllgpu_quartet_t *d = &dev[i];
+    for (e = 0; ok && e < 4; ++e)
+    {
+      ok = prepare_once(p, x, seen, seen_scaler, q->clv_index[e], q->scaler_index[e]);
+      d->clv[e] = q->clv_index[e];
+      d->scaler[e] = q->scaler_index[e];
+      d->matrix[e] = q->matrix_index[e];
+      d->is_tip[e] = pll_tip_by_codes(p, q->clv_index[e]) ? tip_mark : 0u;
+    }
+    d->inner_matrix = q->inner_matrix_index;
+  }
+  free(seen);
+  if (!ok)
+  {
+    free(dev);
+    return fail_quartet();
+  }
+  const int rc = pllgpu_quartet_loglikelihoods(x->ctx, dev, count, freqs_indices, lnl);
+  free(dev);
+  if (rc != 0)
+  {
+    pll_set_gpu_error(who); /* (prints its own line) */
+    return PLL_FAILURE;
+  }
+  return PLL_SUCCESS;
+}

@@ -147,6 +147,16 @@ class Insertion(C.Structure):
     ]
 
 
+class Quartet(C.Structure):
+    """pll_gpu_quartet_t (include/pll_amd.h): the four ends around one inner edge for pll_gpu_quartet_loglikelihoods"""
+    _fields_ = [
+        ("clv_index", C.c_uint * 4),
+        ("scaler_index", C.c_int * 4),
+        ("matrix_index", C.c_uint * 4),
+        ("inner_matrix_index", C.c_uint),
+    ]
+
+
 class Newton(C.Structure):
     """pll_gpu_newton_t (include/pll_amd.h): options of pll_gpu_optimize_branch_length"""
     _fields_ = [
@@ -175,6 +185,7 @@ NEWTON_MAX_ITERS = 64
 NEWTON_CONVERGED, NEWTON_AT_MIN, NEWTON_AT_MAX, NEWTON_STALLED, NEWTON_MAXITER = 0, 1, 2, 3, 4
 
 assert C.sizeof(Insertion) == 24
+assert C.sizeof(Quartet) == 52 and Quartet.scaler_index.offset == 16 and Quartet.inner_matrix_index.offset == 48
 assert C.sizeof(Newton) == 40 and C.sizeof(NewtonResult) == 40
 assert C.sizeof(Partition) == 232 and C.sizeof(Repeats) == 104 and C.sizeof(Operation) == 32
 assert C.sizeof(Parsimony) == 104 and C.sizeof(ParsBuildOp) == 12
@@ -260,6 +271,7 @@ _GPU_PROTOS = {
         C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.POINTER(Insertion), C.c_uint, c_uint_p, c_double_p]),
     "pll_gpu_placement_loglikelihoods": (
         C.c_int, [PartitionP, c_uint_p, C.c_uint, C.c_uint, C.POINTER(Insertion), C.c_uint, c_uint_p, c_double_p]),
+    "pll_gpu_quartet_loglikelihoods": (C.c_int, [PartitionP, C.POINTER(Quartet), C.c_uint, c_uint_p, c_double_p]),
     "pll_gpu_optimize_branch_length": (
         C.c_int, [PartitionP, C.c_int, C.c_int, c_uint_p, c_double_p, C.POINTER(Newton), C.POINTER(NewtonResult), c_double_p]),
     "pll_gpu_last_algorithmic_bytes": (C.c_double, [PartitionP]),
@@ -369,6 +381,17 @@ def make_insertions(rows):
     for o, r in zip(arr, rows):
         (o.child1_clv_index, o.child1_scaler_index, o.child1_matrix_index,
          o.child2_clv_index, o.child2_scaler_index, o.child2_matrix_index) = [int(x) for x in r]
+    return arr
+
+
+def make_quartets(rows):
+    """rows: iterable of ((clv, scaler, matrix) of e0, ... of e1, ... of e2, ... of e3, inner matrix)."""
+    rows = list(rows)
+    arr = (Quartet * max(len(rows), 1))()
+    for o, r in zip(arr, rows):
+        for k in range(4):
+            o.clv_index[k], o.scaler_index[k], o.matrix_index[k] = [int(x) for x in r[k]]
+        o.inner_matrix_index = int(r[4])
     return arr
 
 

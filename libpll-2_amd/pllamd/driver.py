@@ -125,6 +125,39 @@ def insertion_loglikelihoods_per_edge(lib, partition, subtree, candidates, freqs
     return out
 
 
+def quartet_loglikelihoods(lib, partition, quartets, freqs_indices):
+    """pll_gpu_quartet_loglikelihoods: quartets = rows ((clv, scaler, matrix) of e0, of e1, of e2, of e3, inner matrix);
+    a [Q, 3] array from one call, column a = arrangement a: ((e0,e1),(e2,e3)), ((e0,e2),(e1,e3)), ((e0,e3),(e1,e2)).
+    libpll_amd.so only."""
+    rows = list(quartets)
+    out = np.full((len(rows), 3), np.nan)
+    fi = np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+    if not lib.pll_gpu_quartet_loglikelihoods(partition, api.make_quartets(rows), len(rows), api.uptr(fi), api.dptr(out)):
+        raise RuntimeError(f"pll_gpu_quartet_loglikelihoods: [{lib.errno()}] {lib.errmsg()}")
+    return out
+
+
+QUARTET_PAIRS = (((0, 1), (2, 3)), ((0, 2), (1, 3)), ((0, 3), (1, 2)))
+
+
+def quartet_loglikelihoods_per_edge(lib, partition, quartets, freqs_indices, tmp1, tmp2, after_value=None):
+    """the same values the way every libpll offers them: per value one pll_update_partials with two operations into the
+    spare nodes tmp1 / tmp2 = (clv, scaler), then pll_compute_edge_loglikelihood between them over the inner matrix.
+    after_value(i, a, (x, y), (z, w)), if given, runs after each value while both spare nodes still hold it."""
+    fi = np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+    rows = list(quartets)
+    out = np.empty((len(rows), 3))
+    for i, r in enumerate(rows):
+        for a, ((x, y), (z, w)) in enumerate(QUARTET_PAIRS):
+            ops = [(tmp1[0], tmp1[1], r[x][0], r[x][2], r[x][1], r[y][0], r[y][2], r[y][1]),
+                   (tmp2[0], tmp2[1], r[z][0], r[z][2], r[z][1], r[w][0], r[w][2], r[w][1])]
+            lib.pll_update_partials(partition, api.make_ops(ops), 2)
+            out[i, a] = lib.pll_compute_edge_loglikelihood(partition, tmp1[0], tmp1[1], tmp2[0], tmp2[1], int(r[4]), api.uptr(fi), None)
+            if after_value is not None:
+                after_value(i, a, (r[x], r[y]), (r[z], r[w]))
+    return out
+
+
 class Session:
     """A live partition built from a Case (kept open so benches can re-run the hot path)."""
 
