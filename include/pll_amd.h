@@ -170,8 +170,8 @@ typedef struct pll_msa_s
   char **label;
 } pll_msa_t;
 
-/* src/pll.h:468-492; sizeof == 104, offsets asserted in csrc/host/abi_check.c. Only the "fast unweighted parsimony"
- * fields are filled by this library (pll_fastparsimony_init); the weighted (Sankoff) fields stay zero. */
+/* src/pll.h:468-492; sizeof == 104, offsets asserted in csrc/host/abi_check.c. pll_fastparsimony_init fills the "fast
+ * unweighted parsimony" fields and leaves the weighted (Sankoff) ones zero; pll_parsimony_create does the opposite. */
 typedef struct pll_parsimony_s
 {
   unsigned int tips;
@@ -189,8 +189,8 @@ typedef struct pll_parsimony_s
   unsigned int score_buffers;
   unsigned int ancestral_buffers;
   double *score_matrix;
-  double **sbuffer;
-  unsigned int **anc_states;
+  double **sbuffer;            /* host mirror of the device score buffers, see "weighted parsimony" below */
+  unsigned int **anc_states;   /* the result of pll_parsimony_reconstruct */
 } pll_parsimony_t;
 
 /* src/pll.h:495-500; three unsigned int, sizeof == 12 */
@@ -200,6 +200,15 @@ typedef struct pll_pars_buildop_s
   unsigned int child1_score_index;
   unsigned int child2_score_index;
 } pll_pars_buildop_t;
+
+/* src/pll.h:502-508; four unsigned int, sizeof == 16 */
+typedef struct pll_pars_recop_s
+{
+  unsigned int node_score_index;
+  unsigned int node_ancestral_index;
+  unsigned int parent_score_index;
+  unsigned int parent_ancestral_index;
+} pll_pars_recop_t;
 
 /* ---- printers used by the reference's examples and tests (src/pll.h:2590-2600, src/output.c) -- */
 void pll_show_pmatrix(const pll_partition_t *partition, unsigned int index, unsigned int float_precision);
@@ -367,7 +376,8 @@ unsigned int pll_fastparsimony_root_score(const pll_parsimony_t *parsimony, unsi
  * exactly as the reference frees it, the weighted-parsimony buffers included. NULL: nothing. */
 void pll_parsimony_destroy(pll_parsimony_t *parsimony);
 /* New. packedvector[node] and node_cost[node] are a lazily refreshed host mirror in the reference's layout: this
- * downloads one node (node < 0: all). Same contract as pll_gpu_sync_clv. */
+ * downloads one node (node < 0: all). Same contract as pll_gpu_sync_clv. For a weighted structure: sbuffer[node] and
+ * anc_states[node] (see "weighted parsimony" below). */
 int pll_gpu_sync_parsimony(pll_parsimony_t *parsimony, int node);
 /* New. scores[i] = pll_fastparsimony_edge_score(parsimony, pairs[2i], pairs[2i+1]) for i < count: one launch (the pairs
  * on a grid axis) and one copy back. PLL_SUCCESS / PLL_FAILURE + pll_errno; nothing is written on failure. */
@@ -382,10 +392,74 @@ int pll_gpu_fastparsimony_edge_scores(const pll_parsimony_t *parsimony, const un
  * but the scores; one launch and one copy back for all edges. */
 int pll_gpu_fastparsimony_insertion_scores(const pll_parsimony_t *parsimony, unsigned int node, const unsigned int *edges,
                                            unsigned int count, unsigned int *scores);
-/* kernel launches of the last pll_fastparsimony_* / pll_gpu_fastparsimony_* call on the structure */
+/* kernel launches of the last pll_fastparsimony_* / pll_gpu_fastparsimony_* call on the structure - or, for a weighted
+ * structure, of the last pll_parsimony_build / score / reconstruct / pll_gpu_parsimony_insertion_scores call (the
+ * transposing launch that carries stale mirrors up is not counted) */
 unsigned int pll_gpu_fastparsimony_last_launch_count(const pll_parsimony_t *parsimony);
-/* wait for everything enqueued on the structure's stream */
+/* wait for everything enqueued on the structure's stream (either kind) */
 int pll_gpu_synchronize_parsimony(pll_parsimony_t *parsimony);
+
+/* ---- weighted (Sankoff) parsimony (src/pll.h:2535-2559; src/parsimony.c:24-67, :117-383) ----------------------------
+ * The cost of a tree under a states x states matrix of substitution costs, and the ancestral characters that attain it
+ * (examples/parsimony/npr-pars.c). Score buffers, ancestral buffers and the matrix live in HBM; the arithmetic is
+ * binary64 add and min, every min over the same sums as in the reference, so every score buffer carries the reference's
+ * bits. A fast-parsimony structure handed to one of these calls, or a weighted one handed to a pll_fastparsimony_* call,
+ * is refused with PLL_ERROR_PARAM_INVALID.
+ *
+ * Failure convention (the reference has none): pll_errno is PLL_ERROR_PARAM_INVALID (a structure this library did not
+ * create, a NULL argument, an index out of range - a score index must be < tips + score_buffers, an ancestral index in
+ * [tips, tips + ancestral_buffers); the whole list is checked before anything is uploaded or launched),
+ * PLL_ERROR_GPU_UNAVAILABLE (a host-only structure) or PLL_ERROR_GPU_RUNTIME. A score is then -INFINITY, a
+ * reconstruction writes nothing.
+ *
+ * Mirror contract: sbuffer[i] is a lazily refreshed host mirror in the reference's [site][state] layout.
+ * pll_set_parsimony_sequence writes it and marks it stale on the device; every stale buffer goes up before the next
+ * launch, all of them in one copy. What a build computes stays on the device until pll_gpu_sync_parsimony(parsimony, i)
+ * (i < 0: everything) downloads score buffer i and ancestral buffer i, or after every build under
+ * PLL_AMD_EAGER_MIRROR=1 (the parents of the list; examples/parsimony/npr-pars.c:243 reads sbuffer raw). A caller that
+ * writes sbuffer[i] itself says so with pll_gpu_parsimony_invalidate(parsimony, i): the host copy is then the newer one.
+ * anc_states[] needs no sync after pll_parsimony_reconstruct.
+ *
+ * pll_parsimony_create (src/pll.h:2540, src/parsimony.c:117-202): the host fields are exactly the reference's - the
+ * parameters, a private copy of the matrix, sbuffer[0 .. tips + score_buffers) of sites * states zeroed doubles,
+ * anc_states[tips .. tips + ancestral_buffers) of `sites` zeroed words (entries below `tips` NULL), every
+ * fast-parsimony field zero. Deliberate differences: states outside 1..64 (pll_state_t has 64 bits), tips == 0,
+ * sites == 0 or a NULL matrix give NULL with PLL_ERROR_PARAM_INVALID. The structure owns a device record (all buffers,
+ * the matrix, a stream of its own) in the side table of the fast structures. Under PLL_AMD_HOST_ONLY=1 the host fields
+ * are filled and no device is touched; without a device and without that switch: NULL, PLL_ERROR_GPU_UNAVAILABLE. */
+pll_parsimony_t *pll_parsimony_create(unsigned int tips, unsigned int states, unsigned int sites, const double *score_matrix,
+                                      unsigned int score_buffers, unsigned int ancestral_buffers);
+/* src/pll.h:2535, src/parsimony.c:24-67: entry j of a site is 0 where bit j of the mapped character is set and
+ * `largest matrix entry + 1` elsewhere. A character that maps to 0: PLL_FAILURE, PLL_ERROR_TIPDATA_ILLEGALSTATE, the
+ * reference's message in pll_errmsg and on stdout. tip_index >= tips + score_buffers: PLL_ERROR_PARAM_INVALID. */
+int pll_set_parsimony_sequence(pll_parsimony_t *parsimony, unsigned int tip_index, const pll_state_t *map, const char *sequence);
+/* src/pll.h:2547, src/parsimony.c:204-284. The result equals executing the list in order; dependency levels as for
+ * pll_fastparsimony_update_vectors, every level ONE launch. Returns pll_parsimony_score of the last operation's parent.
+ * Synchronous. count == 0 or a NULL list is refused. */
+double pll_parsimony_build(pll_parsimony_t *parsimony, const pll_pars_buildop_t *operations, unsigned int count);
+/* src/pll.h:2556, src/parsimony.c:286-307: the sum over the sites of the smallest entry. One launch and 8 bytes back; the
+ * sum is formed in an order that depends on the site count alone (same bits from run to run; the reference adds site by
+ * site, so the two agree to sites * 2^-52 relative, exactly where every term is an integer). */
+double pll_parsimony_score(pll_parsimony_t *parsimony, unsigned int score_buffer_index);
+/* src/pll.h:2551, src/parsimony.c:309-383, the reference's rule exactly: operation 0 gives its node the character of the
+ * first minimal state; a later one keeps its parent's character where min + 1 > the parent's score at the parent's
+ * character, and takes the character of its own first minimum otherwise. One launch per dependency level (an operation
+ * depends on the earlier one that wrote its parent's ancestral buffer; a parent assigned by an earlier call is simply
+ * read). anc_states[] of every node the list names is copied back before the call returns, in one copy. A map in which
+ * some state has no single-bit character makes the reference index with the trailing-zero count of 0; here such a site
+ * reads state 0 - its value is unspecified, nothing is read out of bounds. */
+void pll_parsimony_reconstruct(pll_parsimony_t *parsimony, const pll_state_t *map, const pll_pars_recop_t *operations,
+                               unsigned int count);
+/* New. The caller has written sbuffer[index] directly: it goes up before the next launch. */
+int pll_gpu_parsimony_invalidate(pll_parsimony_t *parsimony, unsigned int index);
+/* New, the weighted twin of pll_gpu_fastparsimony_insertion_scores. scores[i] is BY DEFINITION what the reference returns
+ * for pll_parsimony_build(parsimony, {{t1, edges[2i], edges[2i+1]}, {t2, t1, node}}, 2) with two spare buffers t1, t2.
+ * No spare buffer is needed - both nodes live in registers and LDS - and nothing is written but the scores. One launch
+ * for all candidates (long lists are cut: pllgpu_spars_insertion_scores in pll_amd_device.h) and one copy back. Every
+ * scores[i] has the same bits alone, among others, in any list order and from run to run. PLL_SUCCESS, or PLL_FAILURE
+ * with pll_errno and scores untouched. count == 0 succeeds without a launch. */
+int pll_gpu_parsimony_insertion_scores(const pll_parsimony_t *parsimony, unsigned int node, const unsigned int *edges,
+                                       unsigned int count, double *scores);
 
 /* ---- the flat core seam of the hot path (src/pll.h:1049-1177 and :1295-1414; bodies in
  * src/core_partials.c:48-1210, src/core_likelihood.c:24-1496) ----------------------------------

@@ -405,6 +405,58 @@ int pllgpu_pars_synchronize(pllgpu_pars_t *pars);
 /* kernel launches of the last update / scores call on the record */
 unsigned int pllgpu_pars_last_launch_count(const pllgpu_pars_t *pars);
 
+/* ---- weighted (Sankoff) parsimony (src/parsimony.c:117-383; csrc/hip/kernels_sankoff.h) -------------------------
+ * The record behind a structure made by pll_parsimony_create: a device (device < 0: PLL_AMD_DEVICE or the calling
+ * thread's current one, as pllgpu_create picks it), a stream, `buffers` score buffers, `ancestral_buffers` ancestral
+ * buffers and the states x states cost matrix. Score buffers live in the tiled sites-contiguous layout of the CLVs - a
+ * tile of 64 sites as [state][64 lanes] doubles - and start as zero, like the ancestral buffers. states 1..64. Score
+ * indices are checked against `buffers`, ancestral indices (counted from the first ancestral buffer) against
+ * `ancestral_buffers`, before anything is launched. */
+typedef struct pllgpu_spars pllgpu_spars_t;
+pllgpu_spars_t *pllgpu_spars_create(int device, unsigned int states, unsigned int sites, unsigned int buffers,
+                                    unsigned int ancestral_buffers, const double *matrix);
+void pllgpu_spars_destroy(pllgpu_spars_t *spars);
+/* host[indices[i]] = buffer indices[i] in the reference's layout ([site][state], src/parsimony.c:155-175), i < count:
+ * one copy for all of them and one transposing launch (k_sankoff_upload / k_sankoff_download; not counted by
+ * pllgpu_spars_last_launch_count). Both synchronise. */
+int pllgpu_spars_upload(pllgpu_spars_t *spars, const unsigned int *indices, unsigned int count, double *const *host);
+int pllgpu_spars_download(pllgpu_spars_t *spars, const unsigned int *indices, unsigned int count, double *const *host);
+/* ancestral buffers [first, first + count) in one copy; host[i] (indexed like the buffers, NULL: skip) receives `sites`
+ * words. Synchronises. */
+int pllgpu_spars_download_ancestral(pllgpu_spars_t *spars, unsigned int first, unsigned int count, unsigned int *const *host);
+/* replaces pll_parsimony_build (src/parsimony.c:204-284) for a list sorted by level, the ops of one level mutually
+ * independent (an op may name its parent as one of its children): one launch per level, then the score of
+ * score_index (below). Synchronises. */
+int pllgpu_spars_build(pllgpu_spars_t *spars, const pllgpu_pars_op_t *ops, unsigned int count, unsigned int score_index,
+                       double *score_host);
+/* replaces pll_parsimony_score (src/parsimony.c:286-307): one launch, 8 bytes back. min(tiles, 1024) workgroups of one
+ * wave walk the site tiles with that stride; their partial sums are added in index order by the one that arrives last,
+ * so the bits of the result depend on the site count alone. Synchronises. */
+int pllgpu_spars_score(pllgpu_spars_t *spars, unsigned int index, double *score_host);
+/* replaces pll_parsimony_reconstruct (src/parsimony.c:309-383) for a list sorted by level: one launch per level.
+ * root != 0: the operation reads no parent (the first of a call). tables: 256 words state -> character (the reference's
+ * revmap), then 256 words character -> state, each < states. Synchronises. */
+typedef struct pllgpu_spars_recop
+{
+  unsigned int node_score, node_ancestral, parent_score, parent_ancestral;
+  unsigned int root;
+  unsigned int level;
+} pllgpu_spars_recop_t;
+int pllgpu_spars_reconstruct(pllgpu_spars_t *spars, const pllgpu_spars_recop_t *ops, unsigned int count, const unsigned int *tables);
+/* scores_host[i] = what pll_parsimony_build returns for {{t1, edges[2i], edges[2i+1]}, {t2, t1, node}}; t1 stays in LDS,
+ * t2 is never formed, nothing is written but the scores. One launch for up to min(4096, 65536 / w) candidates, w =
+ * min(tiles, 64) the workgroups a candidate gets (every candidate owns w partial-sum slots and a ticket; 65536 slots and
+ * 4096 tickets exist); a longer list is cut into launches of that many, in list order. A candidate's sum is formed by its
+ * own workgroups in slot order: the same bits alone, among others and in any list order. One copy back; synchronises;
+ * scores_host is written only on success. */
+int pllgpu_spars_insertion_scores(pllgpu_spars_t *spars, unsigned int node, const unsigned int *edges, unsigned int count,
+                                  double *scores_host);
+int pllgpu_spars_synchronize(pllgpu_spars_t *spars);
+/* kernel launches of the last build / score / reconstruct / insertion call on the record */
+unsigned int pllgpu_spars_last_launch_count(const pllgpu_spars_t *spars);
+/* a call begins: whatever fails before its first launch leaves the count at zero */
+void pllgpu_spars_clear_launch_count(pllgpu_spars_t *spars);
+
 /* ---- the exchange of a site-sharded run (pll_gpu_edge_loglikelihood_allreduce) ---------------- */
 /* make the context's device the calling thread's current one while a collective library enqueues on the context's
  * stream from the host side of this boundary; *previous (-1: nothing changed) goes to pllgpu_leave_device afterwards */

@@ -30,6 +30,7 @@
 #include "kernels_repeats.h"
 #include "kernels_ancestral.h"
 #include "kernels_parsimony.h"
+#include "kernels_sankoff.h"
 #include "kernels_insertion.h"
 #include "kernels_placement.h"
 #include "kernels_quartet.h"
@@ -558,13 +559,15 @@ static inline size_t clv_elems(const pllgpu_ctx *c, unsigned entries)
   return (size_t)entries * c->span;
 }
 
-extern "C" pllgpu_ctx_t *pllgpu_create(const pllgpu_geometry_t *geo, int device)
+// the device a new context or parsimony record lands on (device < 0: PLL_AMD_DEVICE, or the calling thread's current
+// device), checked to be a gfx950; -1 with the error set
+static int pick_device(int device)
 {
   int n = pllgpu_device_count();
   if (n <= 0)
   {
     fail(PLLGPU_ENODEVICE, "no HIP device visible (hipGetDeviceCount = %d)", n);
-    return nullptr;
+    return -1;
   }
   if (device < 0)
   {
@@ -583,20 +586,27 @@ extern "C" pllgpu_ctx_t *pllgpu_create(const pllgpu_geometry_t *geo, int device)
   if (device >= n)
   {
     fail(PLLGPU_EINVAL, "device %d out of range (%d visible)", device, n);
-    return nullptr;
+    return -1;
   }
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) != hipSuccess)
   {
     fail(PLLGPU_ENODEVICE, "hipGetDeviceProperties(%d) failed", device);
-    return nullptr;
+    return -1;
   }
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
   {
     fail(PLLGPU_ENODEVICE, "device %d is %s; this library carries gfx950 (MI355X) code only", device,
          prop.gcnArchName);
-    return nullptr;
+    return -1;
   }
+  return device;
+}
+
+extern "C" pllgpu_ctx_t *pllgpu_create(const pllgpu_geometry_t *geo, int device)
+{
+  device = pick_device(device);
+  if (device < 0) return nullptr;
   if (geo->states < 2 || geo->states > 64 || geo->rate_cats < 1 || geo->rate_cats > (unsigned)kMaxRates)
   {
     fail(PLLGPU_EUNSUPPORTED, "unsupported shape: states=%u (2..64) rate_cats=%u (1..%d)", geo->states,
@@ -4419,25 +4429,30 @@ extern "C" int pllgpu_repeats_classes(pllgpu_ctx_t *c, const pllgpu_repop_t *ops
 // ---- fast parsimony (src/fast_parsimony.c): kernels_parsimony.h --------------------------------------------------
 // A record of its own, not a pllgpu_ctx: the reference's pll_parsimony_t is independent of the partition it was made
 // from, so it owns its stream and ONE device block: [nodes][states][stride] vector words, then the node costs.
-struct pllgpu_pars
+// what both kinds of parsimony record (fast: pllgpu_pars, weighted: pllgpu_spars) own to make a call
+struct ParsCall
 {
   int device = 0;
   hipStream_t stream = nullptr;
-  unsigned states = 0, words = 0, stride = 0, nodes = 0;
-  unsigned *block = nullptr;  // vectors, then costs
-  unsigned *cost = nullptr;   // block + nodes * states * stride
   unsigned *args = nullptr;   // per-call arguments and results: accumulators or scores, then ops / pairs
   unsigned char *args_host = nullptr; // pinned: where a call writes its ops / pairs before they are copied up
   size_t args_bytes = 0;
   hipEvent_t args_copied = nullptr;   // the last copy out of args_host has been made
   unsigned last_launches = 0;
+};
+
+struct pllgpu_pars : ParsCall
+{
+  unsigned states = 0, words = 0, stride = 0, nodes = 0;
+  unsigned *block = nullptr;  // vectors, then costs
+  unsigned *cost = nullptr;   // block + nodes * states * stride
   size_t node_words() const { return (size_t)states * stride; }
 };
 
 struct ParsScope // the record's device for the duration of an entry point, the caller's afterwards
 {
   int prev = -1, rc = 0;
-  explicit ParsScope(const pllgpu_pars *p)
+  explicit ParsScope(const ParsCall *p)
   {
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
     if (prev != p->device)
@@ -4456,7 +4471,7 @@ struct ParsScope // the record's device for the duration of an entry point, the 
   ParsScope pars_scope_(p);                                        \
   if (pars_scope_.rc) return pars_scope_.rc
 
-static int pars_args(pllgpu_pars *p, size_t bytes)
+static int pars_args(ParsCall *p, size_t bytes)
 {
   if (bytes <= p->args_bytes) return 0;
   HIP_TRY(hipStreamSynchronize(p->stream)); // whatever still reads the old block
@@ -4474,7 +4489,7 @@ static int pars_args(pllgpu_pars *p, size_t bytes)
 
 // copy `bytes` at args_host + offset to the same offset of the device block, in stream order. The caller has waited for
 // args_copied before writing there: a call that returns early (update) leaves its copy in flight
-static int pars_args_up(pllgpu_pars *p, size_t offset, size_t bytes)
+static int pars_args_up(ParsCall *p, size_t offset, size_t bytes)
 {
   HIP_TRY(hipMemcpyAsync(reinterpret_cast<unsigned char *>(p->args) + offset, p->args_host + offset, bytes, hipMemcpyHostToDevice, p->stream));
   HIP_TRY(hipEventRecord(p->args_copied, p->stream));
@@ -4698,3 +4713,322 @@ extern "C" int pllgpu_pars_synchronize(pllgpu_pars_t *p)
 }
 
 extern "C" unsigned pllgpu_pars_last_launch_count(const pllgpu_pars_t *p) { return p ? p->last_launches : 0; }
+
+// ---- weighted (Sankoff) parsimony (src/parsimony.c): kernels_sankoff.h ---------------------------------------------
+// A record like the one above, for a structure made by pll_parsimony_create: every score buffer in the tiled layout
+// ([tile][state][64 sites] doubles), every ancestral buffer ([tiles * 64] words), and one block of fixed size: the cost
+// matrix with its rows padded to eight doubles, the partial-sum slots, the result word and the tickets of the sums.
+constexpr unsigned kSpMaxCands = 4096;   // candidates of one insertion launch: one ticket each
+constexpr unsigned kSpMaxSlots = 65536;  // partial sums of one launch
+constexpr unsigned kSpScoreBlocks = 1024; // workgroups of a score at most
+constexpr unsigned kSpInsBlocks = 64;     // workgroups per insertion candidate at most
+
+struct pllgpu_spars : ParsCall
+{
+  SpGeo g{};
+  unsigned nbuf = 0, nanc = 0;
+  int fenced = 0;
+  double *buffers = nullptr;
+  unsigned *ancestral = nullptr;
+  double *fixed = nullptr; // matrix, partials, result, tickets
+  double *matrix = nullptr, *partials = nullptr, *result = nullptr;
+  unsigned *tickets = nullptr;
+  double *stage = nullptr; // buffers in the host mirror's form on their way up or down
+  size_t stage_doubles = 0;
+  size_t anc_words() const { return (size_t)g.tiles * kSpLanes; }
+};
+
+// the instantiation that serves a state count (kernels_sankoff.h): fn(SMAX, NCH) as integral constants
+template <class F>
+static void sp_variant(unsigned states, F &&fn)
+{
+  if (states <= 4) fn(pars_int<4>(), pars_int<4>());
+  else if (states <= 8) fn(pars_int<8>(), pars_int<8>());
+  else if (states <= 24) fn(pars_int<24>(), pars_int<8>());
+  else fn(pars_int<64>(), pars_int<8>());
+}
+
+static void spars_free(pllgpu_spars *p)
+{
+  if (p->stream) (void)hipStreamSynchronize(p->stream);
+  if (p->args) (void)hipFree(p->args);
+  if (p->args_host) (void)hipHostFree(p->args_host);
+  if (p->stage) (void)hipFree(p->stage);
+  if (p->buffers) (void)hipFree(p->buffers);
+  if (p->ancestral) (void)hipFree(p->ancestral);
+  if (p->fixed) (void)hipFree(p->fixed);
+  if (p->args_copied) (void)hipEventDestroy(p->args_copied);
+  if (p->stream) (void)hipStreamDestroy(p->stream);
+  delete p;
+}
+
+extern "C" pllgpu_spars_t *pllgpu_spars_create(int device, unsigned states, unsigned sites, unsigned buffers, unsigned ancestral_buffers,
+                                               const double *matrix)
+{
+  if (states < 1 || states > 64 || sites == 0 || buffers == 0 || !matrix)
+  {
+    fail(PLLGPU_EUNSUPPORTED, "weighted parsimony: unsupported shape: states=%u (1..64) sites=%u buffers=%u", states, sites, buffers);
+    return nullptr;
+  }
+  device = pick_device(device);
+  if (device < 0) return nullptr;
+  pllgpu_spars *p = new pllgpu_spars();
+  p->device = device;
+  p->g.states = states;
+  p->g.sp = (states + 7u) & ~7u;
+  p->g.sites = sites;
+  p->g.tiles = (sites + kSpLanes - 1) / kSpLanes;
+  p->g.buf_doubles = (size_t)p->g.tiles * states * kSpLanes;
+  p->nbuf = buffers;
+  p->nanc = ancestral_buffers;
+  const char *fenced = getenv("PLL_AMD_FENCED_HANDOFF");
+  p->fenced = fenced && *fenced && *fenced != '0';
+  ParsScope scope(p);
+  const size_t matrix_doubles = (size_t)states * p->g.sp;
+  const size_t fixed_bytes = (matrix_doubles + kSpMaxSlots + 2) * sizeof(double) + (kSpMaxCands + 2) * sizeof(unsigned);
+  const size_t buf_bytes = (size_t)buffers * p->g.buf_doubles * sizeof(double);
+  const size_t anc_bytes = (size_t)ancestral_buffers * p->anc_words() * sizeof(unsigned);
+  std::vector<double> padded(matrix_doubles, 0.0);
+  for (unsigned k = 0; k < states; ++k) memcpy(&padded[(size_t)k * p->g.sp], matrix + (size_t)k * states, states * sizeof(double));
+  bool ok = scope.rc == 0 && hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) == hipSuccess &&
+            hipEventCreateWithFlags(&p->args_copied, hipEventDisableTiming) == hipSuccess && hipMalloc((void **)&p->fixed, fixed_bytes) == hipSuccess &&
+            hipMalloc((void **)&p->buffers, buf_bytes) == hipSuccess && (!anc_bytes || hipMalloc((void **)&p->ancestral, anc_bytes) == hipSuccess);
+  // score buffers, ancestral buffers and every ticket start as zero, as the reference's calloc leaves them
+  ok = ok && hipMemsetAsync(p->fixed, 0, fixed_bytes, p->stream) == hipSuccess && hipMemsetAsync(p->buffers, 0, buf_bytes, p->stream) == hipSuccess &&
+       (!anc_bytes || hipMemsetAsync(p->ancestral, 0, anc_bytes, p->stream) == hipSuccess) &&
+       hipMemcpyAsync(p->fixed, padded.data(), matrix_doubles * sizeof(double), hipMemcpyHostToDevice, p->stream) == hipSuccess &&
+       hipStreamSynchronize(p->stream) == hipSuccess;
+  if (!ok)
+  {
+    fail(PLLGPU_ENOMEM, "weighted parsimony: cannot set up %zu bytes on device %d: %s", fixed_bytes + buf_bytes + anc_bytes, device,
+         hipGetErrorString(hipGetLastError()));
+    spars_free(p);
+    return nullptr;
+  }
+  p->matrix = p->fixed;
+  p->partials = p->matrix + matrix_doubles;
+  p->result = p->partials + kSpMaxSlots;
+  p->tickets = reinterpret_cast<unsigned *>(p->result + 2);
+  return p;
+}
+
+extern "C" void pllgpu_spars_destroy(pllgpu_spars_t *p)
+{
+  if (!p) return;
+  ParsScope scope(p);
+  spars_free(p);
+}
+
+static int spars_stage(pllgpu_spars *p, size_t doubles)
+{
+  if (doubles <= p->stage_doubles) return 0;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (p->stage) (void)hipFree(p->stage);
+  p->stage = nullptr;
+  p->stage_doubles = 0;
+  HIP_TRY(hipMalloc((void **)&p->stage, doubles * sizeof(double)));
+  p->stage_doubles = doubles;
+  return 0;
+}
+
+// the list of buffers of an upload or a download, on the device
+static int spars_index_list(pllgpu_spars *p, const unsigned *indices, unsigned count, const char *who)
+{
+  for (unsigned i = 0; i < count; ++i)
+    if (indices[i] >= p->nbuf) return fail(PLLGPU_EINVAL, "%s: buffer %u of %u", who, indices[i], p->nbuf);
+  if (int rc = pars_args(p, (size_t)count * sizeof(unsigned))) return rc;
+  HIP_TRY(hipEventSynchronize(p->args_copied));
+  memcpy(p->args_host, indices, (size_t)count * sizeof(unsigned));
+  return pars_args_up(p, 0, (size_t)count * sizeof(unsigned));
+}
+
+extern "C" int pllgpu_spars_upload(pllgpu_spars_t *p, const unsigned *indices, unsigned count, double *const *host)
+{
+  PARS_ENTER(p);
+  if (!count) return 0;
+  if (!indices || !host) return fail(PLLGPU_EINVAL, "weighted parsimony upload: null argument");
+  const size_t per = (size_t)p->g.sites * p->g.states;
+  if (int rc = spars_index_list(p, indices, count, "weighted parsimony upload")) return rc;
+  if (int rc = spars_stage(p, (size_t)count * per)) return rc;
+  // one copy for all of them; the transposition into tiles happens on the device
+  std::vector<double> staged((size_t)count * per);
+  for (unsigned i = 0; i < count; ++i) memcpy(&staged[(size_t)i * per], host[indices[i]], per * sizeof(double));
+  HIP_TRY(hipMemcpyAsync(p->stage, staged.data(), staged.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  for (unsigned first = 0; first < count; first += kSpMaxBlocksY)
+    hipLaunchKernelGGL(k_sankoff_upload, dim3(p->g.tiles, std::min(kSpMaxBlocksY, count - first)), dim3(kSpLanes), 0, p->stream, p->buffers,
+                       p->stage + (size_t)first * per, p->args + first, p->g);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+
+extern "C" int pllgpu_spars_download(pllgpu_spars_t *p, const unsigned *indices, unsigned count, double *const *host)
+{
+  PARS_ENTER(p);
+  if (!count) return 0;
+  if (!indices || !host) return fail(PLLGPU_EINVAL, "weighted parsimony download: null argument");
+  const size_t per = (size_t)p->g.sites * p->g.states;
+  if (int rc = spars_index_list(p, indices, count, "weighted parsimony download")) return rc;
+  if (int rc = spars_stage(p, (size_t)count * per)) return rc;
+  for (unsigned first = 0; first < count; first += kSpMaxBlocksY)
+    hipLaunchKernelGGL(k_sankoff_download, dim3(p->g.tiles, std::min(kSpMaxBlocksY, count - first)), dim3(kSpLanes), 0, p->stream, p->buffers,
+                       p->stage + (size_t)first * per, p->args + first, p->g);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> staged((size_t)count * per);
+  HIP_TRY(hipMemcpyAsync(staged.data(), p->stage, staged.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  for (unsigned i = 0; i < count; ++i) memcpy(host[indices[i]], &staged[(size_t)i * per], per * sizeof(double));
+  return 0;
+}
+
+extern "C" int pllgpu_spars_download_ancestral(pllgpu_spars_t *p, unsigned first, unsigned count, unsigned *const *host)
+{
+  PARS_ENTER(p);
+  if (first + count > p->nanc || first + count < first) return fail(PLLGPU_EINVAL, "weighted parsimony: ancestral buffers %u+%u of %u", first, count, p->nanc);
+  if (!count) return 0;
+  // one copy for the whole span; host[i] == NULL: not wanted
+  std::vector<unsigned> staged((size_t)count * p->anc_words());
+  HIP_TRY(hipMemcpyAsync(staged.data(), p->ancestral + (size_t)first * p->anc_words(), staged.size() * sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  for (unsigned i = 0; i < count; ++i)
+    if (host[first + i]) memcpy(host[first + i], &staged[(size_t)i * p->anc_words()], (size_t)p->g.sites * sizeof(unsigned));
+  return 0;
+}
+
+// the launch and the 8 bytes back of a score; counts into last_launches
+static int spars_score(pllgpu_spars *p, unsigned index, double *score_host)
+{
+  const unsigned blocks = std::min(p->g.tiles, kSpScoreBlocks);
+  hipLaunchKernelGGL(k_sankoff_score, dim3(blocks), dim3(kSpLanes), 0, p->stream, p->buffers, index, p->g, p->partials, p->tickets, p->result, p->fenced);
+  ++p->last_launches;
+  HIP_TRY(hipGetLastError());
+  double score = 0.0;
+  HIP_TRY(hipMemcpyAsync(&score, p->result, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  *score_host = score;
+  return 0;
+}
+
+extern "C" int pllgpu_spars_build(pllgpu_spars_t *p, const pllgpu_pars_op_t *ops, unsigned count, unsigned score_index, double *score_host)
+{
+  PARS_ENTER(p);
+  p->last_launches = 0;
+  if (!count || !ops || !score_host) return fail(PLLGPU_EINVAL, "weighted parsimony build: empty list or null argument");
+  if (score_index >= p->nbuf) return fail(PLLGPU_EINVAL, "weighted parsimony build: buffer %u of %u", score_index, p->nbuf);
+  for (unsigned i = 0; i < count; ++i)
+    if (ops[i].parent >= p->nbuf || ops[i].child1 >= p->nbuf || ops[i].child2 >= p->nbuf || (i && ops[i].level < ops[i - 1].level))
+      return fail(PLLGPU_EINVAL, "weighted parsimony build: op %u out of range or not sorted by level", i);
+  if (int rc = pars_args(p, (size_t)count * sizeof(SpOp))) return rc;
+  HIP_TRY(hipEventSynchronize(p->args_copied));
+  SpOp *hops = reinterpret_cast<SpOp *>(p->args_host);
+  for (unsigned i = 0; i < count; ++i) hops[i] = SpOp{ops[i].parent, ops[i].child1, ops[i].child2};
+  const SpOp *dops = reinterpret_cast<const SpOp *>(p->args);
+  if (int rc = pars_args_up(p, 0, (size_t)count * sizeof(SpOp))) return rc;
+  for (unsigned i = 0; i < count;)
+  {
+    unsigned j = i;
+    while (j < count && ops[j].level == ops[i].level) ++j;
+    const dim3 grid(p->g.tiles, std::min(j - i, kSpMaxBlocksY));
+    sp_variant(p->g.states, [&](auto smax, auto nch) {
+      hipLaunchKernelGGL((k_sankoff_build<decltype(smax)::value, decltype(nch)::value>), grid, dim3(kSpLanes), 0, p->stream, p->buffers, p->matrix, dops + i, j - i, p->g);
+    });
+    ++p->last_launches;
+    i = j;
+  }
+  HIP_TRY(hipGetLastError());
+  return spars_score(p, score_index, score_host);
+}
+
+extern "C" int pllgpu_spars_score(pllgpu_spars_t *p, unsigned index, double *score_host)
+{
+  PARS_ENTER(p);
+  p->last_launches = 0;
+  if (index >= p->nbuf || !score_host) return fail(PLLGPU_EINVAL, "weighted parsimony score: buffer %u of %u", index, p->nbuf);
+  return spars_score(p, index, score_host);
+}
+
+extern "C" int pllgpu_spars_reconstruct(pllgpu_spars_t *p, const pllgpu_spars_recop_t *ops, unsigned count, const unsigned *tables)
+{
+  PARS_ENTER(p);
+  p->last_launches = 0;
+  if (!count) return 0;
+  if (!ops || !tables) return fail(PLLGPU_EINVAL, "weighted parsimony reconstruct: null argument");
+  for (unsigned i = 0; i < count; ++i)
+    if (ops[i].node_score >= p->nbuf || ops[i].parent_score >= p->nbuf || ops[i].node_ancestral >= p->nanc || ops[i].parent_ancestral >= p->nanc ||
+        (i && ops[i].level < ops[i - 1].level))
+      return fail(PLLGPU_EINVAL, "weighted parsimony reconstruct: op %u out of range or not sorted by level", i);
+  for (unsigned i = 0; i < 256; ++i)
+    if (tables[256 + i] >= p->g.states) return fail(PLLGPU_EINVAL, "weighted parsimony reconstruct: character %u has state %u of %u", i, tables[256 + i], p->g.states);
+  const size_t table_bytes = 512 * sizeof(unsigned);
+  if (int rc = pars_args(p, table_bytes + (size_t)count * sizeof(SpRecOp))) return rc;
+  HIP_TRY(hipEventSynchronize(p->args_copied));
+  memcpy(p->args_host, tables, table_bytes);
+  SpRecOp *hops = reinterpret_cast<SpRecOp *>(p->args_host + table_bytes);
+  for (unsigned i = 0; i < count; ++i) hops[i] = SpRecOp{ops[i].node_score, ops[i].node_ancestral, ops[i].parent_score, ops[i].parent_ancestral, ops[i].root ? 1u : 0u};
+  const SpRecOp *dops = reinterpret_cast<const SpRecOp *>(reinterpret_cast<unsigned char *>(p->args) + table_bytes);
+  if (int rc = pars_args_up(p, 0, table_bytes + (size_t)count * sizeof(SpRecOp))) return rc;
+  for (unsigned i = 0; i < count;)
+  {
+    unsigned j = i;
+    while (j < count && ops[j].level == ops[i].level) ++j;
+    hipLaunchKernelGGL(k_sankoff_reconstruct, dim3(p->g.tiles, std::min(j - i, kSpMaxBlocksY)), dim3(kSpLanes), 0, p->stream, p->buffers, p->ancestral, dops + i, j - i,
+                       p->args, p->g);
+    ++p->last_launches;
+    i = j;
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+
+extern "C" int pllgpu_spars_insertion_scores(pllgpu_spars_t *p, unsigned node, const unsigned *edges, unsigned count, double *scores_host)
+{
+  PARS_ENTER(p);
+  p->last_launches = 0;
+  if (node >= p->nbuf) return fail(PLLGPU_EINVAL, "weighted parsimony insertion scores: buffer %u of %u", node, p->nbuf);
+  if (!count) return 0;
+  if (!edges || !scores_host) return fail(PLLGPU_EINVAL, "weighted parsimony insertion scores: null argument");
+  for (unsigned i = 0; i < 2u * count; ++i)
+    if (edges[i] >= p->nbuf) return fail(PLLGPU_EINVAL, "weighted parsimony insertion scores: buffer %u of %u", edges[i], p->nbuf);
+  // arguments of the call in one block: [count] results, then [count] {a, b}
+  const size_t result_bytes = (size_t)count * sizeof(double);
+  if (int rc = pars_args(p, result_bytes + (size_t)count * sizeof(SpPair))) return rc;
+  HIP_TRY(hipEventSynchronize(p->args_copied));
+  memcpy(p->args_host + result_bytes, edges, (size_t)count * sizeof(SpPair));
+  double *results = reinterpret_cast<double *>(p->args);
+  const SpPair *dedges = reinterpret_cast<const SpPair *>(reinterpret_cast<unsigned char *>(p->args) + result_bytes);
+  if (int rc = pars_args_up(p, result_bytes, (size_t)count * sizeof(SpPair))) return rc;
+  // the cut of a long list: a launch carries as many candidates as have a ticket and a full set of slots
+  const unsigned blocks = std::min(p->g.tiles, kSpInsBlocks);
+  const unsigned per_launch = std::min(kSpMaxCands, kSpMaxSlots / blocks);
+  for (unsigned first = 0; first < count; first += per_launch)
+  {
+    const dim3 grid(blocks, std::min(per_launch, count - first));
+    sp_variant(p->g.states, [&](auto smax, auto nch) {
+      hipLaunchKernelGGL((k_sankoff_insertion<decltype(smax)::value, decltype(nch)::value>), grid, dim3(kSpLanes), 0, p->stream, p->buffers, p->matrix, node, dedges + first, p->g,
+                         p->partials, p->tickets, results + first, p->fenced);
+    });
+    ++p->last_launches;
+  }
+  HIP_TRY(hipGetLastError());
+  // one copy back for all candidates, into memory of our own: the caller's array stays untouched on failure
+  std::vector<double> got(count);
+  HIP_TRY(hipMemcpyAsync(got.data(), results, result_bytes, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  memcpy(scores_host, got.data(), result_bytes);
+  return 0;
+}
+
+extern "C" int pllgpu_spars_synchronize(pllgpu_spars_t *p)
+{
+  PARS_ENTER(p);
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+
+extern "C" unsigned pllgpu_spars_last_launch_count(const pllgpu_spars_t *p) { return p ? p->last_launches : 0; }
+
+extern "C" void pllgpu_spars_clear_launch_count(pllgpu_spars_t *p)
+{
+  if (p) p->last_launches = 0;
+}

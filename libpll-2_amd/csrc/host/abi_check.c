@@ -93,6 +93,11 @@ _Static_assert(sizeof(pll_pars_buildop_t) == 12, "pll_pars_buildop_t size");
 AT(pll_pars_buildop_t, parent_score_index, 0);
 AT(pll_pars_buildop_t, child1_score_index, 4);
 AT(pll_pars_buildop_t, child2_score_index, 8);
+_Static_assert(sizeof(pll_pars_recop_t) == 16, "pll_pars_recop_t size");
+AT(pll_pars_recop_t, node_score_index, 0);
+AT(pll_pars_recop_t, node_ancestral_index, 4);
+AT(pll_pars_recop_t, parent_score_index, 8);
+AT(pll_pars_recop_t, parent_ancestral_index, 12);
 
 /* this library's own: one candidate edge of pll_gpu_insertion_loglikelihoods */
 _Static_assert(sizeof(pll_gpu_insertion_t) == 24, "pll_gpu_insertion_t size");

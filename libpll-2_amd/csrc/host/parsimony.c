@@ -1,5 +1,8 @@
-/* parsimony.c - the bit-parallel Fitch parsimony entry points (src/fast_parsimony.c, src/parsimony.c:69-115).
+/* parsimony.c - the parsimony entry points: bit-parallel Fitch (src/fast_parsimony.c, src/parsimony.c:69-115) and, in the
+ * second half of the file, weighted (Sankoff) parsimony (src/parsimony.c:24-67, :117-383; kernels_sankoff.h behind the
+ * pllgpu_spars_* calls). Both kinds share the side table, the dependency levels and pll_parsimony_destroy.
  *
+ * Fitch:
  * Host side of the feature: site classification and tip packing (pll_fastparsimony_init - one-off integer set-up, done
  * here in C and uploaded once), the side table that ties a pll_parsimony_t to its device record, dependency levels of an
  * operation list, argument checks, the host mirror and pll_parsimony_destroy. The arithmetic of every update and score
@@ -9,6 +12,7 @@
  * structure that reaches pll_parsimony_destroy may have been allocated by another library; so nothing is hidden behind
  * the struct: the device record lives in a table keyed by the structure's address. */
 #include <limits.h>
+#include <math.h>
 #include <pthread.h>
 
 #include "pll_internal.h"
@@ -17,15 +21,25 @@
 /* src/pll.h:77-78 */
 #define PLL_STAT(x) ((pll_hardware.init || pll_hardware_probe()) && pll_hardware.x)
 
+enum { KIND_FAST, KIND_WEIGHTED };
+
 typedef struct pars_record
 {
   const pll_parsimony_t *key;
-  pllgpu_pars_t *dev; /* NULL: made under PLL_AMD_HOST_ONLY=1 */
-  unsigned int nodes; /* tips + 3 * inner_nodes */
-  /* scratch of pll_fastparsimony_update_vectors, [nodes] each: the latest level that writes / reads a node */
+  int kind;            /* KIND_FAST: pll_fastparsimony_init made it; KIND_WEIGHTED: pll_parsimony_create */
+  pllgpu_pars_t *dev;  /* fast; NULL: made under PLL_AMD_HOST_ONLY=1 */
+  pllgpu_spars_t *sdev; /* weighted; NULL: made under PLL_AMD_HOST_ONLY=1 */
+  unsigned int nodes; /* fast: tips + 3 * inner_nodes; weighted: what the level scratch holds (score or ancestral buffers) */
+  /* scratch of assign_levels, [nodes] each: the latest level that writes / reads a node */
   int *wlevel, *rlevel;
   pllgpu_pars_op_t *ops, *sorted;
+  unsigned int *order; /* sorted[i] is entry order[i] of the list */
   unsigned int ops_cap;
+  /* weighted only */
+  unsigned int score_nodes;      /* tips + score_buffers */
+  unsigned char *host_newer;     /* [score_nodes] sbuffer[i] was written on the host after its last upload */
+  unsigned int *indices;         /* [score_nodes] scratch: the buffers of an upload or a download */
+  int eager;                     /* PLL_AMD_EAGER_MIRROR=1 */
   struct pars_record *next;
 } pars_record_t;
 
@@ -59,6 +73,10 @@ static void record_free(pars_record_t *r)
 {
   if (!r) return;
   if (r->dev) pllgpu_pars_destroy(r->dev);
+  if (r->sdev) pllgpu_spars_destroy(r->sdev);
+  free(r->host_newer);
+  free(r->indices);
+  free(r->order);
   free(r->wlevel);
   free(r->rlevel);
   free(r->ops);
@@ -70,7 +88,7 @@ static void record_free(pars_record_t *r)
 static pars_record_t *need_device(const pll_parsimony_t *pars, const char *who)
 {
   pars_record_t *r = pars ? record_find(pars, 0) : NULL;
-  if (!r)
+  if (!r || r->kind != KIND_FAST)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: structure was not created by this library's pll_fastparsimony_init", who);
     return NULL;
@@ -326,9 +344,11 @@ static const pllgpu_pars_op_t *assign_levels(pars_record_t *r, const pll_pars_bu
   {
     free(r->ops);
     free(r->sorted);
+    free(r->order);
     r->ops = (pllgpu_pars_op_t *)malloc(count * sizeof *r->ops);
     r->sorted = (pllgpu_pars_op_t *)malloc(count * sizeof *r->sorted);
-    r->ops_cap = r->ops && r->sorted ? count : 0;
+    r->order = (unsigned int *)malloc(count * sizeof *r->order);
+    r->ops_cap = r->ops && r->sorted && r->order ? count : 0;
     if (!r->ops_cap) return NULL;
   }
   for (i = 0; i < r->nodes; ++i) r->wlevel[i] = r->rlevel[i] = -1;
@@ -355,7 +375,12 @@ static const pllgpu_pars_op_t *assign_levels(pars_record_t *r, const pll_pars_bu
     if (!start) return NULL;
     for (i = 0; i < count; ++i) ++start[r->ops[i].level + 1];
     for (i = 0; i < nlevels; ++i) start[i + 1] += start[i];
-    for (i = 0; i < count; ++i) r->sorted[start[r->ops[i].level]++] = r->ops[i];
+    for (i = 0; i < count; ++i)
+    {
+      const unsigned int at = start[r->ops[i].level]++;
+      r->sorted[at] = r->ops[i];
+      r->order[at] = i;
+    }
     free(start);
   }
   return r->sorted;
@@ -477,10 +502,14 @@ unsigned int pll_fastparsimony_root_score(const pll_parsimony_t *pars, unsigned 
 
 /* ---- mirror, bookkeeping ------------------------------------------------------------------------------------------- */
 
+static int weighted_sync(pars_record_t *r, pll_parsimony_t *pars, int node, const char *who);
+
 int pll_gpu_sync_parsimony(pll_parsimony_t *pars, int node)
 {
   static const char *who = "pll_gpu_sync_parsimony";
-  pars_record_t *r = need_device(pars, who);
+  pars_record_t *r = pars ? record_find(pars, 0) : NULL;
+  if (r && r->kind == KIND_WEIGHTED) return weighted_sync(r, pars, node, who);
+  r = need_device(pars, who);
   if (!r) return PLL_FAILURE;
   if (node >= 0 && !index_ok(r, (unsigned int)node, who)) return PLL_FAILURE;
   if (pllgpu_pars_download(r->dev, node < 0 ? 0u : (unsigned int)node, node < 0 ? r->nodes : 1u, pars->packedvector, pars->node_cost) != 0)
@@ -494,15 +523,386 @@ int pll_gpu_sync_parsimony(pll_parsimony_t *pars, int node)
 unsigned int pll_gpu_fastparsimony_last_launch_count(const pll_parsimony_t *pars)
 {
   pars_record_t *r = pars ? record_find(pars, 0) : NULL;
+  if (r && r->sdev) return pllgpu_spars_last_launch_count(r->sdev);
   return r && r->dev ? pllgpu_pars_last_launch_count(r->dev) : 0;
 }
+
+static int weighted_device(const pars_record_t *r, const char *who);
 
 int pll_gpu_synchronize_parsimony(pll_parsimony_t *pars)
 {
   static const char *who = "pll_gpu_synchronize_parsimony";
-  pars_record_t *r = need_device(pars, who);
+  pars_record_t *r = pars ? record_find(pars, 0) : NULL;
+  if (r && r->kind == KIND_WEIGHTED)
+  {
+    if (!weighted_device(r, who)) return PLL_FAILURE;
+    if (pllgpu_spars_synchronize(r->sdev) != 0)
+    {
+      pll_set_gpu_error(who);
+      return PLL_FAILURE;
+    }
+    return PLL_SUCCESS;
+  }
+  r = need_device(pars, who);
   if (!r) return PLL_FAILURE;
   if (pllgpu_pars_synchronize(r->dev) != 0)
+  {
+    pll_set_gpu_error(who);
+    return PLL_FAILURE;
+  }
+  return PLL_SUCCESS;
+}
+
+/* ==== weighted (Sankoff) parsimony (src/parsimony.c:24-67, :117-383) =================================================
+ * Host side: the fields the reference leaves, argument checks (the whole list before anything is uploaded or launched),
+ * dependency levels, the stale-mirror bookkeeping and the two character tables of a reconstruction. Every add and min
+ * runs on the device. Order of the checks in every call: the structure (PLL_ERROR_PARAM_INVALID), the arguments
+ * (PLL_ERROR_PARAM_INVALID), the device (PLL_ERROR_GPU_UNAVAILABLE for a host-only structure). */
+
+static pars_record_t *weighted_record(const pll_parsimony_t *pars, const char *who)
+{
+  pars_record_t *r = pars ? record_find(pars, 0) : NULL;
+  if (!r || r->kind != KIND_WEIGHTED)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: structure was not created by this library's pll_parsimony_create", who);
+    return NULL;
+  }
+  pllgpu_spars_clear_launch_count(r->sdev); /* a call that fails its checks has launched nothing */
+  return r;
+}
+
+static int weighted_device(const pars_record_t *r, const char *who)
+{
+  if (r->sdev) return 1;
+  pll_set_error(PLL_ERROR_GPU_UNAVAILABLE, "%s: no MI355X behind this structure (PLL_AMD_HOST_ONLY); this library has no CPU path", who);
+  return 0;
+}
+
+static int score_index_ok(const pars_record_t *r, unsigned int index, const char *who)
+{
+  if (index < r->score_nodes) return 1;
+  pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: score index %u out of range (%u buffers)", who, index, r->score_nodes);
+  return 0;
+}
+
+static int anc_index_ok(const pll_parsimony_t *pars, unsigned int index, const char *who)
+{
+  if (index >= pars->tips && index - pars->tips < pars->ancestral_buffers) return 1;
+  pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: ancestral index %u out of range [%u, %u)", who, index, pars->tips,
+                pars->tips + pars->ancestral_buffers);
+  return 0;
+}
+
+pll_parsimony_t *pll_parsimony_create(unsigned int tips, unsigned int states, unsigned int sites, const double *score_matrix,
+                                      unsigned int score_buffers, unsigned int ancestral_buffers)
+{
+  static const char *who = "pll_parsimony_create";
+  unsigned int i;
+  if (states < 1 || states > 64)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: %u states (1..64: pll_state_t has 64 bits)", who, states);
+    return NULL;
+  }
+  if (!tips || !sites || !score_matrix || tips + score_buffers < tips || tips + ancestral_buffers < tips)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: tips = %u, sites = %u, score_matrix %s", who, tips, sites, score_matrix ? "given" : "NULL");
+    return NULL;
+  }
+  pll_parsimony_t *pars = (pll_parsimony_t *)calloc(1, sizeof *pars);
+  pars_record_t *r = (pars_record_t *)calloc(1, sizeof *r);
+  if (!pars || !r) goto nomem;
+  /* src/parsimony.c:135-199: the passed parameters, a private matrix, zeroed buffers; every fast-parsimony field zero */
+  pars->tips = tips;
+  pars->states = states;
+  pars->sites = sites;
+  pars->score_buffers = score_buffers;
+  pars->ancestral_buffers = ancestral_buffers;
+  r->key = pars;
+  r->kind = KIND_WEIGHTED;
+  r->score_nodes = tips + score_buffers;
+  r->nodes = r->score_nodes > ancestral_buffers ? r->score_nodes : ancestral_buffers;
+  r->eager = pll_env_flag("PLL_AMD_EAGER_MIRROR");
+  pars->score_matrix = (double *)calloc((size_t)states * states, sizeof(double));
+  pars->sbuffer = (double **)calloc(r->score_nodes, sizeof(double *));
+  pars->anc_states = (unsigned int **)calloc((size_t)tips + ancestral_buffers, sizeof(unsigned int *));
+  r->wlevel = (int *)malloc(r->nodes * sizeof(int));
+  r->rlevel = (int *)malloc(r->nodes * sizeof(int));
+  r->host_newer = (unsigned char *)calloc(r->score_nodes, 1);
+  r->indices = (unsigned int *)malloc(r->score_nodes * sizeof(unsigned int));
+  if (!pars->score_matrix || !pars->sbuffer || !pars->anc_states || !r->wlevel || !r->rlevel || !r->host_newer || !r->indices) goto nomem;
+  memcpy(pars->score_matrix, score_matrix, (size_t)states * states * sizeof(double));
+  for (i = 0; i < r->score_nodes; ++i)
+    if (!(pars->sbuffer[i] = (double *)calloc((size_t)sites * states, sizeof(double)))) goto nomem;
+  for (i = tips; i < tips + ancestral_buffers; ++i)
+    if (!(pars->anc_states[i] = (unsigned int *)calloc(sites, sizeof(unsigned int)))) goto nomem;
+
+  /* There is no CPU arithmetic behind this library: without a device the structure is refused, as pll_partition_create
+   * refuses a partition, unless the caller asks for a host-only shell */
+  if (!pll_env_flag("PLL_AMD_HOST_ONLY"))
+  {
+    r->sdev = pllgpu_spars_create(-1, states, sites, r->score_nodes, ancestral_buffers, pars->score_matrix);
+    if (!r->sdev)
+    {
+      pll_set_error(PLL_ERROR_GPU_UNAVAILABLE, "MI355X context: %s", pllgpu_last_error());
+      record_free(r);
+      free_host_fields(pars);
+      return NULL;
+    }
+  }
+  record_add(r);
+  return pars;
+
+nomem:
+  pll_set_error(PLL_ERROR_MEM_ALLOC, "Unable to allocate enough memory.");
+  record_free(r);
+  if (pars) free_host_fields(pars);
+  return NULL;
+}
+
+int pll_set_parsimony_sequence(pll_parsimony_t *pars, unsigned int tip_index, const pll_state_t *map, const char *sequence)
+{
+  static const char *who = "pll_set_parsimony_sequence";
+  unsigned int i, j;
+  pars_record_t *r = weighted_record(pars, who);
+  if (!r) return PLL_FAILURE;
+  if (!map || !sequence)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: Parameter value is NULL!", who);
+    return PLL_FAILURE;
+  }
+  if (!score_index_ok(r, tip_index, who)) return PLL_FAILURE;
+  const unsigned int states = pars->states;
+  double *tipstate = pars->sbuffer[tip_index];
+  /* src/parsimony.c:37-42: infinity is the highest score in the matrix plus one */
+  double inf = pars->score_matrix[0];
+  for (i = 1; i < states * states; ++i)
+    if (pars->score_matrix[i] > inf) inf = pars->score_matrix[i];
+  inf++;
+  r->host_newer[tip_index] = 1; /* also when the sequence turns out illegal half way: the host copy has changed */
+  for (i = 0; i < pars->sites; ++i)
+  {
+    pll_state_t c = map[(unsigned char)sequence[i]];
+    if (c == 0)
+    {
+      pll_set_error(PLL_ERROR_TIPDATA_ILLEGALSTATE, "Illegal state code in tip \"%c\"", sequence[i]);
+      printf("%s\n", pll_errmsg); /* src/parsimony.c:50 */
+      return PLL_FAILURE;
+    }
+    for (j = 0; j < states; ++j, c >>= 1) tipstate[j] = (c & 1) ? 0 : inf;
+    tipstate += states;
+  }
+  return PLL_SUCCESS;
+}
+
+int pll_gpu_parsimony_invalidate(pll_parsimony_t *pars, unsigned int index)
+{
+  static const char *who = "pll_gpu_parsimony_invalidate";
+  pars_record_t *r = weighted_record(pars, who);
+  if (!r || !score_index_ok(r, index, who)) return PLL_FAILURE;
+  r->host_newer[index] = 1;
+  return PLL_SUCCESS;
+}
+
+/* every buffer the host wrote since its last upload goes up, all of them in one staging copy */
+static int flush_stale(pars_record_t *r, const pll_parsimony_t *pars, const char *who)
+{
+  unsigned int i, n = 0;
+  for (i = 0; i < r->score_nodes; ++i)
+    if (r->host_newer[i]) r->indices[n++] = i;
+  if (!n) return 1;
+  if (pllgpu_spars_upload(r->sdev, r->indices, n, pars->sbuffer) != 0)
+  {
+    pll_set_gpu_error(who);
+    return 0;
+  }
+  memset(r->host_newer, 0, r->score_nodes);
+  return 1;
+}
+
+double pll_parsimony_build(pll_parsimony_t *pars, const pll_pars_buildop_t *ops, unsigned int count)
+{
+  static const char *who = "pll_parsimony_build";
+  unsigned int i, n = 0;
+  double score = -INFINITY;
+  pars_record_t *r = weighted_record(pars, who);
+  if (!r) return -INFINITY;
+  if (!ops || !count)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: empty operation list", who);
+    return -INFINITY;
+  }
+  for (i = 0; i < count; ++i)
+    if (!score_index_ok(r, ops[i].parent_score_index, who) || !score_index_ok(r, ops[i].child1_score_index, who) ||
+        !score_index_ok(r, ops[i].child2_score_index, who))
+      return -INFINITY;
+  if (!weighted_device(r, who)) return -INFINITY;
+  const pllgpu_pars_op_t *sorted = assign_levels(r, ops, count);
+  if (!sorted)
+  {
+    pll_set_error(PLL_ERROR_MEM_ALLOC, "%s: cannot allocate the level schedule", who);
+    return -INFINITY;
+  }
+  if (!flush_stale(r, pars, who)) return -INFINITY;
+  if (pllgpu_spars_build(r->sdev, sorted, count, ops[count - 1].parent_score_index, &score) != 0)
+  {
+    pll_set_gpu_error(who);
+    return -INFINITY;
+  }
+  if (r->eager)
+  {
+    /* assign_levels has left the level of the last write in wlevel[]: the parents of the list */
+    for (i = 0; i < r->score_nodes; ++i)
+      if (r->wlevel[i] >= 0) r->indices[n++] = i;
+    if (pllgpu_spars_download(r->sdev, r->indices, n, pars->sbuffer) != 0)
+    {
+      pll_set_gpu_error(who);
+      return -INFINITY;
+    }
+  }
+  return score;
+}
+
+double pll_parsimony_score(pll_parsimony_t *pars, unsigned int score_buffer_index)
+{
+  static const char *who = "pll_parsimony_score";
+  double score = -INFINITY;
+  pars_record_t *r = weighted_record(pars, who);
+  if (!r || !score_index_ok(r, score_buffer_index, who) || !weighted_device(r, who)) return -INFINITY;
+  if (!flush_stale(r, pars, who)) return -INFINITY;
+  if (pllgpu_spars_score(r->sdev, score_buffer_index, &score) != 0)
+  {
+    pll_set_gpu_error(who);
+    return -INFINITY;
+  }
+  return score;
+}
+
+static unsigned int state_ctz(pll_state_t x)
+{
+  return (unsigned int)__builtin_ctzll(x);
+}
+
+void pll_parsimony_reconstruct(pll_parsimony_t *pars, const pll_state_t *map, const pll_pars_recop_t *ops, unsigned int count)
+{
+  static const char *who = "pll_parsimony_reconstruct";
+  unsigned int i, lo, hi, tables[512];
+  pll_pars_buildop_t *deps = NULL;
+  pllgpu_spars_recop_t *recops = NULL;
+  unsigned int **wanted = NULL;
+  pars_record_t *r = weighted_record(pars, who);
+  if (!r) goto loud;
+  if (!map || !ops)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: Parameter value is NULL!", who);
+    goto loud;
+  }
+  if (!count) return;
+  for (i = 0; i < count; ++i)
+  {
+    if (!score_index_ok(r, ops[i].node_score_index, who) || !anc_index_ok(pars, ops[i].node_ancestral_index, who)) goto loud;
+    /* the first operation has no parent: the reference never reads those two fields (src/parsimony.c:336-349) */
+    if (i && (!score_index_ok(r, ops[i].parent_score_index, who) || !anc_index_ok(pars, ops[i].parent_ancestral_index, who))) goto loud;
+  }
+  if (!weighted_device(r, who)) goto loud;
+
+  /* src/parsimony.c:327-334, in its loop order: of two characters with the same single bit the later one wins. The
+   * second table is what the reference computes per site, PLL_STATE_CTZ(map[character]); a character without a state in
+   * range (a hole in the reverse map leads to one) counts as state 0 instead of indexing out of bounds */
+  memset(tables, 0, sizeof tables);
+  for (i = 0; i < 256; ++i)
+    if (__builtin_popcountll(map[i]) == 1) tables[state_ctz(map[i])] = i;
+  for (i = 0; i < 256; ++i)
+    tables[256 + i] = map[i] && state_ctz(map[i]) < pars->states ? state_ctz(map[i]) : 0;
+
+  /* levels over the ancestral buffers: an operation reads its parent's and writes its own */
+  deps = (pll_pars_buildop_t *)malloc(count * sizeof *deps);
+  recops = (pllgpu_spars_recop_t *)malloc(count * sizeof *recops);
+  wanted = (unsigned int **)calloc(pars->ancestral_buffers, sizeof *wanted);
+  if (!deps || !recops || !wanted) goto nomem;
+  for (i = 0; i < count; ++i)
+  {
+    deps[i].parent_score_index = ops[i].node_ancestral_index - pars->tips;
+    deps[i].child1_score_index = deps[i].child2_score_index = (i ? ops[i].parent_ancestral_index : ops[i].node_ancestral_index) - pars->tips;
+  }
+  const pllgpu_pars_op_t *sorted = assign_levels(r, deps, count);
+  if (!sorted) goto nomem;
+  lo = hi = sorted[0].parent;
+  for (i = 0; i < count; ++i)
+  {
+    const pll_pars_recop_t *op = &ops[r->order[i]];
+    recops[i].node_score = op->node_score_index;
+    recops[i].node_ancestral = sorted[i].parent;
+    recops[i].parent_score = r->order[i] ? op->parent_score_index : op->node_score_index;
+    recops[i].parent_ancestral = sorted[i].child1;
+    recops[i].root = r->order[i] == 0;
+    recops[i].level = sorted[i].level;
+    if (sorted[i].parent < lo) lo = sorted[i].parent;
+    if (sorted[i].parent > hi) hi = sorted[i].parent;
+    wanted[sorted[i].parent] = pars->anc_states[pars->tips + sorted[i].parent];
+  }
+  if (!flush_stale(r, pars, who)) goto done;
+  /* anc_states[] of every node the list names comes back before the call returns: it is the call's result */
+  if (pllgpu_spars_reconstruct(r->sdev, recops, count, tables) != 0 ||
+      pllgpu_spars_download_ancestral(r->sdev, lo, hi - lo + 1, wanted) != 0)
+  {
+    pll_set_gpu_error(who);
+    goto done;
+  }
+  goto done;
+
+nomem:
+  pll_set_error(PLL_ERROR_MEM_ALLOC, "%s: cannot allocate the level schedule", who);
+loud:
+  fprintf(stderr, "libpll_amd: %s\n", pll_errmsg); /* a void entry point of the reference API: be loud as well */
+done:
+  free(deps);
+  free(recops);
+  free(wanted);
+}
+
+int pll_gpu_parsimony_insertion_scores(const pll_parsimony_t *pars, unsigned int node, const unsigned int *edges, unsigned int count,
+                                       double *scores)
+{
+  static const char *who = "pll_gpu_parsimony_insertion_scores";
+  unsigned int i;
+  pars_record_t *r = weighted_record(pars, who);
+  if (!r || !score_index_ok(r, node, who)) return PLL_FAILURE;
+  if (count && (!edges || !scores))
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: Parameter value is NULL!", who);
+    return PLL_FAILURE;
+  }
+  for (i = 0; i < 2 * count; ++i)
+    if (!score_index_ok(r, edges[i], who)) return PLL_FAILURE;
+  if (!weighted_device(r, who)) return PLL_FAILURE;
+  if (!count) return PLL_SUCCESS;
+  if (!flush_stale(r, pars, who)) return PLL_FAILURE;
+  if (pllgpu_spars_insertion_scores(r->sdev, node, edges, count, scores) != 0)
+  {
+    pll_set_gpu_error(who);
+    return PLL_FAILURE;
+  }
+  return PLL_SUCCESS;
+}
+
+/* pll_gpu_sync_parsimony of a weighted structure: score buffer `node` and, where it has one, ancestral buffer `node`
+ * (node < 0: all of both). A score buffer whose host copy is the newer one is left alone. */
+static int weighted_sync(pars_record_t *r, pll_parsimony_t *pars, int node, const char *who)
+{
+  unsigned int i, n = 0;
+  const unsigned int u = (unsigned int)node;
+  const int has_anc = node >= 0 && u >= pars->tips && u - pars->tips < pars->ancestral_buffers;
+  if (node >= 0 && u >= r->score_nodes && !has_anc)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: index %u names neither a score buffer nor an ancestral buffer", who, u);
+    return PLL_FAILURE;
+  }
+  if (!weighted_device(r, who)) return PLL_FAILURE;
+  for (i = 0; i < r->score_nodes; ++i)
+    if ((node < 0 || i == u) && !r->host_newer[i]) r->indices[n++] = i;
+  if (pllgpu_spars_download(r->sdev, r->indices, n, pars->sbuffer) != 0 ||
+      (node < 0 && pllgpu_spars_download_ancestral(r->sdev, 0, pars->ancestral_buffers, pars->anc_states + pars->tips) != 0) ||
+      (has_anc && pllgpu_spars_download_ancestral(r->sdev, u - pars->tips, 1, pars->anc_states + pars->tips) != 0))
   {
     pll_set_gpu_error(who);
     return PLL_FAILURE;

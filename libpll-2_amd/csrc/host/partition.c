@@ -176,7 +176,7 @@ void pll_partition_destroy(pll_partition_t *p)
   free(p);
 }
 
-static int env_flag(const char *name)
+int pll_env_flag(const char *name)
 {
   const char *v = getenv(name);
   return v && *v && strcmp(v, "0") != 0;
@@ -346,7 +346,7 @@ pll_partition_t *pll_partition_create(unsigned int tips, unsigned int clv_buffer
   x->tip_compact = (unsigned char *)calloc(tips ? tips : 1, 1);
   x->tipcodes = (unsigned char **)calloc(tips ? tips : 1, sizeof(unsigned char *));
   x->ctipmap = (pll_state_t *)calloc(PLL_ASCII_SIZE, sizeof(pll_state_t));
-  x->no_tip_codes = env_flag("PLL_AMD_NO_TIP_CODES");
+  x->no_tip_codes = pll_env_flag("PLL_AMD_NO_TIP_CODES");
   NEED(x->tip_compact && x->tipcodes && x->ctipmap);
   x->eigen_dirty = (unsigned char *)malloc(rate_matrices ? rate_matrices : 1);
   x->pmatrix_stale = (unsigned char *)calloc(prob_matrices ? prob_matrices : 1, 1);
@@ -380,8 +380,8 @@ pll_partition_t *pll_partition_create(unsigned int tips, unsigned int clv_buffer
   x->rate_weights_dirty = x->pattern_weights_dirty = x->prop_invar_dirty = 1;
   x->invariant_dirty = 0;
   x->tipmap_dirty = 0;
-  x->eager_mirror = env_flag("PLL_AMD_EAGER_MIRROR");
-  x->always_upload = env_flag("PLL_AMD_ALWAYS_UPLOAD");
+  x->eager_mirror = pll_env_flag("PLL_AMD_EAGER_MIRROR");
+  x->always_upload = pll_env_flag("PLL_AMD_ALWAYS_UPLOAD");
 
   if (repeats && !pll_repeats_initialize(p))
   {
@@ -392,7 +392,7 @@ pll_partition_t *pll_partition_create(unsigned int tips, unsigned int clv_buffer
   /* device context. There is no CPU arithmetic behind this library: without a device the
    * partition is refused, unless the caller explicitly asks for a host-only shell (CPU tests
    * of the bookkeeping), in which case every compute call fails loudly. */
-  if (env_flag("PLL_AMD_HOST_ONLY"))
+  if (pll_env_flag("PLL_AMD_HOST_ONLY"))
     x->ctx = NULL;
   else
   {

@@ -118,6 +118,8 @@ static inline pll_amd_ext_t *pll_ext(const pll_partition_t *p)
   return x->magic == PLL_AMD_MAGIC ? x : NULL;
 }
 
+/* an environment switch: set, not empty and not "0" */
+int pll_env_flag(const char *name);
 /* error convention of the reference: code + message in thread-locals (src/pll.c:24-25) */
 void pll_set_error(int code, const char *fmt, ...);
 /* map the device layer's status + text onto pll_errno / pll_errmsg */

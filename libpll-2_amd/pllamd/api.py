@@ -135,6 +135,12 @@ class ParsBuildOp(C.Structure):
     _fields_ = [("parent_score_index", C.c_uint), ("child1_score_index", C.c_uint), ("child2_score_index", C.c_uint)]
 
 
+class ParsRecOp(C.Structure):
+    """pll_pars_recop_t (src/pll.h:502-508)"""
+    _fields_ = [("node_score_index", C.c_uint), ("node_ancestral_index", C.c_uint), ("parent_score_index", C.c_uint),
+                ("parent_ancestral_index", C.c_uint)]
+
+
 class Insertion(C.Structure):
     """pll_gpu_insertion_t (include/pll_amd.h): one candidate edge of pll_gpu_insertion_loglikelihoods"""
     _fields_ = [
@@ -188,12 +194,13 @@ assert C.sizeof(Insertion) == 24
 assert C.sizeof(Quartet) == 52 and Quartet.scaler_index.offset == 16 and Quartet.inner_matrix_index.offset == 48
 assert C.sizeof(Newton) == 40 and C.sizeof(NewtonResult) == 40
 assert C.sizeof(Partition) == 232 and C.sizeof(Repeats) == 104 and C.sizeof(Operation) == 32
-assert C.sizeof(Parsimony) == 104 and C.sizeof(ParsBuildOp) == 12
+assert C.sizeof(Parsimony) == 104 and C.sizeof(ParsBuildOp) == 12 and C.sizeof(ParsRecOp) == 16
 
 PartitionP = C.POINTER(Partition)
 ParsimonyP = C.POINTER(Parsimony)
 ParsBuildOpP = C.POINTER(ParsBuildOp)
-ERROR_PARAM_INVALID, ERROR_STEPWISE_UNSUPPORTED = 113, 129
+ParsRecOpP = C.POINTER(ParsRecOp)
+ERROR_PARAM_INVALID, ERROR_TIPDATA_ILLEGALSTATE, ERROR_STEPWISE_UNSUPPORTED = 113, 114, 129
 ERROR_GPU_UNAVAILABLE, ERROR_GPU_RUNTIME, ERROR_GPU_UNSUPPORTED = 900, 901, 902
 UINT_MAX = 0xFFFFFFFF
 
@@ -258,6 +265,12 @@ _PROTOS = {
     "pll_fastparsimony_edge_score_4x4": (C.c_uint, [ParsimonyP, C.c_uint, C.c_uint]),
     "pll_fastparsimony_root_score": (C.c_uint, [ParsimonyP, C.c_uint]),
     "pll_parsimony_destroy": (None, [C.c_void_p]),
+    # weighted parsimony (src/pll.h:2535-2557)
+    "pll_parsimony_create": (ParsimonyP, [C.c_uint, C.c_uint, C.c_uint, c_double_p, C.c_uint, C.c_uint]),
+    "pll_set_parsimony_sequence": (C.c_int, [ParsimonyP, C.c_uint, c_state_p, C.c_char_p]),
+    "pll_parsimony_build": (C.c_double, [ParsimonyP, ParsBuildOpP, C.c_uint]),
+    "pll_parsimony_score": (C.c_double, [ParsimonyP, C.c_uint]),
+    "pll_parsimony_reconstruct": (None, [ParsimonyP, c_state_p, ParsRecOpP, C.c_uint]),
 }
 
 # device-residency extension of libpll_amd.so (include/pll_amd.h); absent from other libraries
@@ -310,6 +323,8 @@ _GPU_PROTOS = {
     "pll_gpu_fastparsimony_insertion_scores": (C.c_int, [ParsimonyP, C.c_uint, c_uint_p, C.c_uint, c_uint_p]),
     "pll_gpu_fastparsimony_last_launch_count": (C.c_uint, [ParsimonyP]),
     "pll_gpu_synchronize_parsimony": (C.c_int, [ParsimonyP]),
+    "pll_gpu_parsimony_invalidate": (C.c_int, [ParsimonyP, C.c_uint]),
+    "pll_gpu_parsimony_insertion_scores": (C.c_int, [ParsimonyP, C.c_uint, c_uint_p, C.c_uint, c_double_p]),
     "pll_gpu_device_count": (C.c_int, []),
     "pll_gpu_available": (C.c_int, []),
 }
@@ -401,6 +416,15 @@ def make_pars_ops(rows):
     arr = (ParsBuildOp * max(len(rows), 1))()
     for o, r in zip(arr, rows):
         o.parent_score_index, o.child1_score_index, o.child2_score_index = [int(x) for x in r]
+    return arr
+
+
+def make_pars_recops(rows):
+    """rows: iterable of (node score, node ancestral, parent score, parent ancestral) indices."""
+    rows = list(rows)
+    arr = (ParsRecOp * max(len(rows), 1))()
+    for o, r in zip(arr, rows):
+        o.node_score_index, o.node_ancestral_index, o.parent_score_index, o.parent_ancestral_index = [int(x) for x in r]
     return arr
 
 

@@ -523,6 +523,83 @@ class ParsimonySession:
         self.close()
 
 
+class SankoffSession:
+    """A pll_parsimony_t made by pll_parsimony_create (src/parsimony.c:117-202) and the calls that drive it. ABI only,
+    like ParsimonySession: the same sequence runs on libpll_amd.so and on the reference; the batched call, the mirror
+    refresh and the launch count exist on libpll_amd.so alone."""
+
+    def __init__(self, lib: api.PllLib, tips, states, sites, matrix, score_buffers, ancestral_buffers):
+        self.lib, self.tips, self.states, self.sites = lib, int(tips), int(states), int(sites)
+        self.buffers, self.ancestral_buffers = self.tips + int(score_buffers), int(ancestral_buffers)
+        m = np.ascontiguousarray(matrix, dtype=np.float64)
+        self.pars = lib.pll_parsimony_create(tips, states, sites, api.dptr(m), score_buffers, ancestral_buffers)
+        if not self.pars:
+            raise RuntimeError(f"pll_parsimony_create failed: [{lib.errno()}] {lib.errmsg()}")
+        self.s = self.pars.contents
+
+    @staticmethod
+    def _map(charmap):
+        return (C.c_ulonglong * 256)(*[int(x) for x in charmap])
+
+    def set_sequence(self, index, charmap, seq):
+        return int(self.lib.pll_set_parsimony_sequence(self.pars, index, self._map(charmap), bytes(seq)))
+
+    def launches(self):
+        count = getattr(self.lib, "pll_gpu_fastparsimony_last_launch_count", None)
+        return int(count(self.pars)) if count else None
+
+    def build(self, ops, per_op=False):
+        """run (parent, child1, child2) rows; returns the score of the last row's parent"""
+        ops = list(ops)
+        arr = api.make_pars_ops(ops)
+        if not per_op:
+            return float(self.lib.pll_parsimony_build(self.pars, arr, len(ops)))
+        for i in range(len(ops)):
+            score = float(self.lib.pll_parsimony_build(self.pars, C.byref(arr[i]), 1))
+        return score
+
+    def score(self, index):
+        return float(self.lib.pll_parsimony_score(self.pars, index))
+
+    def reconstruct(self, charmap, rows):
+        rows = list(rows)
+        self.lib.pll_parsimony_reconstruct(self.pars, self._map(charmap), api.make_pars_recops(rows), len(rows))
+
+    def insertion_scores(self, node, edges):
+        edges = np.ascontiguousarray(edges, dtype=np.uint32).reshape(-1, 2)
+        out = np.full(len(edges), np.nan)
+        if not self.lib.pll_gpu_parsimony_insertion_scores(self.pars, node, api.uptr(edges), len(edges), api.dptr(out)):
+            raise RuntimeError(f"pll_gpu_parsimony_insertion_scores: [{self.lib.errno()}] {self.lib.errmsg()}")
+        return out
+
+    def insertion_scores_per_edge(self, node, edges, spare):
+        """what the batched call is defined by: pll_parsimony_build({{t1, a, b}, {t2, t1, node}}, 2)"""
+        t1, t2 = spare
+        return np.array([self.build([(t1, a, b), (t2, t1, node)]) for a, b in edges])
+
+    def sync(self, node=-1):
+        if self.lib.is_amd and not self.lib.pll_gpu_sync_parsimony(self.pars, node):
+            raise RuntimeError(f"pll_gpu_sync_parsimony: [{self.lib.errno()}] {self.lib.errmsg()}")
+
+    def buffer(self, index):
+        """host copy of a score buffer, [sites][states] (call sync() first on libpll_amd.so)"""
+        return api.as_np(self.s.sbuffer[index], self.sites * self.states, np.float64).reshape(self.sites, self.states).copy()
+
+    def ancestral(self, index):
+        return api.as_np(self.s.anc_states[index], self.sites, np.uint32).copy()
+
+    def close(self):
+        if self.pars:
+            self.lib.pll_parsimony_destroy(self.pars)
+            self.pars = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def run_case(lib: api.PllLib, case: Case, arch: int = api.ARCH_AVX2):
     """Full sequence; returns {'clv': {idx: arr}, 'scaler': {idx: arr}, 'lnl': [...],
     'persite': [...], 'root_lnl': [...], 'root_persite': [...]}. CLVs are scaler-free raw values;
