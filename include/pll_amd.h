@@ -856,6 +856,56 @@ typedef struct pll_gpu_quartet
 } pll_gpu_quartet_t;
 int pll_gpu_quartet_loglikelihoods(pll_partition_t *partition, const pll_gpu_quartet_t *quartets, unsigned int count,
                                    const unsigned int *freqs_indices, double *lnl /* [count][3] */);
+/* ---- the gradient of every branch at once --------------------------------
+ * "What are the first and second derivatives of the log-likelihood with respect to this branch?" for `count` branches in
+ * one call: what a simultaneous Newton or L-BFGS step on all 2T - 3 branches, HMC or variational inference over branch
+ * lengths, or ranking the branches worth optimising asks. d_f[i], dd_f[i] are BY DEFINITION what the reference returns
+ * for pll_update_sumtable(partition, parent_clv_index, child_clv_index, parent_scaler_index, child_scaler_index,
+ * params_indices, tmp) (src/derivatives.c:239-324) followed by pll_compute_likelihood_derivatives(partition,
+ * parent_scaler_index, child_scaler_index, branch_length, params_indices, tmp, &d_f, &dd_f) (src/derivatives.c:333-418,
+ * src/core_derivatives.c:643-694, :696-849): the derivatives of -lnL. No table is needed and none is written: a table row
+ * exists inside the kernel only, and nothing in the partition is written - no CLV, scaler, matrix, tip representation,
+ * class map, resident sumtable or cached launch plan (the two contraction matrices behind pll_update_sumtable are
+ * refreshed through the same bookkeeping, so a later pll_update_sumtable sees what it expects).
+ * Per-site scaling: the scalers are not read - they cancel in L'/L, and the reference reads none. With
+ * PLL_ATTRIB_RATE_SCALERS column k of a site is multiplied by 2^(-256 min(s_k - min_k s_k, PLL_SCALE_RATE_MAXDIFF)), s_k
+ * the parent's count plus the child's, an absent scaler counting 0 (src/core_derivatives.c:420-460). With prop_invar > 0
+ * the rate is rate / (1 - pinv), each category becomes c0 (1 - pinv) + pi[inv] pinv, c1 (1 - pinv), c2 (1 - pinv), and the
+ * invariant term enters unscaled, exactly as in the reference (:676-686). Also served: pattern weights, a params_indices
+ * entry per rate category with rate_matrices > 1, and an eigensystem marked invalid, which is computed first, as
+ * pll_update_sumtable does here.
+ * Either end may be an inner CLV (with or without a scaler), a PLL_ATTRIB_PATTERN_TIP tip, a tip set through
+ * pll_set_tip_states (read as codes where the device holds codes) or a dense tip; the tip may be the parent or the child.
+ * Two ends that the device both holds as codes are refused in every mode (the reference refuses that under
+ * PLL_ATTRIB_PATTERN_TIP; pll_update_sumtable here makes one tip dense otherwise, but this call writes nothing, and no
+ * tree of three or more taxa has such a branch).
+ * Both ends of every branch are read in one launch, so each must hold the named orientation AT THE SAME TIME: a caller
+ * computes the "upward" CLVs into spare clv_buffers slots first, exactly as for the insertion call ("The
+ * gradient of every branch at once"). What the previous pll_update_partials still holds back is launched first and CLVs a
+ * tree launch left pending are stored first: a branch may name a node that traversal produced. A branch may be named twice.
+ * Synchronous: one copy back for all values and one wait. Each value is formed in an order that depends on the site count
+ * alone: it has the same bits alone, among others, in any list order, and from run to run.
+ * PLL_SUCCESS, or PLL_FAILURE with pll_errno, the usual line on stderr and d_f, dd_f untouched. The whole list is checked
+ * before anything is flushed or launched, in this order: PLL_ERROR_PARAM_INVALID for a NULL partition, for a NULL
+ * branches, params_indices or d_f with count > 0, for a CLV or scaler index out of range (a scaler below -1 included), for
+ * a branch length that is negative or not finite, for a params_indices[k] >= rate_matrices and for two code-tip ends;
+ * PLL_ERROR_GPU_UNSUPPORTED for a PLL_ATTRIB_SITE_REPEATS partition and for a partition with any ascertainment-bias
+ * correction (the Stamatakis one included: one rule across the batched calls); PLL_ERROR_GPU_UNAVAILABLE without a
+ * device. count == 0 succeeds without a launch and reads nothing of the list. dd_f may be NULL.
+ * pll_gpu_last_launch_count reports the launches of the call; long lists are cut internally (the rule:
+ * include/pll_amd_device.h, pllgpu_branch_derivatives).
+ * Not offered: the log-likelihood itself, per-site values, any iteration (pll_gpu_optimize_branch_length serves one
+ * branch), site repeats and the ascertainment-bias correction (refused). */
+typedef struct pll_gpu_branch
+{
+  unsigned int parent_clv_index;
+  int parent_scaler_index;      /* PLL_SCALE_BUFFER_NONE or a scale buffer; ignored for a tip */
+  unsigned int child_clv_index;
+  int child_scaler_index;
+  double branch_length;
+} pll_gpu_branch_t;
+int pll_gpu_branch_derivatives(pll_partition_t *partition, const pll_gpu_branch_t *branches, unsigned int count,
+                               const unsigned int *params_indices, double *d_f, double *dd_f /* may be NULL */);
 /* ---- batched placement log-likelihoods ---------------------------------
  * Every query x every candidate edge in one call: the pre-scoring pass of a phylogenetic placement, the first pass of
  * a stepwise addition by likelihood. lnl is [query_count][count], query-major, and lnl[q * count + i] is BY DEFINITION
@@ -972,7 +1022,7 @@ int pll_gpu_rccl_available(void);
 int pll_gpu_timer_start(pll_partition_t *partition);
 double pll_gpu_timer_stop(pll_partition_t *partition);
 /* number of kernel launches issued by the last pll_update_partials, pll_gpu_insertion_loglikelihoods,
- * pll_gpu_placement_loglikelihoods or pll_gpu_quartet_loglikelihoods call */
+ * pll_gpu_placement_loglikelihoods, pll_gpu_quartet_loglikelihoods or pll_gpu_branch_derivatives call */
 unsigned int pll_gpu_last_launch_count(const pll_partition_t *partition);
 /* site repeats: class-map operations computed on the device (launches = 0) / class kernels launched (launches != 0)
  * since the partition was created. An unchanged tree adds nothing, a topology move the ops of its partial traversal */

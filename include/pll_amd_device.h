@@ -251,6 +251,39 @@ typedef struct pllgpu_quartet
 int pllgpu_quartet_loglikelihoods(pllgpu_ctx_t *ctx, const pllgpu_quartet_t *quartets, unsigned int count,
                                   const unsigned int *freqs_indices, double *host_out);
 
+/* The first and second derivative of -lnL with respect to the branch length, for `count` branches at once
+ * (kernels_gradient.h): host_d[i], host_dd[i] replace pllgpu_update_sumtable + pllgpu_likelihood_derivatives for the
+ * branch between parent_clv and child_clv at branch_length - but no table exists: a (site, rate) row is formed in
+ * registers from the two ends and the two contraction matrices (pllgpu_aux_matrix_upload) and contracted at once with the
+ * branch's own (e, l e, l^2 e), which every workgroup forms in LDS from the eigenvalues and rates the context holds.
+ * Nothing the context holds is written. parent_is_tip / child_is_tip: the end is read as tip codes and its scaler index is
+ * not read; at most one end of a branch may be (PLLGPU_EINVAL). Scalers are read with per-rate scalers only (per-site
+ * counts cancel in L'/L): column k of a site is multiplied by 2^(-256 min(s_k - min_k s_k, 4)), s_k the two ends' counts
+ * added, as k_sumtable_excess does to a table. Every index, tip mark and length of the whole list is checked before held
+ * work is launched or anything else happens; class-compressed CLVs anywhere in the context and ascertainment-bias entries
+ * are PLLGPU_EUNSUPPORTED. Held work is launched and pending CLVs are stored first: a branch may name what a traversal
+ * produced.
+ * The cutting rule. B = the workgroups per branch, launch_insertions' cut of the site tiles (T = ceil(sites / 64); 4 x 4:
+ * w = ceil(T / 4096), B = ceil(T / (4 w)); every other shape: w = ceil(T / 1024), B = ceil(T / w)). A workgroup leaves two
+ * partial sums, and a launch carries at most PLLGPU_BRANCH_MAX descriptors (64 bytes each: one piece of the pinned block)
+ * and PLLGPU_INSERTION_MAX_SLOTS partial slots:
+ *   Q = min(count, PLLGPU_BRANCH_MAX, max(1, floor(PLLGPU_INSERTION_MAX_SLOTS / (2 B))))   branches per launch,
+ * grid (B, Q), ceil(count / Q) launches (counted into pllgpu_last_launch_count); one copy back of all 2 count values, one
+ * wait. Each value owns B slots and a ticket of its own: its bits depend on the site count and its own branch alone.
+ * host_d / host_dd (which may be NULL) are written only on success; count == 0 succeeds without a launch. */
+#define PLLGPU_BRANCH_MAX 8192
+typedef struct pllgpu_branch
+{
+  unsigned int parent_clv;
+  int parent_scaler;
+  unsigned int child_clv;
+  int child_scaler;
+  unsigned int parent_is_tip, child_is_tip;
+  double branch_length;
+} pllgpu_branch_t;
+int pllgpu_branch_derivatives(pllgpu_ctx_t *ctx, const pllgpu_branch_t *branches, unsigned int count,
+                              const unsigned int *params_indices, double *host_d, double *host_dd);
+
 /* replaces pll_compute_node_ancestral[_extbuf] (src/likelihood.c:639-823): the marginal state probabilities of
  * the node at edge->parent_clv, [sites][states] unpadded, given the other end edge->child_clv (a CLV, or tip codes
  * with child_is_tip) across edge->matrix. Of `edge`, gather must be 0 and want_persite / device_result / sequence

@@ -65,6 +65,36 @@ __global__ __launch_bounds__(256) void k_diagtable(const DevDiag d)
   for (unsigned idx = threadIdx.x; idx < d.R * d.S; idx += blockDim.x) diag_entry(d, d.branch_length, idx, d.diag + (size_t)idx * 4);
 }
 
+// The model step of one rate category, shared by every kernel that forms derivatives (derivative_sums below,
+// kernels_gradient.h): (c0, c1, c2) = the category's contraction of the site's table row with (e, l e, l^2 e); with a
+// proportion of invariant sites the category becomes c0 (1 - pinv) + pi[inv] pinv, c1 (1 - pinv), c2 (1 - pinv) - the
+// invariant term unscaled (src/core_derivatives.c:676-686) - and enters the site's (L, L', L'') with its weight.
+__device__ __forceinline__ void deriv_rate_add(const double *freqs, const double *prop_invar, const double *rate_weights, unsigned fi, unsigned SP,
+                                               unsigned k, int inv, double c0, double c1, double c2, double &lk0, double &lk1, double &lk2)
+{
+  const double pinv = prop_invar ? prop_invar[fi] : 0.0;
+  if (pinv > 0.0)
+  {
+    const double isl = inv >= 0 ? freqs[(size_t)fi * SP + inv] * pinv : 0.0;
+    c0 = c0 * (1.0 - pinv) + isl;
+    c1 = c1 * (1.0 - pinv);
+    c2 = c2 * (1.0 - pinv);
+  }
+  const double w = rate_weights[k];
+  lk0 += c0 * w;
+  lk1 += c1 * w;
+  lk2 += c2 * w;
+}
+
+// ... and the site's share of the two sums: pattern_weight * (-L'/L) and pattern_weight * ((L'/L)^2 - L''/L) (:687-692)
+__device__ __forceinline__ void deriv_site_add(double lk0, double lk1, double lk2, double pw, double &a1, double &a2)
+{
+  const double d1 = -lk1 / lk0;
+  const double d2 = d1 * d1 - lk2 / lk0;
+  a1 += pw * d1;
+  a2 += pw * d2;
+}
+
 // One evaluation up to its two sums - the one copy of the per-site arithmetic, the block partials and the pairing of
 // additions that k_derivatives and k_derivatives_newton share. true in thread 0 of the workgroup that arrived last, with
 // (sum1, sum2) = (d_f, dd_f) and the ticket back at zero; false everywhere else.
@@ -123,28 +153,9 @@ __device__ __forceinline__ bool derivative_sums(const DevDeriv &d, const GenGeo 
         c1 = fma(s, dk[j * 4 + 1], c1);
         c2 = fma(s, dk[j * 4 + 2], c2);
       }
-      const unsigned fi = d.fidx[k];
-      const double pinv = d.prop_invar ? d.prop_invar[fi] : 0.0;
-      if (pinv > 0.0)
-      {
-        const double isl = inv >= 0 ? d.freqs[(size_t)fi * g.SP + inv] * pinv : 0.0;
-        c0 = c0 * (1.0 - pinv) + isl;
-        c1 = c1 * (1.0 - pinv);
-        c2 = c2 * (1.0 - pinv);
-      }
-      const double w = d.rate_weights[k];
-      lk0 += c0 * w;
-      lk1 += c1 * w;
-      lk2 += c2 * w;
+      deriv_rate_add(d.freqs, d.prop_invar, d.rate_weights, d.fidx[k], g.SP, k, inv, c0, c1, c2, lk0, lk1, lk2);
     }
-    if (valid)
-    {
-      const double d1 = -lk1 / lk0;
-      const double d2 = d1 * d1 - lk2 / lk0;
-      const double pw = (double)d.pattern_weights[n];
-      a1 += pw * d1;
-      a2 += pw * d2;
-    }
+    if (valid) deriv_site_add(lk0, lk1, lk2, (double)d.pattern_weights[n], a1, a2);
   }
   a1 = wave_sum(a1);
   a2 = wave_sum(a2);

@@ -1,0 +1,223 @@
+// kernels_gradient.h - the branch-length gradient (pll_gpu_branch_derivatives).
+//
+// "What are the first and second derivatives of -lnL with respect to this branch?" - asked for every branch of a list in
+// ONE launch. Per branch the reference runs pll_update_sumtable (src/derivatives.c:239-324), which writes a CLV-sized
+// table, and pll_compute_likelihood_derivatives (:333-418, src/core_derivatives.c:643-849), which reads it back. For one
+// evaluation per branch the table is pure overhead: its row of a (site, rate),
+//     sum[j] = (sum_i p_i pi_i Vinv[i][j]) * (sum_i V[j][i] c_i),
+// is two small matrix-vector products and their element-wise product, contracted at once with the branch's own
+// diag[k][j] = (e, l e, l^2 e). Here a row exists in registers only: a branch costs one read of its two ends, no table, no
+// write to HBM and no launch of its own. Nothing is written but two partial sums per workgroup, handed off side by side
+// through plc_publish_chunk<2> (kernels_placement.h): value (d_f | dd_f, branch) owns gridDim.x slots and a ticket, so its
+// bits depend on its own workgroups alone.
+//
+// Grid: x = the site tiles exactly as launch_insertions cuts them (a function of the site count alone), y = the branch.
+// The model travels in a DevEdge (parent, child, mat and the scalers unused; block_sums / counter / result = the slots
+// [value][branch of the launch][workgroup], a ticket per value, the results [value][branch of the call]) and a DevDiag
+// (eigenvalues, rates, prop_invar; diag unused: no table of a branch stands in HBM); m1 / m2 are the two contraction
+// matrices in the PT layout (matrix slots prob_matrices and prob_matrices + 1). The ends and the length of branch y are
+// branches[y], read through the scalar path. As in pll_update_sumtable an end given by codes takes the `left` role (m1);
+// otherwise the parent is left and the child right. Whether an end is a tip is a wave-uniform branch.
+//
+// Per-site scaling cancels in L'/L: no scaler is read. Per-rate scalers: column k of a site is multiplied by
+// 2^(-256 min(s_k - min_k s_k, 4)), s_k = the two ends' counts added (src/core_derivatives.c:420-460) - what
+// k_sumtable_excess does to a table, here applied to the row before it is contracted, as the reference's table holds it.
+#pragma once
+#include "kernels_common.h"
+#include "kernels_dna.h"
+#include "kernels_generic.h"
+#include "kernels_deriv.h" // (after kernels_generic.h: it uses tiled_base)
+#include "kernels_placement.h"
+
+struct BranchDesc // 64 bytes
+{
+  const double *left, *right;        // CLV of the end, or null: a tip given by codes
+  const unsigned char *ltip, *rtip;  // tip codes or null
+  const unsigned *lscaler, *rscaler; // per-rate scalers only; null: the end carries no scaler (or the mode reads none)
+  double t;                          // the branch length
+  double pad_;
+};
+typedef const BranchDesc __attribute__((address_space(4))) *cbranch_p;
+
+__device__ __forceinline__ BranchDesc branch_get(const BranchDesc *branches, unsigned y)
+{
+  cbranch_p p = (cbranch_p)(uintptr_t)branches + y;
+  BranchDesc r;
+  r.left = p->left;
+  r.right = p->right;
+  r.ltip = p->ltip;
+  r.rtip = p->rtip;
+  r.lscaler = p->lscaler;
+  r.rscaler = p->rscaler;
+  r.t = p->t;
+  r.pad_ = 0.0;
+  return r;
+}
+
+// the branch's diag table, [R][S][4] = (e, l e, l^2 e, 0), formed by the workgroup itself from the branch's own length:
+// derivative_sums' local_diag way, with no copy left in HBM
+__device__ __forceinline__ void branch_diag(const DevDiag &dg, double t, double *ldiag)
+{
+  for (unsigned idx = threadIdx.x; idx < dg.R * dg.S; idx += blockDim.x) diag_entry(dg, t, idx, ldiag + (size_t)idx * 4);
+  __syncthreads();
+}
+
+// 2^(-256 excess) of rate k, or 1
+__device__ __forceinline__ double excess_factor(unsigned rs, unsigned mn)
+{
+  const unsigned ex = rate_excess(rs, mn);
+  return ex ? minlh(ex) : 1.0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// 4 states x 4 rates: one wave per 64-site tile, the lane owns its site. Per rate the two ends (8 doubles, or decoded
+// codes), the two 4 x 4 products with the contraction-matrix coefficients through the scalar path, the row, its excess
+// factor and the three contractions with the branch's diag row (16 x 4 doubles in LDS, wave-uniform addresses). No node
+// is kept: register use is small (report in DESIGN.md section 5.9).
+__global__ __launch_bounds__(256) void k_gradient_dna(const DevEdge e, const DevDiag dg, const BranchDesc *branches, const double *m1,
+                                                      const double *m2, unsigned res_stride, unsigned tiles_per_wave)
+{
+  __shared__ double ldiag[16 * 4];
+  const BranchDesc b = branch_get(branches, blockIdx.y);
+  branch_diag(dg, b.t, ldiag);
+  cdouble_p lm = as_const(m1), rm = as_const(m2);
+  const int smode = e.per_rate ? 2 : 0; // per-site counts cancel: not read
+  double a1 = 0.0, a2 = 0.0;
+
+  for (unsigned t = 0; t < tiles_per_wave; ++t)
+  {
+    DnaTile w;
+    if (!dna_tile(w, blockIdx.x, tiles_per_wave, t, e.sites)) break;
+    const unsigned n = w.n;
+    const uint4 ls = dna_load_scaler(b.lscaler, n, smode), rs = dna_load_scaler(b.rscaler, n, smode);
+    const unsigned sk[4] = {ls.x + rs.x, ls.y + rs.y, ls.z + rs.z, ls.w + rs.w};
+    const unsigned mn = min(min(sk[0], sk[1]), min(sk[2], sk[3]));
+    const int inv = e.invariant ? e.invariant[n] : -1;
+    const unsigned lcode = b.ltip ? b.ltip[n] : 0u, rcode = b.rtip ? b.rtip[n] : 0u; // wave-uniform choices
+    double lk0 = 0.0, lk1 = 0.0, lk2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+      double xl[4], xr[4], pa[4], pb[4];
+      if (b.ltip)
+        dna_fetch<true>(xl, nullptr, k, lcode);
+      else
+        dna_fetch<false>(xl, b.left + w.off, k, 0u);
+      if (b.rtip)
+        dna_fetch<true>(xr, nullptr, k, rcode);
+      else
+        dna_fetch<false>(xr, b.right + w.off, k, 0u);
+      dna_matvec(pa, lm + k * 16, xl);
+      dna_matvec(pb, rm + k * 16, xr);
+      const double f = excess_factor(sk[k], mn);
+      // the rate's diag row, read where it is used: an offset the compiler takes as new keeps it from holding all 48
+      // values in vector registers from the top of the kernel to its end (96 registers, two waves per SIMD)
+      unsigned row = k * 16u;
+      asm volatile("" : "+v"(row));
+      double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+      {
+        const double s = pa[j] * pb[j] * f;
+        const double *dk = ldiag + row + j * 4;
+        c0 = fma(s, dk[0], c0);
+        c1 = fma(s, dk[1], c1);
+        c2 = fma(s, dk[2], c2);
+      }
+      deriv_rate_add(e.freqs, e.prop_invar, e.rate_weights, e.fidx[k], 4u, k, inv, c0, c1, c2, lk0, lk1, lk2);
+    }
+    if (w.valid) deriv_site_add(lk0, lk1, lk2, (double)e.pattern_weights[n], a1, a2);
+  }
+  const double sums[2] = {wave_sum(a1), wave_sum(a2)};
+  plc_publish_chunk<2>(e, 0u, 2u, res_stride, sums, 4u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Every other shape (up to 64 states, any rate count): k_insertion_tiled's structure - workgroup = one tile of one branch
+// at a time, wave w of min(R, 4) owns the rate categories w, w + nw, ..., the contraction is kernels_generic.h's and a tip
+// is decoded through the tipmap. The branch's diag table stands in LDS ([R][S][4]: 7.8 KB at 61 x 4). A wave leaves its
+// rates' share of the site's (L, L', L'') in LDS; wave 0 adds the shares in wave order and forms the site's two terms.
+template <int ICH>
+__global__ __launch_bounds__(256) void k_gradient_tiled(const DevEdge e, const DevDiag dg, const BranchDesc *branches, const double *m1,
+                                                        const double *m2, const GenGeo g, const unsigned long long *__restrict__ tipmap,
+                                                        unsigned res_stride, unsigned tiles_per_block)
+{
+  __shared__ double part[3][4][64];
+  extern __shared__ double ldiag[]; // [R][S][4]
+  const BranchDesc b = branch_get(branches, blockIdx.y);
+  branch_diag(dg, b.t, ldiag);
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // (through the scalar path by hand: branch_diag's per-lane stride has the workgroup size in a vector register, and a rate
+  // loop stepping by a vector register reads its matrix coefficients with vector loads)
+  const unsigned nw = __builtin_amdgcn_readfirstlane(blockDim.x >> 6);
+  const unsigned ntiles = (e.sites + 63u) / 64u;
+  const bool ltip = b.ltip != nullptr, rtip = b.rtip != nullptr; // wave-uniform
+  const unsigned *lsc = e.per_rate ? b.lscaler : nullptr, *rsc = e.per_rate ? b.rscaler : nullptr;
+  double a1 = 0.0, a2 = 0.0;
+
+  for (unsigned t = 0; t < tiles_per_block; ++t)
+  {
+    const unsigned tile = blockIdx.x * tiles_per_block + t;
+    if (tile >= ntiles) break; // whole workgroup
+    const unsigned n = tile * 64u + lane;
+    const bool valid = n < e.sites;
+    const unsigned nn = valid ? n : e.sites - 1;
+    const unsigned long long lmask = ltip ? tip_mask(tipmap, b.ltip[nn]) : 0ull;
+    const unsigned long long rmask = rtip ? tip_mask(tipmap, b.rtip[nn]) : 0ull;
+    const size_t base = tiled_base(nn, g.tile_sz);
+    const double *__restrict__ lx = ltip ? nullptr : b.left + base;
+    const double *__restrict__ rx = rtip ? nullptr : b.right + base;
+    const unsigned mn = e.per_rate ? scaler_min(lsc, nn, rsc, nn, g.R) : 0u;
+    const int inv = e.invariant ? e.invariant[nn] : -1;
+
+    double lk0 = 0.0, lk1 = 0.0, lk2 = 0.0;
+    for (unsigned k = wave; k < g.R; k += nw)
+    {
+      const double f = e.per_rate ? excess_factor(scaler_sum_rate(lsc, nn, rsc, nn, g.R, k), mn) : 1.0;
+      double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+      for (unsigned ch = 0; ch < g.nchunks; ++ch)
+      {
+        double A[ICH], B[ICH];
+        if (ltip)
+          contract<ICH, true>(A, m1, k, ch, g, nullptr, lmask);
+        else
+          contract<ICH, false>(A, m1, k, ch, g, lx + (size_t)k * g.S * 64, 0ull);
+        if (rtip)
+          contract<ICH, true>(B, m2, k, ch, g, nullptr, rmask);
+        else
+          contract<ICH, false>(B, m2, k, ch, g, rx + (size_t)k * g.S * 64, 0ull);
+        const double *dk = ldiag + ((size_t)k * g.S + ch * ICH) * 4; // wave-uniform addresses: LDS broadcast
+#pragma unroll
+        for (int i = 0; i < ICH; ++i)
+          if (ch * ICH + i < g.S)
+          {
+            const double s = A[i] * B[i] * f;
+            c0 = fma(s, dk[i * 4 + 0], c0);
+            c1 = fma(s, dk[i * 4 + 1], c1);
+            c2 = fma(s, dk[i * 4 + 2], c2);
+          }
+      }
+      deriv_rate_add(e.freqs, e.prop_invar, e.rate_weights, e.fidx[k], g.SP, k, inv, c0, c1, c2, lk0, lk1, lk2);
+    }
+    part[0][wave][lane] = lk0;
+    part[1][wave][lane] = lk1;
+    part[2][wave][lane] = lk2;
+    __syncthreads();
+    if (wave == 0 && valid)
+    {
+      double s0 = part[0][0][lane], s1 = part[1][0][lane], s2 = part[2][0][lane];
+      for (unsigned w = 1; w < nw; ++w)
+      {
+        s0 += part[0][w][lane];
+        s1 += part[1][w][lane];
+        s2 += part[2][w][lane];
+      }
+      deriv_site_add(s0, s1, s2, (double)e.pattern_weights[n], a1, a2);
+    }
+    __syncthreads(); // part[] is reused by the next tile
+  }
+  // only wave 0 holds sums
+  const double sums[2] = {wave == 0 ? wave_sum(a1) : 0.0, wave == 0 ? wave_sum(a2) : 0.0};
+  plc_publish_chunk<2>(e, 0u, 2u, res_stride, sums, 1u);
+}

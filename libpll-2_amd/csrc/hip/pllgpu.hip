@@ -34,6 +34,7 @@
 #include "kernels_insertion.h"
 #include "kernels_placement.h"
 #include "kernels_quartet.h"
+#include "kernels_gradient.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
@@ -3240,6 +3241,147 @@ extern "C" int pllgpu_quartet_loglikelihoods(pllgpu_ctx_t *c, const pllgpu_quart
   if (c->defer_down) HIP_TRY(stream_wait(c));
   for (unsigned i = 0; i < count; ++i)
     for (unsigned a = 0; a < 3; ++a) host_out[(size_t)3 * i + a] = rows[(size_t)a * count + i];
+  return 0;
+}
+
+// ---- the branch-length gradient (kernels_gradient.h) -------------------------------------------------------------
+// The cutting rule of pllgpu_branch_derivatives (include/pll_amd_device.h states it)
+constexpr unsigned kBranchMax = 8192; // 512 KB of descriptors: one piece of the pinned block
+static_assert(kBranchMax == PLLGPU_BRANCH_MAX && kBranchMax * sizeof(BranchDesc) <= kRingMax, "include/pll_amd_device.h states the cutting rule");
+
+// one launch for branches [first, first + n): descriptors up through the pinned block, the kernel of the shape
+static int launch_branches(pllgpu_ctx *c, DevEdge e, const DevDiag &dg, const pllgpu_branch_t *branches, unsigned first, unsigned n, unsigned count)
+{
+  const size_t bytes = (size_t)n * sizeof(BranchDesc);
+  unsigned char *dev = nullptr;
+  BranchDesc *host = reinterpret_cast<BranchDesc *>(stage_take(c, bytes, &dev));
+  std::vector<BranchDesc> pageable;
+  if (!host)
+  {
+    pageable.resize(n);
+    host = pageable.data();
+  }
+  for (unsigned i = 0; i < n; ++i)
+  {
+    const pllgpu_branch_t &q = branches[first + i];
+    BranchDesc &d = host[i];
+    // an end given by codes takes the left role, as in pllgpu_update_sumtable's callers; otherwise parent left, child right
+    const bool swap = q.child_is_tip != 0;
+    const unsigned lclv = swap ? q.child_clv : q.parent_clv, rclv = swap ? q.parent_clv : q.child_clv;
+    const int lsc = swap ? q.child_scaler : q.parent_scaler, rsc = swap ? q.parent_scaler : q.child_scaler;
+    const bool ltip = (swap ? q.child_is_tip : q.parent_is_tip) != 0;
+    // per-site counts cancel in L'/L: only the per-rate form is read
+    const bool counts = c->geo.per_rate_scalers != 0;
+    if (int rc = end_in_hbm(c, lclv, (ltip || !counts) ? -1 : lsc, ltip, d.left, d.ltip, d.lscaler)) return rc;
+    if (int rc = end_in_hbm(c, rclv, counts ? rsc : -1, false, d.right, d.rtip, d.rscaler)) return rc;
+    d.t = q.branch_length;
+    d.pad_ = 0.0;
+  }
+  HIP_TRY(hipMemcpyAsync(c->ins_cands.p, host, bytes, hipMemcpyHostToDevice, c->stream));
+  const BranchDesc *db = reinterpret_cast<const BranchDesc *>(c->ins_cands.p);
+  const double *m1 = c->pmat.p + (size_t)c->geo.prob_matrices * c->pm_stride, *m2 = m1 + c->pm_stride;
+  e.result = c->ins_results.p + first; // [d_f | dd_f][branch of the call]
+  // launch_insertions' tile walk, unchanged: the order of every sum follows from the site count alone
+  const unsigned tiles = (c->geo.sites + 63) / 64, max_blocks = 1024;
+  if (c->dna_fast)
+  {
+    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
+    const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
+    hipLaunchKernelGGL(k_gradient_dna, dim3(blocks, n), dim3(256), 0, c->stream, e, dg, db, m1, m2, count, tpw);
+  }
+  else
+  {
+    const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
+    const unsigned blocks = (tiles + tpb - 1) / tpb;
+    const unsigned nw = std::min(c->gg.R, 4u);
+    const size_t lds = (size_t)c->gg.R * c->gg.S * 4 * sizeof(double); // the branch's diag table
+    const unsigned long long *tm = tipmap_ptr(c);
+    with_ich(c->ich, [&](auto ICH) {
+      raise_lds_limit(reinterpret_cast<const void *>(&k_gradient_tiled<ICH()>), c->device, lds);
+      hipLaunchKernelGGL((k_gradient_tiled<ICH()>), dim3(blocks, n), dim3(64u * nw), lds, c->stream, e, dg, db, m1, m2, c->gg, tm, count, tpb);
+    });
+  }
+  ++c->last_launches;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pllgpu_branch_derivatives(pllgpu_ctx_t *c, const pllgpu_branch_t *branches, unsigned count, const unsigned *params_indices,
+                                         double *host_d, double *host_dd)
+{
+  CHECK_CTX_KEEP(c);
+  const pllgpu_geometry_t &g = c->geo;
+  c->last_launches = 0;
+  if (!count) return 0;
+  // everything that needs no device state, for the whole list, before held work is touched
+  if (!branches || !host_d || !params_indices) return fail(PLLGPU_EINVAL, "branch derivatives: null argument");
+  if (g.sites == 0 || g.sites != g.sites_alloc) return fail(PLLGPU_EUNSUPPORTED, "branch derivatives with ascertainment-bias entries");
+  for (unsigned k = 0; k < g.rate_cats; ++k)
+    if (params_indices[k] >= g.rate_matrices) return fail(PLLGPU_EINVAL, "params_indices[%u] = %u out of range", k, params_indices[k]);
+  for (unsigned i = 0; i < count; ++i)
+  {
+    const pllgpu_branch_t &q = branches[i];
+    if (q.parent_clv >= g.nodes || q.child_clv >= g.nodes || q.parent_scaler >= (int)g.scale_buffers || q.child_scaler >= (int)g.scale_buffers)
+      return fail(PLLGPU_EINVAL, "branch %u references an index out of range", i);
+    if ((q.parent_is_tip && q.parent_clv >= g.tips) || (q.child_is_tip && q.child_clv >= g.tips))
+      return fail(PLLGPU_EINVAL, "branch %u: an end is marked as a tip and is none", i);
+    if (q.parent_is_tip && q.child_is_tip) return fail(PLLGPU_EINVAL, "branch %u: both ends are given by codes", i);
+    if (!(q.branch_length >= 0.0) || !std::isfinite(q.branch_length)) return fail(PLLGPU_EINVAL, "branch %u: the length is negative or not finite", i);
+  }
+  for (unsigned n = 0; n < g.nodes; ++n)
+    if (c->ids[n] || c->clv_aos[n]) return fail(PLLGPU_EUNSUPPORTED, "branch derivatives over class-compressed CLVs");
+  if (!c->eigenvals.p || !c->rates.p) return fail(PLLGPU_EINVAL, "eigenvalues / category rates were not uploaded");
+  // whatever pllgpu_update_partials holds back goes out as ordinary launches: a branch may name what it produces
+  if (HOLDS_WORK(c) || !c->pending.empty())
+    if (int rc = flush_deferred(c)) return rc;
+
+  DevEdge e;
+  memset(&e, 0, sizeof e);
+  if (int rc = fill_edge_model(c, e, params_indices)) return rc;
+  DevDiag dg;
+  memset(&dg, 0, sizeof dg);
+  for (unsigned k = 0; k < g.rate_cats; ++k) dg.fidx[k] = (unsigned char)params_indices[k];
+  dg.eigenvals = c->eigenvals.p;
+  dg.rates = c->rates.p;
+  dg.prop_invar = c->prop_invar.p;
+  dg.S = g.states;
+  dg.SP = g.states_padded;
+  dg.R = g.rate_cats;
+
+  const unsigned tiles = (g.sites + 63) / 64, max_blocks = 1024;
+  unsigned blocks;
+  if (c->dna_fast)
+  {
+    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
+    blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
+  }
+  else
+  {
+    const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
+    blocks = (tiles + tpb - 1) / tpb;
+  }
+  const unsigned per_launch = (unsigned)std::min<size_t>(std::min(count, kBranchMax), std::max<size_t>(1, kInsMaxSlots / ((size_t)2 * blocks)));
+  {
+    ScratchEpoch scratch_epoch_;
+    if (c->ins_partials.ensure((size_t)2 * per_launch * blocks) || c->ins_results.ensure((size_t)2 * count) ||
+        c->ins_cands.ensure((size_t)per_launch * sizeof(BranchDesc)))
+      return PLLGPU_ENOMEM;
+    if (c->ins_tickets.cap < (size_t)2 * per_launch)
+    {
+      if (c->ins_tickets.ensure((size_t)2 * per_launch)) return PLLGPU_ENOMEM;
+      HIP_TRY(hipMemsetAsync(c->ins_tickets.p, 0, c->ins_tickets.cap * sizeof(unsigned), c->stream));
+    }
+  }
+  e.block_sums = c->ins_partials.p;
+  e.counter = c->ins_tickets.p;
+  for (unsigned first = 0; first < count; first += per_launch)
+    if (int rc = launch_branches(c, e, dg, branches, first, std::min(per_launch, count - first), count)) return rc;
+  // one copy back for all values, one wait; the kernels leave [d_f | dd_f][branch]
+  std::vector<double> rows((size_t)2 * count);
+  HIP_TRY(copy_down(c, rows.data(), c->ins_results.p, rows.size() * sizeof(double)));
+  if (c->defer_down) HIP_TRY(stream_wait(c));
+  memcpy(host_d, rows.data(), (size_t)count * sizeof(double));
+  if (host_dd) memcpy(host_dd, rows.data() + count, (size_t)count * sizeof(double));
   return 0;
 }
 

@@ -113,6 +113,13 @@ AT(pll_gpu_quartet_t, clv_index, 0);
 AT(pll_gpu_quartet_t, scaler_index, 16);
 AT(pll_gpu_quartet_t, matrix_index, 32);
 AT(pll_gpu_quartet_t, inner_matrix_index, 48);
+/* ... and one branch of pll_gpu_branch_derivatives */
+_Static_assert(sizeof(pll_gpu_branch_t) == 24, "pll_gpu_branch_t size");
+AT(pll_gpu_branch_t, parent_clv_index, 0);
+AT(pll_gpu_branch_t, parent_scaler_index, 4);
+AT(pll_gpu_branch_t, child_clv_index, 8);
+AT(pll_gpu_branch_t, child_scaler_index, 12);
+AT(pll_gpu_branch_t, branch_length, 16);
 
 /* the extension block must start 8-byte aligned directly behind the public struct */
 _Static_assert(sizeof(pll_partition_t) % 8 == 0, "extension block alignment");

@@ -163,6 +163,17 @@ class Quartet(C.Structure):
     ]
 
 
+class Branch(C.Structure):
+    """pll_gpu_branch_t (include/pll_amd.h): one branch of pll_gpu_branch_derivatives"""
+    _fields_ = [
+        ("parent_clv_index", C.c_uint),
+        ("parent_scaler_index", C.c_int),
+        ("child_clv_index", C.c_uint),
+        ("child_scaler_index", C.c_int),
+        ("branch_length", C.c_double),
+    ]
+
+
 class Newton(C.Structure):
     """pll_gpu_newton_t (include/pll_amd.h): options of pll_gpu_optimize_branch_length"""
     _fields_ = [
@@ -192,6 +203,7 @@ NEWTON_CONVERGED, NEWTON_AT_MIN, NEWTON_AT_MAX, NEWTON_STALLED, NEWTON_MAXITER =
 
 assert C.sizeof(Insertion) == 24
 assert C.sizeof(Quartet) == 52 and Quartet.scaler_index.offset == 16 and Quartet.inner_matrix_index.offset == 48
+assert C.sizeof(Branch) == 24 and Branch.child_clv_index.offset == 8 and Branch.branch_length.offset == 16
 assert C.sizeof(Newton) == 40 and C.sizeof(NewtonResult) == 40
 assert C.sizeof(Partition) == 232 and C.sizeof(Repeats) == 104 and C.sizeof(Operation) == 32
 assert C.sizeof(Parsimony) == 104 and C.sizeof(ParsBuildOp) == 12 and C.sizeof(ParsRecOp) == 16
@@ -285,6 +297,7 @@ _GPU_PROTOS = {
     "pll_gpu_placement_loglikelihoods": (
         C.c_int, [PartitionP, c_uint_p, C.c_uint, C.c_uint, C.POINTER(Insertion), C.c_uint, c_uint_p, c_double_p]),
     "pll_gpu_quartet_loglikelihoods": (C.c_int, [PartitionP, C.POINTER(Quartet), C.c_uint, c_uint_p, c_double_p]),
+    "pll_gpu_branch_derivatives": (C.c_int, [PartitionP, C.POINTER(Branch), C.c_uint, c_uint_p, c_double_p, c_double_p]),
     "pll_gpu_optimize_branch_length": (
         C.c_int, [PartitionP, C.c_int, C.c_int, c_uint_p, c_double_p, C.POINTER(Newton), C.POINTER(NewtonResult), c_double_p]),
     "pll_gpu_last_algorithmic_bytes": (C.c_double, [PartitionP]),
@@ -407,6 +420,16 @@ def make_quartets(rows):
         for k in range(4):
             o.clv_index[k], o.scaler_index[k], o.matrix_index[k] = [int(x) for x in r[k]]
         o.inner_matrix_index = int(r[4])
+    return arr
+
+
+def make_branches(rows):
+    """rows: iterable of (parent clv, parent scaler, child clv, child scaler, branch length)."""
+    rows = list(rows)
+    arr = (Branch * max(len(rows), 1))()
+    for o, r in zip(arr, rows):
+        o.parent_clv_index, o.parent_scaler_index, o.child_clv_index, o.child_scaler_index = [int(x) for x in r[:4]]
+        o.branch_length = float(r[4])
     return arr
 
 

@@ -158,6 +158,45 @@ def quartet_loglikelihoods_per_edge(lib, partition, quartets, freqs_indices, tmp
     return out
 
 
+def branch_derivatives(lib, partition, rows, params_indices, want_dd=True):
+    """pll_gpu_branch_derivatives: rows (parent clv, parent scaler, child clv, child scaler, t); a [count, 2] array
+    (d_f, dd_f of -lnL) from one call - column 1 stays NaN with want_dd=False (dd_f = NULL). libpll_amd.so only."""
+    rows = list(rows)
+    d, dd = np.full(len(rows), np.nan), np.full(len(rows), np.nan)
+    pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+    if not lib.pll_gpu_branch_derivatives(partition, api.make_branches(rows), len(rows), api.uptr(pi), api.dptr(d),
+                                          api.dptr(dd) if want_dd else None):
+        raise RuntimeError(f"pll_gpu_branch_derivatives: [{lib.errno()}] {lib.errmsg()}")
+    return np.stack([d, dd], axis=1)
+
+
+def branch_derivatives_per_edge(lib, partition, rows, params_indices, sumtable=None):
+    """the same values the way every libpll offers them: per row pll_update_sumtable into one caller-owned table, then
+    pll_compute_likelihood_derivatives at the row's length. The table (sites * rate_cats * states_padded doubles, 64-byte
+    aligned as the reference's kernels store into it) is allocated here unless the caller brings one."""
+    rows = list(rows)
+    pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+    part = partition.contents
+    own = sumtable is None
+    if own:
+        n = int(part.sites) * int(part.rate_cats) * int(part.states_padded)
+        raw = np.zeros(n + 8, dtype=np.float64)
+        off = (-raw.ctypes.data // 8) % 8
+        sumtable = raw[off:off + n]
+    out = np.empty((len(rows), 2))
+    d1, d2 = C.c_double(0), C.c_double(0)
+    for i, (pclv, psc, cclv, csc, t) in enumerate(rows):
+        if not lib.pll_update_sumtable(partition, int(pclv), int(cclv), int(psc), int(csc), api.uptr(pi), api.dptr(sumtable)):
+            raise RuntimeError(f"pll_update_sumtable: [{lib.errno()}] {lib.errmsg()}")
+        if not lib.pll_compute_likelihood_derivatives(partition, int(psc), int(csc), float(t), api.uptr(pi), api.dptr(sumtable),
+                                                      C.byref(d1), C.byref(d2)):
+            raise RuntimeError(f"pll_compute_likelihood_derivatives: [{lib.errno()}] {lib.errmsg()}")
+        out[i] = d1.value, d2.value
+    if own and lib.is_amd:
+        lib.pll_gpu_release_sumtable(partition, api.dptr(sumtable))  # the handle dies with this array
+    return out
+
+
 class Session:
     """A live partition built from a Case (kept open so benches can re-run the hot path)."""
 
