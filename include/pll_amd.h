@@ -856,6 +856,49 @@ typedef struct pll_gpu_quartet
 } pll_gpu_quartet_t;
 int pll_gpu_quartet_loglikelihoods(pll_partition_t *partition, const pll_gpu_quartet_t *quartets, unsigned int count,
                                    const unsigned int *freqs_indices, double *lnl /* [count][3] */);
+/* ---- branch supports: per-site and resampled quartet log-likelihoods ----
+ * "How well supported is each inner branch?" - the SH-like aLRT and the RELL bootstrap need, for every inner edge, the
+ * PER-SITE log-likelihoods of the tree and its two NNI neighbours and the sums of those under a few hundred to a few
+ * thousand resampled site-weight vectors. One call gives both for `count` quartets. Quartets, arrangements a = 0, 1, 2 and
+ * the tip-tip scaling rule are exactly those of pll_gpu_quartet_loglikelihoods; nothing in the partition is written (its
+ * pattern weights included). With u_{i,a}[n] the log-likelihood of site n under arrangement a of quartet i BEFORE the
+ * pattern weight:
+ *   lnl[3 i + a]                              bit for bit what pll_gpu_quartet_loglikelihoods returns for the same list;
+ *   persite[(3 i + a) * sites + n]            u_{i,a}[n] * pattern_weights[n]: the reference's persite_lnl[n] of that value's
+ *                                             pll_compute_edge_loglikelihood (src/core_likelihood.c multiplies before it stores);
+ *   resampled[(i * replicates + b) * 3 + a]   sum_n w_b[n] * u_{i,a}[n] with w_b = replicate_weights + b * sites: what the
+ *                                             reference's per-edge path returns for the value after
+ *                                             pll_set_pattern_weights(partition, w_b). The partition's own pattern weights do
+ *                                             not enter: a replicate's weights replace them. Non-finite values follow IEEE
+ *                                             arithmetic, as the reference's site_lk *= w does (a site of likelihood zero
+ *                                             under weight zero gives NaN).
+ * replicate_weights is [replicates][sites], row b one weight vector as pll_set_pattern_weights takes it; the rows are
+ * uploaded once per call and converted on the device. Each of lnl, resampled, persite may be NULL - not all three;
+ * replicates == 0 is allowed (no weights are read, resampled may be NULL: the per-site form of the existing call), and
+ * with replicates > 0 both replicate_weights and resampled are required.
+ * The sums are formed in binary64 in an order that depends on the site count alone: a resampled value has the same bits
+ * whichever other quartets and replicate rows the call carries, in any order, and from run to run.
+ * Turning lnl / resampled into an SH-aLRT or RELL percentage is a few lines on the caller's side and deliberately not
+ * part of the library ("Branch supports after the search").
+ * PLL_SUCCESS, or PLL_FAILURE with pll_errno, the usual line on stderr and all three outputs untouched. The checks, in
+ * this order: PLL_ERROR_PARAM_INVALID for a NULL partition (count == 0 then succeeds without a launch and without
+ * touching an output), for NULL quartets or freqs_indices, for replicates > 0 with NULL replicate_weights or resampled,
+ * for three NULL outputs, for any index of any quartet or a freqs_indices[k] out of range; PLL_ERROR_GPU_UNSUPPORTED
+ * for a PLL_ATTRIB_SITE_REPEATS partition and for one with an ascertainment-bias correction; PLL_ERROR_GPU_UNAVAILABLE
+ * without a device. Synchronous. pll_gpu_last_launch_count reports the launches of the call (three when nothing is cut: the
+ * quartet launch, the contraction, its reduction); long lists are cut internally (the rule and the one exception to
+ * "untouched" - persite after a device error in a later chunk: include/pll_amd_device.h,
+ * pllgpu_quartet_resampled_loglikelihoods).
+ * Not offered: site repeats and the ascertainment-bias correction (refused), weights that stay on the device between
+ * calls, replicates generated on the device. */
+int pll_gpu_quartet_resampled_loglikelihoods(pll_partition_t *partition, const pll_gpu_quartet_t *quartets, unsigned int count,
+                                             const unsigned int *freqs_indices,
+                                             const unsigned int *replicate_weights /* [replicates][sites] */, unsigned int replicates,
+                                             double *lnl /* [count][3] or NULL */, double *resampled /* [count][replicates][3] */,
+                                             double *persite /* [count][3][sites] or NULL */);
+/* diagnosis: stream-event times in ms of the last such call's first chunk - ms[0] the upload of the weights, ms[1] the
+ * quartet launch, ms[2] contraction + reduction (tools/quartet_resample_probe.py) */
+int pll_gpu_resample_last_times(const pll_partition_t *partition, double *ms /* [3] */);
 /* ---- the gradient of every branch at once --------------------------------
  * "What are the first and second derivatives of the log-likelihood with respect to this branch?" for `count` branches in
  * one call: what a simultaneous Newton or L-BFGS step on all 2T - 3 branches, HMC or variational inference over branch

@@ -251,6 +251,43 @@ typedef struct pllgpu_quartet
 int pllgpu_quartet_loglikelihoods(pllgpu_ctx_t *ctx, const pllgpu_quartet_t *quartets, unsigned int count,
                                   const unsigned int *freqs_indices, double *host_out);
 
+/* The same launch with every site's value kept, and the sums of those values under `replicates` resampled weight vectors
+ * (kernels_quartet.h: the PS instantiations; kernels_resample.h: the contraction). With value v = 3 i + a and u_v[n] the
+ * log-likelihood of site n before its pattern weight:
+ *   host_lnl[v]                                    what pllgpu_quartet_loglikelihoods gives, bit for bit (same launch geometry, same
+ *                                                  hand-off); or NULL
+ *   host_persite[v * sites + n]                    u_v[n] * pattern_weights[n], the product formed on the device; or NULL
+ *   host_resampled[(i * replicates + b) * 3 + a]   sum_n u_v[n] * weights[b * sites + n] in binary64; required iff replicates > 0
+ * weights: [replicates][sites], uploaded as they are and converted on the device; read for n < sites only. All three
+ * outputs NULL, or replicates > 0 without weights or host_resampled, is PLLGPU_EINVAL; every other check is
+ * pllgpu_quartet_loglikelihoods', in its order. Nothing the context holds is written.
+ * Stage 2 splits the sites into S = min(64, ceil(sites / 2048)) ranges of 64 ceil(ceil(sites / S) / 64) sites, a function of
+ * the site count alone, and adds the S partials of an element in range order in a second launch: the bits of a resampled
+ * value depend on the site count, its own quartet and its own row of weights alone.
+ * The cutting rule. M = PLLGPU_RESAMPLE_MAX_BYTES (the environment variable PLL_AMD_RESAMPLE_SCRATCH, read at context
+ * creation, lowers it: tests) bounds the scratch of one chunk: per-site rows, weights, partials and results. With
+ * P = 64 ceil(sites / 64), W = 4 ceil(sites / 4) and Q0 the quartets per launch of pllgpu_quartet_loglikelihoods:
+ *   q = 24 (P if replicates > 0) + 24 (sites if host_persite)         bytes of per-site rows per quartet,
+ *   Q = min(count, Q0, max(1, floor(M / 2 / q)))                        quartets per chunk (Q = min(count, Q0) if q = 0),
+ *   r = 4 W + 24 Q (S + 1)                                              bytes per replicate: weights, partials, results,
+ *   R = min(replicates, max(1, floor((M - q Q) / r)))                   replicates per chunk.
+ * Quartets are cut first, then replicates. Replicate chunks are the outer loop, so every row of weights is uploaded once
+ * per call; inside, each quartet chunk is one stage-1 launch (skipped from the second replicate chunk on when the
+ * quartets are a single chunk: its rows are still there), one contraction and one reduction launch, all counted into
+ * pllgpu_last_launch_count, then one copy back of the chunk's per-site rows and one of its sums. 61 quartets x 100 000
+ * sites x 1000 replicates is one chunk of each (765 MB with host_persite). The scratch comes from the context's block
+ * pool: a second call of the same size allocates nothing.
+ * host_lnl and host_resampled are written only on success; host_persite is written chunk by chunk, so after a DEVICE error
+ * in a later chunk it may hold the earlier ones (every argument error is found before anything is written).
+ * count == 0 succeeds without a launch. */
+#define PLLGPU_RESAMPLE_MAX_BYTES ((size_t)1 << 30)
+int pllgpu_quartet_resampled_loglikelihoods(pllgpu_ctx_t *ctx, const pllgpu_quartet_t *quartets, unsigned int count,
+                                            const unsigned int *freqs_indices, const unsigned int *weights, unsigned int replicates,
+                                            double *host_lnl, double *host_resampled, double *host_persite);
+/* diagnosis (tools/quartet_resample_probe.py): stream-event times of the last such call's first chunk, in ms -
+ * ms[0] the upload of the weights, ms[1] the stage-1 launch with its descriptors, ms[2] contraction + reduction */
+int pllgpu_resample_last_times(const pllgpu_ctx_t *ctx, double *ms);
+
 /* The first and second derivative of -lnL with respect to the branch length, for `count` branches at once
  * (kernels_gradient.h): host_d[i], host_dd[i] replace pllgpu_update_sumtable + pllgpu_likelihood_derivatives for the
  * branch between parent_clv and child_clv at branch_length - but no table exists: a (site, rate) row is formed in

@@ -109,6 +109,26 @@ __device__ __forceinline__ void publish_quartet_sums(const DevEdge &e, unsigned 
   plc_publish_chunk<3>(e, 0u, 3u, res_stride, wave_value, nsum_waves);
 }
 
+// Where the PS instantiations leave every site's value (pll_gpu_quartet_resampled_loglikelihoods);
+// value = 3 * (quartet of the launch) + arrangement. The other instantiations take the argument and never read it.
+struct QuartetSites
+{
+  double *u;        // [value][sites padded to the 64-site tile]: the site's log-likelihood BEFORE its pattern weight, 0.0 in the
+                    // padding lanes (kernels_resample.h contracts these rows with the replicates' weights); or null
+  double *weighted; // [value][sites]: that times the partition's pattern weight - the reference's persite_lnl; or null
+};
+
+// the site's value is final: both forms leave (site n of tile `tile`, a lane past the end: valid false, n clamped). The lane
+// is read from threadIdx again: one register fewer across the kernels' peak.
+__device__ __forceinline__ void quartet_site_store(const QuartetSites &ps, const DevEdge &e, int a, unsigned tile, unsigned n, bool valid, double u,
+                                                   double site)
+{
+  const size_t value = (size_t)3 * blockIdx.y + a;
+  const size_t upad = (size_t)((e.sites + 63u) / 64u) * 64u;
+  if (ps.u) ps.u[value * upad + (size_t)tile * 64u + (threadIdx.x & 63u)] = valid ? u : 0.0;
+  if (ps.weighted && valid) ps.weighted[value * e.sites + n] = site;
+}
+
 // ------------------------------------------------------------------------------------------------
 // 4 states x 4 rates: one wave per 64-site tile, the lane owns its site. The four ends are loaded (or decoded) once and
 // each end's matrix is applied once: pa[x] = P_x e_x, 4 x 16 values = 128 registers that all three arrangements share.
@@ -117,8 +137,10 @@ __device__ __forceinline__ void publish_quartet_sums(const DevEdge &e, unsigned 
 // site likelihood is mixed with the edge kernels' pieces. Two waves per SIMD (256 registers) and no scratch is the budget
 // (DESIGN.md section 5.8 has the report); what it took: the scaling mode at compile time, the per-rate form rate by rate,
 // descriptor and coefficients read where they are used, the running sums in LDS.
-template <int SM> // the partition's scaling mode (1: per site, 2: per rate), at compile time: the other mode's words cost registers
-__global__ __launch_bounds__(256, 2) void k_quartet_dna(const DevEdge e, const QuartetDesc *quartets, unsigned res_stride, unsigned tiles_per_wave)
+// PS: every site's value also leaves through `ps` (QuartetSites above), stored where it is final - far from the register peak.
+template <int SM, bool PS = false> // the partition's scaling mode (1: per site, 2: per rate), at compile time: the other mode's words cost registers
+__global__ __launch_bounds__(256, 2) void k_quartet_dna(const DevEdge e, const QuartetDesc *quartets, unsigned res_stride, unsigned tiles_per_wave,
+                                                        const QuartetSites ps)
 {
   constexpr int scale_mode = SM;
   // the lane's three running sums wait in LDS, each in a word only its lane touches: across the tile loop they would be six
@@ -205,7 +227,15 @@ __global__ __launch_bounds__(256, 2) void k_quartet_dna(const DevEdge e, const Q
       double terma = 0.0, terminv = 0.0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) dna_site_add(e, k, tr[k], rs, scal, inv, terma, terminv);
-      if (w.valid) acc[a][threadIdx.x] += dna_site_finish(e, n, terma, terminv, scal, 0);
+      if constexpr (PS)
+      {
+        const double u = finish_site(terma, terminv, scal, 0);
+        const double site = u * (double)e.pattern_weights[n];
+        quartet_site_store(ps, e, a, w.tile, n, w.valid, u, site);
+        if (w.valid) acc[a][threadIdx.x] += site;
+      }
+      else if (w.valid)
+        acc[a][threadIdx.x] += dna_site_finish(e, n, terma, terminv, scal, 0);
     }
   }
   const double sums[3] = {wave_sum(acc[0][threadIdx.x]), wave_sum(acc[1][threadIdx.x]), wave_sum(acc[2][threadIdx.x])};
@@ -225,10 +255,11 @@ __global__ __launch_bounds__(256, 2) void k_quartet_dna(const DevEdge e, const Q
 // fit): pass 2 forms the products a second time - same arithmetic, same bits - and the second node of the wave's current
 // rate passes through a slab of its own, slab[wave][state][lane]. A lane only ever reads LDS values it wrote itself.
 // Nothing is shared between the arrangements on these shapes: the four P x of a 20 x 4 tile are 160 KB.
-template <int ICH>
+// PS: as k_quartet_dna's.
+template <int ICH, bool PS = false>
 __global__ __launch_bounds__(256) void k_quartet_tiled(const DevEdge e, const QuartetDesc *quartets, const GenGeo g,
                                                        const unsigned long long *__restrict__ tipmap, unsigned res_stride, unsigned tiles_per_block,
-                                                       unsigned keep)
+                                                       unsigned keep, const QuartetSites ps)
 {
   __shared__ unsigned char flags[2][kMaxRates][64];
   __shared__ double part[2][4][64];
@@ -382,7 +413,7 @@ __global__ __launch_bounds__(256) void k_quartet_tiled(const DevEdge e, const Qu
       part[0][wave][lane] = terma;
       part[1][wave][lane] = terminv;
       __syncthreads();
-      if (wave == 0 && valid)
+      if (wave == 0 && (valid || PS))
       {
         double ta = part[0][0][lane], ti = part[1][0][lane];
         for (unsigned w = 1; w < nw; ++w)
@@ -390,10 +421,16 @@ __global__ __launch_bounds__(256) void k_quartet_tiled(const DevEdge e, const Qu
           ta += part[0][w][lane];
           ti += part[1][w][lane];
         }
-        const double site = finish_site(ta, ti, scal, 0) * (double)e.pattern_weights[n];
-        if (a == 0) acc[0] += site;
-        if (a == 1) acc[1] += site;
-        if (a == 2) acc[2] += site;
+        const double u = finish_site(ta, ti, scal, 0), pw = (double)e.pattern_weights[nn];
+        if constexpr (PS) quartet_site_store(ps, e, a, tile, nn, valid, u, u * pw);
+        if (valid)
+        {
+          // the fused form the compiler gives `acc += u * pw` while nothing else reads the product - written out, so that the
+          // instantiation that also stores the product adds the same bits
+          if (a == 0) acc[0] = fma(u, pw, acc[0]);
+          if (a == 1) acc[1] = fma(u, pw, acc[1]);
+          if (a == 2) acc[2] = fma(u, pw, acc[2]);
+        }
       }
       __syncthreads(); // flags[], part[] and node[] are reused by the next arrangement / tile
     }

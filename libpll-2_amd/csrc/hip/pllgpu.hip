@@ -34,6 +34,7 @@
 #include "kernels_insertion.h"
 #include "kernels_placement.h"
 #include "kernels_quartet.h"
+#include "kernels_resample.h"
 #include "kernels_gradient.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -230,6 +231,14 @@ struct pllgpu_ctx
   // pllgpu_placement_loglikelihoods (kernels_placement.h) uses the four above - slots and tickets per (query, candidate)
   // of a launch, the [query][candidate] results of a call - and the code rows of the call's queries
   DevBuf<unsigned char> plc_rows;
+  // pllgpu_quartet_resampled_loglikelihoods (kernels_resample.h): per-site values [value][sites padded], their weighted form
+  // [value][sites], the replicates' weights [replicate][sites padded to 4], partials [split][value][replicate], results
+  // [value][replicate] - of one chunk each, together at most resample_bytes (PLLGPU_RESAMPLE_MAX_BYTES; PLL_AMD_RESAMPLE_SCRATCH lowers it)
+  DevBuf<double> rs_u, rs_weighted, rs_part, rs_out;
+  DevBuf<unsigned> rs_w;
+  size_t resample_bytes = PLLGPU_RESAMPLE_MAX_BYTES;
+  hipEvent_t rs_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the upload, stage 1 and stage 2 of a call's first chunk
+  double rs_ms[3] = {0.0, 0.0, 0.0};
   DevBuf<unsigned char> mfma_flags;      // [op in launch][rate][entry] scaling decisions (kernels_mfma.h)
   DevBuf<double> eigenvals, rates, diag; // derivatives: [rate_matrices][SP], [R], [R][S][4]
   DevBuf<double> newton;                 // pllgpu_optimize_branch_length: the state record (NewtonState), then the trace
@@ -510,6 +519,8 @@ static void derive_geometry(pllgpu_ctx *c)
     if (atoi(v) >= 1) c->newton_batch = (unsigned)std::min(atoi(v), PLLGPU_NEWTON_MAX_ITERS);
   if (const char *v = getenv("PLL_AMD_NO_FUSE_GG"))
     if (*v && *v != '0') c->fuse_gg = false;
+  if (const char *v = getenv("PLL_AMD_RESAMPLE_SCRATCH")) // tests: bytes of scratch the resampling call may use, so that a tiny case is cut
+    if (atoll(v) >= 1) c->resample_bytes = std::min<size_t>((size_t)atoll(v), PLLGPU_RESAMPLE_MAX_BYTES);
   c->subtrees = c->dna_fast;
   if (const char *v = getenv("PLL_AMD_NO_SUBTREES")) // A/B switch: the bottom levels under site repeats go level by level
     if (*v && *v != '0') c->subtrees = false;
@@ -710,6 +721,13 @@ extern "C" void pllgpu_destroy(pllgpu_ctx_t *c)
   c->ins_results.release();
   c->ins_tickets.release();
   c->ins_cands.release();
+  c->rs_u.release();
+  c->rs_weighted.release();
+  c->rs_part.release();
+  c->rs_out.release();
+  c->rs_w.release();
+  for (hipEvent_t ev : c->rs_ev)
+    if (ev) (void)hipEventDestroy(ev);
   c->freqs.release();
   c->rate_weights.release();
   c->prop_invar.release();
@@ -3113,7 +3131,9 @@ constexpr unsigned kQuartetMax = 8192; // 1.1 MB of descriptors: one piece of th
 static_assert(kQuartetMax == PLLGPU_QUARTET_MAX && kQuartetMax * sizeof(QuartetDesc) <= kRingMax, "include/pll_amd_device.h states the cutting rule");
 
 // one launch for quartets [first, first + n): descriptors up through the pinned block, the kernel of the shape
-static int launch_quartets(pllgpu_ctx *c, DevEdge e, const pllgpu_quartet_t *quartets, unsigned first, unsigned n, unsigned count)
+// (sites: the PS instantiations, which leave every site's value through ps as well)
+static int launch_quartets(pllgpu_ctx *c, DevEdge e, const pllgpu_quartet_t *quartets, unsigned first, unsigned n, unsigned count,
+                           bool sites = false, const QuartetSites ps = QuartetSites{nullptr, nullptr})
 {
   const size_t bytes = (size_t)n * sizeof(QuartetDesc);
   unsigned char *dev = nullptr;
@@ -3148,10 +3168,12 @@ static int launch_quartets(pllgpu_ctx *c, DevEdge e, const pllgpu_quartet_t *qua
   {
     const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
     const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
-    if (c->gg.scale_mode == 2)
-      hipLaunchKernelGGL((k_quartet_dna<2>), dim3(blocks, n), dim3(256), 0, c->stream, e, dq, count, tpw);
-    else
-      hipLaunchKernelGGL((k_quartet_dna<1>), dim3(blocks, n), dim3(256), 0, c->stream, e, dq, count, tpw);
+    with_bools(sites, false, [&](auto PS, auto) {
+      if (c->gg.scale_mode == 2)
+        hipLaunchKernelGGL((k_quartet_dna<2, PS()>), dim3(blocks, n), dim3(256), 0, c->stream, e, dq, count, tpw, ps);
+      else
+        hipLaunchKernelGGL((k_quartet_dna<1, PS()>), dim3(blocks, n), dim3(256), 0, c->stream, e, dq, count, tpw, ps);
+    });
   }
   else
   {
@@ -3164,8 +3186,10 @@ static int launch_quartets(pllgpu_ctx *c, DevEdge e, const pllgpu_quartet_t *qua
     const size_t lds = keep ? 2 * node_bytes : (size_t)nw * c->gg.S * 64u * sizeof(double);
     const unsigned long long *tm = tipmap_ptr(c);
     with_ich(c->ich, [&](auto ICH) {
-      raise_lds_limit(reinterpret_cast<const void *>(&k_quartet_tiled<ICH()>), c->device, lds);
-      hipLaunchKernelGGL((k_quartet_tiled<ICH()>), dim3(blocks, n), dim3(64u * nw), lds, c->stream, e, dq, c->gg, tm, count, tpb, keep);
+      with_bools(sites, false, [&](auto PS, auto) {
+        raise_lds_limit(reinterpret_cast<const void *>(&k_quartet_tiled<ICH(), PS()>), c->device, lds);
+        hipLaunchKernelGGL((k_quartet_tiled<ICH(), PS()>), dim3(blocks, n), dim3(64u * nw), lds, c->stream, e, dq, c->gg, tm, count, tpb, keep, ps);
+      });
     });
   }
   ++c->last_launches;
@@ -3173,15 +3197,12 @@ static int launch_quartets(pllgpu_ctx *c, DevEdge e, const pllgpu_quartet_t *qua
   return 0;
 }
 
-extern "C" int pllgpu_quartet_loglikelihoods(pllgpu_ctx_t *c, const pllgpu_quartet_t *quartets, unsigned count, const unsigned *freqs_indices,
-                                             double *host_out)
+// What both quartet calls do before anything is allocated: everything that needs no device state, for the whole list,
+// before held work is touched; held work out; the model of the launches in e; B = the workgroups per quartet.
+static int quartet_call_begin(pllgpu_ctx *c, const pllgpu_quartet_t *quartets, unsigned count, const unsigned *freqs_indices, DevEdge &e,
+                              unsigned &blocks)
 {
-  CHECK_CTX_KEEP(c);
   const pllgpu_geometry_t &g = c->geo;
-  c->last_launches = 0;
-  if (!count) return 0;
-  // everything that needs no device state, for the whole list, before held work is touched
-  if (!quartets || !host_out || !freqs_indices) return fail(PLLGPU_EINVAL, "quartet log-likelihoods: null argument");
   if (g.sites == 0 || g.sites != g.sites_alloc) return fail(PLLGPU_EUNSUPPORTED, "quartet log-likelihoods with ascertainment-bias entries");
   for (unsigned k = 0; k < g.rate_cats; ++k)
     if (freqs_indices[k] >= g.rate_matrices) return fail(PLLGPU_EINVAL, "freqs_indices[%u] = %u out of range", k, freqs_indices[k]);
@@ -3203,12 +3224,10 @@ extern "C" int pllgpu_quartet_loglikelihoods(pllgpu_ctx_t *c, const pllgpu_quart
   if (HOLDS_WORK(c) || !c->pending.empty())
     if (int rc = flush_deferred(c)) return rc;
 
-  DevEdge e;
   memset(&e, 0, sizeof e);
   if (int rc = fill_edge_model(c, e, freqs_indices)) return rc;
 
   const unsigned tiles = (g.sites + 63) / 64, max_blocks = 1024;
-  unsigned blocks;
   if (c->dna_fast)
   {
     const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
@@ -3219,28 +3238,190 @@ extern "C" int pllgpu_quartet_loglikelihoods(pllgpu_ctx_t *c, const pllgpu_quart
     const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
     blocks = (tiles + tpb - 1) / tpb;
   }
-  const unsigned per_launch = (unsigned)std::min<size_t>(std::min(count, kQuartetMax), std::max<size_t>(1, kInsMaxSlots / ((size_t)3 * blocks)));
+  return 0;
+}
+
+// slots, tickets, results and descriptors of launches of up to per_launch quartets of a call of `count`
+static int quartet_scratch(pllgpu_ctx *c, unsigned per_launch, unsigned blocks, unsigned count)
+{
+  if (c->ins_partials.ensure((size_t)3 * per_launch * blocks) || c->ins_results.ensure((size_t)3 * count) ||
+      c->ins_cands.ensure((size_t)per_launch * sizeof(QuartetDesc)))
+    return PLLGPU_ENOMEM;
+  if (c->ins_tickets.cap < (size_t)3 * per_launch)
   {
-    ScratchEpoch scratch_epoch_;
-    if (c->ins_partials.ensure((size_t)3 * per_launch * blocks) || c->ins_results.ensure((size_t)3 * count) ||
-        c->ins_cands.ensure((size_t)per_launch * sizeof(QuartetDesc)))
-      return PLLGPU_ENOMEM;
-    if (c->ins_tickets.cap < (size_t)3 * per_launch)
-    {
-      if (c->ins_tickets.ensure((size_t)3 * per_launch)) return PLLGPU_ENOMEM;
-      HIP_TRY(hipMemsetAsync(c->ins_tickets.p, 0, c->ins_tickets.cap * sizeof(unsigned), c->stream));
-    }
+    if (c->ins_tickets.ensure((size_t)3 * per_launch)) return PLLGPU_ENOMEM;
+    HIP_TRY(hipMemsetAsync(c->ins_tickets.p, 0, c->ins_tickets.cap * sizeof(unsigned), c->stream));
   }
-  e.block_sums = c->ins_partials.p;
-  e.counter = c->ins_tickets.p;
-  for (unsigned first = 0; first < count; first += per_launch)
-    if (int rc = launch_quartets(c, e, quartets, first, std::min(per_launch, count - first), count)) return rc;
-  // one copy back for all values, one wait; the kernels leave [arrangement][quartet], the caller gets [quartet][3]
+  return 0;
+}
+
+// one copy back for all values, one wait; the kernels leave [arrangement][quartet], the caller gets [quartet][3]
+static int quartet_sums_down(pllgpu_ctx *c, unsigned count, double *host_out)
+{
   std::vector<double> rows((size_t)3 * count);
   HIP_TRY(copy_down(c, rows.data(), c->ins_results.p, rows.size() * sizeof(double)));
   if (c->defer_down) HIP_TRY(stream_wait(c));
   for (unsigned i = 0; i < count; ++i)
     for (unsigned a = 0; a < 3; ++a) host_out[(size_t)3 * i + a] = rows[(size_t)a * count + i];
+  return 0;
+}
+
+extern "C" int pllgpu_quartet_loglikelihoods(pllgpu_ctx_t *c, const pllgpu_quartet_t *quartets, unsigned count, const unsigned *freqs_indices,
+                                             double *host_out)
+{
+  CHECK_CTX_KEEP(c);
+  c->last_launches = 0;
+  if (!count) return 0;
+  if (!quartets || !host_out || !freqs_indices) return fail(PLLGPU_EINVAL, "quartet log-likelihoods: null argument");
+  DevEdge e;
+  unsigned blocks;
+  if (int rc = quartet_call_begin(c, quartets, count, freqs_indices, e, blocks)) return rc;
+  const unsigned per_launch = (unsigned)std::min<size_t>(std::min(count, kQuartetMax), std::max<size_t>(1, kInsMaxSlots / ((size_t)3 * blocks)));
+  {
+    ScratchEpoch scratch_epoch_;
+    if (int rc = quartet_scratch(c, per_launch, blocks, count)) return rc;
+  }
+  e.block_sums = c->ins_partials.p;
+  e.counter = c->ins_tickets.p;
+  for (unsigned first = 0; first < count; first += per_launch)
+    if (int rc = launch_quartets(c, e, quartets, first, std::min(per_launch, count - first), count)) return rc;
+  return quartet_sums_down(c, count, host_out);
+}
+
+// ---- resampled quartet log-likelihoods (kernels_resample.h) ---------------------------------
+// The cutting rule of pllgpu_quartet_resampled_loglikelihoods (include/pll_amd_device.h states it)
+struct ResampleCut
+{
+  unsigned upad, wstride, splits, split_len;
+  unsigned quartets, replicates; // per chunk
+};
+
+static ResampleCut resample_cut(unsigned sites, unsigned count, unsigned replicates, bool persite, unsigned per_launch, size_t budget)
+{
+  ResampleCut k;
+  k.upad = (sites + 63u) / 64u * 64u;
+  k.wstride = (sites + 3u) / 4u * 4u;
+  k.splits = resample_splits(sites);
+  k.split_len = resample_split_len(sites);
+  // quartets first: their per-site rows may take half of the scratch ...
+  const size_t per_quartet = (size_t)3 * sizeof(double) * ((replicates ? k.upad : 0u) + (persite ? sites : 0u));
+  k.quartets = (unsigned)std::min<size_t>(std::min(count, per_launch), std::max<size_t>(1, per_quartet ? budget / 2 / per_quartet : count));
+  // ... then replicates: a row of weights, its partials and its results take what is left
+  const size_t used = per_quartet * k.quartets, left = budget > used ? budget - used : 0;
+  const size_t per_replicate = (size_t)k.wstride * sizeof(unsigned) + (size_t)3 * k.quartets * sizeof(double) * (k.splits + 1u);
+  k.replicates = (unsigned)std::min<size_t>(replicates, std::max<size_t>(1, left / per_replicate));
+  return k;
+}
+
+static int resample_events(pllgpu_ctx *c)
+{
+  for (hipEvent_t &ev : c->rs_ev)
+    if (!ev) HIP_TRY(hipEventCreate(&ev));
+  return 0;
+}
+
+extern "C" int pllgpu_quartet_resampled_loglikelihoods(pllgpu_ctx_t *c, const pllgpu_quartet_t *quartets, unsigned count, const unsigned *freqs_indices,
+                                                       const unsigned *weights, unsigned replicates, double *host_lnl, double *host_resampled,
+                                                       double *host_persite)
+{
+  CHECK_CTX_KEEP(c);
+  const unsigned sites = c->geo.sites;
+  c->last_launches = 0;
+  if (!count) return 0;
+  if (!quartets || !freqs_indices) return fail(PLLGPU_EINVAL, "resampled quartet log-likelihoods: null argument");
+  if (replicates && (!weights || !host_resampled)) return fail(PLLGPU_EINVAL, "resampled quartet log-likelihoods: replicates without weights or results");
+  if (!host_lnl && !host_resampled && !host_persite) return fail(PLLGPU_EINVAL, "resampled quartet log-likelihoods: no output asked for");
+  DevEdge e;
+  unsigned blocks;
+  if (int rc = quartet_call_begin(c, quartets, count, freqs_indices, e, blocks)) return rc;
+
+  const unsigned per_launch = (unsigned)std::min<size_t>(std::min(count, kQuartetMax), std::max<size_t>(1, kInsMaxSlots / ((size_t)3 * blocks)));
+  const ResampleCut k = resample_cut(sites, count, replicates, host_persite != nullptr, per_launch, c->resample_bytes);
+  const bool one_quartet_chunk = k.quartets >= count;
+  {
+    ScratchEpoch scratch_epoch_;
+    if (int rc = quartet_scratch(c, k.quartets, blocks, count)) return rc;
+    if ((replicates && (c->rs_u.ensure((size_t)3 * k.quartets * k.upad) || c->rs_w.ensure((size_t)k.replicates * k.wstride) ||
+                        c->rs_part.ensure((size_t)k.splits * 3 * k.quartets * k.replicates) || c->rs_out.ensure((size_t)3 * k.quartets * k.replicates))) ||
+        (host_persite && c->rs_weighted.ensure((size_t)3 * k.quartets * sites)))
+      return PLLGPU_ENOMEM;
+  }
+  if (int rc = resample_events(c)) return rc;
+  // the small outputs are collected here and handed over once everything has succeeded
+  std::vector<double> resampled((size_t)count * replicates * 3), piece((size_t)3 * k.quartets * k.replicates);
+  e.block_sums = c->ins_partials.p;
+  e.counter = c->ins_tickets.p;
+
+  // Replicate chunks outermost: every row of weights goes up once per call. Stage 1 runs once per quartet chunk when the
+  // quartets are one chunk (its rows then stay for every replicate chunk), and again per replicate chunk otherwise - the
+  // same launch, the same bits.
+  for (unsigned r0 = 0; r0 == 0 || r0 < replicates; r0 += std::max(k.replicates, 1u))
+  {
+    const unsigned nr = replicates ? std::min(k.replicates, replicates - r0) : 0u;
+    const bool timed = r0 == 0;
+    if (timed) HIP_TRY(hipEventRecord(c->rs_ev[0], c->stream));
+    if (nr)
+    {
+      const unsigned *src = weights + (size_t)r0 * sites;
+      if (k.wstride == sites)
+        HIP_TRY(hipMemcpyAsync(c->rs_w.p, src, (size_t)nr * sites * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+      else // rows 16 bytes aligned on the device; what lies between a row's end and the next row is never read
+        HIP_TRY(hipMemcpy2DAsync(c->rs_w.p, (size_t)k.wstride * sizeof(unsigned), src, (size_t)sites * sizeof(unsigned), (size_t)sites * sizeof(unsigned),
+                                 nr, hipMemcpyHostToDevice, c->stream));
+    }
+    if (timed) HIP_TRY(hipEventRecord(c->rs_ev[1], c->stream));
+    for (unsigned first = 0; first < count; first += k.quartets)
+    {
+      const unsigned nq = std::min(k.quartets, count - first);
+      const bool want_weighted = host_persite && r0 == 0;
+      if (r0 == 0 || !one_quartet_chunk)
+      {
+        const QuartetSites ps{replicates ? c->rs_u.p : nullptr, want_weighted ? c->rs_weighted.p : nullptr};
+        if (int rc = launch_quartets(c, e, quartets, first, nq, count, true, ps)) return rc;
+      }
+      if (timed && first == 0) HIP_TRY(hipEventRecord(c->rs_ev[2], c->stream));
+      if (nr)
+      {
+        const ResampleGeo rg{3u * nq, nr, sites, k.upad, k.wstride, k.split_len};
+        hipLaunchKernelGGL(k_resample_mfma, dim3((nr + 127u) / 128u, (rg.V + 31u) / 32u, k.splits), dim3(256), 0, c->stream, c->rs_u.p, c->rs_w.p,
+                           c->rs_part.p, rg);
+        const size_t total = (size_t)rg.V * nr;
+        hipLaunchKernelGGL(k_resample_reduce, dim3((unsigned)((total + 255u) / 256u)), dim3(256), 0, c->stream, c->rs_part.p, c->rs_out.p, rg.V, nr,
+                           k.splits);
+        c->last_launches += 2;
+        HIP_TRY(hipGetLastError());
+      }
+      if (timed && first == 0) HIP_TRY(hipEventRecord(c->rs_ev[3], c->stream));
+      // one copy back per chunk: the weighted per-site rows straight into the caller's array, the sums into `resampled`
+      if (want_weighted)
+        HIP_TRY(copy_down(c, host_persite + (size_t)3 * first * sites, c->rs_weighted.p, (size_t)3 * nq * sites * sizeof(double)));
+      if (nr)
+      {
+        HIP_TRY(copy_down(c, piece.data(), c->rs_out.p, (size_t)3 * nq * nr * sizeof(double)));
+        if (c->defer_down) HIP_TRY(stream_wait(c));
+        for (unsigned i = 0; i < nq; ++i)
+          for (unsigned a = 0; a < 3; ++a)
+            for (unsigned b = 0; b < nr; ++b) resampled[((size_t)(first + i) * replicates + r0 + b) * 3 + a] = piece[((size_t)3 * i + a) * nr + b];
+      }
+    }
+  }
+  std::vector<double> lnl((size_t)3 * count);
+  if (int rc = quartet_sums_down(c, count, lnl.data())) return rc;
+  for (int t = 0; t < 3; ++t)
+  {
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->rs_ev[t], c->rs_ev[t + 1]));
+    c->rs_ms[t] = (double)ms;
+  }
+  if (host_lnl) memcpy(host_lnl, lnl.data(), lnl.size() * sizeof(double));
+  if (replicates) memcpy(host_resampled, resampled.data(), resampled.size() * sizeof(double));
+  return 0;
+}
+
+extern "C" int pllgpu_resample_last_times(const pllgpu_ctx_t *c, double *ms)
+{
+  if (!c || !ms) return fail(PLLGPU_EINVAL, "null argument");
+  for (int t = 0; t < 3; ++t) ms[t] = c->rs_ms[t];
   return 0;
 }
 

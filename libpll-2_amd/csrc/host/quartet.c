@@ -1,5 +1,7 @@
 /* quartet.c - pll_gpu_quartet_loglikelihoods: the log-likelihoods of all three pairings of the four subtrees around an
  * inner edge, for `count` quartets in one call: what ranking the NNI neighbourhood of a tree asks.
+ * pll_gpu_quartet_resampled_loglikelihoods: the same values per site and summed under resampled site weights (DESIGN.md
+ * section 5.10): what the SH-like aLRT and RELL supports of the inner branches ask. Both share every check and flush below.
  *
  * lnl[3 i + a] is what the reference returns for pll_update_partials with the two operations {tmp1, s1, x, y} and
  * {tmp2, s2, z, w} of arrangement a (src/partials.c:237-291) followed by pll_compute_edge_loglikelihood(tmp1, s1, tmp2,
@@ -11,9 +13,7 @@
  * once), the error convention. */
 #include "pll_internal.h"
 
-static const char *const who = "pll_gpu_quartet_loglikelihoods";
-
-static int fail_quartet(void)
+static int fail_quartet(const char *who)
 {
   fprintf(stderr, "libpll_amd: %s: [%d] %s\n", who, pll_errno, pll_errmsg);
   return PLL_FAILURE;
@@ -34,21 +34,12 @@ static int prepare_once(pll_partition_t *p, pll_amd_ext_t *x, unsigned char *see
   return pll_prepare_end(p, x, clv, scaler);
 }
 
-int pll_gpu_quartet_loglikelihoods(pll_partition_t *p, const pll_gpu_quartet_t *quartets, unsigned int count,
-                                   const unsigned int *freqs_indices, double *lnl)
+/* Everything a call decides after its NULL checks and before a device is needed, in the stated order: every index of the
+ * whole list, freqs_indices, the refusals, the device. PLL_SUCCESS with the partition's extension in *ext. */
+static int check_list(const char *who, pll_partition_t *p, const pll_gpu_quartet_t *quartets, unsigned int count,
+                      const unsigned int *freqs_indices, pll_amd_ext_t **ext)
 {
   unsigned int i, k, e;
-  if (!p)
-  {
-    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
-    return fail_quartet();
-  }
-  if (!count) return PLL_SUCCESS;
-  if (!quartets || !lnl || !freqs_indices)
-  {
-    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: quartets, lnl or freqs_indices is NULL", who);
-    return fail_quartet();
-  }
   for (i = 0; i < count; ++i)
   {
     const pll_gpu_quartet_t *q = &quartets[i];
@@ -57,34 +48,42 @@ int pll_gpu_quartet_loglikelihoods(pll_partition_t *p, const pll_gpu_quartet_t *
     if (!ok)
     {
       pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: quartet %u has an index out of range", who, i);
-      return fail_quartet();
+      return fail_quartet(who);
     }
   }
   for (k = 0; k < p->rate_cats; ++k)
     if (freqs_indices[k] >= p->rate_matrices)
     {
       pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: freqs_indices[%u] out of range", who, k);
-      return fail_quartet();
+      return fail_quartet(who);
     }
   if (pll_repeats_enabled(p))
   {
     /* the two nodes have no class map */
     pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: PLL_ATTRIB_SITE_REPEATS partitions are not supported", who);
-    return fail_quartet();
+    return fail_quartet(who);
   }
   if (p->attributes & PLL_ATTRIB_AB_MASK)
   {
     pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: the ascertainment-bias correction needs pll_compute_edge_loglikelihood", who);
-    return fail_quartet();
+    return fail_quartet(who);
   }
   pll_amd_ext_t *x = pll_ext(p);
   if (!x || !x->ctx)
   {
     pll_set_error(PLL_ERROR_GPU_UNAVAILABLE, "%s: no MI355X context behind this partition; this library has no CPU path", who);
-    return fail_quartet();
+    return fail_quartet(who);
   }
+  *ext = x;
+  return PLL_SUCCESS;
+}
 
-  /* inputs current on the device: the model, one span over every named matrix, every named end once */
+/* inputs current on the device: the model, one span over every named matrix, every named end once; the device layer's
+ * descriptors of the list in *out (the caller frees them) */
+static int flush_list(const char *who, pll_partition_t *p, pll_amd_ext_t *x, const pll_gpu_quartet_t *quartets, unsigned int count,
+                      pllgpu_quartet_t **out)
+{
+  unsigned int i, e;
   unsigned int lo = quartets[0].inner_matrix_index, hi = lo;
   for (i = 0; i < count; ++i)
     for (e = 0; e < 5; ++e)
@@ -100,7 +99,7 @@ int pll_gpu_quartet_loglikelihoods(pll_partition_t *p, const pll_gpu_quartet_t *
     free(seen);
     free(dev);
     pll_set_error(PLL_ERROR_MEM_ALLOC, "%s: out of memory", who);
-    return fail_quartet();
+    return fail_quartet(who);
   }
   unsigned char *seen_scaler = seen + p->nodes;
   /* a pair of two tips takes no scaling decision where the reference reads both with its tip kernels */
@@ -124,8 +123,30 @@ int pll_gpu_quartet_loglikelihoods(pll_partition_t *p, const pll_gpu_quartet_t *
   if (!ok)
   {
     free(dev);
-    return fail_quartet();
+    return fail_quartet(who);
   }
+  *out = dev;
+  return PLL_SUCCESS;
+}
+
+int pll_gpu_quartet_loglikelihoods(pll_partition_t *p, const pll_gpu_quartet_t *quartets, unsigned int count,
+                                   const unsigned int *freqs_indices, double *lnl)
+{
+  static const char *const who = "pll_gpu_quartet_loglikelihoods";
+  if (!p)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
+    return fail_quartet(who);
+  }
+  if (!count) return PLL_SUCCESS;
+  if (!quartets || !lnl || !freqs_indices)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: quartets, lnl or freqs_indices is NULL", who);
+    return fail_quartet(who);
+  }
+  pll_amd_ext_t *x = NULL;
+  pllgpu_quartet_t *dev = NULL;
+  if (!check_list(who, p, quartets, count, freqs_indices, &x) || !flush_list(who, p, x, quartets, count, &dev)) return PLL_FAILURE;
   const int rc = pllgpu_quartet_loglikelihoods(x->ctx, dev, count, freqs_indices, lnl);
   free(dev);
   if (rc != 0)
@@ -134,4 +155,52 @@ int pll_gpu_quartet_loglikelihoods(pll_partition_t *p, const pll_gpu_quartet_t *
     return PLL_FAILURE;
   }
   return PLL_SUCCESS;
+}
+
+int pll_gpu_quartet_resampled_loglikelihoods(pll_partition_t *p, const pll_gpu_quartet_t *quartets, unsigned int count,
+                                             const unsigned int *freqs_indices, const unsigned int *replicate_weights,
+                                             unsigned int replicates, double *lnl, double *resampled, double *persite)
+{
+  static const char *const who = "pll_gpu_quartet_resampled_loglikelihoods";
+  if (!p)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
+    return fail_quartet(who);
+  }
+  if (!count) return PLL_SUCCESS;
+  if (!quartets || !freqs_indices)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: quartets or freqs_indices is NULL", who);
+    return fail_quartet(who);
+  }
+  if (replicates && (!replicate_weights || !resampled))
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: replicates > 0 and replicate_weights or resampled is NULL", who);
+    return fail_quartet(who);
+  }
+  if (!lnl && !resampled && !persite)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: lnl, resampled and persite are all NULL", who);
+    return fail_quartet(who);
+  }
+  pll_amd_ext_t *x = NULL;
+  pllgpu_quartet_t *dev = NULL;
+  if (!check_list(who, p, quartets, count, freqs_indices, &x) || !flush_list(who, p, x, quartets, count, &dev)) return PLL_FAILURE;
+  /* (pattern weights travel with the model: pll_flush_model) */
+  const int rc = pllgpu_quartet_resampled_loglikelihoods(x->ctx, dev, count, freqs_indices, replicate_weights, replicates, lnl,
+                                                         replicates ? resampled : NULL, persite);
+  free(dev);
+  if (rc != 0)
+  {
+    pll_set_gpu_error(who); /* (prints its own line) */
+    return PLL_FAILURE;
+  }
+  return PLL_SUCCESS;
+}
+
+int pll_gpu_resample_last_times(const pll_partition_t *p, double *ms)
+{
+  pll_amd_ext_t *x = p ? pll_ext(p) : NULL;
+  if (!x || !x->ctx || !ms) return PLL_FAILURE;
+  return pllgpu_resample_last_times(x->ctx, ms) == 0 ? PLL_SUCCESS : PLL_FAILURE;
 }

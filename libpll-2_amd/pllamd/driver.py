@@ -158,6 +158,46 @@ def quartet_loglikelihoods_per_edge(lib, partition, quartets, freqs_indices, tmp
     return out
 
 
+def quartet_resampled_loglikelihoods(lib, partition, quartets, freqs_indices, weights, want_persite=False):
+    """pll_gpu_quartet_resampled_loglikelihoods: quartets as for quartet_loglikelihoods, weights a [replicates, sites]
+    array of site weights (None or zero rows: no replicates). Returns (lnl [Q, 3], resampled [Q, replicates, 3] or None,
+    persite [Q, 3, sites] or None) from one call. libpll_amd.so only."""
+    rows = list(quartets)
+    sites = int(partition.contents.sites)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint32).reshape(-1, sites)
+    reps = 0 if w is None else len(w)
+    lnl = np.full((len(rows), 3), np.nan)
+    res = np.full((len(rows), reps, 3), np.nan) if reps else None
+    per = np.full((len(rows), 3, sites), np.nan) if want_persite else None
+    fi = np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+    if not lib.pll_gpu_quartet_resampled_loglikelihoods(partition, api.make_quartets(rows), len(rows), api.uptr(fi),
+                                                        api.uptr(w) if reps else None, reps, api.dptr(lnl),
+                                                        api.dptr(res) if reps else None, api.dptr(per) if want_persite else None):
+        raise RuntimeError(f"pll_gpu_quartet_resampled_loglikelihoods: [{lib.errno()}] {lib.errmsg()}")
+    return lnl, res, per
+
+
+def quartet_persite_per_edge(lib, partition, quartets, freqs_indices, tmp1, tmp2, after_value=None):
+    """the reference path of quartet_loglikelihoods_per_edge with a persite_lnl buffer per value: (lnl [Q, 3],
+    persite [Q, 3, sites]) - each row what pll_compute_edge_loglikelihood stores, the partition's pattern weights
+    included. after_value as in quartet_loglikelihoods_per_edge. Either library."""
+    fi = np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+    rows = list(quartets)
+    sites = int(partition.contents.sites)
+    out = np.empty((len(rows), 3))
+    per = np.full((len(rows), 3, sites), np.nan)
+    for i, r in enumerate(rows):
+        for a, ((x, y), (z, w)) in enumerate(QUARTET_PAIRS):
+            ops = [(tmp1[0], tmp1[1], r[x][0], r[x][2], r[x][1], r[y][0], r[y][2], r[y][1]),
+                   (tmp2[0], tmp2[1], r[z][0], r[z][2], r[z][1], r[w][0], r[w][2], r[w][1])]
+            lib.pll_update_partials(partition, api.make_ops(ops), 2)
+            out[i, a] = lib.pll_compute_edge_loglikelihood(partition, tmp1[0], tmp1[1], tmp2[0], tmp2[1], int(r[4]), api.uptr(fi),
+                                                           api.dptr(per[i, a]))
+            if after_value is not None:
+                after_value(i, a, (r[x], r[y]), (r[z], r[w]))
+    return out, per
+
+
 def branch_derivatives(lib, partition, rows, params_indices, want_dd=True):
     """pll_gpu_branch_derivatives: rows (parent clv, parent scaler, child clv, child scaler, t); a [count, 2] array
     (d_f, dd_f of -lnL) from one call - column 1 stays NaN with want_dd=False (dd_f = NULL). libpll_amd.so only."""
