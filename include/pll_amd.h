@@ -889,16 +889,57 @@ int pll_gpu_quartet_loglikelihoods(pll_partition_t *partition, const pll_gpu_qua
  * quartet launch, the contraction, its reduction); long lists are cut internally (the rule and the one exception to
  * "untouched" - persite after a device error in a later chunk: include/pll_amd_device.h,
  * pllgpu_quartet_resampled_loglikelihoods).
- * Not offered: site repeats and the ascertainment-bias correction (refused), weights that stay on the device between
- * calls, replicates generated on the device. */
+ * Not offered: site repeats and the ascertainment-bias correction (refused). Replicates generated on the device:
+ * pll_gpu_quartet_rell_loglikelihoods below; weights that stay on the device between calls are not needed with it. */
 int pll_gpu_quartet_resampled_loglikelihoods(pll_partition_t *partition, const pll_gpu_quartet_t *quartets, unsigned int count,
                                              const unsigned int *freqs_indices,
                                              const unsigned int *replicate_weights /* [replicates][sites] */, unsigned int replicates,
                                              double *lnl /* [count][3] or NULL */, double *resampled /* [count][replicates][3] */,
                                              double *persite /* [count][3][sites] or NULL */);
-/* diagnosis: stream-event times in ms of the last such call's first chunk - ms[0] the upload of the weights, ms[1] the
- * quartet launch, ms[2] contraction + reduction (tools/quartet_resample_probe.py) */
+/* diagnosis: stream-event times in ms of the last such call's first chunk - ms[0] what puts the weights in place (the
+ * upload; the draw of pll_gpu_quartet_rell_loglikelihoods), ms[1] the quartet launch, ms[2] contraction + reduction
+ * (tools/quartet_resample_probe.py, tools/quartet_rell_probe.py) */
 int pll_gpu_resample_last_times(const pll_partition_t *partition, double *ms /* [3] */);
+/* ---- RELL weights drawn on the device ------------------------------------
+ * The replicate weights of a RELL or non-parametric bootstrap are random numbers: a caller need neither draw them on a
+ * CPU core nor move them. With p = the partition's pattern weights, total = sum p and cdf[n] = p[0] + ... + p[n], replicate
+ * b is `total` draws; draw j takes a 64-bit word x(seed, b, j) from a counter-based generator (Philox-4x32-10, key = the
+ * two halves of seed, counter = (j >> 1, 0, b, "RELL"); an even j takes words 0-1, an odd j words 2-3), forms
+ * r = floor(x * total / 2^64) and increments w_b[n] for the first n with cdf[n] > r. So a pattern of weight 0 is never
+ * drawn, every row adds up to `total`, a pattern's probability is p[n] / total up to total / 2^64, and row b - b the
+ * ABSOLUTE replicate number - depends on (seed, b, p) alone: not on how many rows a call asks for, how it is cut, or the
+ * run. pllamd/rell.py restates the definition in integer arithmetic; the device equals it bit for bit. For that reason no
+ * handle to weights kept on the device exists: a row is cheaper to draw again than to keep or to move.
+ *
+ * pll_gpu_draw_replicate_weights: rows [first_replicate, first_replicate + replicates) into weights [replicates][sites],
+ * each a vector as pll_set_pattern_weights takes it (a standard bootstrap's rows). The checks, in this order:
+ * PLL_ERROR_PARAM_INVALID for a NULL partition (replicates == 0 then succeeds without a launch), for NULL weights;
+ * PLL_ERROR_GPU_UNSUPPORTED for a PLL_ATTRIB_SITE_REPEATS partition and for one with an ascertainment-bias correction (the
+ * rows could not be fed to the call below); PLL_ERROR_GPU_UNAVAILABLE without a device; PLL_ERROR_PARAM_INVALID when the
+ * pattern weights add up to 0 or to 2^32 or more (the sum is formed on the device; a row's words are 32 bits).
+ *
+ * pll_gpu_quartet_rell_loglikelihoods: pll_gpu_quartet_resampled_loglikelihoods with rows 0 .. replicates - 1 of `seed` in
+ * place of replicate_weights - lnl, resampled and persite have the bits that call returns for those rows. replicate_weights
+ * here is an OUTPUT: NULL, or [replicates][sites], the rows that were used. The partition's pattern weights are what is
+ * resampled; after pll_set_pattern_weights the next call draws from the new weights.
+ * PLL_SUCCESS, or PLL_FAILURE with pll_errno, the usual line on stderr and all outputs untouched. The checks, in this
+ * order: PLL_ERROR_PARAM_INVALID for a NULL partition (count == 0 then succeeds without a launch and without touching an
+ * output), for NULL quartets or freqs_indices, for replicates > 0 with NULL resampled, for lnl, resampled and persite all
+ * NULL, for any index of any quartet or a freqs_indices[k] out of range; PLL_ERROR_GPU_UNSUPPORTED for a
+ * PLL_ATTRIB_SITE_REPEATS partition and for one with an ascertainment-bias correction; PLL_ERROR_GPU_UNAVAILABLE without a
+ * device; with replicates > 0, PLL_ERROR_PARAM_INVALID for pattern weights that add up to 0 or to 2^32 or more.
+ * replicates == 0 is pll_gpu_quartet_resampled_loglikelihoods with replicates == 0. Synchronous. pll_gpu_last_launch_count:
+ * four when nothing is cut (the draw, the quartet launch, the contraction, its reduction), one more when the pattern
+ * weights have changed since the last draw (their prefix sums). Long lists are cut by the rule of
+ * pll_gpu_quartet_resampled_loglikelihoods; the exception to "untouched" is its own - persite, and here replicate_weights,
+ * may hold earlier chunks after a device error in a later chunk (include/pll_amd_device.h). */
+int pll_gpu_draw_replicate_weights(pll_partition_t *partition, unsigned long long seed, unsigned int first_replicate,
+                                   unsigned int replicates, unsigned int *weights /* [replicates][sites] */);
+int pll_gpu_quartet_rell_loglikelihoods(pll_partition_t *partition, const pll_gpu_quartet_t *quartets, unsigned int count,
+                                        const unsigned int *freqs_indices, unsigned long long seed, unsigned int replicates,
+                                        double *lnl /* [count][3] or NULL */, double *resampled /* [count][replicates][3] */,
+                                        double *persite /* [count][3][sites] or NULL */,
+                                        unsigned int *replicate_weights /* out: [replicates][sites], or NULL */);
 /* ---- the gradient of every branch at once --------------------------------
  * "What are the first and second derivatives of the log-likelihood with respect to this branch?" for `count` branches in
  * one call: what a simultaneous Newton or L-BFGS step on all 2T - 3 branches, HMC or variational inference over branch

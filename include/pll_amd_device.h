@@ -284,9 +284,46 @@ int pllgpu_quartet_loglikelihoods(pllgpu_ctx_t *ctx, const pllgpu_quartet_t *qua
 int pllgpu_quartet_resampled_loglikelihoods(pllgpu_ctx_t *ctx, const pllgpu_quartet_t *quartets, unsigned int count,
                                             const unsigned int *freqs_indices, const unsigned int *weights, unsigned int replicates,
                                             double *host_lnl, double *host_resampled, double *host_persite);
-/* diagnosis (tools/quartet_resample_probe.py): stream-event times of the last such call's first chunk, in ms -
- * ms[0] the upload of the weights, ms[1] the stage-1 launch with its descriptors, ms[2] contraction + reduction */
+/* diagnosis (tools/quartet_resample_probe.py, tools/quartet_rell_probe.py): stream-event times of the last such call's
+ * first chunk, in ms - ms[0] what puts the chunk's weights in place (the upload, or the draw of
+ * pllgpu_quartet_rell_loglikelihoods), ms[1] the stage-1 launch with its descriptors, ms[2] contraction + reduction */
 int pllgpu_resample_last_times(const pllgpu_ctx_t *ctx, double *ms);
+
+/* Replicate weights drawn on the device (kernels_rell.h; DESIGN.md section 5.11 is the definition, pllamd/rell.py restates
+ * it in integer arithmetic and the device equals it bit for bit). With p the pattern weights the context holds
+ * (pllgpu_pattern_weights_upload), total = sum p and cdf their prefix sums, row b is `total` draws: draw j takes the 64-bit
+ * word x(seed, b, j) of Philox-4x32-10, forms r = floor(x total / 2^64) and increments the first site n with cdf[n] > r.
+ * b is the ABSOLUTE replicate number: a row is a function of (seed, b, p) and of nothing else - not the chunking, not the
+ * number of rows asked for, not the run - so no handle to weights on the device exists; rows are drawn again instead.
+ * The prefix sums (k_rell_cdf: one launch, counted, and one read-back of `total`) are formed again when
+ * pllgpu_pattern_weights_upload has run since they were last formed and kept otherwise. They live in a buffer of their own,
+ * 8 sites + 16 bytes, OUTSIDE the M of the cutting rule above. total == 0 or total >= 2^32 is PLLGPU_EINVAL (a row's words
+ * are 32 bits).
+ * k_rell_draw fills the rows of the weight scratch the contraction reads, one launch per replicate chunk (counted), grid
+ * (rows, ceil(sites / H)): a workgroup counts the draws that fall into its H sites in LDS and stores its part of the row
+ * once; no global atomics, no memset. H = 32768 sites (128 KB of LDS); the environment variable PLL_AMD_RELL_RANGE, read at context
+ * creation, lowers it to any multiple of 4 >= 4 (tests).
+ *
+ * pllgpu_replicate_weights_draw: rows [first, first + replicates) of the definition, copied to host_out
+ * [replicates][sites]. No quartets, no CLVs; held work stays held. PLLGPU_EUNSUPPORTED for ascertainment-bias entries and
+ * class-compressed CLVs, as the quartet calls (the rows could not be fed to them). The rows go through the weight scratch:
+ * R = min(replicates, max(1, floor(M / (4 W)))) rows per chunk, one draw launch and one copy back per chunk.
+ * replicates == 0 succeeds without a launch.
+ *
+ * pllgpu_quartet_rell_loglikelihoods: pllgpu_quartet_resampled_loglikelihoods with rows 0 .. replicates - 1 of the
+ * definition in place of uploaded ones - the same loop, the same cutting rule (r already holds the 4 W bytes of a row), the
+ * same launches plus one draw launch per replicate chunk: 4 launches uncut, 5 when the prefix sums are formed again. The
+ * checks, in this order, before anything is launched or written: those of pllgpu_quartet_resampled_loglikelihoods, with
+ * "replicates > 0 without host_resampled" in place of "without weights or results"; then, if replicates > 0, the sum of
+ * the pattern weights (above). replicates == 0 is that call with replicates == 0. host_weights_out: NULL, or
+ * [replicates][sites], filled with one copy back per replicate chunk - like host_persite it may hold earlier chunks after a
+ * device error in a later one. */
+int pllgpu_replicate_weights_draw(pllgpu_ctx_t *ctx, unsigned long long seed, unsigned int first, unsigned int replicates,
+                                  unsigned int *host_out);
+int pllgpu_quartet_rell_loglikelihoods(pllgpu_ctx_t *ctx, const pllgpu_quartet_t *quartets, unsigned int count,
+                                       const unsigned int *freqs_indices, unsigned long long seed, unsigned int replicates,
+                                       double *host_lnl, double *host_resampled, double *host_persite,
+                                       unsigned int *host_weights_out);
 
 /* The first and second derivative of -lnL with respect to the branch length, for `count` branches at once
  * (kernels_gradient.h): host_d[i], host_dd[i] replace pllgpu_update_sumtable + pllgpu_likelihood_derivatives for the

@@ -35,6 +35,7 @@
 #include "kernels_placement.h"
 #include "kernels_quartet.h"
 #include "kernels_resample.h"
+#include "kernels_rell.h"
 #include "kernels_gradient.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -183,6 +184,15 @@ constexpr unsigned kAscOff = 8;
 constexpr unsigned kRepHostCap = 1u << 16; // ops of one class-map call whose counts the mapped block holds (larger calls go in pieces)
 constexpr unsigned char kMap8 = 1, kMap32 = 2;
 
+// replicate weights drawn on the device (kernels_rell.h): the prefix sums of the pattern weights, then {total, sites of
+// weight != 1}; stale after every pllgpu_pattern_weights_upload. Outside resample_bytes: 8 x sites + 16 bytes of its own
+struct RellState
+{
+  DevBuf<unsigned long long> cdf;
+  bool stale = true;
+  unsigned long long total = 0, not_one = 0;
+};
+
 struct pllgpu_ctx
 {
   unsigned long long alloc_epoch = 1; // moves whenever one of this context's device blocks is (re)allocated or freed
@@ -239,10 +249,14 @@ struct pllgpu_ctx
   size_t resample_bytes = PLLGPU_RESAMPLE_MAX_BYTES;
   hipEvent_t rs_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the upload, stage 1 and stage 2 of a call's first chunk
   double rs_ms[3] = {0.0, 0.0, 0.0};
+  // replicate weights drawn on the device (kernels_rell.h): made by the first draw - a context that never draws carries
+  // the pointer and nothing else
+  RellState *rell = nullptr;
   DevBuf<unsigned char> mfma_flags;      // [op in launch][rate][entry] scaling decisions (kernels_mfma.h)
   DevBuf<double> eigenvals, rates, diag; // derivatives: [rate_matrices][SP], [R], [R][S][4]
   DevBuf<double> newton;                 // pllgpu_optimize_branch_length: the state record (NewtonState), then the trace
   unsigned newton_batch = 8;             // ... and how many evaluations it enqueues between two polls (tools/newton_device_latency.py)
+  unsigned rell_range = kRellRange;      // k_rell_draw's sites per workgroup; PLL_AMD_RELL_RANGE lowers it (tests: a small case over several ranges)
   DevBuf<double> evecs, ievecs, brlen;   // device P-matrices: [rate_matrices][S][SP] x 2, staged branch lengths
   DevBuf<unsigned> mindex;               // staged matrix indices
   DevBuf<unsigned> rep_table, rep_blocksum, rep_counts; // site-repeats class computation (kernels_repeats.h): arena, bitmaps, counts per op of a call
@@ -521,6 +535,8 @@ static void derive_geometry(pllgpu_ctx *c)
     if (*v && *v != '0') c->fuse_gg = false;
   if (const char *v = getenv("PLL_AMD_RESAMPLE_SCRATCH")) // tests: bytes of scratch the resampling call may use, so that a tiny case is cut
     if (atoll(v) >= 1) c->resample_bytes = std::min<size_t>((size_t)atoll(v), PLLGPU_RESAMPLE_MAX_BYTES);
+  if (const char *v = getenv("PLL_AMD_RELL_RANGE")) // tests: sites per workgroup of k_rell_draw, a multiple of 4
+    if (atoll(v) >= 4) c->rell_range = (unsigned)std::min<long long>(atoll(v) / 4 * 4, kRellRange);
   c->subtrees = c->dna_fast;
   if (const char *v = getenv("PLL_AMD_NO_SUBTREES")) // A/B switch: the bottom levels under site repeats go level by level
     if (*v && *v != '0') c->subtrees = false;
@@ -726,6 +742,8 @@ extern "C" void pllgpu_destroy(pllgpu_ctx_t *c)
   c->rs_part.release();
   c->rs_out.release();
   c->rs_w.release();
+  if (c->rell) c->rell->cdf.release();
+  delete c->rell;
   for (hipEvent_t ev : c->rs_ev)
     if (ev) (void)hipEventDestroy(ev);
   c->freqs.release();
@@ -1089,6 +1107,7 @@ extern "C" int pllgpu_pattern_weights_upload(pllgpu_ctx_t *c, const unsigned *ho
   CHECK_CTX_KEEP_PENDING(c); // (no input of a CLV)
   if (count > c->geo.sites_alloc) return fail(PLLGPU_EINVAL, "pattern weight count %u > %u", count, c->geo.sites_alloc);
   HIP_TRY(hipMemcpyAsync(c->pattern_weights.p, host, count * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+  if (c->rell) c->rell->stale = true; // (kernels_rell.h: the prefix sums are formed again before the next draw)
   return 0;
 }
 
@@ -3320,20 +3339,98 @@ static int resample_events(pllgpu_ctx *c)
   return 0;
 }
 
-extern "C" int pllgpu_quartet_resampled_loglikelihoods(pllgpu_ctx_t *c, const pllgpu_quartet_t *quartets, unsigned count, const unsigned *freqs_indices,
-                                                       const unsigned *weights, unsigned replicates, double *host_lnl, double *host_resampled,
-                                                       double *host_persite)
+// ---- replicate weights drawn on the device (kernels_rell.h) ----------------------------------
+// the prefix sums of the pattern weights the context holds: formed again when the weights have been uploaded since the last
+// time, kept otherwise; {total, sites of weight != 1} come back once per rebuild
+static int rell_cdf_current(pllgpu_ctx *c)
 {
-  CHECK_CTX_KEEP(c);
+  if (!c->rell) c->rell = new RellState;
+  RellState &r = *c->rell;
+  if (!r.stale) return 0;
   const unsigned sites = c->geo.sites;
-  c->last_launches = 0;
-  if (!count) return 0;
-  if (!quartets || !freqs_indices) return fail(PLLGPU_EINVAL, "resampled quartet log-likelihoods: null argument");
-  if (replicates && (!weights || !host_resampled)) return fail(PLLGPU_EINVAL, "resampled quartet log-likelihoods: replicates without weights or results");
-  if (!host_lnl && !host_resampled && !host_persite) return fail(PLLGPU_EINVAL, "resampled quartet log-likelihoods: no output asked for");
+  {
+    ScratchEpoch scratch_epoch_;
+    if (int rc = r.cdf.ensure((size_t)sites + 2u)) return rc;
+  }
+  hipLaunchKernelGGL(k_rell_cdf, dim3(1), dim3(256), 0, c->stream, c->pattern_weights.p, r.cdf.p, r.cdf.p + sites, sites);
+  ++c->last_launches;
+  HIP_TRY(hipGetLastError());
+  unsigned long long summary[2] = {0, 0};
+  HIP_TRY(copy_down(c, summary, r.cdf.p + sites, sizeof summary));
+  if (c->defer_down) HIP_TRY(stream_wait(c));
+  r.total = summary[0];
+  r.not_one = summary[1];
+  r.stale = false;
+  return 0;
+}
+
+// (after rell_cdf_current) a row's words are 32 bits, and a replicate of no draws is none
+static int rell_check_total(const pllgpu_ctx *c, const char *who)
+{
+  if (c->rell->total == 0 || (c->rell->total >> 32))
+    return fail(PLLGPU_EINVAL, "%s: the pattern weights add up to %llu, a replicate needs a sum in [1, 2^32)", who, c->rell->total);
+  return 0;
+}
+
+// rows [first, first + nr) of the definition into c->rs_w, wstride words apart: one launch, grid (rows, ranges)
+static int launch_rell_draw(pllgpu_ctx *c, unsigned long long seed, unsigned first, unsigned nr, unsigned wstride)
+{
+  const unsigned sites = c->geo.sites;
+  // (a grid's second dimension ends at 65535: only a range lowered for tests on a very long alignment could pass it)
+  const unsigned range = std::max(c->rell_range, (sites / 65535u + 4u) / 4u * 4u);
+  const unsigned ranges = (sites + range - 1u) / range;
+  const size_t lds = (size_t)std::min(range, wstride) * sizeof(unsigned);
+  const RellGeo g{seed, first, (unsigned)c->rell->total, sites, wstride, range};
+  auto launch = [&](auto kernel) {
+    raise_lds_limit(reinterpret_cast<const void *>(kernel), c->device, lds);
+    hipLaunchKernelGGL(kernel, dim3(nr, ranges), dim3(kRellThreads), lds, c->stream, c->rell->cdf.p, c->rs_w.p, g);
+  };
+  if (c->rell->not_one == 0) launch(&k_rell_draw<true>); // every weight is 1: cdf[n] = n + 1, the site is r itself
+  else launch(&k_rell_draw<false>);
+  ++c->last_launches;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// nr rows of c->rs_w to the caller's [nr][sites]: one copy, one wait
+static int rell_rows_down(pllgpu_ctx *c, unsigned *host, unsigned nr, unsigned wstride)
+{
+  const unsigned sites = c->geo.sites;
+  if (wstride == sites)
+  {
+    HIP_TRY(copy_down(c, host, c->rs_w.p, (size_t)nr * sites * sizeof(unsigned)));
+    if (c->defer_down) HIP_TRY(stream_wait(c));
+    return 0;
+  }
+  HIP_TRY(hipMemcpy2DAsync(host, (size_t)sites * sizeof(unsigned), c->rs_w.p, (size_t)wstride * sizeof(unsigned), (size_t)sites * sizeof(unsigned), nr,
+                           hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(stream_wait(c));
+  return 0;
+}
+
+// what puts a chunk's rows of weights into c->rs_w: the caller's array, or one k_rell_draw launch for the absolute rows
+// r0 .. r0 + nr of `seed` (weights == nullptr), which then go back to weights_out if that is given
+struct ResampleRows
+{
+  const unsigned *weights;
+  unsigned long long seed;
+  unsigned *weights_out;
+};
+
+// both resampling calls after their own argument checks: the quartet checks, the cut, the loop over the chunks, the copies back
+static int resampled_run(pllgpu_ctx *c, const pllgpu_quartet_t *quartets, unsigned count, const unsigned *freqs_indices, const ResampleRows &rows,
+                         unsigned replicates, double *host_lnl, double *host_resampled, double *host_persite)
+{
+  const unsigned sites = c->geo.sites;
+  const unsigned *weights = rows.weights;
   DevEdge e;
   unsigned blocks;
   if (int rc = quartet_call_begin(c, quartets, count, freqs_indices, e, blocks)) return rc;
+  if (!weights && replicates)
+  {
+    if (int rc = rell_cdf_current(c)) return rc;
+    if (int rc = rell_check_total(c, "rell quartet log-likelihoods")) return rc;
+  }
 
   const unsigned per_launch = (unsigned)std::min<size_t>(std::min(count, kQuartetMax), std::max<size_t>(1, kInsMaxSlots / ((size_t)3 * blocks)));
   const ResampleCut k = resample_cut(sites, count, replicates, host_persite != nullptr, per_launch, c->resample_bytes);
@@ -3360,7 +3457,11 @@ extern "C" int pllgpu_quartet_resampled_loglikelihoods(pllgpu_ctx_t *c, const pl
     const unsigned nr = replicates ? std::min(k.replicates, replicates - r0) : 0u;
     const bool timed = r0 == 0;
     if (timed) HIP_TRY(hipEventRecord(c->rs_ev[0], c->stream));
-    if (nr)
+    if (nr && !weights)
+    {
+      if (int rc = launch_rell_draw(c, rows.seed, r0, nr, k.wstride)) return rc;
+    }
+    else if (nr)
     {
       const unsigned *src = weights + (size_t)r0 * sites;
       if (k.wstride == sites)
@@ -3370,6 +3471,8 @@ extern "C" int pllgpu_quartet_resampled_loglikelihoods(pllgpu_ctx_t *c, const pl
                                  nr, hipMemcpyHostToDevice, c->stream));
     }
     if (timed) HIP_TRY(hipEventRecord(c->rs_ev[1], c->stream));
+    if (nr && rows.weights_out) // one copy back per replicate chunk
+      if (int rc = rell_rows_down(c, rows.weights_out + (size_t)r0 * sites, nr, k.wstride)) return rc;
     for (unsigned first = 0; first < count; first += k.quartets)
     {
       const unsigned nq = std::min(k.quartets, count - first);
@@ -3415,6 +3518,61 @@ extern "C" int pllgpu_quartet_resampled_loglikelihoods(pllgpu_ctx_t *c, const pl
   }
   if (host_lnl) memcpy(host_lnl, lnl.data(), lnl.size() * sizeof(double));
   if (replicates) memcpy(host_resampled, resampled.data(), resampled.size() * sizeof(double));
+  return 0;
+}
+
+extern "C" int pllgpu_quartet_resampled_loglikelihoods(pllgpu_ctx_t *c, const pllgpu_quartet_t *quartets, unsigned count, const unsigned *freqs_indices,
+                                                       const unsigned *weights, unsigned replicates, double *host_lnl, double *host_resampled,
+                                                       double *host_persite)
+{
+  CHECK_CTX_KEEP(c);
+  c->last_launches = 0;
+  if (!count) return 0;
+  if (!quartets || !freqs_indices) return fail(PLLGPU_EINVAL, "resampled quartet log-likelihoods: null argument");
+  if (replicates && (!weights || !host_resampled)) return fail(PLLGPU_EINVAL, "resampled quartet log-likelihoods: replicates without weights or results");
+  if (!host_lnl && !host_resampled && !host_persite) return fail(PLLGPU_EINVAL, "resampled quartet log-likelihoods: no output asked for");
+  return resampled_run(c, quartets, count, freqs_indices, ResampleRows{weights, 0ull, nullptr}, replicates, host_lnl, host_resampled, host_persite);
+}
+
+extern "C" int pllgpu_quartet_rell_loglikelihoods(pllgpu_ctx_t *c, const pllgpu_quartet_t *quartets, unsigned count, const unsigned *freqs_indices,
+                                                  unsigned long long seed, unsigned replicates, double *host_lnl, double *host_resampled,
+                                                  double *host_persite, unsigned *host_weights_out)
+{
+  CHECK_CTX_KEEP(c);
+  c->last_launches = 0;
+  if (!count) return 0;
+  if (!quartets || !freqs_indices) return fail(PLLGPU_EINVAL, "rell quartet log-likelihoods: null argument");
+  if (replicates && !host_resampled) return fail(PLLGPU_EINVAL, "rell quartet log-likelihoods: replicates without results");
+  if (!host_lnl && !host_resampled && !host_persite) return fail(PLLGPU_EINVAL, "rell quartet log-likelihoods: no output asked for");
+  return resampled_run(c, quartets, count, freqs_indices, ResampleRows{nullptr, seed, host_weights_out}, replicates, host_lnl, host_resampled,
+                       host_persite);
+}
+
+extern "C" int pllgpu_replicate_weights_draw(pllgpu_ctx_t *c, unsigned long long seed, unsigned first, unsigned replicates, unsigned *host_out)
+{
+  CHECK_CTX_KEEP(c); // (no CLV is read: held work stays held)
+  const pllgpu_geometry_t &g = c->geo;
+  c->last_launches = 0;
+  if (!replicates) return 0;
+  if (!host_out) return fail(PLLGPU_EINVAL, "replicate weights: null argument");
+  // rows that the quartet call could not take are not handed out: its refusals, with its status
+  if (g.sites == 0 || g.sites != g.sites_alloc) return fail(PLLGPU_EUNSUPPORTED, "replicate weights with ascertainment-bias entries");
+  for (unsigned n = 0; n < g.nodes; ++n)
+    if (c->ids[n] || c->clv_aos[n]) return fail(PLLGPU_EUNSUPPORTED, "replicate weights over class-compressed CLVs");
+  if (int rc = rell_cdf_current(c)) return rc;
+  if (int rc = rell_check_total(c, "replicate weights")) return rc;
+  const unsigned wstride = (g.sites + 3u) / 4u * 4u;
+  const unsigned per_chunk = (unsigned)std::min<size_t>(replicates, std::max<size_t>(1, c->resample_bytes / ((size_t)wstride * sizeof(unsigned))));
+  {
+    ScratchEpoch scratch_epoch_;
+    if (int rc = c->rs_w.ensure((size_t)per_chunk * wstride)) return rc;
+  }
+  for (unsigned r0 = 0; r0 < replicates; r0 += per_chunk)
+  {
+    const unsigned nr = std::min(per_chunk, replicates - r0);
+    if (int rc = launch_rell_draw(c, seed, first + r0, nr, wstride)) return rc;
+    if (int rc = rell_rows_down(c, host_out + (size_t)r0 * g.sites, nr, wstride)) return rc;
+  }
   return 0;
 }
 

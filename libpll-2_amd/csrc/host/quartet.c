@@ -2,6 +2,8 @@
  * inner edge, for `count` quartets in one call: what ranking the NNI neighbourhood of a tree asks.
  * pll_gpu_quartet_resampled_loglikelihoods: the same values per site and summed under resampled site weights (DESIGN.md
  * section 5.10): what the SH-like aLRT and RELL supports of the inner branches ask. Both share every check and flush below.
+ * pll_gpu_quartet_rell_loglikelihoods: that call with the replicates' weights drawn on the device from a seed, and
+ * pll_gpu_draw_replicate_weights: those rows alone.
  *
  * lnl[3 i + a] is what the reference returns for pll_update_partials with the two operations {tmp1, s1, x, y} and
  * {tmp2, s2, z, w} of arrangement a (src/partials.c:237-291) followed by pll_compute_edge_loglikelihood(tmp1, s1, tmp2,
@@ -196,6 +198,91 @@ int pll_gpu_quartet_resampled_loglikelihoods(pll_partition_t *p, const pll_gpu_q
     return PLL_FAILURE;
   }
   return PLL_SUCCESS;
+}
+
+/* the sum of the pattern weights is known on the device only: its refusal is an argument error like the host's own */
+static int fail_device(const char *who, int rc)
+{
+  if (rc != PLLGPU_EINVAL)
+  {
+    pll_set_gpu_error(who); /* (prints its own line) */
+    return PLL_FAILURE;
+  }
+  pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: %s", who, pllgpu_last_error());
+  return fail_quartet(who);
+}
+
+int pll_gpu_quartet_rell_loglikelihoods(pll_partition_t *p, const pll_gpu_quartet_t *quartets, unsigned int count,
+                                        const unsigned int *freqs_indices, unsigned long long seed, unsigned int replicates, double *lnl,
+                                        double *resampled, double *persite, unsigned int *replicate_weights)
+{
+  static const char *const who = "pll_gpu_quartet_rell_loglikelihoods";
+  if (!p)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
+    return fail_quartet(who);
+  }
+  if (!count) return PLL_SUCCESS;
+  if (!quartets || !freqs_indices)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: quartets or freqs_indices is NULL", who);
+    return fail_quartet(who);
+  }
+  if (replicates && !resampled)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: replicates > 0 and resampled is NULL", who);
+    return fail_quartet(who);
+  }
+  if (!lnl && !resampled && !persite)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: lnl, resampled and persite are all NULL", who);
+    return fail_quartet(who);
+  }
+  pll_amd_ext_t *x = NULL;
+  pllgpu_quartet_t *dev = NULL;
+  if (!check_list(who, p, quartets, count, freqs_indices, &x) || !flush_list(who, p, x, quartets, count, &dev)) return PLL_FAILURE;
+  /* (pattern weights travel with the model: pll_flush_model - the device forms their prefix sums again after an upload) */
+  const int rc = pllgpu_quartet_rell_loglikelihoods(x->ctx, dev, count, freqs_indices, seed, replicates, lnl, replicates ? resampled : NULL,
+                                                    persite, replicates ? replicate_weights : NULL);
+  free(dev);
+  return rc != 0 ? fail_device(who, rc) : PLL_SUCCESS;
+}
+
+int pll_gpu_draw_replicate_weights(pll_partition_t *p, unsigned long long seed, unsigned int first_replicate, unsigned int replicates,
+                                   unsigned int *weights)
+{
+  static const char *const who = "pll_gpu_draw_replicate_weights";
+  if (!p)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
+    return fail_quartet(who);
+  }
+  if (!replicates) return PLL_SUCCESS;
+  if (!weights)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: weights is NULL", who);
+    return fail_quartet(who);
+  }
+  /* rows the quartet call could not take are not handed out: its refusals */
+  if (pll_repeats_enabled(p))
+  {
+    pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: PLL_ATTRIB_SITE_REPEATS partitions are not supported", who);
+    return fail_quartet(who);
+  }
+  if (p->attributes & PLL_ATTRIB_AB_MASK)
+  {
+    pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: partitions with an ascertainment-bias correction are not supported", who);
+    return fail_quartet(who);
+  }
+  pll_amd_ext_t *x = pll_ext(p);
+  if (!x || !x->ctx)
+  {
+    pll_set_error(PLL_ERROR_GPU_UNAVAILABLE, "%s: no MI355X context behind this partition; this library has no CPU path", who);
+    return fail_quartet(who);
+  }
+  if (!pll_flush_model(p, x)) return fail_quartet(who); /* the device's copy of the pattern weights is the partition's */
+  const int rc = pllgpu_replicate_weights_draw(x->ctx, seed, first_replicate, replicates, weights);
+  return rc != 0 ? fail_device(who, rc) : PLL_SUCCESS;
 }
 
 int pll_gpu_resample_last_times(const pll_partition_t *p, double *ms)

@@ -177,6 +177,34 @@ def quartet_resampled_loglikelihoods(lib, partition, quartets, freqs_indices, we
     return lnl, res, per
 
 
+def quartet_rell_loglikelihoods(lib, partition, quartets, freqs_indices, seed, replicates, want_persite=False, want_weights=False):
+    """pll_gpu_quartet_rell_loglikelihoods: quartet_resampled_loglikelihoods with rows 0 .. replicates - 1 of `seed` drawn on
+    the device (pllamd.rell is their definition). Returns (lnl [Q, 3], resampled [Q, replicates, 3] or None, persite
+    [Q, 3, sites] or None, weights uint32 [replicates, sites] or None) from one call. libpll_amd.so only."""
+    rows = list(quartets)
+    sites, reps = int(partition.contents.sites), int(replicates)
+    lnl = np.full((len(rows), 3), np.nan)
+    res = np.full((len(rows), reps, 3), np.nan) if reps else None
+    per = np.full((len(rows), 3, sites), np.nan) if want_persite else None
+    w = np.full((reps, sites), 0xFFFFFFFF, dtype=np.uint32) if want_weights and reps else None
+    fi = np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+    if not lib.pll_gpu_quartet_rell_loglikelihoods(partition, api.make_quartets(rows), len(rows), api.uptr(fi), int(seed), reps, api.dptr(lnl),
+                                                   api.dptr(res) if reps else None, api.dptr(per) if want_persite else None,
+                                                   api.uptr(w) if w is not None else None):
+        raise RuntimeError(f"pll_gpu_quartet_rell_loglikelihoods: [{lib.errno()}] {lib.errmsg()}")
+    return lnl, res, per, w
+
+
+def draw_replicate_weights(lib, partition, seed, first, replicates):
+    """pll_gpu_draw_replicate_weights: rows [first, first + replicates) of `seed` for the partition's pattern weights, a
+    uint32 [replicates, sites] array (pllamd.rell.replicate_weights is their definition). libpll_amd.so only."""
+    sites = int(partition.contents.sites)
+    w = np.full((int(replicates), sites), 0xFFFFFFFF, dtype=np.uint32)
+    if not lib.pll_gpu_draw_replicate_weights(partition, int(seed), int(first), int(replicates), api.uptr(w) if len(w) else None):
+        raise RuntimeError(f"pll_gpu_draw_replicate_weights: [{lib.errno()}] {lib.errmsg()}")
+    return w
+
+
 def quartet_persite_per_edge(lib, partition, quartets, freqs_indices, tmp1, tmp2, after_value=None):
     """the reference path of quartet_loglikelihoods_per_edge with a persite_lnl buffer per value: (lnl [Q, 3],
     persite [Q, 3, sites]) - each row what pll_compute_edge_loglikelihood stores, the partition's pattern weights
