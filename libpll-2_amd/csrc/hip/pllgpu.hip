@@ -2385,39 +2385,55 @@ static int launch_edge_mfma(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather)
   return 0;
 }
 
+// The tile walk of every kernel that sums over the sites (the edge evaluation and each batched call): the grid's x axis
+// and the tiles each wave or workgroup walks. The order of every sum follows from it, so it depends on the site count
+// and the shape alone, and this is the only place it is written.
+struct TileWalk
+{
+  unsigned blocks, tiles_per;
+};
+
+static TileWalk tile_walk(const pllgpu_ctx *c)
+{
+  const unsigned tiles = (c->geo.sites + 63) / 64, max_blocks = 1024;
+  TileWalk w;
+  if (c->dna_fast)
+  {
+    // 4 waves = 4 tiles per workgroup, tiles_per consecutive tiles per wave
+    w.tiles_per = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
+    w.blocks = (tiles + 4 * w.tiles_per - 1) / (4 * w.tiles_per);
+  }
+  else
+  {
+    // one tile per workgroup pass (the waves split its rate categories), tiles_per tiles per workgroup
+    w.tiles_per = (tiles + max_blocks - 1) / max_blocks;
+    w.blocks = (tiles + w.tiles_per - 1) / w.tiles_per;
+  }
+  return w;
+}
+
 // the evaluation's one launch: which kernel family takes it
 static int launch_edge(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather, const TailCall *tail, const ChainTailCall *ctail)
 {
-  const unsigned tiles = (c->geo.sites + 63) / 64;
-  const unsigned max_blocks = 1024;
   if (c->use_mfma && c->mfma_ng == 16 && !e.is_root) return launch_edge_mfma(c, e, ctip, gather);
   if (c->dna_fast && ctail)
   {
     launch_edge_chain(c, e, *ctail);
     ++c->last_launches;
+    return 0;
+  }
+  const TileWalk w = tile_walk(c);
+  if (c->dna_fast && tail)
+  {
+    if (int rc = launch_edge_tail(c, e, *tail, w.blocks, w.tiles_per)) return rc;
+    ++c->last_launches;
   }
   else if (c->dna_fast)
-  {
-    // 4 waves = 4 tiles per workgroup, tpw consecutive tiles per wave
-    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
-    const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
-    if (tail)
-    {
-      if (int rc = launch_edge_tail(c, e, *tail, blocks, tpw)) return rc;
-      ++c->last_launches;
-    }
-    else
-      with_bools(ctip, gather, [&](auto CT, auto GA) {
-        hipLaunchKernelGGL((k_edge_dna<CT(), GA()>), dim3(blocks), dim3(256), 0, c->stream, e, tpw);
-      });
-  }
+    with_bools(ctip, gather, [&](auto CT, auto GA) {
+      hipLaunchKernelGGL((k_edge_dna<CT(), GA()>), dim3(w.blocks), dim3(256), 0, c->stream, e, w.tiles_per);
+    });
   else
-  {
-    // one tile per workgroup pass (the waves split its rate categories), tpw tiles per workgroup
-    const unsigned tpw = (tiles + max_blocks - 1) / max_blocks;
-    const unsigned blocks = (tiles + tpw - 1) / tpw;
-    with_ich(c->ich, [&](auto ICH) { launch_edge_generic<ICH()>(c, e, blocks, tpw, ctip, gather); });
-  }
+    with_ich(c->ich, [&](auto ICH) { launch_edge_generic<ICH()>(c, e, w.blocks, w.tiles_per, ctip, gather); });
   return 0;
 }
 
@@ -2853,6 +2869,98 @@ struct ScratchEpoch
   ~ScratchEpoch() { t_epoch = prev; }
 };
 
+// ---- what every batched call is made of ---------------------------------------------------
+// The refusals and checks that need no device state, each with the call's noun in its message. A call runs them and
+// its own list checks in its own order: the order decides which error a doubly wrong input reports.
+static int refuse_ascertainment(const pllgpu_ctx *c, const char *noun)
+{
+  if (c->geo.sites == 0 || c->geo.sites != c->geo.sites_alloc) return fail(PLLGPU_EUNSUPPORTED, "%s with ascertainment-bias entries", noun);
+  return 0;
+}
+
+static int check_rate_indices(const pllgpu_ctx *c, const char *name, const unsigned *indices)
+{
+  for (unsigned k = 0; k < c->geo.rate_cats; ++k)
+    if (indices[k] >= c->geo.rate_matrices) return fail(PLLGPU_EINVAL, "%s[%u] = %u out of range", name, k, indices[k]);
+  return 0;
+}
+
+static int refuse_compressed(const pllgpu_ctx *c, const char *noun)
+{
+  for (unsigned n = 0; n < c->geo.nodes; ++n)
+    if (c->ids[n] || c->clv_aos[n]) return fail(PLLGPU_EUNSUPPORTED, "%s over class-compressed CLVs", noun);
+  return 0;
+}
+
+// Last of the preamble, the first step that touches device state: whatever pllgpu_update_partials holds back goes out as
+// ordinary launches (an item of the list may name what it produces), then the model of the launches in a zeroed e.
+static int batch_edge(pllgpu_ctx *c, DevEdge &e, const unsigned *rate_indices)
+{
+  if (HOLDS_WORK(c) || !c->pending.empty())
+    if (int rc = flush_deferred(c)) return rc;
+  memset(&e, 0, sizeof e);
+  return fill_edge_model(c, e, rate_indices);
+}
+
+// The cutting rule of the one-level calls (include/pll_amd_device.h states it): items per launch, each of `values` sums
+// over `blocks` workgroups
+static unsigned batch_items(unsigned count, unsigned max_items, unsigned values, unsigned blocks)
+{
+  return (unsigned)std::min<size_t>(std::min(count, max_items), std::max<size_t>(1, kInsMaxSlots / ((size_t)values * blocks)));
+}
+
+// The scratch of a call: `slots` partial sums and `tickets` tickets per launch, `results` values per call, `desc_bytes` of
+// descriptors per launch. Tickets are zero between launches; new ones are zeroed here.
+static int batch_scratch(pllgpu_ctx *c, DevEdge &e, size_t slots, size_t tickets, size_t results, size_t desc_bytes)
+{
+  ScratchEpoch scratch_epoch_;
+  if (c->ins_partials.ensure(slots) || c->ins_results.ensure(results) || c->ins_cands.ensure(desc_bytes)) return PLLGPU_ENOMEM;
+  if (c->ins_tickets.cap < tickets)
+  {
+    if (c->ins_tickets.ensure(tickets)) return PLLGPU_ENOMEM;
+    HIP_TRY(hipMemsetAsync(c->ins_tickets.p, 0, c->ins_tickets.cap * sizeof(unsigned), c->stream));
+  }
+  e.block_sums = c->ins_partials.p;
+  e.counter = c->ins_tickets.p;
+  return 0;
+}
+
+// n descriptors to device_dst: through the pinned block, or from pageable memory that lives until the copy call has
+// returned. fill(T &d, unsigned i) writes the i-th; a status other than 0 ends the upload.
+template <class T, class Fill>
+static int stage_up(pllgpu_ctx *c, void *device_dst, unsigned n, Fill fill)
+{
+  const size_t bytes = (size_t)n * sizeof(T);
+  unsigned char *dev = nullptr;
+  T *host = reinterpret_cast<T *>(stage_take(c, bytes, &dev));
+  std::vector<T> pageable;
+  if (!host)
+  {
+    pageable.resize(n);
+    host = pageable.data();
+  }
+  for (unsigned i = 0; i < n; ++i)
+    if (int rc = fill(host[i], i)) return rc;
+  HIP_TRY(hipMemcpyAsync(device_dst, host, bytes, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+// how every launch helper ends
+static int launched(pllgpu_ctx *c)
+{
+  ++c->last_launches;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// how every call ends: n values of ins_results to the host in one copy, one wait
+static int results_down(pllgpu_ctx *c, double *host, size_t n)
+{
+  HIP_TRY(copy_down(c, host, c->ins_results.p, n * sizeof(double)));
+  if (c->defer_down) HIP_TRY(stream_wait(c));
+  return 0;
+}
+
 static int check_insertion_end(const pllgpu_ctx *c, unsigned clv, int scaler, unsigned matrix, bool is_tip, const char *what, unsigned i)
 {
   const pllgpu_geometry_t &g = c->geo;
@@ -2862,45 +2970,42 @@ static int check_insertion_end(const pllgpu_ctx *c, unsigned clv, int scaler, un
   return 0;
 }
 
-// one launch for candidates [first, first + n): descriptors up through the pinned block, the kernel of the shape
-static int launch_insertions(pllgpu_ctx *c, DevEdge e, const pllgpu_insertion_t *cands, unsigned first, unsigned n, bool stip)
+// the candidate list of the insertion and placement calls
+static int check_candidates(const pllgpu_ctx *c, const pllgpu_insertion_t *cands, unsigned count)
 {
-  const size_t bytes = (size_t)n * sizeof(InsCand);
-  unsigned char *dev = nullptr;
-  InsCand *host = reinterpret_cast<InsCand *>(stage_take(c, bytes, &dev));
-  std::vector<InsCand> pageable;
-  if (!host)
+  for (unsigned i = 0; i < count; ++i)
   {
-    pageable.resize(n);
-    host = pageable.data();
+    if (int rc = check_insertion_end(c, cands[i].child1_clv, cands[i].child1_scaler, cands[i].child1_matrix, cands[i].child1_is_tip != 0, "child1", i)) return rc;
+    if (int rc = check_insertion_end(c, cands[i].child2_clv, cands[i].child2_scaler, cands[i].child2_matrix, cands[i].child2_is_tip != 0, "child2", i)) return rc;
   }
-  for (unsigned i = 0; i < n; ++i)
-  {
+  return 0;
+}
+
+// the descriptors of candidates [first, first + n) on the device: the only place an InsCand is filled
+static int upload_candidates(pllgpu_ctx *c, const pllgpu_insertion_t *cands, unsigned first, unsigned n)
+{
+  return stage_up<InsCand>(c, c->ins_cands.p, n, [&](InsCand &d, unsigned i) {
     const pllgpu_insertion_t &q = cands[first + i];
-    InsCand &d = host[i];
     if (int rc = end_in_hbm(c, q.child1_clv, q.child1_is_tip ? -1 : q.child1_scaler, q.child1_is_tip != 0, d.left, d.ltip, d.lscaler)) return rc;
     if (int rc = end_in_hbm(c, q.child2_clv, q.child2_is_tip ? -1 : q.child2_scaler, q.child2_is_tip != 0, d.right, d.rtip, d.rscaler)) return rc;
     d.lmat = c->pmat.p + (size_t)q.child1_matrix * c->pm_stride;
     d.rmat = c->pmat.p + (size_t)q.child2_matrix * c->pm_stride;
-  }
-  HIP_TRY(hipMemcpyAsync(c->ins_cands.p, host, bytes, hipMemcpyHostToDevice, c->stream));
+    return 0;
+  });
+}
+
+// one launch for candidates [first, first + n): their descriptors up, the kernel of the shape
+static int launch_insertions(pllgpu_ctx *c, DevEdge e, const TileWalk &w, const pllgpu_insertion_t *cands, unsigned first, unsigned n, bool stip)
+{
+  if (int rc = upload_candidates(c, cands, first, n)) return rc;
   const InsCand *dc = reinterpret_cast<const InsCand *>(c->ins_cands.p);
   e.result = c->ins_results.p + first;
-  // the tile walk of launch_edge: the grid's x axis, and with it the order of every candidate's sum, follows from the
-  // site count alone
-  const unsigned tiles = (c->geo.sites + 63) / 64, max_blocks = 1024;
   if (c->dna_fast)
-  {
-    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
-    const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
     with_bools(stip, false, [&](auto ST, auto) {
-      hipLaunchKernelGGL((k_insertion_dna<ST()>), dim3(blocks, n), dim3(256), 0, c->stream, e, dc, c->gg.scale_mode, tpw);
+      hipLaunchKernelGGL((k_insertion_dna<ST()>), dim3(w.blocks, n), dim3(256), 0, c->stream, e, dc, c->gg.scale_mode, w.tiles_per);
     });
-  }
   else
   {
-    const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
-    const unsigned blocks = (tiles + tpb - 1) / tpb;
     const unsigned threads = 64u * std::min(c->gg.R, 4u);
     size_t lds = (size_t)c->gg.tile_sz * sizeof(double);
     const unsigned keep = lds <= kInsLdsMax ? 1u : 0u;
@@ -2909,13 +3014,11 @@ static int launch_insertions(pllgpu_ctx *c, DevEdge e, const pllgpu_insertion_t 
     with_ich(c->ich, [&](auto ICH) {
       with_bools(stip, false, [&](auto ST, auto) {
         raise_lds_limit(reinterpret_cast<const void *>(&k_insertion_tiled<ICH(), ST()>), c->device, lds);
-        hipLaunchKernelGGL((k_insertion_tiled<ICH(), ST()>), dim3(blocks, n), dim3(threads), lds, c->stream, e, dc, c->gg, tm, tpb, keep);
+        hipLaunchKernelGGL((k_insertion_tiled<ICH(), ST()>), dim3(w.blocks, n), dim3(threads), lds, c->stream, e, dc, c->gg, tm, w.tiles_per, keep);
       });
     });
   }
-  ++c->last_launches;
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launched(c);
 }
 
 extern "C" int pllgpu_insertion_loglikelihoods(pllgpu_ctx_t *c, unsigned subtree_clv, int subtree_scaler, unsigned subtree_matrix,
@@ -2926,88 +3029,28 @@ extern "C" int pllgpu_insertion_loglikelihoods(pllgpu_ctx_t *c, unsigned subtree
   const pllgpu_geometry_t &g = c->geo;
   c->last_launches = 0;
   if (!count) return 0;
+  static const char noun[] = "insertion log-likelihoods";
   // everything that needs no device state, for the whole list, before held work is touched
-  if (!cands || !host_out || !freqs_indices) return fail(PLLGPU_EINVAL, "insertion log-likelihoods: null argument");
-  if (g.sites == 0 || g.sites != g.sites_alloc) return fail(PLLGPU_EUNSUPPORTED, "insertion log-likelihoods with ascertainment-bias entries");
+  if (!cands || !host_out || !freqs_indices) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
+  if (int rc = refuse_ascertainment(c, noun)) return rc;
   if (subtree_clv >= g.nodes || subtree_matrix >= g.prob_matrices || subtree_scaler >= (int)g.scale_buffers || (subtree_is_tip && subtree_clv >= g.tips))
     return fail(PLLGPU_EINVAL, "the subtree end references an index out of range");
-  for (unsigned k = 0; k < g.rate_cats; ++k)
-    if (freqs_indices[k] >= g.rate_matrices) return fail(PLLGPU_EINVAL, "freqs_indices[%u] = %u out of range", k, freqs_indices[k]);
-  for (unsigned i = 0; i < count; ++i)
-  {
-    if (int rc = check_insertion_end(c, cands[i].child1_clv, cands[i].child1_scaler, cands[i].child1_matrix, cands[i].child1_is_tip != 0, "child1", i)) return rc;
-    if (int rc = check_insertion_end(c, cands[i].child2_clv, cands[i].child2_scaler, cands[i].child2_matrix, cands[i].child2_is_tip != 0, "child2", i)) return rc;
-  }
-  for (unsigned n = 0; n < g.nodes; ++n)
-    if (c->ids[n] || c->clv_aos[n]) return fail(PLLGPU_EUNSUPPORTED, "insertion log-likelihoods over class-compressed CLVs");
-  // whatever pllgpu_update_partials holds back goes out as ordinary launches: a candidate may name what it produces
-  if (HOLDS_WORK(c) || !c->pending.empty())
-    if (int rc = flush_deferred(c)) return rc;
-
+  if (int rc = check_rate_indices(c, "freqs_indices", freqs_indices)) return rc;
+  if (int rc = check_candidates(c, cands, count)) return rc;
+  if (int rc = refuse_compressed(c, noun)) return rc;
   DevEdge e;
-  memset(&e, 0, sizeof e);
+  if (int rc = batch_edge(c, e, freqs_indices)) return rc;
   if (int rc = build_edge_child(c, subtree_clv, subtree_is_tip ? -1 : subtree_scaler, subtree_matrix, subtree_is_tip != 0, e)) return rc;
-  if (int rc = fill_edge_model(c, e, freqs_indices)) return rc;
 
-  const unsigned tiles = (g.sites + 63) / 64, max_blocks = 1024;
-  unsigned blocks;
-  if (c->dna_fast)
-  {
-    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
-    blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
-  }
-  else
-  {
-    const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
-    blocks = (tiles + tpb - 1) / tpb;
-  }
-  const unsigned per_launch = (unsigned)std::min<size_t>(std::min(count, kInsMaxCands), std::max<size_t>(1, kInsMaxSlots / blocks));
-  {
-    ScratchEpoch scratch_epoch_;
-    if (c->ins_partials.ensure((size_t)per_launch * blocks) || c->ins_results.ensure(count) || c->ins_cands.ensure((size_t)per_launch * sizeof(InsCand)))
-      return PLLGPU_ENOMEM;
-    if (c->ins_tickets.cap < per_launch)
-    {
-      if (c->ins_tickets.ensure(per_launch)) return PLLGPU_ENOMEM;
-      HIP_TRY(hipMemsetAsync(c->ins_tickets.p, 0, c->ins_tickets.cap * sizeof(unsigned), c->stream));
-    }
-  }
-  e.block_sums = c->ins_partials.p;
-  e.counter = c->ins_tickets.p;
+  const TileWalk w = tile_walk(c);
+  const unsigned per_launch = batch_items(count, kInsMaxCands, 1, w.blocks);
+  if (int rc = batch_scratch(c, e, (size_t)per_launch * w.blocks, per_launch, count, (size_t)per_launch * sizeof(InsCand))) return rc;
   for (unsigned first = 0; first < count; first += per_launch)
-    if (int rc = launch_insertions(c, e, cands, first, std::min(per_launch, count - first), subtree_is_tip != 0)) return rc;
-  // one copy back for all candidates, one wait
-  HIP_TRY(copy_down(c, host_out, c->ins_results.p, (size_t)count * sizeof(double)));
-  if (c->defer_down) HIP_TRY(stream_wait(c));
-  return 0;
+    if (int rc = launch_insertions(c, e, w, cands, first, std::min(per_launch, count - first), subtree_is_tip != 0)) return rc;
+  return results_down(c, host_out, count);
 }
 
 // ---- batched placement log-likelihoods (kernels_placement.h) -------------------------------------------------
-// the candidates' descriptors of launches [first, first + n) on the device (launch_insertions' own, for several launches)
-static int upload_candidates(pllgpu_ctx *c, const pllgpu_insertion_t *cands, unsigned first, unsigned n)
-{
-  const size_t bytes = (size_t)n * sizeof(InsCand);
-  unsigned char *dev = nullptr;
-  InsCand *host = reinterpret_cast<InsCand *>(stage_take(c, bytes, &dev));
-  std::vector<InsCand> pageable;
-  if (!host)
-  {
-    pageable.resize(n);
-    host = pageable.data();
-  }
-  for (unsigned i = 0; i < n; ++i)
-  {
-    const pllgpu_insertion_t &q = cands[first + i];
-    InsCand &d = host[i];
-    if (int rc = end_in_hbm(c, q.child1_clv, q.child1_is_tip ? -1 : q.child1_scaler, q.child1_is_tip != 0, d.left, d.ltip, d.lscaler)) return rc;
-    if (int rc = end_in_hbm(c, q.child2_clv, q.child2_is_tip ? -1 : q.child2_scaler, q.child2_is_tip != 0, d.right, d.rtip, d.rscaler)) return rc;
-    d.lmat = c->pmat.p + (size_t)q.child1_matrix * c->pm_stride;
-    d.rmat = c->pmat.p + (size_t)q.child2_matrix * c->pm_stride;
-  }
-  HIP_TRY(hipMemcpyAsync(c->ins_cands.p, host, bytes, hipMemcpyHostToDevice, c->stream));
-  return 0;
-}
-
 // The cutting rule of pllgpu_placement_loglikelihoods (include/pll_amd_device.h states it): candidates per launch, queries
 // per launch (whole chunks), the chunk of the shape.
 struct PlacementCut
@@ -3022,20 +3065,11 @@ static_assert(kPlcDnaChunk == PLLGPU_PLACEMENT_CHUNK_DNA && kPlcTiledChunk == PL
 static PlacementCut placement_cut(const pllgpu_ctx *c, unsigned queries, unsigned count)
 {
   PlacementCut k;
-  const unsigned tiles = (c->geo.sites + 63) / 64, max_blocks = 1024;
-  if (c->dna_fast)
-  {
-    k.tiles_per = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
-    k.blocks = (tiles + 4 * k.tiles_per - 1) / (4 * k.tiles_per);
-    k.chunk = kPlcDnaChunk;
-  }
-  else
-  {
-    k.tiles_per = (tiles + max_blocks - 1) / max_blocks;
-    k.blocks = (tiles + k.tiles_per - 1) / k.tiles_per;
-    k.chunk = kPlcTiledChunk;
-  }
-  k.cands = (unsigned)std::min<size_t>(std::min(count, kInsMaxCands), std::max<size_t>(1, kInsMaxSlots / ((size_t)k.blocks * k.chunk)));
+  const TileWalk w = tile_walk(c);
+  k.blocks = w.blocks;
+  k.tiles_per = w.tiles_per;
+  k.chunk = c->dna_fast ? kPlcDnaChunk : kPlcTiledChunk;
+  k.cands = batch_items(count, kInsMaxCands, k.chunk, k.blocks); // a candidate with one chunk of queries
   const size_t chunks = std::min<size_t>(std::max<size_t>(1, kInsMaxSlots / ((size_t)k.blocks * k.cands) / k.chunk), 65535u);
   k.queries = (unsigned)std::min<size_t>(queries, chunks * k.chunk);
   return k;
@@ -3063,9 +3097,7 @@ static int launch_placements(pllgpu_ctx *c, DevEdge e, const PlacementCut &k, un
                          k.tiles_per, keep);
     });
   }
-  ++c->last_launches;
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launched(c);
 }
 
 extern "C" int pllgpu_placement_loglikelihoods(pllgpu_ctx_t *c, const unsigned *query_tips, unsigned queries, unsigned pendant_matrix,
@@ -3075,62 +3107,37 @@ extern "C" int pllgpu_placement_loglikelihoods(pllgpu_ctx_t *c, const unsigned *
   const pllgpu_geometry_t &g = c->geo;
   c->last_launches = 0;
   if (!queries || !count) return 0;
+  static const char noun[] = "placement log-likelihoods";
   // everything that needs no device state, for both lists, before held work is touched
-  if (!query_tips || !cands || !host_out || !freqs_indices) return fail(PLLGPU_EINVAL, "placement log-likelihoods: null argument");
+  if (!query_tips || !cands || !host_out || !freqs_indices) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
   // one query is what the insertion call serves, with the same checks and the same bits: there is no node to share
   if (queries == 1 && query_tips[0] < g.tips)
     return pllgpu_insertion_loglikelihoods(c, query_tips[0], -1, pendant_matrix, 1u, cands, count, freqs_indices, host_out);
-  if (g.sites == 0 || g.sites != g.sites_alloc) return fail(PLLGPU_EUNSUPPORTED, "placement log-likelihoods with ascertainment-bias entries");
+  if (int rc = refuse_ascertainment(c, noun)) return rc;
   for (unsigned q = 0; q < queries; ++q)
     if (query_tips[q] >= g.tips) return fail(PLLGPU_EINVAL, "query %u: %u is no tip", q, query_tips[q]);
   if (pendant_matrix >= g.prob_matrices) return fail(PLLGPU_EINVAL, "the pendant matrix index is out of range");
-  for (unsigned k = 0; k < g.rate_cats; ++k)
-    if (freqs_indices[k] >= g.rate_matrices) return fail(PLLGPU_EINVAL, "freqs_indices[%u] = %u out of range", k, freqs_indices[k]);
-  for (unsigned i = 0; i < count; ++i)
-  {
-    if (int rc = check_insertion_end(c, cands[i].child1_clv, cands[i].child1_scaler, cands[i].child1_matrix, cands[i].child1_is_tip != 0, "child1", i)) return rc;
-    if (int rc = check_insertion_end(c, cands[i].child2_clv, cands[i].child2_scaler, cands[i].child2_matrix, cands[i].child2_is_tip != 0, "child2", i)) return rc;
-  }
-  for (unsigned n = 0; n < g.nodes; ++n)
-    if (c->ids[n] || c->clv_aos[n]) return fail(PLLGPU_EUNSUPPORTED, "placement log-likelihoods over class-compressed CLVs");
+  if (int rc = check_rate_indices(c, "freqs_indices", freqs_indices)) return rc;
+  if (int rc = check_candidates(c, cands, count)) return rc;
+  if (int rc = refuse_compressed(c, noun)) return rc;
   for (unsigned q = 0; q < queries; ++q)
     if (!c->tipchars[query_tips[q]].p) return fail(PLLGPU_EINVAL, "query %u: tip %u has no codes on the device", q, query_tips[q]);
-  // whatever pllgpu_update_partials holds back goes out as ordinary launches: a candidate may name what it produces
-  if (HOLDS_WORK(c) || !c->pending.empty())
-    if (int rc = flush_deferred(c)) return rc;
-
   DevEdge e;
-  memset(&e, 0, sizeof e);
+  if (int rc = batch_edge(c, e, freqs_indices)) return rc;
   e.mat = c->pmat.p + (size_t)pendant_matrix * c->pm_stride;
-  if (int rc = fill_edge_model(c, e, freqs_indices)) return rc;
 
   const PlacementCut k = placement_cut(c, queries, count);
-  const size_t pairs = (size_t)k.queries * k.cands, row_bytes = (size_t)queries * sizeof(const unsigned char *);
+  const size_t pairs = (size_t)k.queries * k.cands;
+  if (int rc = batch_scratch(c, e, pairs * k.blocks, pairs, (size_t)queries * count, (size_t)k.cands * sizeof(InsCand))) return rc;
   {
     ScratchEpoch scratch_epoch_;
-    if (c->ins_partials.ensure(pairs * k.blocks) || c->ins_results.ensure((size_t)queries * count) ||
-        c->ins_cands.ensure((size_t)k.cands * sizeof(InsCand)) || c->plc_rows.ensure(row_bytes))
-      return PLLGPU_ENOMEM;
-    if (c->ins_tickets.cap < pairs)
-    {
-      if (c->ins_tickets.ensure(pairs)) return PLLGPU_ENOMEM;
-      HIP_TRY(hipMemsetAsync(c->ins_tickets.p, 0, c->ins_tickets.cap * sizeof(unsigned), c->stream));
-    }
+    if (c->plc_rows.ensure((size_t)queries * sizeof(const unsigned char *))) return PLLGPU_ENOMEM;
   }
-  {
-    unsigned char *dev = nullptr;
-    const unsigned char **host = reinterpret_cast<const unsigned char **>(stage_take(c, row_bytes, &dev));
-    std::vector<const unsigned char *> pageable;
-    if (!host)
-    {
-      pageable.resize(queries);
-      host = pageable.data();
-    }
-    for (unsigned q = 0; q < queries; ++q) host[q] = c->tipchars[query_tips[q]].p;
-    HIP_TRY(hipMemcpyAsync(c->plc_rows.p, host, row_bytes, hipMemcpyHostToDevice, c->stream));
-  }
-  e.block_sums = c->ins_partials.p;
-  e.counter = c->ins_tickets.p;
+  if (int rc = stage_up<const unsigned char *>(c, c->plc_rows.p, queries, [&](const unsigned char *&row, unsigned q) {
+        row = c->tipchars[query_tips[q]].p;
+        return 0;
+      }))
+    return rc;
   for (unsigned first = 0; first < count; first += k.cands)
   {
     const unsigned n = std::min(k.cands, count - first);
@@ -3138,10 +3145,7 @@ extern "C" int pllgpu_placement_loglikelihoods(pllgpu_ctx_t *c, const unsigned *
     for (unsigned q0 = 0; q0 < queries; q0 += k.queries)
       if (int rc = launch_placements(c, e, k, q0, std::min(k.queries, queries - q0), first, n, count)) return rc;
   }
-  // one copy back for the whole matrix, one wait
-  HIP_TRY(copy_down(c, host_out, c->ins_results.p, (size_t)queries * count * sizeof(double)));
-  if (c->defer_down) HIP_TRY(stream_wait(c));
-  return 0;
+  return results_down(c, host_out, (size_t)queries * count);
 }
 
 // ---- batched NNI scores (kernels_quartet.h) ------------------------------------------------------------------
@@ -3149,24 +3153,13 @@ extern "C" int pllgpu_placement_loglikelihoods(pllgpu_ctx_t *c, const unsigned *
 constexpr unsigned kQuartetMax = 8192; // 1.1 MB of descriptors: one piece of the pinned block
 static_assert(kQuartetMax == PLLGPU_QUARTET_MAX && kQuartetMax * sizeof(QuartetDesc) <= kRingMax, "include/pll_amd_device.h states the cutting rule");
 
-// one launch for quartets [first, first + n): descriptors up through the pinned block, the kernel of the shape
+// one launch for quartets [first, first + n): their descriptors up, the kernel of the shape
 // (sites: the PS instantiations, which leave every site's value through ps as well)
-static int launch_quartets(pllgpu_ctx *c, DevEdge e, const pllgpu_quartet_t *quartets, unsigned first, unsigned n, unsigned count,
+static int launch_quartets(pllgpu_ctx *c, DevEdge e, const TileWalk &w, const pllgpu_quartet_t *quartets, unsigned first, unsigned n, unsigned count,
                            bool sites = false, const QuartetSites ps = QuartetSites{nullptr, nullptr})
 {
-  const size_t bytes = (size_t)n * sizeof(QuartetDesc);
-  unsigned char *dev = nullptr;
-  QuartetDesc *host = reinterpret_cast<QuartetDesc *>(stage_take(c, bytes, &dev));
-  std::vector<QuartetDesc> pageable;
-  if (!host)
-  {
-    pageable.resize(n);
-    host = pageable.data();
-  }
-  for (unsigned i = 0; i < n; ++i)
-  {
+  const int up = stage_up<QuartetDesc>(c, c->ins_cands.p, n, [&](QuartetDesc &d, unsigned i) {
     const pllgpu_quartet_t &q = quartets[first + i];
-    QuartetDesc &d = host[i];
     d.tt_rule = 0u;
     d.pad_ = 0u;
     for (unsigned x = 0; x < 4; ++x)
@@ -3177,27 +3170,20 @@ static int launch_quartets(pllgpu_ctx *c, DevEdge e, const pllgpu_quartet_t *qua
       if (tip && (q.is_tip[x] & PLLGPU_QUARTET_TIP_PATTERN)) d.tt_rule |= 1u << x;
     }
     d.inner = c->pmat.p + (size_t)q.inner_matrix * c->pm_stride;
-  }
-  HIP_TRY(hipMemcpyAsync(c->ins_cands.p, host, bytes, hipMemcpyHostToDevice, c->stream));
+    return 0;
+  });
+  if (up) return up;
   const QuartetDesc *dq = reinterpret_cast<const QuartetDesc *>(c->ins_cands.p);
   e.result = c->ins_results.p + first; // [arrangement][quartet of the call]
-  // launch_insertions' tile walk, unchanged: the order of every sum follows from the site count alone
-  const unsigned tiles = (c->geo.sites + 63) / 64, max_blocks = 1024;
   if (c->dna_fast)
-  {
-    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
-    const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
     with_bools(sites, false, [&](auto PS, auto) {
       if (c->gg.scale_mode == 2)
-        hipLaunchKernelGGL((k_quartet_dna<2, PS()>), dim3(blocks, n), dim3(256), 0, c->stream, e, dq, count, tpw, ps);
+        hipLaunchKernelGGL((k_quartet_dna<2, PS()>), dim3(w.blocks, n), dim3(256), 0, c->stream, e, dq, count, w.tiles_per, ps);
       else
-        hipLaunchKernelGGL((k_quartet_dna<1, PS()>), dim3(blocks, n), dim3(256), 0, c->stream, e, dq, count, tpw, ps);
+        hipLaunchKernelGGL((k_quartet_dna<1, PS()>), dim3(w.blocks, n), dim3(256), 0, c->stream, e, dq, count, w.tiles_per, ps);
     });
-  }
   else
   {
-    const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
-    const unsigned blocks = (tiles + tpb - 1) / tpb;
     const unsigned nw = std::min(c->gg.R, 4u);
     const size_t node_bytes = (size_t)c->gg.R * c->gg.S * 64u * sizeof(double);
     // both nodes of an arrangement in LDS, or (recompute path) one rate of the second node per wave
@@ -3207,24 +3193,21 @@ static int launch_quartets(pllgpu_ctx *c, DevEdge e, const pllgpu_quartet_t *qua
     with_ich(c->ich, [&](auto ICH) {
       with_bools(sites, false, [&](auto PS, auto) {
         raise_lds_limit(reinterpret_cast<const void *>(&k_quartet_tiled<ICH(), PS()>), c->device, lds);
-        hipLaunchKernelGGL((k_quartet_tiled<ICH(), PS()>), dim3(blocks, n), dim3(64u * nw), lds, c->stream, e, dq, c->gg, tm, count, tpb, keep, ps);
+        hipLaunchKernelGGL((k_quartet_tiled<ICH(), PS()>), dim3(w.blocks, n), dim3(64u * nw), lds, c->stream, e, dq, c->gg, tm, count, w.tiles_per, keep, ps);
       });
     });
   }
-  ++c->last_launches;
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launched(c);
 }
 
-// What both quartet calls do before anything is allocated: everything that needs no device state, for the whole list,
-// before held work is touched; held work out; the model of the launches in e; B = the workgroups per quartet.
-static int quartet_call_begin(pllgpu_ctx *c, const pllgpu_quartet_t *quartets, unsigned count, const unsigned *freqs_indices, DevEdge &e,
-                              unsigned &blocks)
+// What the quartet calls do before anything is allocated: everything that needs no device state, for the whole list,
+// before held work is touched; held work out; the model of the launches in e.
+static int quartet_call_begin(pllgpu_ctx *c, const pllgpu_quartet_t *quartets, unsigned count, const unsigned *freqs_indices, DevEdge &e)
 {
+  static const char noun[] = "quartet log-likelihoods";
   const pllgpu_geometry_t &g = c->geo;
-  if (g.sites == 0 || g.sites != g.sites_alloc) return fail(PLLGPU_EUNSUPPORTED, "quartet log-likelihoods with ascertainment-bias entries");
-  for (unsigned k = 0; k < g.rate_cats; ++k)
-    if (freqs_indices[k] >= g.rate_matrices) return fail(PLLGPU_EINVAL, "freqs_indices[%u] = %u out of range", k, freqs_indices[k]);
+  if (int rc = refuse_ascertainment(c, noun)) return rc;
+  if (int rc = check_rate_indices(c, "freqs_indices", freqs_indices)) return rc;
   for (unsigned i = 0; i < count; ++i)
   {
     const pllgpu_quartet_t &q = quartets[i];
@@ -3237,49 +3220,21 @@ static int quartet_call_begin(pllgpu_ctx *c, const pllgpu_quartet_t *quartets, u
     }
     if (q.inner_matrix >= g.prob_matrices) return fail(PLLGPU_EINVAL, "quartet %u: the inner matrix index is out of range", i);
   }
-  for (unsigned n = 0; n < g.nodes; ++n)
-    if (c->ids[n] || c->clv_aos[n]) return fail(PLLGPU_EUNSUPPORTED, "quartet log-likelihoods over class-compressed CLVs");
-  // whatever pllgpu_update_partials holds back goes out as ordinary launches: a quartet may name what it produces
-  if (HOLDS_WORK(c) || !c->pending.empty())
-    if (int rc = flush_deferred(c)) return rc;
-
-  memset(&e, 0, sizeof e);
-  if (int rc = fill_edge_model(c, e, freqs_indices)) return rc;
-
-  const unsigned tiles = (g.sites + 63) / 64, max_blocks = 1024;
-  if (c->dna_fast)
-  {
-    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
-    blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
-  }
-  else
-  {
-    const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
-    blocks = (tiles + tpb - 1) / tpb;
-  }
-  return 0;
+  if (int rc = refuse_compressed(c, noun)) return rc;
+  return batch_edge(c, e, freqs_indices);
 }
 
 // slots, tickets, results and descriptors of launches of up to per_launch quartets of a call of `count`
-static int quartet_scratch(pllgpu_ctx *c, unsigned per_launch, unsigned blocks, unsigned count)
+static int quartet_scratch(pllgpu_ctx *c, DevEdge &e, unsigned per_launch, unsigned blocks, unsigned count)
 {
-  if (c->ins_partials.ensure((size_t)3 * per_launch * blocks) || c->ins_results.ensure((size_t)3 * count) ||
-      c->ins_cands.ensure((size_t)per_launch * sizeof(QuartetDesc)))
-    return PLLGPU_ENOMEM;
-  if (c->ins_tickets.cap < (size_t)3 * per_launch)
-  {
-    if (c->ins_tickets.ensure((size_t)3 * per_launch)) return PLLGPU_ENOMEM;
-    HIP_TRY(hipMemsetAsync(c->ins_tickets.p, 0, c->ins_tickets.cap * sizeof(unsigned), c->stream));
-  }
-  return 0;
+  return batch_scratch(c, e, (size_t)3 * per_launch * blocks, (size_t)3 * per_launch, (size_t)3 * count, (size_t)per_launch * sizeof(QuartetDesc));
 }
 
 // one copy back for all values, one wait; the kernels leave [arrangement][quartet], the caller gets [quartet][3]
 static int quartet_sums_down(pllgpu_ctx *c, unsigned count, double *host_out)
 {
   std::vector<double> rows((size_t)3 * count);
-  HIP_TRY(copy_down(c, rows.data(), c->ins_results.p, rows.size() * sizeof(double)));
-  if (c->defer_down) HIP_TRY(stream_wait(c));
+  if (int rc = results_down(c, rows.data(), rows.size())) return rc;
   for (unsigned i = 0; i < count; ++i)
     for (unsigned a = 0; a < 3; ++a) host_out[(size_t)3 * i + a] = rows[(size_t)a * count + i];
   return 0;
@@ -3293,17 +3248,12 @@ extern "C" int pllgpu_quartet_loglikelihoods(pllgpu_ctx_t *c, const pllgpu_quart
   if (!count) return 0;
   if (!quartets || !host_out || !freqs_indices) return fail(PLLGPU_EINVAL, "quartet log-likelihoods: null argument");
   DevEdge e;
-  unsigned blocks;
-  if (int rc = quartet_call_begin(c, quartets, count, freqs_indices, e, blocks)) return rc;
-  const unsigned per_launch = (unsigned)std::min<size_t>(std::min(count, kQuartetMax), std::max<size_t>(1, kInsMaxSlots / ((size_t)3 * blocks)));
-  {
-    ScratchEpoch scratch_epoch_;
-    if (int rc = quartet_scratch(c, per_launch, blocks, count)) return rc;
-  }
-  e.block_sums = c->ins_partials.p;
-  e.counter = c->ins_tickets.p;
+  if (int rc = quartet_call_begin(c, quartets, count, freqs_indices, e)) return rc;
+  const TileWalk w = tile_walk(c);
+  const unsigned per_launch = batch_items(count, kQuartetMax, 3, w.blocks);
+  if (int rc = quartet_scratch(c, e, per_launch, w.blocks, count)) return rc;
   for (unsigned first = 0; first < count; first += per_launch)
-    if (int rc = launch_quartets(c, e, quartets, first, std::min(per_launch, count - first), count)) return rc;
+    if (int rc = launch_quartets(c, e, w, quartets, first, std::min(per_launch, count - first), count)) return rc;
   return quartet_sums_down(c, count, host_out);
 }
 
@@ -3353,8 +3303,7 @@ static int rell_cdf_current(pllgpu_ctx *c)
     if (int rc = r.cdf.ensure((size_t)sites + 2u)) return rc;
   }
   hipLaunchKernelGGL(k_rell_cdf, dim3(1), dim3(256), 0, c->stream, c->pattern_weights.p, r.cdf.p, r.cdf.p + sites, sites);
-  ++c->last_launches;
-  HIP_TRY(hipGetLastError());
+  if (int rc = launched(c)) return rc;
   unsigned long long summary[2] = {0, 0};
   HIP_TRY(copy_down(c, summary, r.cdf.p + sites, sizeof summary));
   if (c->defer_down) HIP_TRY(stream_wait(c));
@@ -3387,9 +3336,7 @@ static int launch_rell_draw(pllgpu_ctx *c, unsigned long long seed, unsigned fir
   };
   if (c->rell->not_one == 0) launch(&k_rell_draw<true>); // every weight is 1: cdf[n] = n + 1, the site is r itself
   else launch(&k_rell_draw<false>);
-  ++c->last_launches;
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launched(c);
 }
 
 // nr rows of c->rs_w to the caller's [nr][sites]: one copy, one wait
@@ -3424,20 +3371,19 @@ static int resampled_run(pllgpu_ctx *c, const pllgpu_quartet_t *quartets, unsign
   const unsigned sites = c->geo.sites;
   const unsigned *weights = rows.weights;
   DevEdge e;
-  unsigned blocks;
-  if (int rc = quartet_call_begin(c, quartets, count, freqs_indices, e, blocks)) return rc;
+  if (int rc = quartet_call_begin(c, quartets, count, freqs_indices, e)) return rc;
+  const TileWalk w = tile_walk(c);
   if (!weights && replicates)
   {
     if (int rc = rell_cdf_current(c)) return rc;
     if (int rc = rell_check_total(c, "rell quartet log-likelihoods")) return rc;
   }
 
-  const unsigned per_launch = (unsigned)std::min<size_t>(std::min(count, kQuartetMax), std::max<size_t>(1, kInsMaxSlots / ((size_t)3 * blocks)));
-  const ResampleCut k = resample_cut(sites, count, replicates, host_persite != nullptr, per_launch, c->resample_bytes);
+  const ResampleCut k = resample_cut(sites, count, replicates, host_persite != nullptr, batch_items(count, kQuartetMax, 3, w.blocks), c->resample_bytes);
   const bool one_quartet_chunk = k.quartets >= count;
+  if (int rc = quartet_scratch(c, e, k.quartets, w.blocks, count)) return rc;
   {
     ScratchEpoch scratch_epoch_;
-    if (int rc = quartet_scratch(c, k.quartets, blocks, count)) return rc;
     if ((replicates && (c->rs_u.ensure((size_t)3 * k.quartets * k.upad) || c->rs_w.ensure((size_t)k.replicates * k.wstride) ||
                         c->rs_part.ensure((size_t)k.splits * 3 * k.quartets * k.replicates) || c->rs_out.ensure((size_t)3 * k.quartets * k.replicates))) ||
         (host_persite && c->rs_weighted.ensure((size_t)3 * k.quartets * sites)))
@@ -3446,8 +3392,6 @@ static int resampled_run(pllgpu_ctx *c, const pllgpu_quartet_t *quartets, unsign
   if (int rc = resample_events(c)) return rc;
   // the small outputs are collected here and handed over once everything has succeeded
   std::vector<double> resampled((size_t)count * replicates * 3), piece((size_t)3 * k.quartets * k.replicates);
-  e.block_sums = c->ins_partials.p;
-  e.counter = c->ins_tickets.p;
 
   // Replicate chunks outermost: every row of weights goes up once per call. Stage 1 runs once per quartet chunk when the
   // quartets are one chunk (its rows then stay for every replicate chunk), and again per replicate chunk otherwise - the
@@ -3480,7 +3424,7 @@ static int resampled_run(pllgpu_ctx *c, const pllgpu_quartet_t *quartets, unsign
       if (r0 == 0 || !one_quartet_chunk)
       {
         const QuartetSites ps{replicates ? c->rs_u.p : nullptr, want_weighted ? c->rs_weighted.p : nullptr};
-        if (int rc = launch_quartets(c, e, quartets, first, nq, count, true, ps)) return rc;
+        if (int rc = launch_quartets(c, e, w, quartets, first, nq, count, true, ps)) return rc;
       }
       if (timed && first == 0) HIP_TRY(hipEventRecord(c->rs_ev[2], c->stream));
       if (nr)
@@ -3554,13 +3498,13 @@ extern "C" int pllgpu_replicate_weights_draw(pllgpu_ctx_t *c, unsigned long long
   const pllgpu_geometry_t &g = c->geo;
   c->last_launches = 0;
   if (!replicates) return 0;
-  if (!host_out) return fail(PLLGPU_EINVAL, "replicate weights: null argument");
+  static const char noun[] = "replicate weights";
+  if (!host_out) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
   // rows that the quartet call could not take are not handed out: its refusals, with its status
-  if (g.sites == 0 || g.sites != g.sites_alloc) return fail(PLLGPU_EUNSUPPORTED, "replicate weights with ascertainment-bias entries");
-  for (unsigned n = 0; n < g.nodes; ++n)
-    if (c->ids[n] || c->clv_aos[n]) return fail(PLLGPU_EUNSUPPORTED, "replicate weights over class-compressed CLVs");
+  if (int rc = refuse_ascertainment(c, noun)) return rc;
+  if (int rc = refuse_compressed(c, noun)) return rc;
   if (int rc = rell_cdf_current(c)) return rc;
-  if (int rc = rell_check_total(c, "replicate weights")) return rc;
+  if (int rc = rell_check_total(c, noun)) return rc;
   const unsigned wstride = (g.sites + 3u) / 4u * 4u;
   const unsigned per_chunk = (unsigned)std::min<size_t>(replicates, std::max<size_t>(1, c->resample_bytes / ((size_t)wstride * sizeof(unsigned))));
   {
@@ -3588,22 +3532,12 @@ extern "C" int pllgpu_resample_last_times(const pllgpu_ctx_t *c, double *ms)
 constexpr unsigned kBranchMax = 8192; // 512 KB of descriptors: one piece of the pinned block
 static_assert(kBranchMax == PLLGPU_BRANCH_MAX && kBranchMax * sizeof(BranchDesc) <= kRingMax, "include/pll_amd_device.h states the cutting rule");
 
-// one launch for branches [first, first + n): descriptors up through the pinned block, the kernel of the shape
-static int launch_branches(pllgpu_ctx *c, DevEdge e, const DevDiag &dg, const pllgpu_branch_t *branches, unsigned first, unsigned n, unsigned count)
+// one launch for branches [first, first + n): their descriptors up, the kernel of the shape
+static int launch_branches(pllgpu_ctx *c, DevEdge e, const TileWalk &w, const DevDiag &dg, const pllgpu_branch_t *branches, unsigned first, unsigned n,
+                           unsigned count)
 {
-  const size_t bytes = (size_t)n * sizeof(BranchDesc);
-  unsigned char *dev = nullptr;
-  BranchDesc *host = reinterpret_cast<BranchDesc *>(stage_take(c, bytes, &dev));
-  std::vector<BranchDesc> pageable;
-  if (!host)
-  {
-    pageable.resize(n);
-    host = pageable.data();
-  }
-  for (unsigned i = 0; i < n; ++i)
-  {
+  const int up = stage_up<BranchDesc>(c, c->ins_cands.p, n, [&](BranchDesc &d, unsigned i) {
     const pllgpu_branch_t &q = branches[first + i];
-    BranchDesc &d = host[i];
     // an end given by codes takes the left role, as in pllgpu_update_sumtable's callers; otherwise parent left, child right
     const bool swap = q.child_is_tip != 0;
     const unsigned lclv = swap ? q.child_clv : q.parent_clv, rclv = swap ? q.parent_clv : q.child_clv;
@@ -3615,34 +3549,25 @@ static int launch_branches(pllgpu_ctx *c, DevEdge e, const DevDiag &dg, const pl
     if (int rc = end_in_hbm(c, rclv, counts ? rsc : -1, false, d.right, d.rtip, d.rscaler)) return rc;
     d.t = q.branch_length;
     d.pad_ = 0.0;
-  }
-  HIP_TRY(hipMemcpyAsync(c->ins_cands.p, host, bytes, hipMemcpyHostToDevice, c->stream));
+    return 0;
+  });
+  if (up) return up;
   const BranchDesc *db = reinterpret_cast<const BranchDesc *>(c->ins_cands.p);
   const double *m1 = c->pmat.p + (size_t)c->geo.prob_matrices * c->pm_stride, *m2 = m1 + c->pm_stride;
   e.result = c->ins_results.p + first; // [d_f | dd_f][branch of the call]
-  // launch_insertions' tile walk, unchanged: the order of every sum follows from the site count alone
-  const unsigned tiles = (c->geo.sites + 63) / 64, max_blocks = 1024;
   if (c->dna_fast)
-  {
-    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
-    const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
-    hipLaunchKernelGGL(k_gradient_dna, dim3(blocks, n), dim3(256), 0, c->stream, e, dg, db, m1, m2, count, tpw);
-  }
+    hipLaunchKernelGGL(k_gradient_dna, dim3(w.blocks, n), dim3(256), 0, c->stream, e, dg, db, m1, m2, count, w.tiles_per);
   else
   {
-    const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
-    const unsigned blocks = (tiles + tpb - 1) / tpb;
     const unsigned nw = std::min(c->gg.R, 4u);
     const size_t lds = (size_t)c->gg.R * c->gg.S * 4 * sizeof(double); // the branch's diag table
     const unsigned long long *tm = tipmap_ptr(c);
     with_ich(c->ich, [&](auto ICH) {
       raise_lds_limit(reinterpret_cast<const void *>(&k_gradient_tiled<ICH()>), c->device, lds);
-      hipLaunchKernelGGL((k_gradient_tiled<ICH()>), dim3(blocks, n), dim3(64u * nw), lds, c->stream, e, dg, db, m1, m2, c->gg, tm, count, tpb);
+      hipLaunchKernelGGL((k_gradient_tiled<ICH()>), dim3(w.blocks, n), dim3(64u * nw), lds, c->stream, e, dg, db, m1, m2, c->gg, tm, count, w.tiles_per);
     });
   }
-  ++c->last_launches;
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launched(c);
 }
 
 extern "C" int pllgpu_branch_derivatives(pllgpu_ctx_t *c, const pllgpu_branch_t *branches, unsigned count, const unsigned *params_indices,
@@ -3652,11 +3577,11 @@ extern "C" int pllgpu_branch_derivatives(pllgpu_ctx_t *c, const pllgpu_branch_t 
   const pllgpu_geometry_t &g = c->geo;
   c->last_launches = 0;
   if (!count) return 0;
+  static const char noun[] = "branch derivatives";
   // everything that needs no device state, for the whole list, before held work is touched
-  if (!branches || !host_d || !params_indices) return fail(PLLGPU_EINVAL, "branch derivatives: null argument");
-  if (g.sites == 0 || g.sites != g.sites_alloc) return fail(PLLGPU_EUNSUPPORTED, "branch derivatives with ascertainment-bias entries");
-  for (unsigned k = 0; k < g.rate_cats; ++k)
-    if (params_indices[k] >= g.rate_matrices) return fail(PLLGPU_EINVAL, "params_indices[%u] = %u out of range", k, params_indices[k]);
+  if (!branches || !host_d || !params_indices) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
+  if (int rc = refuse_ascertainment(c, noun)) return rc;
+  if (int rc = check_rate_indices(c, "params_indices", params_indices)) return rc;
   for (unsigned i = 0; i < count; ++i)
   {
     const pllgpu_branch_t &q = branches[i];
@@ -3667,16 +3592,10 @@ extern "C" int pllgpu_branch_derivatives(pllgpu_ctx_t *c, const pllgpu_branch_t 
     if (q.parent_is_tip && q.child_is_tip) return fail(PLLGPU_EINVAL, "branch %u: both ends are given by codes", i);
     if (!(q.branch_length >= 0.0) || !std::isfinite(q.branch_length)) return fail(PLLGPU_EINVAL, "branch %u: the length is negative or not finite", i);
   }
-  for (unsigned n = 0; n < g.nodes; ++n)
-    if (c->ids[n] || c->clv_aos[n]) return fail(PLLGPU_EUNSUPPORTED, "branch derivatives over class-compressed CLVs");
+  if (int rc = refuse_compressed(c, noun)) return rc;
   if (!c->eigenvals.p || !c->rates.p) return fail(PLLGPU_EINVAL, "eigenvalues / category rates were not uploaded");
-  // whatever pllgpu_update_partials holds back goes out as ordinary launches: a branch may name what it produces
-  if (HOLDS_WORK(c) || !c->pending.empty())
-    if (int rc = flush_deferred(c)) return rc;
-
   DevEdge e;
-  memset(&e, 0, sizeof e);
-  if (int rc = fill_edge_model(c, e, params_indices)) return rc;
+  if (int rc = batch_edge(c, e, params_indices)) return rc;
   DevDiag dg;
   memset(&dg, 0, sizeof dg);
   for (unsigned k = 0; k < g.rate_cats; ++k) dg.fidx[k] = (unsigned char)params_indices[k];
@@ -3687,38 +3606,15 @@ extern "C" int pllgpu_branch_derivatives(pllgpu_ctx_t *c, const pllgpu_branch_t 
   dg.SP = g.states_padded;
   dg.R = g.rate_cats;
 
-  const unsigned tiles = (g.sites + 63) / 64, max_blocks = 1024;
-  unsigned blocks;
-  if (c->dna_fast)
-  {
-    const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
-    blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
-  }
-  else
-  {
-    const unsigned tpb = (tiles + max_blocks - 1) / max_blocks;
-    blocks = (tiles + tpb - 1) / tpb;
-  }
-  const unsigned per_launch = (unsigned)std::min<size_t>(std::min(count, kBranchMax), std::max<size_t>(1, kInsMaxSlots / ((size_t)2 * blocks)));
-  {
-    ScratchEpoch scratch_epoch_;
-    if (c->ins_partials.ensure((size_t)2 * per_launch * blocks) || c->ins_results.ensure((size_t)2 * count) ||
-        c->ins_cands.ensure((size_t)per_launch * sizeof(BranchDesc)))
-      return PLLGPU_ENOMEM;
-    if (c->ins_tickets.cap < (size_t)2 * per_launch)
-    {
-      if (c->ins_tickets.ensure((size_t)2 * per_launch)) return PLLGPU_ENOMEM;
-      HIP_TRY(hipMemsetAsync(c->ins_tickets.p, 0, c->ins_tickets.cap * sizeof(unsigned), c->stream));
-    }
-  }
-  e.block_sums = c->ins_partials.p;
-  e.counter = c->ins_tickets.p;
+  const TileWalk w = tile_walk(c);
+  const unsigned per_launch = batch_items(count, kBranchMax, 2, w.blocks);
+  if (int rc = batch_scratch(c, e, (size_t)2 * per_launch * w.blocks, (size_t)2 * per_launch, (size_t)2 * count, (size_t)per_launch * sizeof(BranchDesc)))
+    return rc;
   for (unsigned first = 0; first < count; first += per_launch)
-    if (int rc = launch_branches(c, e, dg, branches, first, std::min(per_launch, count - first), count)) return rc;
-  // one copy back for all values, one wait; the kernels leave [d_f | dd_f][branch]
+    if (int rc = launch_branches(c, e, w, dg, branches, first, std::min(per_launch, count - first), count)) return rc;
+  // the kernels leave [d_f | dd_f][branch]
   std::vector<double> rows((size_t)2 * count);
-  HIP_TRY(copy_down(c, rows.data(), c->ins_results.p, rows.size() * sizeof(double)));
-  if (c->defer_down) HIP_TRY(stream_wait(c));
+  if (int rc = results_down(c, rows.data(), rows.size())) return rc;
   memcpy(host_d, rows.data(), (size_t)count * sizeof(double));
   if (host_dd) memcpy(host_dd, rows.data() + count, (size_t)count * sizeof(double));
   return 0;

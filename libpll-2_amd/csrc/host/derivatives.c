@@ -395,11 +395,10 @@ int pll_gpu_optimize_branch_length(pll_partition_t *p, int parent_scaler_index, 
 }
 
 /* pll_gpu_branch_derivatives (include/pll_amd.h): d_f and dd_f of `count` branches in one call,
- * without a table (csrc/hip/kernels_gradient.h). This function, as insertion.c for its call: validation of the whole list
- * before anything is flushed or launched, the refusals, which ends the device reads as tip codes, the flushes (model,
- * the two contraction matrices, every named CLV and scaler once), the error convention. */
-static int fail_branches(void) { return fail_loudly("pll_gpu_branch_derivatives"); }
-
+ * without a table (csrc/hip/kernels_gradient.h). This function: validation of the whole list before anything is flushed
+ * or launched, which ends the device reads as tip codes, the flushes (model, the two contraction matrices, every named
+ * CLV and scaler once). The refusals, the once-per-call bookkeeping of the flushes and the error convention are batch.c's,
+ * shared with the other batched calls. */
 int pll_gpu_branch_derivatives(pll_partition_t *p, const pll_gpu_branch_t *branches, unsigned int count,
                                const unsigned int *params_indices, double *d_f, double *dd_f)
 {
@@ -408,13 +407,13 @@ int pll_gpu_branch_derivatives(pll_partition_t *p, const pll_gpu_branch_t *branc
   if (!p)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
-    return fail_branches();
+    return pll_batch_fail(who);
   }
   if (!count) return PLL_SUCCESS;
   if (!branches || !params_indices || !d_f)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: branches, params_indices or d_f is NULL", who);
-    return fail_branches();
+    return pll_batch_fail(who);
   }
   for (i = 0; i < count; ++i)
   {
@@ -424,81 +423,46 @@ int pll_gpu_branch_derivatives(pll_partition_t *p, const pll_gpu_branch_t *branc
         b->child_scaler_index >= (int)p->scale_buffers)
     {
       pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: branch %u has an index out of range", who, i);
-      return fail_branches();
+      return pll_batch_fail(who);
     }
     if (!(b->branch_length >= 0) || !isfinite(b->branch_length))
     {
       pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: the length of branch %u is negative or not finite", who, i);
-      return fail_branches();
+      return pll_batch_fail(who);
     }
   }
   for (k = 0; k < p->rate_cats; ++k)
     if (params_indices[k] >= p->rate_matrices)
     {
       pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: params_indices[%u] out of range", who, k);
-      return fail_branches();
+      return pll_batch_fail(who);
     }
   for (i = 0; i < count; ++i)
     if (pll_tip_by_codes(p, branches[i].parent_clv_index) && pll_tip_by_codes(p, branches[i].child_clv_index))
     {
       /* pll_update_sumtable makes one of them dense; this call writes nothing */
       pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: both ends of branch %u are tips given by codes", who, i);
-      return fail_branches();
+      return pll_batch_fail(who);
     }
-  if (pll_repeats_enabled(p))
-  {
-    pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: PLL_ATTRIB_SITE_REPEATS partitions are not supported", who);
-    return fail_branches();
-  }
-  if (p->attributes & PLL_ATTRIB_AB_MASK)
-  {
-    pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: the ascertainment-bias correction needs pll_compute_likelihood_derivatives", who);
-    return fail_branches();
-  }
-  pll_amd_ext_t *x = pll_ext(p);
-  if (!x || !x->ctx)
-  {
-    pll_set_error(PLL_ERROR_GPU_UNAVAILABLE, "%s: no MI355X context behind this partition; this library has no CPU path", who);
-    return fail_branches();
-  }
+  pll_amd_ext_t *x = NULL;
+  if (!pll_batch_refusals_and_device(who, p, "pll_compute_likelihood_derivatives", &x)) return PLL_FAILURE;
 
   /* the reference reads whatever eigensystem is stored; an invalid one is computed here, as pll_update_sumtable does */
   for (k = 0; k < p->rate_cats; ++k)
     if (!p->eigen_decomp_valid[params_indices[k]] && !pll_update_eigen(p, params_indices[k])) return PLL_FAILURE;
-  if (!flush_deriv_model(p, x) || !flush_aux_matrices(p, x, params_indices)) return fail_branches();
+  if (!flush_deriv_model(p, x) || !flush_aux_matrices(p, x, params_indices)) return pll_batch_fail(who);
 
   /* every named end current on the device, each index once */
-  unsigned char *seen = (unsigned char *)calloc((size_t)p->nodes + p->scale_buffers + 1, 1);
-  pllgpu_branch_t *dev = (pllgpu_branch_t *)malloc(sizeof(pllgpu_branch_t) * count);
-  if (!seen || !dev)
-  {
-    free(seen);
-    free(dev);
-    pll_set_error(PLL_ERROR_MEM_ALLOC, "%s: out of memory", who);
-    return fail_branches();
-  }
-  unsigned char *seen_scaler = seen + p->nodes;
+  pll_batch_seen_t seen;
+  pllgpu_branch_t *dev = (pllgpu_branch_t *)pll_batch_alloc(who, p, &seen, sizeof(pllgpu_branch_t) * count);
+  if (!dev) return PLL_FAILURE;
   int ok = 1;
   for (i = 0; ok && i < count; ++i)
   {
     const pll_gpu_branch_t *b = &branches[i];
     const unsigned int clv[2] = {b->parent_clv_index, b->child_clv_index};
     const int scaler[2] = {b->parent_scaler_index, b->child_scaler_index};
-    int e;
-    for (e = 0; ok && e < 2; ++e)
-    {
-      const int tip = pll_tip_by_codes(p, clv[e]);
-      if (!seen[clv[e]])
-      {
-        seen[clv[e]] = 1;
-        ok = pll_flush_clv(p, x, clv[e]);
-      }
-      if (ok && !tip && scaler[e] >= 0 && !seen_scaler[scaler[e]])
-      {
-        seen_scaler[scaler[e]] = 1;
-        ok = pll_flush_scaler(p, x, scaler[e]);
-      }
-    }
+    ok = pll_batch_prepare_once(p, x, &seen, clv[0], scaler[0]) && pll_batch_prepare_once(p, x, &seen, clv[1], scaler[1]);
     dev[i].parent_clv = clv[0];
     dev[i].parent_scaler = scaler[0];
     dev[i].child_clv = clv[1];
@@ -507,11 +471,11 @@ int pll_gpu_branch_derivatives(pll_partition_t *p, const pll_gpu_branch_t *branc
     dev[i].child_is_tip = pll_tip_by_codes(p, clv[1]) ? 1u : 0u;
     dev[i].branch_length = b->branch_length;
   }
-  free(seen);
+  pll_batch_seen_free(&seen);
   if (!ok)
   {
     free(dev);
-    return fail_branches();
+    return pll_batch_fail(who);
   }
   const int rc = pllgpu_branch_derivatives(x->ctx, dev, count, params_indices, d_f, dd_f);
   free(dev);

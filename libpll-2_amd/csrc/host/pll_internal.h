@@ -152,6 +152,29 @@ int pll_tip_by_codes(const pll_partition_t *p, unsigned int clv_index);
 /* give a compact tip a dense device CLV again (someone needs it as an ordinary CLV) */
 void pll_tip_densify(pll_partition_t *p, unsigned int clv_index);
 
+/* ---- what the batched calls share (batch.c) ---- */
+/* the error convention's last step: pll_errno and pll_errmsg are set, one line on stderr; returns PLL_FAILURE */
+int pll_batch_fail(const char *who);
+/* an end of a list item: its CLV, scaler and matrix indices exist */
+int pll_batch_end_in_range(const pll_partition_t *p, unsigned int clv, int scaler, unsigned int matrix);
+/* Site repeats refused, then the ascertainment-bias correction (its message names reference_call as the way to go, or
+ * only refuses: NULL), then no device behind the partition - printed as pll_batch_fail does. PLL_SUCCESS with the
+ * partition's extension in *ext. The two halves are for a call with a check of its own between them. */
+int pll_batch_refusals_and_device(const char *who, const pll_partition_t *p, const char *reference_call, pll_amd_ext_t **ext);
+int pll_batch_refusals(const char *who, const pll_partition_t *p, const char *reference_call);
+int pll_batch_device(const char *who, const pll_partition_t *p, pll_amd_ext_t **ext);
+/* which CLVs and scalers a call has brought up to date already */
+typedef struct pll_batch_seen
+{
+  unsigned char *clv, *scaler;
+} pll_batch_seen_t;
+/* the record of a call, and `list_bytes` (not 0) for its list as the device layer takes it: the list, which the caller
+ * frees, or NULL, nothing allocated and the out-of-memory failure printed */
+void *pll_batch_alloc(const char *who, const pll_partition_t *p, pll_batch_seen_t *seen, size_t list_bytes);
+void pll_batch_seen_free(pll_batch_seen_t *seen);
+/* pll_prepare_end for one end of a list item, each CLV and each scaler once per call */
+int pll_batch_prepare_once(pll_partition_t *p, pll_amd_ext_t *x, pll_batch_seen_t *seen, unsigned int clv, int scaler);
+
 /* pll_gpu_edge_loglikelihood_async with the sequence word chosen by the caller (group.c) */
 int pll_gpu_edge_loglikelihood_numbered(pll_partition_t *p, unsigned int parent_clv_index, int parent_scaler_index,
                                         unsigned int child_clv_index, int child_scaler_index, unsigned int matrix_index,

@@ -10,31 +10,10 @@
  * s2, inner_matrix_index, ...) (src/likelihood.c:586-636) - but neither tmp exists: both nodes live in the kernel's
  * registers or LDS (csrc/hip/kernels_quartet.h) and nothing in the partition is written.
  *
- * This file, as insertion.c for its call: validation of the whole list before anything is flushed or launched, the
- * refusals, which ends the device reads as tip codes, the flushes (model, one matrix span, every named CLV and scaler
- * once), the error convention. */
+ * This file: validation of the whole list before anything is flushed or launched, which ends the device reads as tip
+ * codes, the flushes (model, one matrix span, every named CLV and scaler once). The refusals, the once-per-call
+ * bookkeeping of the flushes and the error convention are batch.c's, shared with the other batched calls. */
 #include "pll_internal.h"
-
-static int fail_quartet(const char *who)
-{
-  fprintf(stderr, "libpll_amd: %s: [%d] %s\n", who, pll_errno, pll_errmsg);
-  return PLL_FAILURE;
-}
-
-static int end_in_range(const pll_partition_t *p, unsigned int clv, int scaler, unsigned int matrix)
-{
-  return clv < p->nodes && matrix < p->prob_matrices && scaler >= PLL_SCALE_BUFFER_NONE && scaler < (int)p->scale_buffers;
-}
-
-/* the CLV (or tip codes) and scaler of one end on the device, each index once per call */
-static int prepare_once(pll_partition_t *p, pll_amd_ext_t *x, unsigned char *seen_clv, unsigned char *seen_scaler, unsigned int clv, int scaler)
-{
-  const int wants_scaler = scaler >= 0 && !pll_tip_by_codes(p, clv);
-  if (seen_clv[clv] && !(wants_scaler && !seen_scaler[scaler])) return 1;
-  seen_clv[clv] = 1;
-  if (wants_scaler) seen_scaler[scaler] = 1;
-  return pll_prepare_end(p, x, clv, scaler);
-}
 
 /* Everything a call decides after its NULL checks and before a device is needed, in the stated order: every index of the
  * whole list, freqs_indices, the refusals, the device. PLL_SUCCESS with the partition's extension in *ext. */
@@ -46,38 +25,20 @@ static int check_list(const char *who, pll_partition_t *p, const pll_gpu_quartet
   {
     const pll_gpu_quartet_t *q = &quartets[i];
     int ok = q->inner_matrix_index < p->prob_matrices;
-    for (e = 0; e < 4; ++e) ok = ok && end_in_range(p, q->clv_index[e], q->scaler_index[e], q->matrix_index[e]);
+    for (e = 0; e < 4; ++e) ok = ok && pll_batch_end_in_range(p, q->clv_index[e], q->scaler_index[e], q->matrix_index[e]);
     if (!ok)
     {
       pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: quartet %u has an index out of range", who, i);
-      return fail_quartet(who);
+      return pll_batch_fail(who);
     }
   }
   for (k = 0; k < p->rate_cats; ++k)
     if (freqs_indices[k] >= p->rate_matrices)
     {
       pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: freqs_indices[%u] out of range", who, k);
-      return fail_quartet(who);
+      return pll_batch_fail(who);
     }
-  if (pll_repeats_enabled(p))
-  {
-    /* the two nodes have no class map */
-    pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: PLL_ATTRIB_SITE_REPEATS partitions are not supported", who);
-    return fail_quartet(who);
-  }
-  if (p->attributes & PLL_ATTRIB_AB_MASK)
-  {
-    pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: the ascertainment-bias correction needs pll_compute_edge_loglikelihood", who);
-    return fail_quartet(who);
-  }
-  pll_amd_ext_t *x = pll_ext(p);
-  if (!x || !x->ctx)
-  {
-    pll_set_error(PLL_ERROR_GPU_UNAVAILABLE, "%s: no MI355X context behind this partition; this library has no CPU path", who);
-    return fail_quartet(who);
-  }
-  *ext = x;
-  return PLL_SUCCESS;
+  return pll_batch_refusals_and_device(who, p, "pll_compute_edge_loglikelihood", ext);
 }
 
 /* inputs current on the device: the model, one span over every named matrix, every named end once; the device layer's
@@ -94,16 +55,9 @@ static int flush_list(const char *who, pll_partition_t *p, pll_amd_ext_t *x, con
       if (m < lo) lo = m;
       if (m > hi) hi = m;
     }
-  unsigned char *seen = (unsigned char *)calloc((size_t)p->nodes + p->scale_buffers + 1, 1);
-  pllgpu_quartet_t *dev = (pllgpu_quartet_t *)malloc(sizeof(pllgpu_quartet_t) * count);
-  if (!seen || !dev)
-  {
-    free(seen);
-    free(dev);
-    pll_set_error(PLL_ERROR_MEM_ALLOC, "%s: out of memory", who);
-    return fail_quartet(who);
-  }
-  unsigned char *seen_scaler = seen + p->nodes;
+  pll_batch_seen_t seen;
+  pllgpu_quartet_t *dev = (pllgpu_quartet_t *)pll_batch_alloc(who, p, &seen, sizeof(pllgpu_quartet_t) * count);
+  if (!dev) return PLL_FAILURE;
   /* a pair of two tips takes no scaling decision where the reference reads both with its tip kernels */
   const unsigned int tip_mark = PLLGPU_QUARTET_TIP_CODES | ((p->attributes & PLL_ATTRIB_PATTERN_TIP) ? PLLGPU_QUARTET_TIP_PATTERN : 0u);
   int ok = pll_flush_model(p, x) && pll_flush_pmatrix(p, x, lo, hi);
@@ -113,7 +67,7 @@ static int flush_list(const char *who, pll_partition_t *p, pll_amd_ext_t *x, con
     pllgpu_quartet_t *d = &dev[i];
     for (e = 0; ok && e < 4; ++e)
     {
-      ok = prepare_once(p, x, seen, seen_scaler, q->clv_index[e], q->scaler_index[e]);
+      ok = pll_batch_prepare_once(p, x, &seen, q->clv_index[e], q->scaler_index[e]);
       d->clv[e] = q->clv_index[e];
       d->scaler[e] = q->scaler_index[e];
       d->matrix[e] = q->matrix_index[e];
@@ -121,11 +75,11 @@ static int flush_list(const char *who, pll_partition_t *p, pll_amd_ext_t *x, con
     }
     d->inner_matrix = q->inner_matrix_index;
   }
-  free(seen);
+  pll_batch_seen_free(&seen);
   if (!ok)
   {
     free(dev);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   *out = dev;
   return PLL_SUCCESS;
@@ -138,13 +92,13 @@ int pll_gpu_quartet_loglikelihoods(pll_partition_t *p, const pll_gpu_quartet_t *
   if (!p)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   if (!count) return PLL_SUCCESS;
   if (!quartets || !lnl || !freqs_indices)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: quartets, lnl or freqs_indices is NULL", who);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   pll_amd_ext_t *x = NULL;
   pllgpu_quartet_t *dev = NULL;
@@ -167,23 +121,23 @@ int pll_gpu_quartet_resampled_loglikelihoods(pll_partition_t *p, const pll_gpu_q
   if (!p)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   if (!count) return PLL_SUCCESS;
   if (!quartets || !freqs_indices)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: quartets or freqs_indices is NULL", who);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   if (replicates && (!replicate_weights || !resampled))
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: replicates > 0 and replicate_weights or resampled is NULL", who);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   if (!lnl && !resampled && !persite)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: lnl, resampled and persite are all NULL", who);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   pll_amd_ext_t *x = NULL;
   pllgpu_quartet_t *dev = NULL;
@@ -209,7 +163,7 @@ static int fail_device(const char *who, int rc)
     return PLL_FAILURE;
   }
   pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: %s", who, pllgpu_last_error());
-  return fail_quartet(who);
+  return pll_batch_fail(who);
 }
 
 int pll_gpu_quartet_rell_loglikelihoods(pll_partition_t *p, const pll_gpu_quartet_t *quartets, unsigned int count,
@@ -220,23 +174,23 @@ int pll_gpu_quartet_rell_loglikelihoods(pll_partition_t *p, const pll_gpu_quarte
   if (!p)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   if (!count) return PLL_SUCCESS;
   if (!quartets || !freqs_indices)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: quartets or freqs_indices is NULL", who);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   if (replicates && !resampled)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: replicates > 0 and resampled is NULL", who);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   if (!lnl && !resampled && !persite)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: lnl, resampled and persite are all NULL", who);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   pll_amd_ext_t *x = NULL;
   pllgpu_quartet_t *dev = NULL;
@@ -255,32 +209,18 @@ int pll_gpu_draw_replicate_weights(pll_partition_t *p, unsigned long long seed, 
   if (!p)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   if (!replicates) return PLL_SUCCESS;
   if (!weights)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: weights is NULL", who);
-    return fail_quartet(who);
+    return pll_batch_fail(who);
   }
   /* rows the quartet call could not take are not handed out: its refusals */
-  if (pll_repeats_enabled(p))
-  {
-    pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: PLL_ATTRIB_SITE_REPEATS partitions are not supported", who);
-    return fail_quartet(who);
-  }
-  if (p->attributes & PLL_ATTRIB_AB_MASK)
-  {
-    pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: partitions with an ascertainment-bias correction are not supported", who);
-    return fail_quartet(who);
-  }
-  pll_amd_ext_t *x = pll_ext(p);
-  if (!x || !x->ctx)
-  {
-    pll_set_error(PLL_ERROR_GPU_UNAVAILABLE, "%s: no MI355X context behind this partition; this library has no CPU path", who);
-    return fail_quartet(who);
-  }
-  if (!pll_flush_model(p, x)) return fail_quartet(who); /* the device's copy of the pattern weights is the partition's */
+  pll_amd_ext_t *x = NULL;
+  if (!pll_batch_refusals_and_device(who, p, NULL, &x)) return PLL_FAILURE;
+  if (!pll_flush_model(p, x)) return pll_batch_fail(who); /* the device's copy of the pattern weights is the partition's */
   const int rc = pllgpu_replicate_weights_draw(x->ctx, seed, first_replicate, replicates, weights);
   return rc != 0 ? fail_device(who, rc) : PLL_SUCCESS;
 }

@@ -188,6 +188,22 @@ def test_geometry_edges(amd_lib, monkeypatch, shape, sites):
         assert fenced.tobytes() == full.tobytes()
 
 
+def test_a_list_longer_than_one_launch(amd_lib):
+    """more candidates than one launch carries descriptors for (16384; include/pll_amd_device.h states the cutting rule):
+    the second launch's values land behind the first's, each with the bits it has in a short list"""
+    dims = (4, 4, 20, 65)
+    exp, _ = _reference(dims, 0)
+    with _bed(amd_lib, dims, 0) as b:
+        rows = b.prepare()
+        assert len(rows) == 37
+        short = b.batched(_query(b.lay), rows)
+        _check(short, exp, "the short list")
+        times = 16384 // len(rows) + 1
+        got = b.batched(_query(b.lay), rows * times)
+        assert amd_lib.pll_gpu_last_launch_count(b.p) == 2
+        assert got.tobytes() == np.tile(short, times).tobytes()
+
+
 @pytest.mark.parametrize("attrs", ["plain", "rate_scalers"])
 def test_a_tile_too_large_for_lds(amd_lib, attrs):
     """20 states x 16 rates: the inserted node's tile (R x S = 320 > 288 values per lane) does not fit the 144 KB the kernel

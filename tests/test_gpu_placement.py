@@ -105,6 +105,26 @@ def test_site_counts_around_the_tile(amd_lib, ref_lib, monkeypatch, shape, sites
         assert fenced.tobytes() == full.tobytes()
 
 
+def test_a_list_longer_than_one_launch(amd_lib, ref_lib):
+    """more candidates than one launch carries descriptors for (16384; include/pll_amd_device.h states the cutting rule),
+    two queries so that the call is not the insertion call's: the second launch's values land behind the first's in
+    every query's row, each with the bits it has in a short list"""
+    dims = (4, 4, 20, 65)
+    exp, _ = PC.reference(ref_lib, dims, 0, 2, range(2))
+    with PC.bed(amd_lib, dims, 0, 2) as b:
+        rows = b.prepare()
+        assert len(rows) == 37
+        tips = [b.lay.T, b.lay.T + 1]
+        short = PC.placement(b, tips, rows)
+        _check(short, exp, "the short list")
+        times = 16384 // len(rows) + 1
+        got = PC.placement(b, tips, rows * times)
+        launches = amd_lib.pll_gpu_last_launch_count(b.p)
+        assert launches == PC.launches(dims[0], dims[1], dims[3], len(tips), len(rows) * times) == 2
+        for q in range(len(tips)):
+            assert got[q].tobytes() == np.tile(short[q], times).tobytes(), q
+
+
 MODEL = {
     "invariant_sites": dict(prop_invar=0.3),
     "two_frequency_sets": dict(rate_matrices=2, freqs_indices=(0, 1, 0, 1)),
