@@ -990,6 +990,53 @@ typedef struct pll_gpu_branch
 } pll_gpu_branch_t;
 int pll_gpu_branch_derivatives(pll_partition_t *partition, const pll_gpu_branch_t *branches, unsigned int count,
                                const unsigned int *params_indices, double *d_f, double *dd_f /* may be NULL */);
+/* ---- rate-category posteriors, site rates and EM weight steps ----------
+ * The per-category site likelihoods of one edge - what every evaluation kernel mixes away in registers - and what model
+ * optimisation makes of them: FreeRate (+R) and mixture (LG4X) weights, empirical-Bayes site rates, a pinv step. The
+ * seven edge arguments are those of pll_compute_edge_loglikelihood. With w the category weights, pi_f(k) / p_f(k) the
+ * frequency set and prop_invar of category k, r the category rates and pw the pattern weights:
+ *   l[n][k] = sum_j pi_f(k)[j] x_k[n][j] (P_k y_k[n])[j]
+ *   s[n][k] = the scaling counts of both ends added: per site (the same for every k), or per rate (PLL_ATTRIB_RATE_SCALERS)
+ *   c[n]    = min_k s[n][k]            u[n][k] = l[n][k] * 2^(-256 min(s[n][k] - c[n], 4))    (what the edge kernels mix)
+ *   A[n][k] = w_k (1 - p_f(k)) u[n][k]
+ *   I[n][k] = w_k p_f(k) pi_f(k)[inv_n] if p_f(k) > 0 and site n is invariant, else 0
+ * and, where c[n] > 0 and sum_k I > 0, A multiplied by 2^(-256 min(c[n], 4)) (src/core_likelihood.c:1156-1174);
+ * L[n] = sum_k (A + I). Each output may be NULL (not all five); host layouts are site-major:
+ *   cat_lnl[n][k]   = log(l[n][k]) - 256 ln2 * s[n][k]      exact: no cap at 4, no weight, no pinv, no pattern weight; -inf where l = 0
+ *   posterior[n][k] = (A[n][k] + I[n][k]) / L[n]            rows sum to 1
+ *   site_rates[n]   = sum_k (A[n][k] / L[n]) * r_k          the invariant share has rate 0
+ *   weight_sums[k]  = sum_n pw[n] * posterior[n][k]         the EM numerator
+ *   lnl             = sum_n pw[n] * site lnL                what pll_compute_edge_loglikelihood returns
+ * A site with L[n] = 0 gets a zero posterior row and rate, adds nothing to weight_sums and makes lnl -inf.
+ * The ends are oriented exactly as pll_compute_edge_loglikelihood orients them. What the previous pll_update_partials
+ * still holds back is launched first and pending CLVs are stored first: an edge may name what a traversal produced.
+ * Nothing in the partition is written. Synchronous: one copy back per output asked for and one wait; every sum is
+ * formed in an order that depends on the site count alone. pll_gpu_last_launch_count: 1 with cat_lnl alone, 2 with
+ * posterior or site_rates, 3 with weight_sums or lnl.
+ * PLL_SUCCESS, or PLL_FAILURE with pll_errno, the usual line on stderr and every output untouched. The checks, all before
+ * anything is launched or written, in this order: PLL_ERROR_PARAM_INVALID for a NULL partition, a NULL freqs_indices or
+ * five NULL outputs; PLL_ERROR_PARAM_INVALID for an index out of range (a scaler below -1 included), a freqs_indices[k]
+ * >= rate_matrices or two PLL_ATTRIB_PATTERN_TIP tip ends; PLL_ERROR_GPU_UNSUPPORTED for a PLL_ATTRIB_SITE_REPEATS
+ * partition and for one with an ascertainment-bias correction; PLL_ERROR_GPU_UNAVAILABLE without a device. */
+int pll_gpu_edge_category_posteriors(pll_partition_t *partition, unsigned int parent_clv_index, int parent_scaler_index,
+                                     unsigned int child_clv_index, int child_scaler_index, unsigned int matrix_index,
+                                     const unsigned int *freqs_indices, double *cat_lnl /* [sites][rate_cats] or NULL */,
+                                     double *posterior /* [sites][rate_cats] or NULL */, double *site_rates /* [sites] or NULL */,
+                                     double *weight_sums /* [rate_cats] or NULL */, double *lnl /* 1 or NULL */);
+/* EM steps on the category weights over the same edge, in one call: the CLVs are read once, every step is a stream over
+ * sites x rate_cats doubles on the device. Row 0 of weights_out is the start - start_weights, or the partition's
+ * rate_weights for NULL - row i + 1 is S_k / (S_0 + ... + S_{R-1}), added in that order, with S = weight_sums evaluated
+ * under row i, and lnl_out[i] (lnl_out may be NULL) is lnl under row i. steps == 0 is one evaluation. The partition's own
+ * weights are neither read after row 0 is formed nor written: the caller hands the row it wants to
+ * pll_set_category_weights. pll_gpu_last_launch_count: 1 + 2 (steps + 1), with no host wait between the launches.
+ * The checks and their order are those above, with, among the first: NULL weights_out, steps > PLL_GPU_EM_MAX_STEPS, a
+ * start weight that is negative or not finite, or start weights summing to 0 (PLL_ERROR_PARAM_INVALID). */
+#define PLL_GPU_EM_MAX_STEPS 1024
+int pll_gpu_category_weights_em(pll_partition_t *partition, unsigned int parent_clv_index, int parent_scaler_index,
+                                unsigned int child_clv_index, int child_scaler_index, unsigned int matrix_index,
+                                const unsigned int *freqs_indices, const double *start_weights /* [rate_cats] or NULL */,
+                                unsigned int steps, double *weights_out /* [steps + 1][rate_cats] */,
+                                double *lnl_out /* [steps + 1] or NULL */);
 /* ---- batched placement log-likelihoods ---------------------------------
  * Every query x every candidate edge in one call: the pre-scoring pass of a phylogenetic placement, the first pass of
  * a stepwise addition by likelihood. lnl is [query_count][count], query-major, and lnl[q * count + i] is BY DEFINITION

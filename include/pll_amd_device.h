@@ -367,6 +367,41 @@ int pllgpu_branch_derivatives(pllgpu_ctx_t *ctx, const pllgpu_branch_t *branches
  * ends are honoured (kernels_ancestral.h), which the reference does not do. */
 int pllgpu_node_ancestral(pllgpu_ctx_t *ctx, const pllgpu_edge_t *edge, double *host_out, void *device_out);
 
+/* The per-category site likelihoods of an edge and what model optimisation makes of them (kernels_category.h). With
+ * l[n][k] = sum_j pi_f(k)[j] x_k[n][j] (P_k y_k[n])[j], s[n][k] the scaling counts of both ends added (per site, or per
+ * rate), c[n] = min_k s[n][k], u = l * 2^(-256 min(s - c, 4)), A[n][k] = w_k (1 - p_f(k)) u[n][k], I[n][k] =
+ * w_k p_f(k) pi_f(k)[inv_n] (p_f(k) > 0 and site n invariant, else 0), A multiplied by 2^(-256 min(c, 4)) where c > 0 and
+ * sum_k I > 0 (finish_site's rule), L[n] = sum_k (A + I):
+ *   cat_lnl[n][k]   = log(l[n][k]) - 256 ln2 * s[n][k]        posterior[n][k] = (A[n][k] + I[n][k]) / L[n]
+ *   site_rates[n]   = sum_k (A[n][k] / L[n]) * r_k             weight_sums[k]  = sum_n pw[n] * posterior[n][k]
+ *   lnl             = sum_n pw[n] * finish_site(sum_k A, sum_k I, c[n])     (what pllgpu_edge_loglikelihood returns)
+ * Host layouts are site-major; each output may be NULL, not all five. A site with L = 0 has a zero row and rate.
+ * Of `edge`, gather must be 0 and want_persite / device_result / sequence are not used. Checks, in this order and all
+ * before anything is launched: null arguments, the edge's indices (check_edge), class-compressed CLVs and
+ * ascertainment-bias entries (PLLGPU_EUNSUPPORTED). Held work is launched and pending CLVs are stored first.
+ * The launch rule (counted into pllgpu_last_launch_count). Stage A, one launch, writes the table u as [k][sites rounded
+ * up to 64], a count word per site and cat_lnl: 4 x 4 with T = ceil(sites / 64), w = ceil(T / 16384), ceil(T / (4 w))
+ * workgroups of 256; every other shape w = ceil(T / 4096), ceil(T / w) workgroups of 64 min(rate_cats, 4). Stage B,
+ * k_category_mix, B = min(ceil(sites / 256), 1024) workgroups of 256 walking the 256-site tiles with stride B, mixes
+ * the table under one row of weights in device memory and leaves rate_cats + 1 partial sums per workgroup; stage C,
+ * k_category_reduce, one workgroup, adds each value's B partials in ascending order. 1 launch when only cat_lnl is asked,
+ * 2 with posterior or site_rates, 3 with weight_sums or lnl; then one copy back per output and one wait. Scratch from
+ * the context's block pool: 8 rate_cats sites_padded + 4 sites bytes, 8 (rate_cats + 1) B of partials, the staging of
+ * the outputs asked for. Outputs are written only on success. */
+int pllgpu_edge_category_posteriors(pllgpu_ctx_t *ctx, const pllgpu_edge_t *edge, double *host_cat_lnl, double *host_posterior,
+                                    double *host_site_rates, double *host_weight_sums, double *host_lnl);
+
+/* EM on the category weights over the same table: stage A once, then stages B and C `steps + 1` times, evaluation i
+ * under row i of a device array [steps + 1][rate_cats] whose row 0 is start_weights and whose row i + 1 stage C forms
+ * as S_k / (S_0 + ... + S_{R-1}) (added in that order), S = weight_sums under row i. 1 + 2 (steps + 1) launches with no
+ * host wait between them, one copy back of the rows (host_weights, [steps + 1][rate_cats]) and one of the evaluations'
+ * lnl (host_lnl, [steps + 1], may be NULL), one wait. The context's rate_weights are neither read nor written. NULL
+ * start_weights or host_weights, steps > PLLGPU_EM_MAX_STEPS, a start weight that is negative or not finite or a start
+ * row summing to 0 are PLLGPU_EINVAL, before the checks above. */
+#define PLLGPU_EM_MAX_STEPS 1024
+int pllgpu_category_weights_em(pllgpu_ctx_t *ctx, const pllgpu_edge_t *edge, const double *start_weights, unsigned int steps,
+                               double *host_weights, double *host_lnl);
+
 /* ---- transition matrices on the device ---------------------------- */
 /* eigensystem of rate matrix `index` in the reference's layouts: eigenvecs[j*sp+i],
  * inv_eigenvecs[i*sp+j] ([states][states_padded] each), eigenvals[states_padded] */

@@ -29,6 +29,7 @@
 #include "kernels_lean.h"
 #include "kernels_repeats.h"
 #include "kernels_ancestral.h"
+#include "kernels_category.h"
 #include "kernels_parsimony.h"
 #include "kernels_sankoff.h"
 #include "kernels_insertion.h"
@@ -286,6 +287,11 @@ struct pllgpu_ctx
   double seq_override = 0.0;     // pllgpu_edge_t.sequence of the evaluation being issued (0: number it here)
   DevBuf<double> reduce;         // {lnL, sequence}: the operand of a caller's all-reduce (pllgpu_reduce_buffer)
   DevBuf<double> ancestral;      // [sites][states] staging of pllgpu_node_ancestral's host output, allocated on first use
+  // pllgpu_edge_category_posteriors / pllgpu_category_weights_em (kernels_category.h): the table [R][sites padded to 64],
+  // the count word per site, partials [R + 1][B], results [evaluation][R + 1], the EM call's weight rows [steps + 1][R],
+  // and the staging of the three per-site outputs - each allocated on first use
+  DevBuf<double> cat_table, cat_partials, cat_results, cat_weights, cat_lnl, cat_posterior, cat_rates;
+  DevBuf<unsigned> cat_count;
   std::vector<double> stage;     // host staging for the P-matrix re-layout
   std::vector<unsigned char> stage8; // ... and for a class map that goes up as bytes
   unsigned last_launches = 0;
@@ -753,6 +759,14 @@ extern "C" void pllgpu_destroy(pllgpu_ctx_t *c)
   c->block_sums.release();
   c->reduce.release();
   c->ancestral.release();
+  c->cat_table.release();
+  c->cat_partials.release();
+  c->cat_results.release();
+  c->cat_weights.release();
+  c->cat_lnl.release();
+  c->cat_posterior.release();
+  c->cat_rates.release();
+  c->cat_count.release();
   c->counter.release();
   c->mfma_flags.release();
   c->eigenvals.release();
@@ -3677,6 +3691,177 @@ extern "C" int pllgpu_node_ancestral(pllgpu_ctx_t *c, const pllgpu_edge_t *ed, d
   if (!host_out) return 0; // stream-ordered: the table stays where the caller asked for it
   HIP_TRY(hipMemcpyAsync(host_out, c->ancestral.p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(stream_wait(c));
+  return 0;
+}
+
+// ---- rate-category posteriors, site rates and EM weight steps (kernels_category.h) -------------------------
+static_assert(PLLGPU_EM_MAX_STEPS == 1024, "include/pll_amd_device.h states the limit");
+
+// what both calls share: the edge as stage A reads it, the model as stage B reads it, the grid of stages B and C
+struct CategoryCall
+{
+  DevCategory a;
+  DevCategoryMix m;
+  unsigned blocks; // B = min(ceil(sites / 256), 1024)
+  bool ctip;
+};
+
+// Every check, in the order the header states, then - the first step that touches device state - held work out and
+// pending CLVs stored, the edge and the model resolved and the scratch taken. `sums`: stage B leaves partials;
+// `evaluations`: how many {weight_sums, lnl} records the results buffer holds.
+static int category_begin(pllgpu_ctx *c, const pllgpu_edge_t *ed, const char *noun, bool want_cat_lnl, bool want_posterior, bool want_rates, bool sums,
+                          size_t evaluations, CategoryCall &k)
+{
+  const pllgpu_geometry_t &g = c->geo;
+  if (!ed || !ed->freqs_indices) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
+  if (int rc = check_edge(c, ed, nullptr)) return rc;
+  if (ed->gather) return fail(PLLGPU_EUNSUPPORTED, "%s of class-compressed CLVs", noun);
+  if (int rc = refuse_ascertainment(c, noun)) return rc;
+  if (int rc = refuse_compressed(c, noun)) return rc;
+  if (want_rates && !c->rates.p) return fail(PLLGPU_EINVAL, "%s: category rates were not uploaded", noun);
+  if (HOLDS_WORK(c) || !c->pending.empty())
+    if (int rc = flush_deferred(c)) return rc;
+  if (int rc = build_edge(c, ed, k.a.e)) return rc;
+  if (int rc = fill_edge_model(c, k.a.e, ed->freqs_indices)) return rc;
+  k.ctip = ed->child_is_tip != 0;
+  k.blocks = std::min((g.sites + 255u) / 256u, 1024u);
+  const unsigned pad = (g.sites + 63u) / 64u * 64u;
+  const size_t R = g.rate_cats;
+  {
+    ScratchEpoch scratch_epoch_;
+    if (c->cat_table.ensure(R * pad) || c->cat_count.ensure(g.sites)) return PLLGPU_ENOMEM;
+    if (sums && (c->cat_partials.ensure((R + 1) * k.blocks) || c->cat_results.ensure(evaluations * (R + 1)))) return PLLGPU_ENOMEM;
+    if ((want_cat_lnl && c->cat_lnl.ensure(R * g.sites)) || (want_posterior && c->cat_posterior.ensure(R * g.sites)) ||
+        (want_rates && c->cat_rates.ensure(g.sites)))
+      return PLLGPU_ENOMEM;
+  }
+  k.a.table = c->cat_table.p;
+  k.a.count = c->cat_count.p;
+  k.a.cat_lnl = want_cat_lnl ? c->cat_lnl.p : nullptr;
+  k.a.pad = pad;
+
+  DevCategoryMix &m = k.m;
+  memset(&m, 0, sizeof m);
+  m.table = c->cat_table.p;
+  m.count = c->cat_count.p;
+  m.weights = c->rate_weights.p;
+  m.freqs = k.a.e.freqs;
+  m.prop_invar = k.a.e.prop_invar;
+  m.rates = c->rates.p;
+  m.invariant = k.a.e.invariant;
+  m.pattern_weights = k.a.e.pattern_weights;
+  m.posterior = want_posterior ? c->cat_posterior.p : nullptr;
+  m.site_rates = want_rates ? c->cat_rates.p : nullptr;
+  m.partials = sums ? c->cat_partials.p : nullptr;
+  m.sites = g.sites;
+  m.pad = pad;
+  m.R = g.rate_cats;
+  m.SP = g.states_padded;
+  memcpy(m.fidx, k.a.e.fidx, sizeof m.fidx);
+  return 0;
+}
+
+template <int ICH>
+static void launch_category_generic(pllgpu_ctx *c, const DevCategory &a, unsigned blocks, unsigned tpw, bool ctip)
+{
+  const unsigned long long *tm = tipmap_ptr(c);
+  const unsigned nw = std::min(c->gg.R, 4u); // one wave per rate category of the tile, up to 4
+  with_bools(ctip, false, [&](auto CT, auto) {
+    hipLaunchKernelGGL((k_category_tiled<ICH, CT()>), dim3(blocks), dim3(64u * nw), 0, c->stream, a, c->gg, tm, tpw);
+  });
+}
+
+// stage A: the 4 x 4 form or the tiled one, tile walk as launch_ancestral
+static int launch_category_table(pllgpu_ctx *c, const CategoryCall &k)
+{
+  const unsigned tiles = (c->geo.sites + 63) / 64;
+  const unsigned max_blocks = 1024;
+  if (c->dna_fast)
+  {
+    const unsigned tpw = (tiles + 4 * 4 * max_blocks - 1) / (4 * 4 * max_blocks);
+    const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
+    with_bools(k.ctip, false, [&](auto CT, auto) { hipLaunchKernelGGL((k_category_dna<CT()>), dim3(blocks), dim3(256), 0, c->stream, k.a, tpw); });
+    return launched(c);
+  }
+  const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
+  const unsigned blocks = (tiles + tpw - 1) / tpw;
+  with_ich(c->ich, [&](auto ICH) { launch_category_generic<ICH()>(c, k.a, blocks, tpw, k.ctip); });
+  return launched(c);
+}
+
+// stages B and C of one evaluation under the weight row `weights`: its {weight_sums, lnl} to record `record` of the
+// results, the row that follows to `next` (or nowhere)
+static int launch_category_mix(pllgpu_ctx *c, CategoryCall &k, const double *weights, size_t record, double *next)
+{
+  k.m.weights = weights;
+  hipLaunchKernelGGL(k_category_mix, dim3(k.blocks), dim3(256), 0, c->stream, k.m);
+  if (int rc = launched(c)) return rc;
+  if (!k.m.partials) return 0;
+  hipLaunchKernelGGL(k_category_reduce, dim3(1), dim3(256), 0, c->stream, k.m.partials, k.blocks, k.m.R, c->cat_results.p + record * (k.m.R + 1u), next);
+  return launched(c);
+}
+
+extern "C" int pllgpu_edge_category_posteriors(pllgpu_ctx_t *c, const pllgpu_edge_t *ed, double *host_cat_lnl, double *host_posterior,
+                                               double *host_site_rates, double *host_weight_sums, double *host_lnl)
+{
+  CHECK_CTX_KEEP(c);
+  const pllgpu_geometry_t &g = c->geo;
+  c->last_launches = 0;
+  static const char noun[] = "category posteriors";
+  if (!host_cat_lnl && !host_posterior && !host_site_rates && !host_weight_sums && !host_lnl) return fail(PLLGPU_EINVAL, "%s: no output asked for", noun);
+  const bool sums = host_weight_sums || host_lnl;
+  CategoryCall k;
+  if (int rc = category_begin(c, ed, noun, host_cat_lnl != nullptr, host_posterior != nullptr, host_site_rates != nullptr, sums, 1, k)) return rc;
+  if (int rc = launch_category_table(c, k)) return rc;
+  if (host_posterior || host_site_rates || sums)
+    if (int rc = launch_category_mix(c, k, c->rate_weights.p, 0, nullptr)) return rc;
+  // one copy back per output, one wait; the sums are handed over once everything has succeeded
+  const size_t R = g.rate_cats;
+  std::vector<double> record(R + 1);
+  if (host_cat_lnl) HIP_TRY(hipMemcpyAsync(host_cat_lnl, c->cat_lnl.p, R * g.sites * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (host_posterior) HIP_TRY(hipMemcpyAsync(host_posterior, c->cat_posterior.p, R * g.sites * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (host_site_rates) HIP_TRY(hipMemcpyAsync(host_site_rates, c->cat_rates.p, g.sites * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (sums) HIP_TRY(hipMemcpyAsync(record.data(), c->cat_results.p, (R + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(stream_wait(c));
+  if (host_weight_sums) memcpy(host_weight_sums, record.data(), R * sizeof(double));
+  if (host_lnl) *host_lnl = record[R];
+  return 0;
+}
+
+extern "C" int pllgpu_category_weights_em(pllgpu_ctx_t *c, const pllgpu_edge_t *ed, const double *start_weights, unsigned steps, double *host_weights,
+                                          double *host_lnl)
+{
+  CHECK_CTX_KEEP(c);
+  const pllgpu_geometry_t &g = c->geo;
+  c->last_launches = 0;
+  static const char noun[] = "category weights EM";
+  if (!start_weights || !host_weights) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
+  if (steps > PLLGPU_EM_MAX_STEPS) return fail(PLLGPU_EINVAL, "%s: %u steps, at most %u", noun, steps, (unsigned)PLLGPU_EM_MAX_STEPS);
+  double total = 0.0;
+  for (unsigned i = 0; i < g.rate_cats; ++i)
+  {
+    if (!(start_weights[i] >= 0.0) || !std::isfinite(start_weights[i])) return fail(PLLGPU_EINVAL, "%s: start weight %u is negative or not finite", noun, i);
+    total += start_weights[i];
+  }
+  if (!(total > 0.0)) return fail(PLLGPU_EINVAL, "%s: the start weights sum to 0", noun);
+  const size_t R = g.rate_cats, rows = (size_t)steps + 1;
+  CategoryCall k;
+  if (int rc = category_begin(c, ed, noun, false, false, false, true, rows, k)) return rc;
+  {
+    ScratchEpoch scratch_epoch_;
+    if (c->cat_weights.ensure(rows * R)) return PLLGPU_ENOMEM;
+  }
+  HIP_TRY(copy_up(c, c->cat_weights.p, start_weights, R * sizeof(double)));
+  if (int rc = launch_category_table(c, k)) return rc;
+  for (size_t i = 0; i < rows; ++i)
+    if (int rc = launch_category_mix(c, k, c->cat_weights.p + i * R, i, i + 1 < rows ? c->cat_weights.p + (i + 1) * R : nullptr)) return rc;
+  std::vector<double> weights(rows * R), records(rows * (R + 1));
+  HIP_TRY(hipMemcpyAsync(weights.data(), c->cat_weights.p, weights.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (host_lnl) HIP_TRY(hipMemcpyAsync(records.data(), c->cat_results.p, records.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(stream_wait(c));
+  memcpy(host_weights, weights.data(), weights.size() * sizeof(double));
+  if (host_lnl)
+    for (size_t i = 0; i < rows; ++i) host_lnl[i] = records[i * (R + 1) + R];
   return 0;
 }
 

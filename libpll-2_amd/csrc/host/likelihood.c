@@ -96,6 +96,44 @@ static int swap_is_exact(const pll_partition_t *p, const pll_amd_ext_t *x, unsig
   return 1;
 }
 
+int pll_edge_orient(pll_partition_t *p, pll_amd_ext_t *x, unsigned int parent_clv_index, int parent_scaler_index,
+                    unsigned int child_clv_index, int child_scaler_index, unsigned int matrix_index,
+                    const unsigned int *freqs_indices, pllgpu_edge_t *e)
+{
+  if (pll_tip_by_codes(p, parent_clv_index) && pll_tip_by_codes(p, child_clv_index))
+  {
+    if (p->attributes & PLL_ATTRIB_PATTERN_TIP)
+    {
+      pll_set_error(PLL_ERROR_PARAM_INVALID, "pll_compute_edge_loglikelihood: both ends are pattern tips");
+      return PLL_FAILURE;
+    }
+    pll_tip_densify(p, parent_clv_index); /* two compact tips: one of them becomes a dense CLV */
+  }
+  if (pll_tip_by_codes(p, parent_clv_index) && !(p->attributes & PLL_ATTRIB_PATTERN_TIP) &&
+      !swap_is_exact(p, x, matrix_index, freqs_indices))
+    pll_tip_densify(p, parent_clv_index); /* keep the caller's orientation (src/likelihood.c:626-634) */
+  const int ptip = pll_tip_by_codes(p, parent_clv_index);
+  const int ctip = pll_tip_by_codes(p, child_clv_index);
+  if (!pll_flush_model(p, x) || !pll_flush_pmatrix(p, x, matrix_index, matrix_index) ||
+      !pll_prepare_end(p, x, parent_clv_index, parent_scaler_index) ||
+      !pll_prepare_end(p, x, child_clv_index, child_scaler_index))
+    return PLL_FAILURE;
+
+  memset(e, 0, sizeof *e);
+  /* the inner node plays "parent" when the other end is a tip given by codes
+   * (src/likelihood.c:612-624); P is symmetric in the reversible sense used there */
+  e->parent_clv = ptip ? child_clv_index : parent_clv_index;
+  e->parent_scaler = ptip ? child_scaler_index : parent_scaler_index;
+  e->child_clv = ptip ? parent_clv_index : child_clv_index;
+  e->child_scaler = (ptip || ctip) ? PLL_SCALE_BUFFER_NONE : child_scaler_index;
+  e->child_is_tip = (ptip || ctip);
+  e->matrix = matrix_index;
+  e->gather = pll_repeats_enabled(p) &&
+              (p->repeats->pernode_ids[parent_clv_index] || p->repeats->pernode_ids[child_clv_index]);
+  e->freqs_indices = freqs_indices;
+  return PLL_SUCCESS;
+}
+
 static double edge_lnl(pll_partition_t *p, unsigned int parent_clv_index, int parent_scaler_index,
                        unsigned int child_clv_index, int child_scaler_index, unsigned int matrix_index,
                        const unsigned int *freqs_indices, double *persite_lnl, double *device_result, double sequence)
@@ -112,38 +150,10 @@ static double edge_lnl(pll_partition_t *p, unsigned int parent_clv_index, int pa
     pll_set_error(PLL_ERROR_PARAM_INVALID, "pll_compute_edge_loglikelihood: index out of range");
     return fail_lnl("pll_compute_edge_loglikelihood");
   }
-  if (pll_tip_by_codes(p, parent_clv_index) && pll_tip_by_codes(p, child_clv_index))
-  {
-    if (p->attributes & PLL_ATTRIB_PATTERN_TIP)
-    {
-      pll_set_error(PLL_ERROR_PARAM_INVALID, "pll_compute_edge_loglikelihood: both ends are pattern tips");
-      return fail_lnl("pll_compute_edge_loglikelihood");
-    }
-    pll_tip_densify(p, parent_clv_index); /* two compact tips: one of them becomes a dense CLV */
-  }
-  if (pll_tip_by_codes(p, parent_clv_index) && !(p->attributes & PLL_ATTRIB_PATTERN_TIP) &&
-      !swap_is_exact(p, x, matrix_index, freqs_indices))
-    pll_tip_densify(p, parent_clv_index); /* keep the caller's orientation (src/likelihood.c:626-634) */
-  const int ptip = pll_tip_by_codes(p, parent_clv_index);
-  const int ctip = pll_tip_by_codes(p, child_clv_index);
-  if (!pll_flush_model(p, x) || !pll_flush_pmatrix(p, x, matrix_index, matrix_index) ||
-      !pll_prepare_end(p, x, parent_clv_index, parent_scaler_index) ||
-      !pll_prepare_end(p, x, child_clv_index, child_scaler_index))
-    return fail_lnl("pll_compute_edge_loglikelihood");
-
   pllgpu_edge_t e;
-  memset(&e, 0, sizeof e);
-  /* the inner node plays "parent" when the other end is a tip given by codes
-   * (src/likelihood.c:612-624); P is symmetric in the reversible sense used there */
-  e.parent_clv = ptip ? child_clv_index : parent_clv_index;
-  e.parent_scaler = ptip ? child_scaler_index : parent_scaler_index;
-  e.child_clv = ptip ? parent_clv_index : child_clv_index;
-  e.child_scaler = (ptip || ctip) ? PLL_SCALE_BUFFER_NONE : child_scaler_index;
-  e.child_is_tip = (ptip || ctip);
-  e.matrix = matrix_index;
-  e.gather = pll_repeats_enabled(p) &&
-             (p->repeats->pernode_ids[parent_clv_index] || p->repeats->pernode_ids[child_clv_index]);
-  e.freqs_indices = freqs_indices;
+  if (!pll_edge_orient(p, x, parent_clv_index, parent_scaler_index, child_clv_index, child_scaler_index, matrix_index,
+                       freqs_indices, &e))
+    return fail_lnl("pll_compute_edge_loglikelihood");
   e.want_persite = persite_lnl != NULL;
   e.device_result = device_result;
   e.sequence = sequence;

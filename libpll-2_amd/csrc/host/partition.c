@@ -676,6 +676,11 @@ int pll_flush_eigen(pll_partition_t *p, pll_amd_ext_t *x)
       GPU_TRY(pllgpu_eigen_upload(x->ctx, i, p->eigenvecs[i], p->inv_eigenvecs[i], p->eigenvals[i]), "eigensystem upload");
       x->eigen_dirty[i] = 0;
     }
+  return pll_flush_rates(p, x);
+}
+
+int pll_flush_rates(pll_partition_t *p, pll_amd_ext_t *x)
+{
   if (x->rates_dirty || x->always_upload)
   {
     GPU_TRY(pllgpu_rates_upload(x->ctx, p->rates), "category rates upload");

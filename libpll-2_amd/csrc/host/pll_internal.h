@@ -132,6 +132,8 @@ int pll_flush_clv(pll_partition_t *p, pll_amd_ext_t *x, unsigned int clv_index);
 int pll_flush_scaler(pll_partition_t *p, pll_amd_ext_t *x, int scaler_index);
 /* model arrays + eigensystems + category rates: what the derivative and P-matrix kernels read */
 int pll_flush_eigen(pll_partition_t *p, pll_amd_ext_t *x);
+/* the category rates alone */
+int pll_flush_rates(pll_partition_t *p, pll_amd_ext_t *x);
 /* class maps of the parents of `ops` on the device, dependency level by level (repeats.c) */
 int pll_update_repeats_device(pll_partition_t *p, pll_amd_ext_t *x, const pll_operation_t *ops,
                               unsigned int count, const unsigned int *level, unsigned int nlevels);
@@ -143,6 +145,14 @@ void pll_pmatrix_formed_on_device(const pll_partition_t *p, pll_amd_ext_t *x, co
                                   unsigned int matrix_index);
 /* one end of an edge evaluation: its CLV (or tip codes), its scaler vector and its class map (likelihood.c) */
 int pll_prepare_end(pll_partition_t *p, pll_amd_ext_t *x, unsigned int clv, int scaler);
+/* The two ends of an edge as the evaluation kernels take them, for indices that are in range (likelihood.c): a parent
+ * that the device reads as tip codes is swapped with the child when that is exact and given a dense CLV otherwise, of
+ * two compact tips one is densified, two PLL_ATTRIB_PATTERN_TIP tips are PLL_ERROR_PARAM_INVALID; then the model, the
+ * matrix and both ends are brought up to date on the device and *e is filled (zeroed first; want_persite, device_result
+ * and sequence are the caller's). PLL_SUCCESS, or PLL_FAILURE with pll_errno set. */
+int pll_edge_orient(pll_partition_t *p, pll_amd_ext_t *x, unsigned int parent_clv_index, int parent_scaler_index,
+                    unsigned int child_clv_index, int child_scaler_index, unsigned int matrix_index,
+                    const unsigned int *freqs_indices, pllgpu_edge_t *e);
 /* the class map of `node` (all nodes: node < 0) was written by something other than the class kernels, or must be
  * taken as such: whatever was derived from it is computed again by the next pll_update_repeats */
 void pll_maps_touched(pll_amd_ext_t *x, const pll_partition_t *p, int node);

@@ -368,6 +368,41 @@ class Session:
             raise RuntimeError(f"pll_compute_node_ancestral: [{self.lib.errno()}] {self.lib.errmsg()}")
         return out
 
+    CATEGORY_OUTPUTS = ("cat_lnl", "posterior", "site_rates", "weight_sums", "lnl")
+
+    def edge_categories(self, edge, want=CATEGORY_OUTPUTS):
+        """pll_gpu_edge_category_posteriors on edge = (parent, pscaler, child, cscaler, matrix): a dict of the outputs
+        named in `want` - cat_lnl and posterior [sites, rate_cats], site_rates [sites], weight_sums [rate_cats], lnl"""
+        c = self.case
+        shapes = {"cat_lnl": (c.sites, c.rate_cats), "posterior": (c.sites, c.rate_cats), "site_rates": (c.sites,),
+                  "weight_sums": (c.rate_cats,), "lnl": (1,)}
+        unknown = set(want) - set(shapes)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        out = {k: np.zeros(shapes[k]) for k in self.CATEGORY_OUTPUTS if k in want}
+        ok = self.lib.pll_gpu_edge_category_posteriors(
+            self.p, edge[0], edge[1], edge[2], edge[3], edge[4], api.uptr(self._fi),
+            *[api.dptr(out[k]) if k in out else None for k in self.CATEGORY_OUTPUTS])
+        if not ok:
+            raise RuntimeError(f"pll_gpu_edge_category_posteriors: [{self.lib.errno()}] {self.lib.errmsg()}")
+        if "lnl" in out:
+            out["lnl"] = float(out["lnl"][0])
+        return out
+
+    def category_weights_em(self, edge, start, steps):
+        """pll_gpu_category_weights_em: (weights [steps + 1, rate_cats], lnl [steps + 1]); start None = the partition's
+        rate_weights"""
+        c = self.case
+        w = np.zeros((steps + 1, c.rate_cats))
+        lnl = np.zeros(steps + 1)
+        s = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
+        ok = self.lib.pll_gpu_category_weights_em(
+            self.p, edge[0], edge[1], edge[2], edge[3], edge[4], api.uptr(self._fi),
+            None if s is None else api.dptr(s), steps, api.dptr(w), api.dptr(lnl))
+        if not ok:
+            raise RuntimeError(f"pll_gpu_category_weights_em: [{self.lib.errno()}] {self.lib.errmsg()}")
+        return w, lnl
+
     def insertion_lnls(self, subtree, candidates):
         """log-likelihood of inserting subtree = (clv, scaler, matrix) into every candidate edge, one call"""
         return insertion_loglikelihoods(self.lib, self.p, subtree, candidates, self._fi)
