@@ -990,6 +990,48 @@ typedef struct pll_gpu_branch
 } pll_gpu_branch_t;
 int pll_gpu_branch_derivatives(pll_partition_t *partition, const pll_gpu_branch_t *branches, unsigned int count,
                                const unsigned int *params_indices, double *d_f, double *dd_f /* may be NULL */);
+/* ---- rate and alpha gradients: per-category branch derivatives ----------
+ * The same launch keeping each rate category's share of a branch's d_f, and the contraction of those shares that is the
+ * gradient of -lnL with respect to the category rates (FreeRate rates; through dr_k/dalpha the gamma shape alpha) and to a
+ * common multiplier of all branch lengths (the per-partition scaler of a proportional-branch-length analysis). With the
+ * reference's own quantities (src/core_derivatives.c:643-694, :757-772, :843-847) - per site n and category k,
+ * (c0_k, c1_k, c2_k) the contraction of the site's table row with (e, l e, l^2 e) after the per-rate excess factor and
+ * after the invariant-sites step (c1_k (1 - pinv)), lk0 = sum_k w_k c0_k the site's site_lk[0], pw the pattern weights:
+ *   d_cat[i][k] = sum_n pw[n] * ( - w_k c1_k[n] / lk0[n] )        so that sum_k d_cat[i][k] = d_f[i] up to rounding
+ *   d_rates[k]  = sum_i (t_i / r_k) * d_cat[i][k]                 added in list order i = 0 .. count-1
+ *   d_scale     = sum_i  t_i * d_f[i]                             added in list order
+ * t_i = branches[i].branch_length, r_k = the partition's category rate. The log-likelihood depends on r_k only through
+ * the products r_k t_b / (1 - pinv) of the branches b, so d_rates[k] is d(-lnL)/dr_k and d_scale the derivative with
+ * respect to a multiplier of all lengths at 1 - PROVIDED the list names every branch of the tree exactly once, each end
+ * oriented towards its branch ("Gradients of rates, alpha and the branch-length scaler"). The call does
+ * not check that: it contracts what it is given. d_rates is the derivative with the other rates and the weights held
+ * fixed: no renormalisation of the mean rate is applied.
+ * Everything else is pll_gpu_branch_derivatives': what the ends may be, the flush of held work and pending CLVs, nothing
+ * in the partition written, synchronous with one copy back and one wait, the checks and their order, the refusals (site
+ * repeats and any ascertainment-bias correction: PLL_ERROR_GPU_UNSUPPORTED; no device: PLL_ERROR_GPU_UNAVAILABLE), outputs
+ * untouched on failure. Added among the first checks, after the NULL partition: count == 0 succeeds without a launch and
+ * leaves every output untouched except d_rates[0..rate_cats) and d_scale, which are set to 0; PLL_ERROR_PARAM_INVALID
+ * when every output is NULL; then the NULL list, the list checks and the two refusals as in pll_gpu_branch_derivatives;
+ * then, for pll_gpu_rate_gradient with d_rates asked, PLL_ERROR_PARAM_INVALID for a category rate that is not > 0 and
+ * finite (t / r is the chain rule; a rate of zero has a finite derivative that this formula does not give) - before the
+ * device is asked for, so before anything is flushed or launched. The same call with d_rates NULL takes such a rate.
+ * Bits: d_f and dd_f are bit for bit pll_gpu_branch_derivatives' for the same list; every d_cat value has the same bits
+ * alone, among others, in any list order and from run to run; d_rates and d_scale are formed on the device from those
+ * values, each product rounded and then added in list order - the bits of that loop written over the outputs of
+ * pll_gpu_branch_category_derivatives.
+ * pll_gpu_last_launch_count: one per cut of the list (the rule for R + 2 values per workgroup: include/pll_amd_device.h,
+ * pllgpu_branch_category_derivatives), plus one when d_rates or d_scale is asked for. PLL_ERROR_GPU_UNSUPPORTED also
+ * where a shape other than 4 states x 4 categories needs more than 152 KB of LDS (32 rate_cats (states + 32) bytes).
+ * Not offered: second derivatives with respect to rates (cross-branch terms), any iteration or line search, site repeats,
+ * ascertainment bias; sharded runs add d_rates / d_scale of the shards with pll_gpu_group_sum. */
+int pll_gpu_branch_category_derivatives(pll_partition_t *partition, const pll_gpu_branch_t *branches, unsigned int count,
+                                        const unsigned int *params_indices,
+                                        double *d_cat /* [count][rate_cats] */,
+                                        double *d_f /* [count] or NULL */, double *dd_f /* [count] or NULL */);
+int pll_gpu_rate_gradient(pll_partition_t *partition, const pll_gpu_branch_t *branches, unsigned int count,
+                          const unsigned int *params_indices,
+                          double *d_rates /* [rate_cats] or NULL */, double *d_scale /* 1 or NULL */,
+                          double *d_cat /* [count][rate_cats] or NULL */, double *d_f /* [count] or NULL */);
 /* ---- rate-category posteriors, site rates and EM weight steps ----------
  * The per-category site likelihoods of one edge - what every evaluation kernel mixes away in registers - and what model
  * optimisation makes of them: FreeRate (+R) and mixture (LG4X) weights, empirical-Bayes site rates, a pinv step. The

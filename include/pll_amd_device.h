@@ -358,6 +358,29 @@ typedef struct pllgpu_branch
 int pllgpu_branch_derivatives(pllgpu_ctx_t *ctx, const pllgpu_branch_t *branches, unsigned int count,
                               const unsigned int *params_indices, double *host_d, double *host_dd);
 
+/* The same launch keeping what it otherwise drops (kernels_gradient.h, CAT): per branch i and rate category k,
+ *   host_d_cat[i][k] = sum_n pw[n] * ( - w_k c1_k[n] / L[n] ),   c1_k after the excess factor and the (1 - pinv) step,
+ * category k's share of host_d[i] (sum_k host_d_cat[i][k] = host_d[i] up to rounding), and their contraction with the
+ * lengths t_i and the category rates r_k the context holds, formed on the device by k_rate_gradient in list order:
+ *   host_d_rates[k] = sum_i (t_i / r_k) * host_d_cat[i][k]      host_d_scale = sum_i t_i * host_d[i]
+ * (each product rounded, then added: i = 0 .. count-1). The rates are not checked: a rate of zero gives what the
+ * division gives. Any output may be NULL, not all five (PLLGPU_EINVAL, the first check); every other check, the
+ * refusals, the flush of held work and the ends are pllgpu_branch_derivatives', through the same code. host_d / host_dd
+ * have the bits pllgpu_branch_derivatives gives them, and every host_d_cat value the same bits alone, among others and in
+ * any list order.
+ * The cutting rule. B as above; with R = rate_cats a workgroup leaves R + 2 partial sums (d_f, dd_f, d_cat[0..R)), each
+ * with B slots and a ticket of its own, published at most 32 at a time:
+ *   Q = min(count, PLLGPU_BRANCH_MAX, max(1, floor(PLLGPU_INSERTION_MAX_SLOTS / ((R + 2) B))))   branches per launch,
+ * grid (B, Q), ceil(count / Q) launches, plus ONE launch of k_rate_gradient (one workgroup, behind the last cut on the
+ * same stream, no host wait between; the lengths of all count branches go up once, 8 bytes each) when host_d_rates or
+ * host_d_scale is asked for. One copy back of everything, one wait. Every other shape than 4 x 4 keeps 1 KB of LDS per
+ * rate category beside the branch's diag table: PLLGPU_EUNSUPPORTED where 32 R (states + 32) bytes exceed 152 KB (the last
+ * check: held work has been launched by then, nothing else has happened).
+ * count == 0 succeeds without a launch: host_d_rates[0..R) and host_d_scale are set to 0, nothing else is written. */
+int pllgpu_branch_category_derivatives(pllgpu_ctx_t *ctx, const pllgpu_branch_t *branches, unsigned int count,
+                                       const unsigned int *params_indices, double *host_d_cat, double *host_d, double *host_dd,
+                                       double *host_d_rates, double *host_d_scale);
+
 /* replaces pll_compute_node_ancestral[_extbuf] (src/likelihood.c:639-823): the marginal state probabilities of
  * the node at edge->parent_clv, [sites][states] unpadded, given the other end edge->child_clv (a CLV, or tip codes
  * with child_is_tip) across edge->matrix. Of `edge`, gather must be 0 and want_persite / device_result / sequence

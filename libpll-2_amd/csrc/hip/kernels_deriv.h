@@ -69,8 +69,12 @@ __global__ __launch_bounds__(256) void k_diagtable(const DevDiag d)
 // kernels_gradient.h): (c0, c1, c2) = the category's contraction of the site's table row with (e, l e, l^2 e); with a
 // proportion of invariant sites the category becomes c0 (1 - pinv) + pi[inv] pinv, c1 (1 - pinv), c2 (1 - pinv) - the
 // invariant term unscaled (src/core_derivatives.c:676-686) - and enters the site's (L, L', L'') with its weight.
-__device__ __forceinline__ void deriv_rate_add(const double *freqs, const double *prop_invar, const double *rate_weights, unsigned fi, unsigned SP,
-                                               unsigned k, int inv, double c0, double c1, double c2, double &lk0, double &lk1, double &lk2)
+// CAT (kernels_gradient.h): the category's own share c1 w of L', after the pinv step, is handed
+// back as well. It is a product of its own: the three sums above it are formed exactly as without it.
+template <bool CAT>
+__device__ __forceinline__ void deriv_rate_add_share(const double *freqs, const double *prop_invar, const double *rate_weights, unsigned fi,
+                                                     unsigned SP, unsigned k, int inv, double c0, double c1, double c2, double &lk0, double &lk1,
+                                                     double &lk2, double &c1w)
 {
   const double pinv = prop_invar ? prop_invar[fi] : 0.0;
   if (pinv > 0.0)
@@ -84,6 +88,14 @@ __device__ __forceinline__ void deriv_rate_add(const double *freqs, const double
   lk0 += c0 * w;
   lk1 += c1 * w;
   lk2 += c2 * w;
+  if (CAT) c1w = c1 * w;
+}
+
+__device__ __forceinline__ void deriv_rate_add(const double *freqs, const double *prop_invar, const double *rate_weights, unsigned fi, unsigned SP,
+                                               unsigned k, int inv, double c0, double c1, double c2, double &lk0, double &lk1, double &lk2)
+{
+  double unused;
+  deriv_rate_add_share<false>(freqs, prop_invar, rate_weights, fi, SP, k, inv, c0, c1, c2, lk0, lk1, lk2, unused);
 }
 
 // ... and the site's share of the two sums: pattern_weight * (-L'/L) and pattern_weight * ((L'/L)^2 - L''/L) (:687-692)

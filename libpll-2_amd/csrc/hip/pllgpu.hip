@@ -3545,10 +3545,18 @@ extern "C" int pllgpu_resample_last_times(const pllgpu_ctx_t *c, double *ms)
 // The cutting rule of pllgpu_branch_derivatives (include/pll_amd_device.h states it)
 constexpr unsigned kBranchMax = 8192; // 512 KB of descriptors: one piece of the pinned block
 static_assert(kBranchMax == PLLGPU_BRANCH_MAX && kBranchMax * sizeof(BranchDesc) <= kRingMax, "include/pll_amd_device.h states the cutting rule");
+constexpr size_t kGradLdsMax = 152 * 1024; // k_gradient_tiled's dynamic LDS, beside its static 8 KB
 
-// one launch for branches [first, first + n): their descriptors up, the kernel of the shape
+// the dynamic LDS of k_gradient_tiled: the branch's diag table [R][S][4]; cat: and the two [R][64] rows of the categories
+static size_t branch_lds(const pllgpu_ctx *c, bool cat)
+{
+  return ((size_t)c->gg.R * c->gg.S * 4 + (cat ? (size_t)2 * c->gg.R * 64 : 0)) * sizeof(double);
+}
+
+// one launch for branches [first, first + n): their descriptors up, the kernel of the shape. cat: the R + 2 values of
+// pllgpu_branch_category_derivatives instead of the two of pllgpu_branch_derivatives
 static int launch_branches(pllgpu_ctx *c, DevEdge e, const TileWalk &w, const DevDiag &dg, const pllgpu_branch_t *branches, unsigned first, unsigned n,
-                           unsigned count)
+                           unsigned count, bool cat)
 {
   const int up = stage_up<BranchDesc>(c, c->ins_cands.p, n, [&](BranchDesc &d, unsigned i) {
     const pllgpu_branch_t &q = branches[first + i];
@@ -3568,32 +3576,36 @@ static int launch_branches(pllgpu_ctx *c, DevEdge e, const TileWalk &w, const De
   if (up) return up;
   const BranchDesc *db = reinterpret_cast<const BranchDesc *>(c->ins_cands.p);
   const double *m1 = c->pmat.p + (size_t)c->geo.prob_matrices * c->pm_stride, *m2 = m1 + c->pm_stride;
-  e.result = c->ins_results.p + first; // [d_f | dd_f][branch of the call]
+  e.result = c->ins_results.p + first; // [d_f | dd_f | d_cat[0..R)][branch of the call]
   if (c->dna_fast)
-    hipLaunchKernelGGL(k_gradient_dna, dim3(w.blocks, n), dim3(256), 0, c->stream, e, dg, db, m1, m2, count, w.tiles_per);
+    with_bools(cat, false, [&](auto CAT, auto) {
+      hipLaunchKernelGGL(k_gradient_dna<CAT()>, dim3(w.blocks, n), dim3(256), 0, c->stream, e, dg, db, m1, m2, count, w.tiles_per);
+    });
   else
   {
     const unsigned nw = std::min(c->gg.R, 4u);
-    const size_t lds = (size_t)c->gg.R * c->gg.S * 4 * sizeof(double); // the branch's diag table
+    const size_t lds = branch_lds(c, cat);
     const unsigned long long *tm = tipmap_ptr(c);
     with_ich(c->ich, [&](auto ICH) {
-      raise_lds_limit(reinterpret_cast<const void *>(&k_gradient_tiled<ICH()>), c->device, lds);
-      hipLaunchKernelGGL((k_gradient_tiled<ICH()>), dim3(w.blocks, n), dim3(64u * nw), lds, c->stream, e, dg, db, m1, m2, c->gg, tm, count, w.tiles_per);
+      with_bools(cat, false, [&](auto CAT, auto) {
+        raise_lds_limit(reinterpret_cast<const void *>(&k_gradient_tiled<ICH(), CAT()>), c->device, lds);
+        hipLaunchKernelGGL((k_gradient_tiled<ICH(), CAT()>), dim3(w.blocks, n), dim3(64u * nw), lds, c->stream, e, dg, db, m1, m2, c->gg, tm, count,
+                           w.tiles_per);
+      });
     });
   }
   return launched(c);
 }
 
-extern "C" int pllgpu_branch_derivatives(pllgpu_ctx_t *c, const pllgpu_branch_t *branches, unsigned count, const unsigned *params_indices,
-                                         double *host_d, double *host_dd)
+// What both gradient entries do after their own argument checks, in the order include/pll_amd_device.h states: the list
+// checks and refusals that need no device state, then - the first step that touches it - held work out, the model of the
+// launches in e and the branch's model in dg. outputs_ok: the entry's own outputs are there.
+static int branch_call_begin(pllgpu_ctx *c, const pllgpu_branch_t *branches, unsigned count, const unsigned *params_indices, bool outputs_ok,
+                             const char *noun, DevEdge &e, DevDiag &dg)
 {
-  CHECK_CTX_KEEP(c);
   const pllgpu_geometry_t &g = c->geo;
-  c->last_launches = 0;
-  if (!count) return 0;
-  static const char noun[] = "branch derivatives";
   // everything that needs no device state, for the whole list, before held work is touched
-  if (!branches || !host_d || !params_indices) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
+  if (!branches || !outputs_ok || !params_indices) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
   if (int rc = refuse_ascertainment(c, noun)) return rc;
   if (int rc = check_rate_indices(c, "params_indices", params_indices)) return rc;
   for (unsigned i = 0; i < count; ++i)
@@ -3608,9 +3620,7 @@ extern "C" int pllgpu_branch_derivatives(pllgpu_ctx_t *c, const pllgpu_branch_t 
   }
   if (int rc = refuse_compressed(c, noun)) return rc;
   if (!c->eigenvals.p || !c->rates.p) return fail(PLLGPU_EINVAL, "eigenvalues / category rates were not uploaded");
-  DevEdge e;
   if (int rc = batch_edge(c, e, params_indices)) return rc;
-  DevDiag dg;
   memset(&dg, 0, sizeof dg);
   for (unsigned k = 0; k < g.rate_cats; ++k) dg.fidx[k] = (unsigned char)params_indices[k];
   dg.eigenvals = c->eigenvals.p;
@@ -3619,18 +3629,88 @@ extern "C" int pllgpu_branch_derivatives(pllgpu_ctx_t *c, const pllgpu_branch_t 
   dg.S = g.states;
   dg.SP = g.states_padded;
   dg.R = g.rate_cats;
+  return 0;
+}
+
+extern "C" int pllgpu_branch_derivatives(pllgpu_ctx_t *c, const pllgpu_branch_t *branches, unsigned count, const unsigned *params_indices,
+                                         double *host_d, double *host_dd)
+{
+  CHECK_CTX_KEEP(c);
+  c->last_launches = 0;
+  if (!count) return 0;
+  DevEdge e;
+  DevDiag dg;
+  if (int rc = branch_call_begin(c, branches, count, params_indices, host_d != nullptr, "branch derivatives", e, dg)) return rc;
 
   const TileWalk w = tile_walk(c);
   const unsigned per_launch = batch_items(count, kBranchMax, 2, w.blocks);
   if (int rc = batch_scratch(c, e, (size_t)2 * per_launch * w.blocks, (size_t)2 * per_launch, (size_t)2 * count, (size_t)per_launch * sizeof(BranchDesc)))
     return rc;
   for (unsigned first = 0; first < count; first += per_launch)
-    if (int rc = launch_branches(c, e, w, dg, branches, first, std::min(per_launch, count - first), count)) return rc;
+    if (int rc = launch_branches(c, e, w, dg, branches, first, std::min(per_launch, count - first), count, false)) return rc;
   // the kernels leave [d_f | dd_f][branch]
   std::vector<double> rows((size_t)2 * count);
   if (int rc = results_down(c, rows.data(), rows.size())) return rc;
   memcpy(host_d, rows.data(), (size_t)count * sizeof(double));
   if (host_dd) memcpy(host_dd, rows.data() + count, (size_t)count * sizeof(double));
+  return 0;
+}
+
+// The per-category form (include/pll_amd_device.h states its cutting rule): R + 2 values per branch, then - when the
+// contraction is asked for - the lengths of the whole list up once and k_rate_gradient behind the last cut.
+extern "C" int pllgpu_branch_category_derivatives(pllgpu_ctx_t *c, const pllgpu_branch_t *branches, unsigned count, const unsigned *params_indices,
+                                                  double *host_d_cat, double *host_d, double *host_dd, double *host_d_rates, double *host_d_scale)
+{
+  CHECK_CTX_KEEP(c);
+  const unsigned R = c->geo.rate_cats, V = R + 2u;
+  c->last_launches = 0;
+  const bool want_sums = host_d_rates || host_d_scale;
+  if (!count)
+  {
+    // sums over no branch
+    if (host_d_rates) std::fill(host_d_rates, host_d_rates + R, 0.0);
+    if (host_d_scale) *host_d_scale = 0.0;
+    return 0;
+  }
+  static const char noun[] = "branch category derivatives";
+  if (!host_d_cat && !host_d && !host_dd && !want_sums) return fail(PLLGPU_EINVAL, "%s: no output asked for", noun);
+  DevEdge e;
+  DevDiag dg;
+  if (int rc = branch_call_begin(c, branches, count, params_indices, true, noun, e, dg)) return rc;
+  if (!c->dna_fast && branch_lds(c, true) > kGradLdsMax)
+    return fail(PLLGPU_EUNSUPPORTED, "%s: %u states x %u rate categories need %zu bytes of LDS per workgroup", noun, c->geo.states, R, branch_lds(c, true));
+
+  const TileWalk w = tile_walk(c);
+  const unsigned per_launch = batch_items(count, kBranchMax, V, w.blocks);
+  // results: [R + 2][count] from the kernels, then the lengths [count] and k_rate_gradient's [R + 1]
+  const size_t values = (size_t)V * count, tail = want_sums ? (size_t)count + R + 1u : 0u;
+  if (int rc = batch_scratch(c, e, (size_t)V * per_launch * w.blocks, (size_t)V * per_launch, values + tail, (size_t)per_launch * sizeof(BranchDesc)))
+    return rc;
+  for (unsigned first = 0; first < count; first += per_launch)
+    if (int rc = launch_branches(c, e, w, dg, branches, first, std::min(per_launch, count - first), count, true)) return rc;
+  if (want_sums)
+  {
+    double *lengths = c->ins_results.p + values, *out = lengths + count;
+    if (int rc = stage_up<double>(c, lengths, count, [&](double &t, unsigned i) {
+          t = branches[i].branch_length;
+          return 0;
+        }))
+      return rc;
+    const size_t lds = (size_t)V * (kRateRows + 1u) * sizeof(double); // 34 KB at 64 categories
+    raise_lds_limit(reinterpret_cast<const void *>(&k_rate_gradient), c->device, lds);
+    hipLaunchKernelGGL(k_rate_gradient, dim3(1), dim3(256), lds, c->stream, c->ins_results.p, lengths, c->rates.p, count, R, out);
+    if (int rc = launched(c)) return rc;
+  }
+  // one copy back of everything the launches left, one wait; the caller's arrays are written last
+  std::vector<double> rows(values + tail);
+  if (int rc = results_down(c, rows.data(), rows.size())) return rc;
+  if (host_d) memcpy(host_d, rows.data(), (size_t)count * sizeof(double));
+  if (host_dd) memcpy(host_dd, rows.data() + count, (size_t)count * sizeof(double));
+  if (host_d_cat)
+    for (unsigned i = 0; i < count; ++i)
+      for (unsigned k = 0; k < R; ++k) host_d_cat[(size_t)i * R + k] = rows[(size_t)(k + 2u) * count + i];
+  if (host_d_rates) memcpy(host_d_rates, rows.data() + values + count, (size_t)R * sizeof(double));
+  if (host_d_scale) *host_d_scale = rows[values + count + R];
   return 0;
 }
 

@@ -395,24 +395,44 @@ int pll_gpu_optimize_branch_length(pll_partition_t *p, int parent_scaler_index, 
 }
 
 /* pll_gpu_branch_derivatives (include/pll_amd.h): d_f and dd_f of `count` branches in one call,
- * without a table (csrc/hip/kernels_gradient.h). This function: validation of the whole list before anything is flushed
- * or launched, which ends the device reads as tip codes, the flushes (model, the two contraction matrices, every named
- * CLV and scaler once). The refusals, the once-per-call bookkeeping of the flushes and the error convention are batch.c's,
- * shared with the other batched calls. */
-int pll_gpu_branch_derivatives(pll_partition_t *p, const pll_gpu_branch_t *branches, unsigned int count,
-                               const unsigned int *params_indices, double *d_f, double *dd_f)
+ * without a table (csrc/hip/kernels_gradient.h); pll_gpu_branch_category_derivatives and pll_gpu_rate_gradient (section
+ * 5.13): the same call keeping each rate category's share and contracting it. branch_call is the body of all three:
+ * validation of the whole list before anything is flushed or launched, which ends the device reads as tip codes, the
+ * flushes (model, the two contraction matrices, every named CLV and scaler once). The refusals, the once-per-call
+ * bookkeeping of the flushes and the error convention are batch.c's, shared with the other batched calls. */
+typedef struct branch_outputs
 {
-  static const char who[] = "pll_gpu_branch_derivatives";
+  double *d_f, *dd_f;                /* every entry */
+  double *d_cat, *d_rates, *d_scale; /* the per-category entries; d_rates / d_scale: pll_gpu_rate_gradient */
+  int per_category;                  /* 0: pll_gpu_branch_derivatives, whose d_f is mandatory */
+} branch_outputs_t;
+
+static int branch_call(const char *who, pll_partition_t *p, const pll_gpu_branch_t *branches, unsigned int count,
+                       const unsigned int *params_indices, const branch_outputs_t *out)
+{
   unsigned int i, k;
   if (!p)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
     return pll_batch_fail(who);
   }
-  if (!count) return PLL_SUCCESS;
-  if (!branches || !params_indices || !d_f)
+  if (!count)
   {
-    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: branches, params_indices or d_f is NULL", who);
+    /* sums over no branch */
+    if (out->d_rates)
+      for (k = 0; k < p->rate_cats; ++k) out->d_rates[k] = 0.0;
+    if (out->d_scale) *out->d_scale = 0.0;
+    return PLL_SUCCESS;
+  }
+  if (out->per_category && !out->d_f && !out->dd_f && !out->d_cat && !out->d_rates && !out->d_scale)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: every output is NULL", who);
+    return pll_batch_fail(who);
+  }
+  if (!branches || !params_indices || (!out->per_category && !out->d_f))
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, out->per_category ? "%s: branches or params_indices is NULL" : "%s: branches, params_indices or d_f is NULL",
+                  who);
     return pll_batch_fail(who);
   }
   for (i = 0; i < count; ++i)
@@ -445,7 +465,16 @@ int pll_gpu_branch_derivatives(pll_partition_t *p, const pll_gpu_branch_t *branc
       return pll_batch_fail(who);
     }
   pll_amd_ext_t *x = NULL;
-  if (!pll_batch_refusals_and_device(who, p, "pll_compute_likelihood_derivatives", &x)) return PLL_FAILURE;
+  if (!pll_batch_refusals(who, p, "pll_compute_likelihood_derivatives")) return PLL_FAILURE;
+  if (out->d_rates)
+    for (k = 0; k < p->rate_cats; ++k)
+      if (!(p->rates[k] > 0) || !isfinite(p->rates[k]))
+      {
+        /* t / r is the chain rule; a rate of zero has a finite derivative that it does not give */
+        pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: category rate %u is %g; d_rates needs rates that are > 0 and finite", who, k, p->rates[k]);
+        return pll_batch_fail(who);
+      }
+  if (!pll_batch_device(who, p, &x)) return PLL_FAILURE;
 
   /* the reference reads whatever eigensystem is stored; an invalid one is computed here, as pll_update_sumtable does */
   for (k = 0; k < p->rate_cats; ++k)
@@ -477,7 +506,9 @@ int pll_gpu_branch_derivatives(pll_partition_t *p, const pll_gpu_branch_t *branc
     free(dev);
     return pll_batch_fail(who);
   }
-  const int rc = pllgpu_branch_derivatives(x->ctx, dev, count, params_indices, d_f, dd_f);
+  const int rc = out->per_category ? pllgpu_branch_category_derivatives(x->ctx, dev, count, params_indices, out->d_cat, out->d_f, out->dd_f,
+                                                                        out->d_rates, out->d_scale)
+                                   : pllgpu_branch_derivatives(x->ctx, dev, count, params_indices, out->d_f, out->dd_f);
   free(dev);
   if (rc != 0)
   {
@@ -485,4 +516,25 @@ int pll_gpu_branch_derivatives(pll_partition_t *p, const pll_gpu_branch_t *branc
     return PLL_FAILURE;
   }
   return PLL_SUCCESS;
+}
+
+int pll_gpu_branch_derivatives(pll_partition_t *p, const pll_gpu_branch_t *branches, unsigned int count,
+                               const unsigned int *params_indices, double *d_f, double *dd_f)
+{
+  const branch_outputs_t out = {d_f, dd_f, NULL, NULL, NULL, 0};
+  return branch_call("pll_gpu_branch_derivatives", p, branches, count, params_indices, &out);
+}
+
+int pll_gpu_branch_category_derivatives(pll_partition_t *p, const pll_gpu_branch_t *branches, unsigned int count,
+                                        const unsigned int *params_indices, double *d_cat, double *d_f, double *dd_f)
+{
+  const branch_outputs_t out = {d_f, dd_f, d_cat, NULL, NULL, 1};
+  return branch_call("pll_gpu_branch_category_derivatives", p, branches, count, params_indices, &out);
+}
+
+int pll_gpu_rate_gradient(pll_partition_t *p, const pll_gpu_branch_t *branches, unsigned int count, const unsigned int *params_indices,
+                          double *d_rates, double *d_scale, double *d_cat, double *d_f)
+{
+  const branch_outputs_t out = {d_f, NULL, d_cat, d_rates, d_scale, 1};
+  return branch_call("pll_gpu_rate_gradient", p, branches, count, params_indices, &out);
 }

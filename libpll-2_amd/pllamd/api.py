@@ -304,6 +304,10 @@ _GPU_PROTOS = {
     "pll_gpu_quartet_rell_loglikelihoods": (
         C.c_int, [PartitionP, C.POINTER(Quartet), C.c_uint, c_uint_p, C.c_ulonglong, C.c_uint, c_double_p, c_double_p, c_double_p, c_uint_p]),
     "pll_gpu_branch_derivatives": (C.c_int, [PartitionP, C.POINTER(Branch), C.c_uint, c_uint_p, c_double_p, c_double_p]),
+    "pll_gpu_branch_category_derivatives": (
+        C.c_int, [PartitionP, C.POINTER(Branch), C.c_uint, c_uint_p, c_double_p, c_double_p, c_double_p]),
+    "pll_gpu_rate_gradient": (
+        C.c_int, [PartitionP, C.POINTER(Branch), C.c_uint, c_uint_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "pll_gpu_edge_category_posteriors": (
         C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "pll_gpu_category_weights_em": (

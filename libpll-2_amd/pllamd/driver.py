@@ -238,6 +238,35 @@ def branch_derivatives(lib, partition, rows, params_indices, want_dd=True):
     return np.stack([d, dd], axis=1)
 
 
+def branch_category_derivatives(lib, partition, rows, params_indices, want_d=True, want_dd=True):
+    """pll_gpu_branch_category_derivatives: rows as branch_derivatives; (d_cat [count, rate_cats], d_f [count], dd_f [count]) from
+    one call - d_f / dd_f stay NaN where not asked for (NULL). libpll_amd.so only."""
+    rows = list(rows)
+    R = int(partition.contents.rate_cats)
+    cat, d, dd = np.full((len(rows), R), np.nan), np.full(len(rows), np.nan), np.full(len(rows), np.nan)
+    pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+    if not lib.pll_gpu_branch_category_derivatives(partition, api.make_branches(rows), len(rows), api.uptr(pi), api.dptr(cat),
+                                                   api.dptr(d) if want_d else None, api.dptr(dd) if want_dd else None):
+        raise RuntimeError(f"pll_gpu_branch_category_derivatives: [{lib.errno()}] {lib.errmsg()}")
+    return cat, d, dd
+
+
+def rate_gradient(lib, partition, rows, params_indices, want_rates=True, want_scale=True, want_cat=True, want_d=True):
+    """pll_gpu_rate_gradient: rows as branch_derivatives; a dict d_rates [rate_cats], d_scale (float), d_cat [count, rate_cats],
+    d_f [count] from one call - NaN where not asked for (NULL). d_rates / d_scale are gradients of -lnL only where the rows
+    name every branch of the tree once, each end oriented towards its branch. libpll_amd.so only."""
+    rows = list(rows)
+    R = int(partition.contents.rate_cats)
+    rates, scale = np.full(R, np.nan), np.full(1, np.nan)
+    cat, d = np.full((len(rows), R), np.nan), np.full(len(rows), np.nan)
+    pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+    if not lib.pll_gpu_rate_gradient(partition, api.make_branches(rows), len(rows), api.uptr(pi), api.dptr(rates) if want_rates else None,
+                                     api.dptr(scale) if want_scale else None, api.dptr(cat) if want_cat else None,
+                                     api.dptr(d) if want_d else None):
+        raise RuntimeError(f"pll_gpu_rate_gradient: [{lib.errno()}] {lib.errmsg()}")
+    return {"d_rates": rates, "d_scale": float(scale[0]), "d_cat": cat, "d_f": d}
+
+
 def branch_derivatives_per_edge(lib, partition, rows, params_indices, sumtable=None):
     """the same values the way every libpll offers them: per row pll_update_sumtable into one caller-owned table, then
     pll_compute_likelihood_derivatives at the row's length. The table (sites * rate_cats * states_padded doubles, 64-byte
