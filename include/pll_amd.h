@@ -1198,7 +1198,10 @@ double pll_gpu_timer_stop(pll_partition_t *partition);
  * pll_gpu_placement_loglikelihoods, pll_gpu_quartet_loglikelihoods or pll_gpu_branch_derivatives call */
 unsigned int pll_gpu_last_launch_count(const pll_partition_t *partition);
 /* site repeats: class-map operations computed on the device (launches = 0) / class kernels launched (launches != 0)
- * since the partition was created. An unchanged tree adds nothing, a topology move the ops of its partial traversal */
+ * since the partition was created. An unchanged tree adds nothing, a topology move the ops of its partial traversal.
+ * launches = 2: the class-map calls the device has served - one per pll_update_partials that had maps to compute, one
+ * per dependency level with work under PLL_AMD_REP_LEVEL_SYNC=1 or a caller's enable_repeats; a call that runs its
+ * levels a second time because its level forecast was wrong counts once */
 unsigned long long pll_gpu_class_map_work(const pll_partition_t *partition, int launches);
 /* pll_update_partials calls whose launches came from a plan the partition's device context had kept, since it was
  * created. A context's plans depend on ITS device blocks only: other partitions coming, growing and going leave them */

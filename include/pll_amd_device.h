@@ -86,7 +86,9 @@ int pllgpu_device_count(void);
 /* the device a context created now with device = -1 would live on (PLL_AMD_DEVICE=<n>, else the calling thread's
  * current HIP device); -2: any of them in turn (PLL_AMD_DEVICE=auto); and the device a context does live on */
 /* site repeats, since the context was created: class-map ops handed to the device (launches = 0) or class kernels
- * launched (launches = 1) - what the version stamps of repeats.c save is visible here */
+ * launched (launches = 1) - what the version stamps of repeats.c save is visible here; launches = 2: the
+ * pllgpu_repeats_classes calls served (non-empty lists that passed the checks; a call that runs its levels a second
+ * time because its level forecast was wrong counts once) */
 unsigned long long pllgpu_class_map_work(const pllgpu_ctx_t *ctx, int launches);
 /* op lists launched from a plan the context had kept (the same list over blocks that have not moved), ever */
 unsigned long long pllgpu_plan_replays(const pllgpu_ctx_t *ctx);

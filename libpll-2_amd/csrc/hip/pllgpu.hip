@@ -296,6 +296,7 @@ struct pllgpu_ctx
   std::vector<unsigned char> stage8; // ... and for a class map that goes up as bytes
   unsigned last_launches = 0;
   unsigned long long rep_ops_total = 0, rep_launches_total = 0; // class-map ops handed to the device / class kernels launched, ever
+  unsigned long long rep_calls_total = 0;                       // pllgpu_repeats_classes calls served (a repeat after a wrong forecast is none)
   double last_bytes = 0.0;       // algorithmic HBM bytes of the last update_partials call
   bool no_tip_columns = false;   // PLL_AMD_NO_TIP_COLUMNS=1: tips always through the FMA contraction
   bool tt_stream = true;         // PLL_AMD_TT_STREAM=0: plain tip x tip levels of 33..64 states through k_partials_mfma's column route (round 5) - the control
@@ -893,6 +894,31 @@ static hipError_t copy_up(pllgpu_ctx *c, void *dst, const void *host, size_t byt
     return hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, c->stream);
   }
   return hipMemcpyAsync(dst, host, bytes, hipMemcpyHostToDevice, c->stream);
+}
+
+// Wait until a word of mapped host memory, stored by a kernel on the stream, carries `value`: a poll (a stream
+// synchronise costs ~15 us of wake-up latency on a ~5 us kernel), and ONE stream synchronise once that has taken
+// `limit_ms`, so that a failed launch cannot hang the caller - who checks the word again where it matters.
+template <typename T>
+static int wait_for_word(pllgpu_ctx *c, const T *word, T value, int limit_ms)
+{
+  const auto t0 = std::chrono::steady_clock::now();
+  unsigned spins = 0;
+  while (__atomic_load_n(word, __ATOMIC_ACQUIRE) != value)
+    if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(limit_ms))
+    {
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      break;
+    }
+  return 0;
+}
+
+// wait until result[1] carries `sequence`, the word the last workgroup of a kernel stores next to its value
+static int wait_for_sequence(pllgpu_ctx *c, double sequence)
+{
+  unsigned long long seq_bits;
+  memcpy(&seq_bits, &sequence, sizeof seq_bits);
+  return wait_for_word(c, (const unsigned long long *)&c->result_host[1], seq_bits, 20);
 }
 
 // device -> host and wait
@@ -2488,8 +2514,6 @@ static int run_lnl(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather, const unsi
     c->seq += 1.0;
     e.sequence = c->seq;
   }
-  unsigned long long seq_bits;
-  memcpy(&seq_bits, &e.sequence, sizeof seq_bits);
   if (int rc = launch_edge(c, e, ctip, gather, tail, ctail)) return rc;
   HIP_TRY(hipGetLastError());
   if (device_result) return 0; // asynchronous: the value stays on the device
@@ -2500,21 +2524,8 @@ static int run_lnl(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather, const unsi
   }
   else
   {
-    // the last workgroup stores {lnL, sequence} into mapped host memory: poll the sequence word for
-    // a bounded time (a stream synchronise costs ~15 us of wake-up latency on a ~5 us kernel), then
-    // fall back to the synchronise so a failed launch cannot hang the caller
-    volatile double *res = c->result_host;
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (__atomic_load_n((const unsigned long long *)&res[1], __ATOMIC_ACQUIRE) != seq_bits)
-    {
-      if ((++spins & 1023u) == 0 &&
-          std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20))
-      {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        break;
-      }
-    }
+    // the last workgroup stores {lnL, sequence} into mapped host memory
+    if (int rc = wait_for_sequence(c, e.sequence)) return rc;
   }
   *lnl_out = c->result_host[0];
   return 0;
@@ -4155,7 +4166,11 @@ extern "C" double pllgpu_timer_stop(pllgpu_ctx_t *c)
 
 extern "C" unsigned pllgpu_last_launch_count(const pllgpu_ctx_t *c) { return c ? c->last_launches : 0; }
 extern "C" unsigned long long pllgpu_plan_replays(const pllgpu_ctx_t *c) { return c ? c->plan_replays : 0ull; }
-extern "C" unsigned long long pllgpu_class_map_work(const pllgpu_ctx_t *c, int launches) { return !c ? 0ull : launches ? c->rep_launches_total : c->rep_ops_total; }
+extern "C" unsigned long long pllgpu_class_map_work(const pllgpu_ctx_t *c, int launches)
+{
+  if (!c) return 0ull;
+  return launches == 2 ? c->rep_calls_total : launches ? c->rep_launches_total : c->rep_ops_total;
+}
 
 // ---- branch-length derivatives ------------------------------------------------------------------
 extern "C" int pllgpu_eigenvals_upload(pllgpu_ctx_t *c, unsigned index, const double *host)
@@ -4332,25 +4347,6 @@ static double next_sequence(pllgpu_ctx *c)
 {
   c->seq += 1.0;
   return c->seq;
-}
-
-// wait until result[1] carries `sequence`: a poll of mapped memory, a stream synchronise once that has taken 20 ms
-static int wait_for_sequence(pllgpu_ctx *c, double sequence)
-{
-  unsigned long long seq_bits;
-  memcpy(&seq_bits, &sequence, sizeof seq_bits);
-  volatile double *res = c->result_host;
-  const auto t0 = std::chrono::steady_clock::now();
-  unsigned spins = 0;
-  while (__atomic_load_n((const unsigned long long *)&res[1], __ATOMIC_ACQUIRE) != seq_bits)
-  {
-    if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20))
-    {
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      break;
-    }
-  }
-  return 0;
 }
 
 extern "C" int pllgpu_likelihood_derivatives(pllgpu_ctx_t *c, unsigned slot, double branch_length,
@@ -4699,374 +4695,7 @@ extern "C" int pllgpu_repeats_download(pllgpu_ctx_t *c, unsigned node, unsigned 
   return 0;
 }
 
-// Class maps of a whole op list: every dependency level goes through k_rep_mark + k_rep_assign, the levels back to back,
-// and the host reads all class counts once at the end (kernels_repeats.h). What the host must know BEFORE a level's
-// counts exist - how large a table slice an op may need - comes from upper bounds: an op's classes are at most its
-// cells, its cells at most the product of its children's bounds, and a compressed parent's table is smaller than
-// lookup_size by the rule itself.
-extern "C" int pllgpu_repeats_classes(pllgpu_ctx_t *c, const pllgpu_repop_t *ops, unsigned count, unsigned lookup_size, unsigned *counts_out)
-{
-  CHECK_CTX(c);
-  const pllgpu_geometry_t &g = c->geo;
-  const unsigned sites = g.sites;
-  if (!count) return 0;
-  if (count > c->rep_host_cap) return fail(PLLGPU_EINVAL, "class maps of %u ops in one call (at most %u)", count, c->rep_host_cap);
-  const unsigned words = (sites + 31u) / 32u;
-  const size_t wstride = ((size_t)words + kRepScanChunk - 1u) / kRepScanChunk * kRepScanChunk;
-  // k_rep_bits: 4 ... 32 ranges of the sites per op, each a multiple of 1024 bitmap words (its LDS)
-  const unsigned bit_ranges = std::max(4u, std::min(kRepBitsMaxRanges, (words + 2047u) / 2048u));
-  const unsigned bit_words = ((words + bit_ranges - 1u) / bit_ranges + kRepScanThreads - 1u) / kRepScanThreads * kRepScanThreads;
-  const size_t op_scratch = 2u * wstride + 2u * kRepBitsMaxRanges; // per op of a launch: bitmap, running counts, the ranges' totals and starts
-  const size_t table_cap = (size_t)64 << 20; // cells per launch (256 MB); a single larger op still gets its slice
-  const size_t melems = map_elems(c);
-  // How many of the levels to launch. The kernels decide by themselves which parents are compressed, but every level costs
-  // its launches even when none is; where compression ended the last time an op list of this length came is remembered,
-  // only the levels up to there are launched, and the rule (src/repeats.c:100-110) is evaluated HERE for the ops above,
-  // from the counts that came back: if it admits one of them after all, the whole call is repeated with every level.
-  unsigned ncut = count;
-  unsigned long long key = 1469598103934665603ull; // FNV-1a over what identifies the list (two lists of one length differ in where compression ends)
-  for (unsigned i = 0; i < count; ++i)
-    for (unsigned w : {ops[i].parent, ops[i].left, ops[i].right, ops[i].level})
-      key = (key ^ w) * 1099511628211ull;
-  if (c->rep_hints && c->rep_hint_count == count && c->rep_hint_key == key)
-  {
-    ncut = 0;
-    while (ncut < count && ops[ncut].level <= c->rep_hint_level && c->rep_hint_any) ++ncut;
-  }
-
-  // bounds, checks, buffers - everything that may allocate (and so synchronise) before the first launch
-  std::vector<unsigned long long> ub_cells(count);
-  std::vector<unsigned> ub_classes(count);
-  for (unsigned i = 0; i < count; ++i)
-  {
-    const pllgpu_repop_t &o = ops[i];
-    if (o.parent >= g.nodes || o.left >= g.nodes || o.right >= g.nodes) return fail(PLLGPU_EINVAL, "repeats op references a node out of range");
-    if (i && o.level < ops[i - 1].level) return fail(PLLGPU_EINVAL, "repeats ops are not sorted by level");
-    if ((o.lsrc >= 0 && ((unsigned)o.lsrc >= i || ops[o.lsrc].level >= o.level || ops[o.lsrc].parent != o.left)) ||
-        (o.rsrc >= 0 && ((unsigned)o.rsrc >= i || ops[o.rsrc].level >= o.level || ops[o.rsrc].parent != o.right)))
-      return fail(PLLGPU_EINVAL, "repeats op %u: a child's producer is not an op of a lower level", i);
-    const unsigned long long bl = o.lsrc >= 0 ? ub_classes[o.lsrc] : o.nleft, br = o.rsrc >= 0 ? ub_classes[o.rsrc] : o.nright;
-    unsigned long long cells = bl * br;
-    if (o.force)
-    {
-      if (o.lsrc >= 0 || o.rsrc >= 0) return fail(PLLGPU_EINVAL, "repeats op %u: a decision taken by the host needs both children's counts", i);
-      if (!cells) return fail(PLLGPU_EINVAL, "repeats op: children %u / %u have no class maps on the device", o.left, o.right);
-    }
-    else if (cells >= lookup_size)
-      cells = lookup_size ? lookup_size - 1u : 0u;
-    if (cells >= 0x7FFFFFFFull) return fail(PLLGPU_EINVAL, "repeats table of %llu cells exceeds 31-bit addressing", cells);
-    ub_cells[i] = cells;
-    ub_classes[i] = (unsigned)std::min<unsigned long long>(cells, sites);
-    // children that come from outside the call: their maps in the form their class count asks for
-    const unsigned kid[2] = {o.left, o.right}, kn[2] = {o.nleft, o.nright};
-    const int ksrc[2] = {o.lsrc, o.rsrc};
-    for (int k = 0; k < 2 && cells && i < ncut; ++k)
-    {
-      if (ksrc[k] >= 0 || !kn[k]) continue;
-      if (kn[k] <= kRepNarrow)
-      {
-        if (int rc = narrow_map(c, kid[k])) return rc;
-      }
-      else if (!wide_map(c, kid[k]))
-        return fail(PLLGPU_EINVAL, "repeats op: child %u has no class maps on the device", kid[k]);
-    }
-    if (!cells || i >= ncut) continue; // cannot be compressed / not launched: nothing to write
-    if (int rc = c->site_id8[o.parent].ensure(melems)) return rc;
-    if (ub_classes[i] > kRepNarrow)
-      if (int rc = c->site_id[o.parent].ensure(melems)) return rc;
-    if (int rc = c->id_site[o.parent].ensure(ub_classes[i])) return rc;
-    if (int rc = c->lent[o.parent].ensure(ub_classes[i])) return rc;
-    if (int rc = c->rent[o.parent].ensure(ub_classes[i])) return rc;
-  }
-  HIP_TRY(hipGetLastError());
-
-  // launches: the ops of a level, up to kRepOps and table_cap cells at a time
-  struct Launch
-  {
-    unsigned first, n, wgs, mark_lds, assign_lds;
-    bool rank; // some op's table may be a large one: k_rep_fold + k_rep_scan + k_rep_rank between k_rep_mark and k_rep_assign
-    bool narrow, general; // the builds of k_rep_mark its ops may need (kernels_repeats.h)
-    size_t max_cells;     // the largest table an op of the launch may have
-    bool fused;           // some op has fused children
-    bool assign;          // some op's site -> class pass is k_rep_assign's (not every one deferred to the parent's k_rep_mark)
-  };
-  std::vector<Launch> launches;
-  std::vector<RepOp> &rops = c->rep_ops_host;
-  rops.assign(ncut, RepOp());
-  // A child's site -> class pass inside its parent's k_rep_mark (kernels_repeats.h: kRepFuseLeft): for a child X of the call
-  // whose table is small for sure, over byte maps, read by exactly one launched op P whose children's maps are both bytes
-  std::vector<unsigned> fuse(ncut, 0u);
-  std::vector<int> final_slot(ncut, -1);
-  unsigned ndeferred = 0;
-  if (c->rep_fuse)
-  {
-    std::vector<unsigned> readers(ncut, 0u);
-    for (unsigned i = 0; i < ncut; ++i)
-    {
-      if (ops[i].lsrc >= 0) ++readers[ops[i].lsrc];
-      if (ops[i].rsrc >= 0) ++readers[ops[i].rsrc];
-    }
-    auto bytes = [&](int src, unsigned given) { return (src >= 0 ? ub_classes[src] : given) <= kRepNarrow; };
-    for (unsigned i = 0; i < ncut; ++i)
-    {
-      const pllgpu_repop_t &o = ops[i];
-      if (o.force || !bytes(o.lsrc, o.nleft) || !bytes(o.rsrc, o.nright) || (o.lsrc >= 0 && o.lsrc == o.rsrc)) continue;
-      const int kid[2] = {o.lsrc, o.rsrc};
-      for (int k = 0; k < 2; ++k)
-      {
-        const int x = kid[k];
-        if (x < 0 || readers[x] != 1u || ops[x].force || !ub_cells[x] || ub_cells[x] > kRepFuseCells) continue;
-        if (!bytes(ops[x].lsrc, ops[x].nleft) || !bytes(ops[x].rsrc, ops[x].nright)) continue;
-        fuse[i] |= k ? kRepFuseRight : kRepFuseLeft;
-        fuse[x] |= kRepDeferred;
-        final_slot[x] = (int)ndeferred++;
-      }
-    }
-    if (int rc = c->rep_final.ensure((size_t)std::max(1u, ndeferred) * kRepFuseCells)) return rc;
-  }
-  size_t arena = 0;
-  for (unsigned done = 0; done < ncut;)
-  {
-    unsigned room = 0;
-    while (done + room < ncut && room < (unsigned)kRepOps && ops[done + room].level == ops[done].level) ++room;
-    // workgroups per op: ~512 per launch - all resident at once, and on a 125k-site shard measurably better than 1024
-    // (how they split into table parts and site ranges: k_rep_mark)
-    const unsigned wgs = c->rep_wgs ? c->rep_wgs : std::max(1u, std::min(64u, (512u + room - 1u) / room));
-    Launch L = {done, 0, wgs, kRepSmallCells, 64, false, false, false, 0, false, false};
-    size_t cells = 0;
-    for (unsigned k = 0; k < room; ++k)
-    {
-      const unsigned i = done + k;
-      const size_t ub = (size_t)ub_cells[i];
-      // all copies of the table (k_rep_mark): a small one has a copy per workgroup, a large one up to max_ranges - and only
-      // while its parts are fewer than the workgroups
-      const size_t slice = ((ub <= kRepSmallCells ? ub * wgs : std::max(ub, std::min(ub * c->rep_max_ranges, (size_t)kRepLdsCells * wgs))) + 3u) & ~(size_t)3u;
-      if (ub > kRepSmallCells) L.rank = true;
-      L.max_cells = std::max(L.max_cells, ub);
-      {
-        const unsigned long long bl = ops[i].lsrc >= 0 ? ub_classes[ops[i].lsrc] : ops[i].nleft, br = ops[i].rsrc >= 0 ? ub_classes[ops[i].rsrc] : ops[i].nright;
-        // the narrow build for the ops that are its for sure; an op that only may turn out so goes with the general build
-        if (bl <= kRepNarrow && br <= kRepNarrow && ub <= kRepSmallCells) L.narrow = true;
-        else L.general = true;
-      }
-      if (k && cells + slice > table_cap) break;
-      RepOp &r = rops[i];
-      const pllgpu_repop_t &o = ops[i];
-      r.l8 = c->site_id8[o.left].p;
-      r.r8 = c->site_id8[o.right].p;
-      r.l32 = c->site_id[o.left].p;
-      r.r32 = c->site_id[o.right].p;
-      r.p8 = c->site_id8[o.parent].p;
-      r.p32 = c->site_id[o.parent].p;
-      r.pids = c->id_site[o.parent].p;
-      r.lent = c->lent[o.parent].p;
-      r.rent = c->rent[o.parent].p;
-      r.table = reinterpret_cast<unsigned *>(cells); // offset for now: the arena may still grow
-      r.bitmap = reinterpret_cast<unsigned *>((size_t)k * op_scratch);
-      r.keep = nullptr;
-      if (ub > kRepSmallCells)
-      {
-        // (zeroed when it is new: its last word says whether the rest is what the node's maps derive from)
-        DevBuf<unsigned> &kb = c->rep_keep[o.parent];
-        const size_t had = kb.cap;
-        if (int rc = kb.ensure((size_t)words + 1u)) return rc;
-        if (kb.cap != had) HIP_TRY(hipMemsetAsync(kb.p, 0, kb.cap * sizeof(unsigned), c->stream));
-        r.keep = kb.p;
-      }
-      r.lsrc = o.lsrc;
-      r.rsrc = o.rsrc;
-      r.nleft = o.nleft;
-      r.nright = o.nright;
-      r.slot = i;
-      r.force = o.force ? 1u : 0u;
-      r.slice = (unsigned)std::min<size_t>(slice, 0x7FFFFFFFu);
-      r.flags = fuse[i];
-      if (fuse[i] & (kRepFuseLeft | kRepFuseRight)) L.fused = true;
-      if (!(fuse[i] & kRepDeferred) && ub) L.assign = true;
-      cells += slice;
-      L.mark_lds = std::max<unsigned>(L.mark_lds, (unsigned)std::min<size_t>(ub, kRepLdsCells));
-      if (ub <= kRepAssignLds) L.assign_lds = std::max<unsigned>(L.assign_lds, (unsigned)((ub + 3u) & ~(size_t)3u));
-      ++L.n;
-    }
-    arena = std::max(arena, cells);
-    launches.push_back(L);
-    done += L.n;
-  }
-  if (ncut)
-  {
-  c->rep_ops_total += ncut;
-  if (int rc = c->rep_table.ensure(arena)) return rc;
-  {
-    // per op of a launch: the bitmap (zero between launches: k_rep_assign clears what k_rep_mark set), then the running counts
-    const size_t had = c->rep_blocksum.cap;
-    if (int rc = c->rep_blocksum.ensure((size_t)kRepOps * op_scratch)) return rc;
-    if (c->rep_blocksum.cap != had || c->rep_scratch_dirty) HIP_TRY(hipMemsetAsync(c->rep_blocksum.p, 0, c->rep_blocksum.cap * sizeof(unsigned), c->stream));
-    if (c->rep_scratch_dirty) HIP_TRY(hipMemsetAsync(c->rep_sync.p, 0, c->rep_sync.cap * sizeof(unsigned), c->stream));
-    c->rep_scratch_dirty = true; // until this call has gone through
-  }
-  if (int rc = c->rep_counts.ensure(count)) return rc;
-  if (int rc = c->rep_ops.ensure((size_t)count * sizeof(RepOp))) return rc;
-  for (unsigned i = 0; i < ncut; ++i)
-  {
-    rops[i].table = c->rep_table.p + reinterpret_cast<size_t>(rops[i].table);
-    rops[i].bitmap = c->rep_blocksum.p + reinterpret_cast<size_t>(rops[i].bitmap);
-    rops[i].final = final_slot[i] >= 0 ? c->rep_final.p + (size_t)final_slot[i] * kRepFuseCells : rops[i].table;
-  }
-  // the descriptors go up unless the device array holds exactly these (the same list over the same buffers: the re-evaluation
-  // of one tree - a copy of 14 KB is 5 us on the stream, ahead of the first launch)
-  if (c->rep_ops_sent.size() != (size_t)ncut * sizeof(RepOp) || c->rep_ops_sent_at != c->rep_ops.p ||
-      memcmp(c->rep_ops_sent.data(), rops.data(), c->rep_ops_sent.size()) != 0)
-  {
-    // (staged in the context's pinned block; ordered behind the previous call's kernels)
-    HIP_TRY(copy_up(c, c->rep_ops.p, rops.data(), (size_t)ncut * sizeof(RepOp)));
-    c->rep_ops_sent.assign(reinterpret_cast<const unsigned char *>(rops.data()), reinterpret_cast<const unsigned char *>(rops.data() + ncut));
-    c->rep_ops_sent_at = c->rep_ops.p;
-  }
-  c->rep_host[c->rep_host_cap + 1u] = 0u;
-  RepPack pk;
-  memset(&pk, 0, sizeof pk);
-  pk.counts = c->rep_counts.p;
-  pk.tickets = c->rep_sync.p;
-  pk.launch_ticket = c->rep_sync.p + kRepOps;
-  pk.changed = c->rep_changed.p;
-  pk.all_ops = reinterpret_cast<const RepOp *>(c->rep_ops.p);
-  pk.max_ranges = c->rep_max_ranges;
-  pk.host_counts = c->rep_host_dev;
-  pk.ncounts = ncut;
-  pk.host_cap = c->rep_host_cap;
-  pk.sites = sites;
-  pk.lookup = lookup_size;
-  pk.wstride = (unsigned)wstride;
-  pk.sequence = ++c->rep_seq;
-  pk.fenced = c->fenced;
-  for (size_t li = 0; li < launches.size(); ++li)
-  {
-    const Launch &L = launches[li];
-    pk.ops = reinterpret_cast<const RepOp *>(c->rep_ops.p) + L.first;
-    pk.nops = L.n;
-    pk.mark_wgs = L.wgs;
-    pk.mark_lds_cells = L.mark_lds;
-    const bool last = li + 1 == launches.size();
-    pk.has_rank = L.rank ? 1u : 0u;
-    pk.publish = last && !L.rank ? 1u : 0u;
-    const unsigned n8 = (L.n + 7u) / 8u * 8u;
-    pk.has_narrow = L.narrow ? 1u : 0u;
-    pk.has_general = L.general || !L.narrow ? 1u : 0u;
-    c->rep_launches_total += (pk.has_narrow ? 1u : 0u) + (pk.has_general ? 1u : 0u) + (L.rank ? 3u : 0u) + (L.assign ? 1u : 0u);
-    if (pk.has_narrow && L.fused)
-      hipLaunchKernelGGL(k_rep_mark_narrow_fused, dim3(n8 * L.wgs), dim3(kRepThreads), kRepSmallCells * sizeof(unsigned), c->stream, pk);
-    else if (pk.has_narrow)
-      hipLaunchKernelGGL(k_rep_mark_narrow, dim3(n8 * L.wgs), dim3(kRepThreads), kRepSmallCells * sizeof(unsigned), c->stream, pk);
-    if (pk.has_general)
-    {
-      const size_t mark_bytes = (size_t)L.mark_lds * sizeof(unsigned);
-      raise_lds_limit((const void *)k_rep_mark, c->device, mark_bytes);
-      hipLaunchKernelGGL(k_rep_mark, dim3(n8 * L.wgs), dim3(kRepThreads), mark_bytes, c->stream, pk);
-    }
-    if (L.rank)
-    {
-      // the bitmap of first sites: in LDS per (op, range of sites) where the tables are small enough for every range's
-      // workgroup to read all cells (k_rep_bits), else by atomics in k_rep_fold and one workgroup per op (k_rep_scan)
-      const bool bits = c->rep_bits && L.max_cells <= kRepBitsCells;
-      pk.bit_ranges = bits ? bit_ranges : 0u;
-      pk.bit_words = bits ? bit_words : 0u;
-      hipLaunchKernelGGL(k_rep_fold, dim3(n8 * kRepFoldTiles), dim3(kRepFoldThreads), 0, c->stream, pk);
-      pk.publish = last ? 1u : 0u;
-      if (bits)
-        hipLaunchKernelGGL(k_rep_bits, dim3(n8 * bit_ranges), dim3(kRepScanThreads), (size_t)bit_words * sizeof(unsigned), c->stream, pk);
-      else
-        hipLaunchKernelGGL(k_rep_scan, dim3(L.n), dim3(kRepScanThreads), 0, c->stream, pk);
-      hipLaunchKernelGGL(k_rep_rank, dim3(n8 * kRepRankTiles), dim3(kRepRankThreads), 0, c->stream, pk);
-    }
-    // k_rep_assign: a workgroup takes 1..4 rounds of 16384 sites - ~512 workgroups per launch, more rounds where a large
-    // table has to be brought into LDS first
-    pk.lds_cells = L.assign_lds;
-    const size_t assign_bytes = (size_t)L.assign_lds * sizeof(unsigned short);
-    const unsigned per_round = kRepAssignThreads * 16u, rounds = (sites + per_round - 1u) / per_round;
-    pk.assign_iters = std::max(1u, std::min(4u, rounds * L.n / (assign_bytes > 32768 ? 256u : 512u)));
-    pk.wgs = (rounds + pk.assign_iters - 1u) / pk.assign_iters;
-    raise_lds_limit((const void *)k_rep_assign, c->device, assign_bytes);
-    if (L.assign) hipLaunchKernelGGL(k_rep_assign, dim3(n8 * pk.wgs), dim3(kRepAssignThreads), assign_bytes, c->stream, pk);
-  }
-  HIP_TRY(hipGetLastError());
-  // the class counts arrive in mapped host memory as soon as the last k_rep_mark knows them (its k_rep_assign still
-  // runs; whatever uses the maps is ordered behind it by the stream): poll the sequence word for a bounded time
-  {
-    volatile unsigned *seq = c->rep_host + c->rep_host_cap;
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (__atomic_load_n(seq, __ATOMIC_ACQUIRE) != pk.sequence)
-      if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50))
-      {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        break;
-      }
-    if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) != pk.sequence) return fail(PLLGPU_ERUNTIME, "class counts did not arrive");
-    if (c->rep_host[c->rep_host_cap + 1u]) return fail(PLLGPU_ERUNTIME, "class maps: a table outgrew what the host had planned for it (%u)", c->rep_host[c->rep_host_cap + 1u]);
-  }
-  c->rep_scratch_dirty = false;
-  }
-  // the ops above the launched levels: the rule, from the counts below them
-  for (unsigned i = 0; i < ncut; ++i) counts_out[i] = c->rep_host[i];
-  for (unsigned i = ncut; i < count; ++i)
-  {
-    const pllgpu_repop_t &o = ops[i];
-    auto ids_of = [&](int src, unsigned given) -> unsigned long long {
-      if (src < 0) return given;
-      const unsigned w = counts_out[src], n = w & ~kRepFlag;
-      return (w & kRepFlag) && n < sites ? n : 0u;
-    };
-    const unsigned long long nl = ids_of(o.lsrc, o.nleft), nr = ids_of(o.rsrc, o.nright), cells = nl * nr;
-    if (o.force || (cells && cells < lookup_size && nl <= sites / 2u && nr <= sites / 2u))
-    {
-      c->rep_hint_count = 0; // the forecast was wrong: every level this time
-      return pllgpu_repeats_classes(c, ops, count, lookup_size, counts_out);
-    }
-    counts_out[i] = 0u;
-  }
-  c->rep_hint_count = count;
-  c->rep_hint_key = key;
-  c->rep_hint_any = false;
-  c->rep_hint_level = 0;
-  for (unsigned i = 0; i < count; ++i)
-    if (counts_out[i] & kRepFlag)
-    {
-      c->rep_hint_any = true;
-      c->rep_hint_level = std::max(c->rep_hint_level, ops[i].level);
-    }
-  // cached launches (LevelPlan) carry class counts and pointers, not contents: they stay valid when this call found what the
-  // last one found - the re-evaluation of one tree, again and again, with the reference's pll_update_partials
-  bool reshaped = false;
-  for (unsigned i = 0; i < count; ++i)
-  {
-    const unsigned word = counts_out[i], classes = word & ~kRepFlag;
-    const unsigned parent = ops[i].parent;
-    if (!(word & kRepFlag))
-    {
-      reshaped = reshaped || c->rep_left[parent] != -1 || c->rep_right[parent] != -1 || c->map_forms[parent] != 0;
-      c->rep_left[parent] = c->rep_right[parent] = -1;
-      c->map_forms[parent] = 0;
-      c->map_widened[parent] = 0;
-      continue;
-    }
-    if ((unsigned long long)classes > ub_cells[i]) return fail(PLLGPU_ERUNTIME, "class maps: op %u reports %u classes of at most %llu", i, classes, ub_cells[i]);
-    const unsigned char form = classes <= kRepNarrow ? kMap8 : kMap32;
-    reshaped = reshaped || c->rep_left[parent] != (int)ops[i].left || c->rep_right[parent] != (int)ops[i].right || !(c->map_forms[parent] & form);
-    c->rep_left[parent] = (int)ops[i].left;
-    c->rep_right[parent] = (int)ops[i].right;
-    c->map_forms[parent] = form;
-    if (form == kMap8 && c->map_widened[parent])
-    {
-      // a cached launch reads this node's 32-bit form: bring it up to date behind the bytes
-      c->map_widened[parent] = 0;
-      if (!wide_map(c, parent)) return fail(PLLGPU_ENOMEM, "class maps: no room for the 32-bit form of node %u", parent);
-    }
-  }
-  if (reshaped) ++c->maps_epoch;
-  ++c->maps_version;
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
+#include "class_map_plan.h"
 
 // ---- fast parsimony (src/fast_parsimony.c): kernels_parsimony.h --------------------------------------------------
 // A record of its own, not a pllgpu_ctx: the reference's pll_parsimony_t is independent of the partition it was made

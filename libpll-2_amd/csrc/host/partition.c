@@ -368,6 +368,7 @@ pll_partition_t *pll_partition_create(unsigned int tips, unsigned int clv_buffer
     const char *v = getenv("PLL_AMD_REP_STAMPS");
     x->map_stamps = !(v && *v == '0');
   }
+  x->level_sync = pll_env_flag("PLL_AMD_REP_LEVEL_SYNC");
   x->aux_params = (unsigned int *)malloc(sizeof(unsigned int) * rate_cats);
   NEED(x->clv_side && x->scaler_side && x->scaler_entries && x->tipchars_dirty && x->repeats_dirty &&
        x->pmatrix_dirty && x->freqs_dirty && x->eigen_dirty && x->aux_params);

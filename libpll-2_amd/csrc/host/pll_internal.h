@@ -73,6 +73,7 @@ typedef struct pll_amd_ext
   struct pll_map_stamp *map_stamp; /* [nodes] */
   unsigned long long map_clock;
   int map_stamps;                  /* PLL_AMD_REP_STAMPS=0: every call recomputes every map (bit-identity control) */
+  int level_sync;                  /* PLL_AMD_REP_LEVEL_SYNC=1: class maps level by level with the decisions on the host (repeats.c) */
   int rates_dirty;
   unsigned int eigen_version;   /* bumped whenever an eigensystem or frequency vector changes */
   unsigned int aux_version;     /* eigen_version the device contraction matrices were built from */

@@ -326,192 +326,241 @@ static int classes_call(pll_partition_t *p, pll_amd_ext_t *x, const pll_operatio
   return PLL_SUCCESS;
 }
 
+/* what becomes of an op of the list in a whole-list call (rep_scratch_t::keep) ... */
+enum
+{
+  OP_STANDS = 0,    /* its stamp holds: the parent's map is what it would be computed to */
+  OP_TO_DEVICE = 1, /* goes down with the call */
+  OP_SETTLED = 2    /* cannot be compressed whatever the device finds: the host's bookkeeping alone */
+};
+/* ... and who writes a node's map (rep_scratch_t::producer): the place in the call of the op that does, or */
+enum
+{
+  MAP_FROM_OUTSIDE = -1, /* nothing of the call */
+  MAP_SETTLED = -2       /* an op that is settled here */
+};
+
+/* the scratch of one pll_update_repeats_device: ONE block, taken and released there */
+typedef struct rep_scratch
+{
+  pllgpu_repop_t *rop;  /* [count] the call (the block's start) */
+  unsigned int *idx;    /* [count] place in the call -> op of the list */
+  unsigned int *counts; /* [count] what the call returns */
+  unsigned int *pos;    /* [count] op of the list -> its place in the call */
+  unsigned int *start;  /* [nlevels + 1] where a level's ops begin in the call */
+  int *producer;        /* [nodes] */
+  unsigned char *keep;  /* [count] */
+} rep_scratch_t;
+
+static int scratch_take(rep_scratch_t *s, unsigned int count, unsigned int nlevels, unsigned int nodes)
+{
+  const size_t words = (size_t)3 * count + nlevels + 1 + nodes;
+  s->rop = (pllgpu_repop_t *)malloc(sizeof(pllgpu_repop_t) * count + sizeof(unsigned int) * words + count);
+  if (!s->rop) return 0;
+  s->idx = (unsigned int *)(s->rop + count);
+  s->counts = s->idx + count;
+  s->pos = s->counts + count;
+  s->start = s->pos + count;
+  s->producer = (int *)(s->start + nlevels + 1);
+  s->keep = (unsigned char *)(s->producer + nodes);
+  return 1;
+}
+
+/* an op as pllgpu_repeats_classes wants it: a child comes from the op at lsrc / rsrc of the call, or (-1) from outside
+ * it with the class count the host knows */
+static void fill_repop(pllgpu_repop_t *o, const pll_repeats_t *r, const pll_operation_t *op, int lsrc, int rsrc,
+                       unsigned int level, unsigned int force)
+{
+  o->parent = op->parent_clv_index;
+  o->left = op->child1_clv_index;
+  o->right = op->child2_clv_index;
+  o->lsrc = lsrc;
+  o->rsrc = rsrc;
+  o->nleft = lsrc >= 0 ? 0 : r->pernode_ids[o->left];
+  o->nright = rsrc >= 0 ? 0 : r->pernode_ids[o->right];
+  o->level = level;
+  o->force = force;
+}
+
+/* Which ops have anything to compute: in list order, so that a parent sees the versions its children's maps have
+ * when ITS turn comes (a child written by an earlier op of the list that is computed again has a new one).
+ * ... and which of those cannot be compressed whatever the device finds: the rule (src/repeats.c:100-110) wants
+ * both children compressed, so a parent over a child that is not - known here for a child from outside the call, and
+ * from there up the list - stays uncompressed: no launch, the host's bookkeeping alone. In a tree search that is most of
+ * a partial traversal (the path from the moved edge to the evaluated one runs through large subtrees).
+ * Leaves keep[] and every OP_TO_DEVICE op's place in the call, ordered by level (stable); returns how many those are. */
+static unsigned int sort_ops(pll_partition_t *p, pll_amd_ext_t *x, const pll_operation_t *ops, unsigned int count,
+                             const unsigned int *level, unsigned int nlevels, rep_scratch_t *s)
+{
+  pll_repeats_t *r = p->repeats;
+  const int stamps = x->map_stamps && r->reallocate_repeats == pll_default_reallocate_repeats;
+  int *producer = s->producer;
+  unsigned int i, l, kept = 0;
+  memset(s->start, 0, sizeof(unsigned int) * (nlevels + 1));
+  for (i = 0; i < p->nodes; ++i) producer[i] = MAP_FROM_OUTSIDE;
+  for (i = 0; i < count; ++i)
+  {
+    s->keep[i] = (stamps && stamp_holds(x, r, &ops[i])) ? OP_STANDS : OP_TO_DEVICE;
+    if (s->keep[i] == OP_STANDS) continue;
+    stamp_set(x, r, &ops[i]);
+    const unsigned int left = ops[i].child1_clv_index, right = ops[i].child2_clv_index;
+    if (producer[left] == MAP_SETTLED || producer[right] == MAP_SETTLED || (producer[left] == MAP_FROM_OUTSIDE && !r->pernode_ids[left]) ||
+        (producer[right] == MAP_FROM_OUTSIDE && !r->pernode_ids[right]))
+    {
+      s->keep[i] = OP_SETTLED;
+      producer[ops[i].parent_clv_index] = MAP_SETTLED;
+      continue;
+    }
+    producer[ops[i].parent_clv_index] = 0; /* (an op of the call: its place follows) */
+    s->start[level[i] + 1]++;
+    ++kept;
+  }
+  for (l = 0; l < nlevels; ++l) s->start[l + 1] += s->start[l];
+  for (i = 0; i < count; ++i)
+    if (s->keep[i] == OP_TO_DEVICE) s->pos[i] = s->start[level[i]]++;
+  return kept;
+}
+
+/* The whole list in one call, under the reference's own rule: the decisions are the device's. */
+static int update_whole_list(pll_partition_t *p, pll_amd_ext_t *x, const pll_operation_t *ops, unsigned int count,
+                             const unsigned int *level, unsigned int nlevels, rep_scratch_t *s, int *changed)
+{
+  pll_repeats_t *r = p->repeats;
+  int *producer = s->producer;
+  const unsigned int kept = sort_ops(p, x, ops, count, level, nlevels, s);
+  unsigned int i;
+  int ok = PLL_FAILURE, failed = 0;
+  /* a child's producer is the latest earlier op of the CALL that writes it */
+  for (i = 0; i < p->nodes; ++i) producer[i] = MAP_FROM_OUTSIDE;
+  for (i = 0; i < count && !failed; ++i)
+  {
+    if (s->keep[i] == OP_STANDS) continue;
+    const pll_operation_t *op = &ops[i];
+    const unsigned int left = op->child1_clv_index, right = op->child2_clv_index, parent = op->parent_clv_index;
+    x->repeats_dirty[parent] = 0;
+    if (s->keep[i] == OP_SETTLED)
+    {
+      producer[parent] = MAP_FROM_OUTSIDE; /* (nothing of the call reads a settled parent's map: whoever does is settled too) */
+      continue;
+    }
+    pllgpu_repop_t *o = &s->rop[s->pos[i]];
+    fill_repop(o, r, op, producer[left], producer[right], level[i], 0);
+    s->idx[s->pos[i]] = i;
+    /* tips: host-built maps go up now */
+    if (o->lsrc < 0 && o->nleft && !pll_flush_repeats(p, x, left)) failed = 1;
+    if (o->rsrc < 0 && o->nright && !pll_flush_repeats(p, x, right)) failed = 1;
+    producer[parent] = (int)s->pos[i];
+  }
+  if (!failed) ok = classes_call(p, x, ops, s->rop, s->idx, kept, s->counts, changed);
+  for (i = 0; i < count && ok; ++i)
+    if (s->keep[i] == OP_SETTLED) ok = follow_count(p, x, &ops[i], 0u, changed);
+  /* every op names the scaler slot its parent's classes go with, the later op of the list last as in the reference
+   * (src/repeats.c:328-369 sets the field on every call): an op whose map stands - it was skipped above - may come
+   * back with another slot than last time, or another op may have used its slot in between */
+  for (i = 0; i < count && ok; ++i)
+  {
+    const int slot = ops[i].parent_scaler_index;
+    if (slot != PLL_SCALE_BUFFER_NONE) r->perscale_ids[slot] = r->pernode_ids[ops[i].parent_clv_index];
+  }
+  if (!ok) /* whatever the device left of these maps is not what their stamps say */
+    for (i = 0; i < count; ++i)
+      if (s->keep[i] != OP_STANDS) pll_maps_touched(x, p, (int)ops[i].parent_clv_index);
+  return ok;
+}
+
+/* the rule said no: the parent stays uncompressed, on the host and on the device */
+static int leave_uncompressed(pll_partition_t *p, pll_amd_ext_t *x, const pll_operation_t *op, int *changed)
+{
+  const pll_repeats_t *r = p->repeats;
+  const unsigned int parent = op->parent_clv_index;
+  if (x->repeats_count[parent] || r->pernode_ids[parent] || r->pernode_allocated_clvs[parent] != p->sites) *changed = 1;
+  adopt_classes(p, op, 0, 0);
+  x->repeats_stale[parent] = 0;
+  x->repeats_count[parent] = 0;
+  if (pllgpu_repeats_set_ids(x->ctx, parent, 0) != 0)
+  {
+    pll_set_gpu_error("pll_update_repeats");
+    return PLL_FAILURE;
+  }
+  return PLL_SUCCESS;
+}
+
+/* Level by level with the decisions on the host: enable_repeats is asked with the counts of the levels below in
+ * pernode_ids, as the reference has them. No stamps kept (a caller's rule may depend on anything). A level goes down
+ * in calls of at most PLLGPU_REPEATS_MAX_OPS ops. */
+static int update_by_level(pll_partition_t *p, pll_amd_ext_t *x, const pll_operation_t *ops, unsigned int count,
+                           const unsigned int *level, unsigned int nlevels, rep_scratch_t *s, int *changed)
+{
+  pll_repeats_t *r = p->repeats;
+  unsigned int l, i, n;
+  int ok = PLL_SUCCESS;
+  for (i = 0; i < count; ++i) pll_maps_touched(x, p, (int)ops[i].parent_clv_index);
+  for (l = 0; l < nlevels && ok; ++l)
+  {
+    n = 0;
+    for (i = 0; i < count && ok; ++i)
+    {
+      if (level[i] != l) continue;
+      const pll_operation_t *op = &ops[i];
+      const unsigned int left = op->child1_clv_index, right = op->child2_clv_index;
+      x->repeats_dirty[op->parent_clv_index] = 0;
+      if (!r->enable_repeats(p, left, right))
+      {
+        ok = leave_uncompressed(p, x, op, changed);
+        continue;
+      }
+      /* tips: host-built maps go up now; inner children were produced by an earlier level */
+      if (!pll_flush_repeats(p, x, left) || !pll_flush_repeats(p, x, right))
+      {
+        ok = PLL_FAILURE;
+        continue;
+      }
+      fill_repop(&s->rop[n], r, op, -1, -1, 0, 1);
+      s->idx[n++] = i;
+      if (n == PLLGPU_REPEATS_MAX_OPS)
+      {
+        ok = classes_call(p, x, ops, s->rop, s->idx, n, s->counts, changed);
+        n = 0;
+      }
+    }
+    if (ok) ok = classes_call(p, x, ops, s->rop, s->idx, n, s->counts, changed);
+  }
+  return ok;
+}
+
 /* Class maps of an op list on the device. With the reference's own decision rule (pll_default_enable_repeats) the
  * whole list goes down in one call: the rule is a function of the children's class counts, which the device holds
  * before the host does, so the levels run back to back and the host reads all counts once (round 4: a blocking
  * hand-off per level - the callback wanted the counts on the host). A caller-supplied enable_repeats keeps that form:
- * the callback is asked level by level, with the counts of the levels below in pernode_ids as the reference has them.
- * PLL_AMD_REP_LEVEL_SYNC=1 takes the level-by-level form for the default rule too (A/B, tests). */
+ * the callback is asked level by level. PLL_AMD_REP_LEVEL_SYNC=1, read when the partition is created, takes the
+ * level-by-level form for the default rule too (A/B, tests). */
 int pll_update_repeats_device(pll_partition_t *p, pll_amd_ext_t *x, const pll_operation_t *ops,
                               unsigned int count, const unsigned int *level, unsigned int nlevels)
 {
   const int was_fast = x->fast_valid;
-  int changed = 0;
+  int changed = 0, ok;
   x->fast_valid = 0;
   pll_repeats_t *r = p->repeats;
-  unsigned int l, i, n;
-  int ok = PLL_FAILURE;
+  rep_scratch_t s;
   if (!r->lookup_buffer)
   {
     pll_resize_repeats_lookup(p, PLL_REPEATS_LOOKUP_SIZE); /* its SIZE bounds the pair table */
     changed = 1;
   }
-  pllgpu_repop_t *rop = (pllgpu_repop_t *)malloc(sizeof(pllgpu_repop_t) * count);
-  unsigned int *idx = (unsigned int *)malloc(sizeof(unsigned int) * 2 * count);
-  int *producer = (int *)malloc(sizeof(int) * (p->nodes ? p->nodes : 1));
-  if (!rop || !idx || !producer)
+  if (!scratch_take(&s, count, nlevels, p->nodes))
   {
     pll_set_error(PLL_ERROR_MEM_ALLOC, "Unable to allocate enough memory for repeats structure.");
-    goto done;
+    return PLL_FAILURE;
   }
-  unsigned int *counts = idx + count;
-  static int level_sync = -1;
-  if (level_sync < 0)
-  {
-    const char *v = getenv("PLL_AMD_REP_LEVEL_SYNC");
-    level_sync = (v && *v && *v != '0') ? 1 : 0;
-  }
-  if (r->enable_repeats == pll_default_enable_repeats && !level_sync && count <= PLLGPU_REPEATS_MAX_OPS)
-  {
-    /* which ops have anything to compute: in list order, so that a parent sees the versions its children's maps have
-     * when ITS turn comes (a child written by an earlier op of the list that is computed again has a new one) */
-    unsigned char *keep = (unsigned char *)malloc(count);
-    unsigned int *start = (unsigned int *)calloc(nlevels + 1, sizeof(unsigned int));
-    unsigned int *pos = (unsigned int *)malloc(sizeof(unsigned int) * count); /* op of the list -> its place in the call */
-    if (!keep || !start || !pos)
-    {
-      free(keep);
-      free(start);
-      free(pos);
-      pll_set_error(PLL_ERROR_MEM_ALLOC, "Unable to allocate enough memory for repeats structure.");
-      goto done;
-    }
-    const int stamps = x->map_stamps && r->reallocate_repeats == pll_default_reallocate_repeats;
-    /* ... and which of those cannot be compressed whatever the device finds: the rule (src/repeats.c:100-110) wants
-     * both children compressed, so a parent over a child that is not - known here for a child from outside the call, and
-     * from there up the list - stays uncompressed: no launch, the host's bookkeeping alone. In a tree search that is most of
-     * a partial traversal (the path from the moved edge to the evaluated one runs through large subtrees):
-     * keep = 1: to the device, 2: settled here. producer[]: -1 outside the call, -2 settled here, else the place in the call */
-    unsigned int kept = 0;
-    for (i = 0; i < p->nodes; ++i) producer[i] = -1;
-    for (i = 0; i < count; ++i)
-    {
-      keep[i] = !(stamps && stamp_holds(x, r, &ops[i]));
-      if (!keep[i]) continue;
-      stamp_set(x, r, &ops[i]);
-      const unsigned int left = ops[i].child1_clv_index, right = ops[i].child2_clv_index;
-      if (producer[left] == -2 || producer[right] == -2 || (producer[left] == -1 && !r->pernode_ids[left]) ||
-          (producer[right] == -1 && !r->pernode_ids[right]))
-      {
-        keep[i] = 2;
-        producer[ops[i].parent_clv_index] = -2;
-        continue;
-      }
-      producer[ops[i].parent_clv_index] = 0; /* (its place follows) */
-      start[level[i] + 1]++;
-      ++kept;
-    }
-    /* order by level (stable); a child's producer is the latest earlier op of the CALL that writes it */
-    for (l = 0; l < nlevels; ++l) start[l + 1] += start[l];
-    for (i = 0; i < count; ++i)
-      if (keep[i] == 1) pos[i] = start[level[i]]++;
-    for (i = 0; i < p->nodes; ++i) producer[i] = -1;
-    int failed = 0;
-    for (i = 0; i < count && !failed; ++i)
-    {
-      if (!keep[i]) continue;
-      const pll_operation_t *op = &ops[i];
-      const unsigned int left = op->child1_clv_index, right = op->child2_clv_index, parent = op->parent_clv_index;
-      x->repeats_dirty[parent] = 0;
-      if (keep[i] == 2)
-      {
-        producer[parent] = -1; /* (nothing of the call reads a settled parent's map: whoever does is settled too) */
-        continue;
-      }
-      pllgpu_repop_t *o = &rop[pos[i]];
-      o->parent = parent;
-      o->left = left;
-      o->right = right;
-      o->lsrc = producer[left];
-      o->rsrc = producer[right];
-      o->nleft = o->lsrc >= 0 ? 0 : r->pernode_ids[left];
-      o->nright = o->rsrc >= 0 ? 0 : r->pernode_ids[right];
-      o->level = level[i];
-      o->force = 0;
-      idx[pos[i]] = i;
-      /* tips: host-built maps go up now */
-      if (o->lsrc < 0 && o->nleft && !pll_flush_repeats(p, x, left)) failed = 1;
-      if (o->rsrc < 0 && o->nright && !pll_flush_repeats(p, x, right)) failed = 1;
-      producer[parent] = (int)pos[i];
-    }
-    free(start);
-    free(pos);
-    if (!failed) ok = classes_call(p, x, ops, rop, idx, kept, counts, &changed);
-    for (i = 0; i < count && ok; ++i)
-      if (keep[i] == 2) ok = follow_count(p, x, &ops[i], 0u, &changed);
-    /* every op names the scaler slot its parent's classes go with, the later op of the list last as in the reference
-     * (src/repeats.c:328-369 sets the field on every call): an op whose map stands - it was skipped above - may come
-     * back with another slot than last time, or another op may have used its slot in between */
-    for (i = 0; i < count && ok; ++i)
-    {
-      const int slot = ops[i].parent_scaler_index;
-      if (slot != PLL_SCALE_BUFFER_NONE) r->perscale_ids[slot] = r->pernode_ids[ops[i].parent_clv_index];
-    }
-    if (!ok) /* whatever the device left of these maps is not what their stamps say */
-      for (i = 0; i < count; ++i)
-        if (keep[i]) pll_maps_touched(x, p, (int)ops[i].parent_clv_index);
-    free(keep);
-    if (failed) goto done;
-  }
+  if (r->enable_repeats == pll_default_enable_repeats && !x->level_sync && count <= PLLGPU_REPEATS_MAX_OPS)
+    ok = update_whole_list(p, x, ops, count, level, nlevels, &s, &changed);
   else
-  {
-    ok = PLL_SUCCESS;
-    /* level by level with the decisions on the host: no stamps kept (a caller's rule may depend on anything) */
-    for (i = 0; i < count; ++i) pll_maps_touched(x, p, (int)ops[i].parent_clv_index);
-    for (l = 0; l < nlevels && ok; ++l)
-    {
-      n = 0;
-      for (i = 0; i < count && ok; ++i)
-      {
-        if (level[i] != l) continue;
-        const pll_operation_t *op = &ops[i];
-        const unsigned int left = op->child1_clv_index, right = op->child2_clv_index, parent = op->parent_clv_index;
-        x->repeats_dirty[parent] = 0;
-        if (!r->enable_repeats(p, left, right))
-        {
-          if (x->repeats_count[parent] || r->pernode_ids[parent] || r->pernode_allocated_clvs[parent] != p->sites) changed = 1;
-          adopt_classes(p, op, 0, 0);
-          x->repeats_stale[parent] = 0;
-          x->repeats_count[parent] = 0;
-          if (pllgpu_repeats_set_ids(x->ctx, parent, 0) != 0) goto gpu_fail;
-          continue;
-        }
-        /* tips: host-built maps go up now; inner children were produced by an earlier level */
-        if (!pll_flush_repeats(p, x, left) || !pll_flush_repeats(p, x, right))
-        {
-          ok = PLL_FAILURE;
-          break;
-        }
-        rop[n].parent = parent;
-        rop[n].left = left;
-        rop[n].right = right;
-        rop[n].nleft = r->pernode_ids[left];
-        rop[n].nright = r->pernode_ids[right];
-        rop[n].lsrc = rop[n].rsrc = -1;
-        rop[n].level = 0;
-        rop[n].force = 1;
-        idx[n++] = i;
-        if (n == PLLGPU_REPEATS_MAX_OPS)
-        {
-          ok = classes_call(p, x, ops, rop, idx, n, counts, &changed);
-          n = 0;
-        }
-      }
-      if (ok) ok = classes_call(p, x, ops, rop, idx, n, counts, &changed);
-    }
-  }
+    ok = update_by_level(p, x, ops, count, level, nlevels, &s, &changed);
   if (ok && x->eager_mirror) ok = pll_gpu_sync_repeats(p, -1);
   /* every class count as it was: the classified list of the last whole pll_update_partials (partials.c: fast path) is
    * still the right one */
   if (ok && !changed) x->fast_valid = was_fast;
-  goto done;
-gpu_fail:
-  pll_set_gpu_error("pll_update_repeats");
-  ok = PLL_FAILURE;
-done:
-  free(rop);
-  free(idx);
-  free(producer);
+  free(s.rop);
   return ok;
 }
 

@@ -284,6 +284,50 @@ def test_class_maps_do_not_depend_on_how_the_launches_are_cut(amd_lib, ref_lib, 
     assert abs(res[True][1] - res[False][1]) <= 1e-10 * abs(res[False][1])
 
 
+def test_the_level_switch_belongs_to_the_partition_created_under_it(amd_lib, ref_lib, monkeypatch):
+    """PLL_AMD_REP_LEVEL_SYNC is read when a partition is created, as the other switches are: three partitions of one
+    process - variable unset, set, unset again - take the whole-list form, the level-by-level form and the whole-list form
+    again. Which form ran shows in pll_gpu_class_map_work(p, 2), the class-map calls the partition's device has served:
+    one for the whole list, one per dependency level that has work level by level. (The switch used to be latched by
+    the first class-map call of the process.) All three leave the reference's maps."""
+    case = W.make_case("rep", attributes=api.SITE_REPEATS, states=4, tips=16, sites=300, mutate_pct=30, seed=82)
+    batch = case.op_batches[0]
+    ops = api.make_ops(batch)
+    with driver.Session(ref_lib, case, api.ARCH_AVX2) as s:
+        ref_lib.pll_update_partials(s.p, ops, len(batch))
+        want = (_maps(ref_lib, s, case.sites, through_accessors=True), s.edge_lnl(case.edges[0], persite=False)[0])
+        lookup = s.part.repeats.contents.lookup_buffer_size
+    # the levels at which the rule (src/repeats.c:100-110) admits an op, from the reference's counts: a whole traversal
+    # writes every node once, so an op's level is one above its children's producers
+    assert len({int(r[0]) for r in batch}) == len(batch)
+    level, busy = {}, set()
+    for r in batch:
+        parent, left, right = int(r[0]), int(r[2]), int(r[5])
+        level[parent] = 1 + max(level.get(left, -1), level.get(right, -1))
+        nl, nr = want[0][left][0], want[0][right][0]
+        if 0 < nl * nr < lookup and nl <= case.sites // 2 and nr <= case.sites // 2:
+            busy.add(level[parent])
+    assert len(busy) > 1
+    calls = []
+    for value in (None, "1", None):
+        if value is None:
+            monkeypatch.delenv("PLL_AMD_REP_LEVEL_SYNC", raising=False)
+        else:
+            monkeypatch.setenv("PLL_AMD_REP_LEVEL_SYNC", value)
+        with driver.Session(amd_lib, case, api.ARCH_AVX2) as s:
+            assert amd_lib.pll_gpu_class_map_work(s.p, 2) == 0
+            amd_lib.pll_update_partials(s.p, ops, len(batch))
+            calls.append(amd_lib.pll_gpu_class_map_work(s.p, 2))
+            got = (_maps(amd_lib, s, case.sites, through_accessors=True), s.edge_lnl(case.edges[0], persite=False)[0])
+        for node, (a, b) in enumerate(zip(got[0], want[0])):
+            assert a[0] == b[0] and a[3] == b[3] and a[4] == b[4], (value, node, a[0], b[0])
+            if a[0]:
+                assert (a[1] == b[1]).all() and (a[2] == b[2]).all(), (value, node)
+        assert abs(got[1] - want[1]) <= 1e-10 * abs(want[1]), value
+    print("class-map calls served:", calls, "levels with work:", sorted(busy))
+    assert calls == [1, len(busy), 1]
+
+
 def test_a_wrong_level_forecast_is_repaired(amd_lib, ref_lib):
     """the levels a class-map call launches follow where compression ended the last time (pllgpu_repeats_classes);
     sequences that compress deeper than the last ones did must still get the reference's maps - the call notices that
