@@ -1032,6 +1032,70 @@ int pll_gpu_rate_gradient(pll_partition_t *partition, const pll_gpu_branch_t *br
                           const unsigned int *params_indices,
                           double *d_rates /* [rate_cats] or NULL */, double *d_scale /* 1 or NULL */,
                           double *d_cat /* [count][rate_cats] or NULL */, double *d_f /* [count] or NULL */);
+/* ---- the model gradient: dlnL/dQ, GTR rates and frequencies ----------
+ * The gradient of -lnL with respect to the substitution parameters and the state frequencies from one device call over the
+ * list that pll_gpu_branch_derivatives reads: both ends of every branch, oriented towards it. Notation for one partition:
+ * U = inv_eigenvecs[m], U^-1 = eigenvecs[m], lam = eigenvals[m] (the reference forms P = U diag(exp(lam tau)) U^-1,
+ * src/core_pmatrix.c:213-234, so Q_m = U diag(lam) U^-1); row b of the list has the parent end p, the child end c and the
+ * length t_b - roles, tips, per-rate scalers and the excess factor f_k exactly as in pll_gpu_branch_derivatives; w_k, r_k,
+ * pinv_k, m(k) = params_indices[k], the pattern weights pw[n]; L_n the site's site_lk[0] of
+ * src/core_derivatives.c:676-686 (the invariant term included, after the excess factors); tau_bk = r_k t_b / (1 - pinv_k).
+ *   A_i(n,k)     = sum_x pi_x p_x(n,k) U[x][i]            B_j(n,k) = sum_y U^-1[j][y] c_y(n,k)     (the row's two factors)
+ *   H_bk[i][j]   = sum_n pw[n] * w_k (1 - pinv_k) f_k(n) A_i(n,k) B_j(n,k) / L_n
+ *   Phi_bk[i][j] = tau e^{lam_j tau} * g((lam_i - lam_j) tau),   g(x) = expm1(x)/x, g(0) = 1    (so Phi_ii = tau e^{lam_i tau})
+ *   W_m[i][j]    = sum_b (in list order) sum_{k: m(k)=m} Phi_bk[i][j] * H_bk[i][j]
+ *   d_q[m][x][y] = - sum_ij U^-1[i][x] W_m[i][j] U[y][j]                                         = d(-lnL)/dQ_m[x][y]
+ *   d_root[m][x] = - (1/pi_x) sum_{k: m(k)=m} sum_ij U^-1[i][x] U[x][j] e^{lam_j tau_0k} H_0k[i][j]   (branches[0] only)
+ * d_q is the derivative of -lnL with respect to every entry of the rate matrix taken as independent, the per-category time
+ * scaling included, each P_bk in the orientation the list gives it; it does not depend on the choice of eigenvectors. The
+ * log-likelihood is multilinear in the P_bk, so for any parameter theta that keeps the model reversible
+ *   d(-lnL)/dtheta = sum_xy d_q[m][x][y] dQ_m[x][y]/dtheta
+ * PROVIDED the list names every branch of the tree exactly once, each end oriented towards its branch - the proviso of
+ * pll_gpu_rate_gradient, and not checked here either. d_root is the explicit dependence of -lnL on pi through the root
+ * sum, needed for the frequency gradient alone and taken at branches[0]: a change of pi moves the matrices out of
+ * reversibility with the old pi, so for d_root / d_freqs the orientation of the rows counts - branches[0] is the edge whose
+ * two ends point at each other (the root edge of the traversal) and every other row has the root-side end as its parent,
+ * which is the list of INTEGRATION.md with the root edge moved to the front. d_subst cares neither which way a row points
+ * (d_q itself does: a flipped row contributes its transpose) nor which row comes first. Phi is evaluated through expm1 in a form without
+ * positive exponents: coinciding and nearly coinciding eigenvalues (JC69) never meet a divided difference.
+ * pll_gpu_subst_gradient_from_dq applies the chain rule to the library's own parametrisation (src/models.c:182-256
+ * without the square-root symmetrisation): s_p = subst_params[p] / subst_params[last], a_xy = s_xy pi_y (x != y), a_xx =
+ * - sum_{y != x} a_xy, mean = 2 sum_{x<y} s_xy pi_x pi_y, Q = a / mean. d_subst[p] is the derivative with respect to
+ * subst_params[m][p], the array as the caller set it, the division by the last entry applied (so sum_p subst_params[p]
+ * d_subst[p] = 0); d_freqs[x] the derivative with respect to frequencies[m][x] with the other frequencies held fixed - no
+ * renormalisation: the Q part through a and mean, plus d_root (a caller with normalised frequencies uses g_x - sum_y pi_y
+ * g_y). A scalar host routine in closed form, O(states^2) in all; it needs no device and reads subst_params / frequencies
+ * of the partition. PLL_ERROR_PARAM_INVALID for a NULL partition or d_q_m, for both outputs NULL, for a params_index out
+ * of range, for a frequency of the set <= PLL_EIGEN_MINFREQ (the reference eliminates such states) and for
+ * subst_params[last] <= 0. pll_gpu_subst_gradient is the device call followed by that routine for every rate matrix that
+ * a category uses; an unused one gets zeros.
+ * Everything else is pll_gpu_branch_category_derivatives': what the ends may be, the flush of held work and pending CLVs,
+ * nothing in the partition written (an invalid eigensystem is computed first, as pll_update_sumtable does), synchronous
+ * with one copy back and one wait, the checks and their order (d_q mandatory where d_f is there), the refusals
+ * (PLL_ERROR_GPU_UNSUPPORTED for site repeats, any ascertainment-bias correction; PLL_ERROR_PARAM_INVALID for two code-tip
+ * ends; no device: PLL_ERROR_GPU_UNAVAILABLE), outputs untouched on failure. count == 0 succeeds without a launch and sets
+ * every output to zeros. Added: after the two refusals and before the device is asked for, PLL_ERROR_GPU_UNSUPPORTED when
+ * d_root / d_freqs is asked while prop_invar of a used rate matrix is > 0 (that needs a per-state sum over the invariant
+ * sites); d_q and d_subst are served with any pinv; then, for every output, the shape's need of LDS (below). pll_gpu_subst_gradient checks first of all, after the NULL partition,
+ * count == 0 and both outputs NULL, what the chain rule asks of every used set. Shapes other than 4 states x 4 categories
+ * whose two parked vectors exceed the LDS of a workgroup are PLL_ERROR_GPU_UNSUPPORTED (the rule:
+ * include/pll_amd_device.h, pllgpu_qmatrix_gradient; 20 states x 4 and 61 x 2 fit, 61 x 4 does not).
+ * Bits: every output has the same bits from run to run for the same partition and list; sums over sites are formed in an
+ * order that depends on the shape alone, sums over branches in list order; no floating-point atomics.
+ * pll_gpu_last_launch_count: three per cut of the list plus one (the rule: include/pll_amd_device.h).
+ * Not offered: site repeats, ascertainment bias, the frequency gradient with pinv > 0, second derivatives, any optimiser,
+ * non-reversible models; sharded runs add the shards' d_q with pll_gpu_group_sum. */
+int pll_gpu_qmatrix_gradient(pll_partition_t *partition, const pll_gpu_branch_t *branches, unsigned int count,
+                             const unsigned int *params_indices,
+                             double *d_q    /* [rate_matrices][states][states] */,
+                             double *d_root /* [rate_matrices][states] or NULL */);
+int pll_gpu_subst_gradient_from_dq(const pll_partition_t *partition, unsigned int params_index,
+                                   const double *d_q_m /* [states][states] */, const double *d_root_m /* [states] or NULL */,
+                                   double *d_subst /* [states (states-1)/2] or NULL */, double *d_freqs /* [states] or NULL */);
+int pll_gpu_subst_gradient(pll_partition_t *partition, const pll_gpu_branch_t *branches, unsigned int count,
+                           const unsigned int *params_indices,
+                           double *d_subst /* [rate_matrices][states (states-1)/2] or NULL */,
+                           double *d_freqs /* [rate_matrices][states] or NULL */);
 /* ---- rate-category posteriors, site rates and EM weight steps ----------
  * The per-category site likelihoods of one edge - what every evaluation kernel mixes away in registers - and what model
  * optimisation makes of them: FreeRate (+R) and mixture (LG4X) weights, empirical-Bayes site rates, a pinv step. The

@@ -383,6 +383,34 @@ int pllgpu_branch_category_derivatives(pllgpu_ctx_t *ctx, const pllgpu_branch_t 
                                        const unsigned int *params_indices, double *host_d_cat, double *host_d, double *host_dd,
                                        double *host_d_rates, double *host_d_scale);
 
+/* The model gradient (kernels_qgradient.h): the derivative of -lnL with respect to every entry of every rate matrix,
+ * host_d_q [rate_matrices][states][states], and - host_d_root [rate_matrices][states], or NULL - the explicit dependence of
+ * -lnL on the frequencies through the root sum taken at branches[0]; include/pll_amd.h (pll_gpu_qmatrix_gradient) holds the
+ * definitions. The list, its checks and their order, the refusals, the flush of held work, what the ends may be and how
+ * scalers are read are pllgpu_branch_derivatives', through the same code; host_d_q must not be NULL (PLLGPU_EINVAL). A rate
+ * matrix that no category uses gets zeros. The eigenvectors are those of the two contraction matrices
+ * (pllgpu_aux_matrix_upload) and the frequencies the context holds. Nothing the context holds is written.
+ * The cutting rule. B = the workgroups per branch, a function of the shape alone (T = ceil(sites / 64); 4 x 4: w =
+ * ceil(T / (4 PLLGPU_QGRADIENT_MAX_BLOCKS)), B = ceil(T / (4 w)); every other shape: P = states rounded up to a multiple of
+ * 16, M = min(PLLGPU_QGRADIENT_MAX_BLOCKS, max(4, floor(16384 / P^2))), w = ceil(T / M), B = ceil(T / w) - 4 workgroups at
+ * 61 states). A workgroup leaves V = U states^2 values in a slot of its own, U the number of rate matrices that a category
+ * uses, and twice that when host_d_root is asked; a launch carries at most PLLGPU_BRANCH_MAX descriptors and
+ * PLLGPU_INSERTION_MAX_SLOTS partial slots:
+ *   Q = min(count, PLLGPU_BRANCH_MAX, max(1, floor(PLLGPU_INSERTION_MAX_SLOTS / (V B))))   branches per launch,
+ * grid (B, Q). Behind every cut two small launches add the slots of each branch in slot order and the branches in list
+ * order; behind the last cut one launch transforms the sums with the eigenvectors: 3 ceil(count / Q) + 1 launches (counted
+ * into pllgpu_last_launch_count), no host wait between them, one copy back, one wait. No ticket and no atomic: the bits
+ * follow from the shape and the list. Every other shape than 4 x 4 parks both eigenbasis vectors of a tile in LDS:
+ * PLLGPU_EUNSUPPORTED where PLLGPU_QGRADIENT_LDS_BYTES = 8 (4 R states + 256 + 64 R + 130 R P) exceed
+ * PLLGPU_QGRADIENT_LDS_MAX = 160 KB (the last check here: held work has been launched by then, nothing else has happened;
+ * the host layer asks the same question before it asks for the device).
+ * count == 0 succeeds without a launch: host_d_q and host_d_root are set to 0. */
+#define PLLGPU_QGRADIENT_MAX_BLOCKS 64
+#define PLLGPU_QGRADIENT_LDS_MAX (160ul * 1024ul)
+#define PLLGPU_QGRADIENT_LDS_BYTES(S, R) (8ul * (4ul * (R) * (S) + 256ul + 64ul * (R) + 130ul * (R) * (((S) + 15ul) / 16ul * 16ul)))
+int pllgpu_qmatrix_gradient(pllgpu_ctx_t *ctx, const pllgpu_branch_t *branches, unsigned int count,
+                            const unsigned int *params_indices, double *host_d_q, double *host_d_root);
+
 /* replaces pll_compute_node_ancestral[_extbuf] (src/likelihood.c:639-823): the marginal state probabilities of
  * the node at edge->parent_clv, [sites][states] unpadded, given the other end edge->child_clv (a CLV, or tip codes
  * with child_is_tip) across edge->matrix. Of `edge`, gather must be 0 and want_persite / device_result / sequence

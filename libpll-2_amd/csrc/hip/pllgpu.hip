@@ -38,6 +38,7 @@
 #include "kernels_resample.h"
 #include "kernels_rell.h"
 #include "kernels_gradient.h"
+#include "kernels_qgradient.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
@@ -3564,26 +3565,29 @@ static size_t branch_lds(const pllgpu_ctx *c, bool cat)
   return ((size_t)c->gg.R * c->gg.S * 4 + (cat ? (size_t)2 * c->gg.R * 64 : 0)) * sizeof(double);
 }
 
+// the descriptor of one branch of a list (every call over pllgpu_branch_t rows)
+static int branch_desc(pllgpu_ctx *c, const pllgpu_branch_t &q, BranchDesc &d)
+{
+  // an end given by codes takes the left role, as in pllgpu_update_sumtable's callers; otherwise parent left, child right
+  const bool swap = q.child_is_tip != 0;
+  const unsigned lclv = swap ? q.child_clv : q.parent_clv, rclv = swap ? q.parent_clv : q.child_clv;
+  const int lsc = swap ? q.child_scaler : q.parent_scaler, rsc = swap ? q.parent_scaler : q.child_scaler;
+  const bool ltip = (swap ? q.child_is_tip : q.parent_is_tip) != 0;
+  // per-site counts cancel in L'/L: only the per-rate form is read
+  const bool counts = c->geo.per_rate_scalers != 0;
+  if (int rc = end_in_hbm(c, lclv, (ltip || !counts) ? -1 : lsc, ltip, d.left, d.ltip, d.lscaler)) return rc;
+  if (int rc = end_in_hbm(c, rclv, counts ? rsc : -1, false, d.right, d.rtip, d.rscaler)) return rc;
+  d.t = q.branch_length;
+  d.pad_ = 0.0;
+  return 0;
+}
+
 // one launch for branches [first, first + n): their descriptors up, the kernel of the shape. cat: the R + 2 values of
 // pllgpu_branch_category_derivatives instead of the two of pllgpu_branch_derivatives
 static int launch_branches(pllgpu_ctx *c, DevEdge e, const TileWalk &w, const DevDiag &dg, const pllgpu_branch_t *branches, unsigned first, unsigned n,
                            unsigned count, bool cat)
 {
-  const int up = stage_up<BranchDesc>(c, c->ins_cands.p, n, [&](BranchDesc &d, unsigned i) {
-    const pllgpu_branch_t &q = branches[first + i];
-    // an end given by codes takes the left role, as in pllgpu_update_sumtable's callers; otherwise parent left, child right
-    const bool swap = q.child_is_tip != 0;
-    const unsigned lclv = swap ? q.child_clv : q.parent_clv, rclv = swap ? q.parent_clv : q.child_clv;
-    const int lsc = swap ? q.child_scaler : q.parent_scaler, rsc = swap ? q.parent_scaler : q.child_scaler;
-    const bool ltip = (swap ? q.child_is_tip : q.parent_is_tip) != 0;
-    // per-site counts cancel in L'/L: only the per-rate form is read
-    const bool counts = c->geo.per_rate_scalers != 0;
-    if (int rc = end_in_hbm(c, lclv, (ltip || !counts) ? -1 : lsc, ltip, d.left, d.ltip, d.lscaler)) return rc;
-    if (int rc = end_in_hbm(c, rclv, counts ? rsc : -1, false, d.right, d.rtip, d.rscaler)) return rc;
-    d.t = q.branch_length;
-    d.pad_ = 0.0;
-    return 0;
-  });
+  const int up = stage_up<BranchDesc>(c, c->ins_cands.p, n, [&](BranchDesc &d, unsigned i) { return branch_desc(c, branches[first + i], d); });
   if (up) return up;
   const BranchDesc *db = reinterpret_cast<const BranchDesc *>(c->ins_cands.p);
   const double *m1 = c->pmat.p + (size_t)c->geo.prob_matrices * c->pm_stride, *m2 = m1 + c->pm_stride;
@@ -3722,6 +3726,149 @@ extern "C" int pllgpu_branch_category_derivatives(pllgpu_ctx_t *c, const pllgpu_
       for (unsigned k = 0; k < R; ++k) host_d_cat[(size_t)i * R + k] = rows[(size_t)(k + 2u) * count + i];
   if (host_d_rates) memcpy(host_d_rates, rows.data() + values + count, (size_t)R * sizeof(double));
   if (host_d_scale) *host_d_scale = rows[values + count + R];
+  return 0;
+}
+
+// ---- the model gradient (kernels_qgradient.h) ------------------------------------------------------------------
+constexpr unsigned kQgMaxBlocks = 64;        // workgroups per branch at most
+constexpr size_t kQgLdsMax = 160 * 1024;     // k_qgradient_mfma's LDS is all dynamic
+static_assert(kQgMaxBlocks == PLLGPU_QGRADIENT_MAX_BLOCKS && kQgLdsMax == PLLGPU_QGRADIENT_LDS_MAX &&
+                  qg_lds_doubles(61, 2) * sizeof(double) == PLLGPU_QGRADIENT_LDS_BYTES(61, 2) &&
+                  qg_lds_doubles(5, 7) * sizeof(double) == PLLGPU_QGRADIENT_LDS_BYTES(5, 7),
+              "include/pll_amd_device.h states the cutting rule and the LDS a shape needs");
+
+// The workgroups per branch and the tiles each wave (4 x 4) or workgroup walks: a function of the shape alone
+// (include/pll_amd_device.h states the rule)
+static TileWalk qgradient_walk(const pllgpu_ctx *c)
+{
+  const unsigned tiles = (c->geo.sites + 63) / 64;
+  TileWalk w;
+  if (c->dna_fast)
+  {
+    w.tiles_per = (tiles + 4 * kQgMaxBlocks - 1) / (4 * kQgMaxBlocks);
+    w.blocks = (tiles + 4 * w.tiles_per - 1) / (4 * w.tiles_per);
+  }
+  else
+  {
+    const unsigned spad = (c->geo.states + 15u) / 16u * 16u;
+    const unsigned bmax = std::min(kQgMaxBlocks, std::max(4u, 16384u / (spad * spad)));
+    w.tiles_per = (tiles + bmax - 1) / bmax;
+    w.blocks = (tiles + w.tiles_per - 1) / w.tiles_per;
+  }
+  return w;
+}
+
+// the accumulator blocks a wave of k_qgradient_mfma holds -> fn(Int<NACC>)
+template <class F>
+static void with_nacc(unsigned per_wave, F &&fn)
+{
+  if (per_wave <= 1)
+    fn(Int<1>());
+  else if (per_wave <= 2)
+    fn(Int<2>());
+  else if (per_wave <= 4)
+    fn(Int<4>());
+  else
+    fn(Int<8>());
+}
+
+extern "C" int pllgpu_qmatrix_gradient(pllgpu_ctx_t *c, const pllgpu_branch_t *branches, unsigned count, const unsigned *params_indices,
+                                       double *host_d_q, double *host_d_root)
+{
+  CHECK_CTX_KEEP(c);
+  const pllgpu_geometry_t &g = c->geo;
+  const unsigned S = g.states, SS = S * S, R = g.rate_cats;
+  c->last_launches = 0;
+  if (!count)
+  {
+    // sums over no branch
+    if (host_d_q) std::fill(host_d_q, host_d_q + (size_t)g.rate_matrices * SS, 0.0);
+    if (host_d_root) std::fill(host_d_root, host_d_root + (size_t)g.rate_matrices * S, 0.0);
+    return 0;
+  }
+  static const char noun[] = "rate-matrix gradient";
+  DevEdge e;
+  DevDiag dg;
+  if (int rc = branch_call_begin(c, branches, count, params_indices, host_d_q != nullptr, noun, e, dg)) return rc;
+
+  // the used rate matrices in ascending order, and each category's place among them
+  QGeo q;
+  memset(&q, 0, sizeof q);
+  std::vector<unsigned> used;
+  for (unsigned m = 0; m < g.rate_matrices; ++m)
+    for (unsigned k = 0; k < R; ++k)
+      if (params_indices[k] == m)
+      {
+        q.kfirst[used.size()] = (unsigned char)k;
+        used.push_back(m);
+        break;
+      }
+  for (unsigned k = 0; k < R; ++k) q.mslot[k] = (unsigned char)(std::find(used.begin(), used.end(), params_indices[k]) - used.begin());
+  q.S = S;
+  q.SP = g.states_padded;
+  q.SPT = c->gg.SPT;
+  q.R = R;
+  q.Spad = (S + 15u) / 16u * 16u;
+  q.nm = (unsigned)used.size();
+  const unsigned half = q.nm * SS;
+  q.slot = host_d_root ? 2u * half : half;
+  const unsigned nblk = q.Spad / 16u, per_wave = (R * nblk * nblk + 3u) / 4u;
+  const size_t lds = qg_lds_doubles(S, R) * sizeof(double);
+  if (!c->dna_fast && (lds > kQgLdsMax || per_wave > 8u))
+    return fail(PLLGPU_EUNSUPPORTED, "%s: %u states x %u rate categories need %zu bytes of LDS per workgroup", noun, S, R, lds);
+
+  const TileWalk w = qgradient_walk(c);
+  const unsigned per_launch = batch_items(count, kBranchMax, q.slot, w.blocks);
+  // results: W [slot], then d_q [nm][S][S] and d_root [nm][S]
+  const size_t results = (size_t)q.slot + half + (size_t)q.nm * S;
+  if (int rc = batch_scratch(c, e, (size_t)q.slot * per_launch * w.blocks, 0, results, (size_t)per_launch * sizeof(BranchDesc))) return rc;
+  double *const W = c->ins_results.p, *const dq = W + q.slot, *const droot = dq + half;
+  const double *m1 = c->pmat.p + (size_t)g.prob_matrices * c->pm_stride, *m2 = m1 + c->pm_stride;
+  for (unsigned first = 0; first < count; first += per_launch)
+  {
+    const unsigned n = std::min(per_launch, count - first);
+    if (int rc = stage_up<BranchDesc>(c, c->ins_cands.p, n, [&](BranchDesc &d, unsigned i) {
+          if (int rc2 = branch_desc(c, branches[first + i], d)) return rc2;
+          d.pad_ = branches[first + i].child_is_tip ? 1.0 : 0.0; // the left end is the child: H arrives transposed
+          return 0;
+        }))
+      return rc;
+    const BranchDesc *db = reinterpret_cast<const BranchDesc *>(c->ins_cands.p);
+    const unsigned root_first = host_d_root && first == 0 ? 1u : 0u;
+    if (c->dna_fast)
+      hipLaunchKernelGGL(k_qgradient_dna, dim3(w.blocks, n), dim3(256), 0, c->stream, e, dg, q, db, m1, m2, c->ins_partials.p, w.tiles_per, root_first);
+    else
+    {
+      const unsigned long long *tm = tipmap_ptr(c);
+      with_ich(c->ich, [&](auto ICH) {
+        with_nacc(per_wave, [&](auto NACC) {
+          raise_lds_limit(reinterpret_cast<const void *>(&k_qgradient_mfma<ICH(), NACC()>), c->device, lds);
+          hipLaunchKernelGGL((k_qgradient_mfma<ICH(), NACC()>), dim3(w.blocks, n), dim3(256), lds, c->stream, e, dg, q, db, m1, m2, c->gg, tm,
+                             c->ins_partials.p, w.tiles_per, root_first);
+        });
+      });
+    }
+    if (int rc = launched(c)) return rc;
+    const unsigned vblocks = (q.slot + 255u) / 256u;
+    hipLaunchKernelGGL(k_qgradient_slots, dim3(vblocks, n), dim3(256), 0, c->stream, c->ins_partials.p, q.slot, half, w.blocks, root_first);
+    if (int rc = launched(c)) return rc;
+    hipLaunchKernelGGL(k_qgradient_branches, dim3(vblocks), dim3(256), 0, c->stream, c->ins_partials.p, W, q.slot, half, w.blocks, n,
+                       first == 0 ? 1u : 0u);
+    if (int rc = launched(c)) return rc;
+  }
+  hipLaunchKernelGGL(k_qgradient_transform, dim3(q.nm), dim3(256), (size_t)SS * sizeof(double), c->stream, W, m1, m2, c->freqs.p, q, dg,
+                     host_d_root ? 1u : 0u, dq, droot);
+  if (int rc = launched(c)) return rc;
+  // one copy back, one wait; the caller's arrays are written last: zeros for a rate matrix that no category uses
+  std::vector<double> rows(results);
+  if (int rc = results_down(c, rows.data(), rows.size())) return rc;
+  std::fill(host_d_q, host_d_q + (size_t)g.rate_matrices * SS, 0.0);
+  if (host_d_root) std::fill(host_d_root, host_d_root + (size_t)g.rate_matrices * S, 0.0);
+  for (unsigned ms = 0; ms < q.nm; ++ms)
+  {
+    memcpy(host_d_q + (size_t)used[ms] * SS, rows.data() + q.slot + (size_t)ms * SS, (size_t)SS * sizeof(double));
+    if (host_d_root) memcpy(host_d_root + (size_t)used[ms] * S, rows.data() + q.slot + half + (size_t)ms * S, (size_t)S * sizeof(double));
+  }
   return 0;
 }
 

@@ -396,7 +396,8 @@ int pll_gpu_optimize_branch_length(pll_partition_t *p, int parent_scaler_index, 
 
 /* pll_gpu_branch_derivatives (include/pll_amd.h): d_f and dd_f of `count` branches in one call,
  * without a table (csrc/hip/kernels_gradient.h); pll_gpu_branch_category_derivatives and pll_gpu_rate_gradient (section
- * 5.13): the same call keeping each rate category's share and contracting it. branch_call is the body of all three:
+ * 5.13): the same call keeping each rate category's share and contracting it; pll_gpu_qmatrix_gradient (section 5.14): the
+ * outer product where those keep the element-wise one. branch_call is the body of all four:
  * validation of the whole list before anything is flushed or launched, which ends the device reads as tip codes, the
  * flushes (model, the two contraction matrices, every named CLV and scaler once). The refusals, the once-per-call
  * bookkeeping of the flushes and the error convention are batch.c's, shared with the other batched calls. */
@@ -405,6 +406,8 @@ typedef struct branch_outputs
   double *d_f, *dd_f;                /* every entry */
   double *d_cat, *d_rates, *d_scale; /* the per-category entries; d_rates / d_scale: pll_gpu_rate_gradient */
   int per_category;                  /* 0: pll_gpu_branch_derivatives, whose d_f is mandatory */
+  double *d_q, *d_root;              /* pll_gpu_qmatrix_gradient (qmatrix != 0): d_q is mandatory */
+  int qmatrix;
 } branch_outputs_t;
 
 static int branch_call(const char *who, pll_partition_t *p, const pll_gpu_branch_t *branches, unsigned int count,
@@ -422,6 +425,8 @@ static int branch_call(const char *who, pll_partition_t *p, const pll_gpu_branch
     if (out->d_rates)
       for (k = 0; k < p->rate_cats; ++k) out->d_rates[k] = 0.0;
     if (out->d_scale) *out->d_scale = 0.0;
+    if (out->d_q) memset(out->d_q, 0, sizeof(double) * p->rate_matrices * p->states * p->states);
+    if (out->d_root) memset(out->d_root, 0, sizeof(double) * p->rate_matrices * p->states);
     return PLL_SUCCESS;
   }
   if (out->per_category && !out->d_f && !out->dd_f && !out->d_cat && !out->d_rates && !out->d_scale)
@@ -429,9 +434,11 @@ static int branch_call(const char *who, pll_partition_t *p, const pll_gpu_branch
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: every output is NULL", who);
     return pll_batch_fail(who);
   }
-  if (!branches || !params_indices || (!out->per_category && !out->d_f))
+  if (!branches || !params_indices || (out->qmatrix ? !out->d_q : (!out->per_category && !out->d_f)))
   {
-    pll_set_error(PLL_ERROR_PARAM_INVALID, out->per_category ? "%s: branches or params_indices is NULL" : "%s: branches, params_indices or d_f is NULL",
+    pll_set_error(PLL_ERROR_PARAM_INVALID, out->qmatrix        ? "%s: branches, params_indices or d_q is NULL"
+                                           : out->per_category ? "%s: branches or params_indices is NULL"
+                                                               : "%s: branches, params_indices or d_f is NULL",
                   who);
     return pll_batch_fail(who);
   }
@@ -474,6 +481,22 @@ static int branch_call(const char *who, pll_partition_t *p, const pll_gpu_branch
         pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: category rate %u is %g; d_rates needs rates that are > 0 and finite", who, k, p->rates[k]);
         return pll_batch_fail(who);
       }
+  if (out->d_root)
+    for (k = 0; k < p->rate_cats; ++k)
+      if (p->prop_invar[params_indices[k]] > 0)
+      {
+        /* the invariant term pinv pi[inv] of a site depends on pi: a per-state sum over the invariant sites, not formed */
+        pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: the frequency part (d_root / d_freqs) with prop_invar %g of rate matrix %u > 0", who,
+                      p->prop_invar[params_indices[k]], params_indices[k]);
+        return pll_batch_fail(who);
+      }
+  if (out->qmatrix && !(p->states == 4 && p->rate_cats == 4) &&
+      PLLGPU_QGRADIENT_LDS_BYTES((unsigned long)p->states, (unsigned long)p->rate_cats) > PLLGPU_QGRADIENT_LDS_MAX)
+  {
+    pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: %u states x %u rate categories need %lu bytes of LDS per workgroup, more than %lu", who, p->states,
+                  p->rate_cats, PLLGPU_QGRADIENT_LDS_BYTES((unsigned long)p->states, (unsigned long)p->rate_cats), PLLGPU_QGRADIENT_LDS_MAX);
+    return pll_batch_fail(who);
+  }
   if (!pll_batch_device(who, p, &x)) return PLL_FAILURE;
 
   /* the reference reads whatever eigensystem is stored; an invalid one is computed here, as pll_update_sumtable does */
@@ -506,7 +529,8 @@ static int branch_call(const char *who, pll_partition_t *p, const pll_gpu_branch
     free(dev);
     return pll_batch_fail(who);
   }
-  const int rc = out->per_category ? pllgpu_branch_category_derivatives(x->ctx, dev, count, params_indices, out->d_cat, out->d_f, out->dd_f,
+  const int rc = out->qmatrix      ? pllgpu_qmatrix_gradient(x->ctx, dev, count, params_indices, out->d_q, out->d_root)
+                 : out->per_category ? pllgpu_branch_category_derivatives(x->ctx, dev, count, params_indices, out->d_cat, out->d_f, out->dd_f,
                                                                         out->d_rates, out->d_scale)
                                    : pllgpu_branch_derivatives(x->ctx, dev, count, params_indices, out->d_f, out->dd_f);
   free(dev);
@@ -521,20 +545,181 @@ static int branch_call(const char *who, pll_partition_t *p, const pll_gpu_branch
 int pll_gpu_branch_derivatives(pll_partition_t *p, const pll_gpu_branch_t *branches, unsigned int count,
                                const unsigned int *params_indices, double *d_f, double *dd_f)
 {
-  const branch_outputs_t out = {d_f, dd_f, NULL, NULL, NULL, 0};
+  const branch_outputs_t out = {d_f, dd_f, NULL, NULL, NULL, 0, NULL, NULL, 0};
   return branch_call("pll_gpu_branch_derivatives", p, branches, count, params_indices, &out);
 }
 
 int pll_gpu_branch_category_derivatives(pll_partition_t *p, const pll_gpu_branch_t *branches, unsigned int count,
                                         const unsigned int *params_indices, double *d_cat, double *d_f, double *dd_f)
 {
-  const branch_outputs_t out = {d_f, dd_f, d_cat, NULL, NULL, 1};
+  const branch_outputs_t out = {d_f, dd_f, d_cat, NULL, NULL, 1, NULL, NULL, 0};
   return branch_call("pll_gpu_branch_category_derivatives", p, branches, count, params_indices, &out);
 }
 
 int pll_gpu_rate_gradient(pll_partition_t *p, const pll_gpu_branch_t *branches, unsigned int count, const unsigned int *params_indices,
                           double *d_rates, double *d_scale, double *d_cat, double *d_f)
 {
-  const branch_outputs_t out = {d_f, NULL, d_cat, d_rates, d_scale, 1};
+  const branch_outputs_t out = {d_f, NULL, d_cat, d_rates, d_scale, 1, NULL, NULL, 0};
   return branch_call("pll_gpu_rate_gradient", p, branches, count, params_indices, &out);
+}
+
+/* ---- the model gradient (include/pll_amd.h; csrc/hip/kernels_qgradient.h) ---------------- */
+int pll_gpu_qmatrix_gradient(pll_partition_t *p, const pll_gpu_branch_t *branches, unsigned int count, const unsigned int *params_indices,
+                             double *d_q, double *d_root)
+{
+  const branch_outputs_t out = {NULL, NULL, NULL, NULL, NULL, 0, d_q, d_root, 1};
+  return branch_call("pll_gpu_qmatrix_gradient", p, branches, count, params_indices, &out);
+}
+
+/* what the chain rule needs of rate matrix m: every frequency above PLL_EIGEN_MINFREQ (the reference eliminates the other
+ * states from the eigensystem) and a positive last exchangeability (everything is relative to it) */
+static int chain_rule_ok(const char *who, const pll_partition_t *p, unsigned int m)
+{
+  const unsigned int s = p->states, np = s * (s - 1) / 2;
+  unsigned int i;
+  for (i = 0; i < s; ++i)
+    if (!(p->frequencies[m][i] > 1e-6 /* PLL_EIGEN_MINFREQ */))
+    {
+      pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: frequency %u of set %u is %g, not above PLL_EIGEN_MINFREQ", who, i, m, p->frequencies[m][i]);
+      return pll_batch_fail(who);
+    }
+  if (!(p->subst_params[m][np - 1] > 0))
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: the last substitution parameter of set %u is %g, not > 0", who, m, p->subst_params[m][np - 1]);
+    return pll_batch_fail(who);
+  }
+  return PLL_SUCCESS;
+}
+
+/* With D_xy = d_q[x][y] - d_q[x][x] (an off-diagonal entry of a moves its row's diagonal the other way), Q = a / mean and
+ * E = sum_{x != y} D_xy Q_xy:   dF = (1 / mean) sum_{x != y} D_xy da_xy - (E / mean) dmean.
+ *   a_xy = s_xy pi_y, mean = 2 sum_{x<y} s_xy pi_x pi_y:
+ *   dF/ds_xy  = (D_xy pi_y + D_yx pi_x - 2 E pi_x pi_y) / mean                         (x < y)
+ *   dF/dpi_z  = (sum_{x != z} D_xz s_xz - 2 E sum_{x != z} s_xz pi_x) / mean + d_root[z]
+ * and s_p = subst_params[p] / subst_params[last]. O(states^2) in all. */
+int pll_gpu_subst_gradient_from_dq(const pll_partition_t *p, unsigned int params_index, const double *d_q_m, const double *d_root_m,
+                                   double *d_subst, double *d_freqs)
+{
+  static const char who[] = "pll_gpu_subst_gradient_from_dq";
+  unsigned int x, y, k;
+  if (!p || !d_q_m || (!d_subst && !d_freqs))
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition or d_q is NULL, or no output is asked for", who);
+    return pll_batch_fail(who);
+  }
+  if (params_index >= p->rate_matrices)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: params_index %u out of range", who, params_index);
+    return pll_batch_fail(who);
+  }
+  if (!chain_rule_ok(who, p, params_index)) return PLL_FAILURE;
+  const unsigned int s = p->states, np = s * (s - 1) / 2;
+  const double *pi = p->frequencies[params_index], *sub = p->subst_params[params_index];
+  const double last = sub[np - 1];
+  double *ds = (double *)malloc(sizeof(double) * (np + s));
+  if (!ds)
+  {
+    pll_set_error(PLL_ERROR_MEM_ALLOC, "Unable to allocate enough memory.");
+    return pll_batch_fail(who);
+  }
+  double *col = ds + np; /* per state z: sum_{x != z} D_xz s_xz - 2 E sum_{x != z} s_xz pi_x, built in two passes */
+  double mean = 0.0, e_mean = 0.0; /* e_mean = E mean = sum_{x != y} D_xy a_xy / mean */
+  for (x = 0, k = 0; x < s; ++x)
+    for (y = x + 1; y < s; ++y, ++k)
+    {
+      const double sxy = sub[k] / last;
+      const double dxy = d_q_m[x * s + y] - d_q_m[x * s + x], dyx = d_q_m[y * s + x] - d_q_m[y * s + y];
+      mean += 2.0 * sxy * pi[x] * pi[y];
+      e_mean += dxy * sxy * pi[y] + dyx * sxy * pi[x];
+    }
+  const double e = e_mean / mean; /* = E: e_mean carries a, not Q = a / mean */
+  for (x = 0; x < s; ++x) col[x] = 0.0;
+  for (x = 0, k = 0; x < s; ++x)
+    for (y = x + 1; y < s; ++y, ++k)
+    {
+      const double sxy = sub[k] / last;
+      const double dxy = d_q_m[x * s + y] - d_q_m[x * s + x], dyx = d_q_m[y * s + x] - d_q_m[y * s + y];
+      ds[k] = (dxy * pi[y] + dyx * pi[x] - 2.0 * e * pi[x] * pi[y]) / mean;
+      col[y] += dxy * sxy - 2.0 * e * sxy * pi[x];
+      col[x] += dyx * sxy - 2.0 * e * sxy * pi[y];
+    }
+  if (d_subst)
+  {
+    /* s_p = subst_params[p] / last for p < last; the last entry moves every other s_p */
+    double tail = 0.0;
+    for (k = 0; k + 1 < np; ++k)
+    {
+      d_subst[k] = ds[k] / last;
+      tail -= sub[k] * d_subst[k];
+    }
+    d_subst[np - 1] = tail / last;
+  }
+  if (d_freqs)
+    for (x = 0; x < s; ++x) d_freqs[x] = col[x] / mean + (d_root_m ? d_root_m[x] : 0.0);
+  free(ds);
+  return PLL_SUCCESS;
+}
+
+int pll_gpu_subst_gradient(pll_partition_t *p, const pll_gpu_branch_t *branches, unsigned int count, const unsigned int *params_indices,
+                           double *d_subst, double *d_freqs)
+{
+  static const char who[] = "pll_gpu_subst_gradient";
+  unsigned int k, m;
+  if (!p)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition is NULL", who);
+    return pll_batch_fail(who);
+  }
+  const unsigned int s = p->states, np = s * (s - 1) / 2;
+  if (!count)
+  {
+    /* sums over no branch */
+    if (d_subst) memset(d_subst, 0, sizeof(double) * p->rate_matrices * np);
+    if (d_freqs) memset(d_freqs, 0, sizeof(double) * p->rate_matrices * s);
+    return PLL_SUCCESS;
+  }
+  if (!d_subst && !d_freqs)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: every output is NULL", who);
+    return pll_batch_fail(who);
+  }
+  /* what the chain rule asks of the used sets, before anything else is looked at (a params_indices that cannot be read
+   * for this is reported by the list checks below) */
+  if (params_indices)
+  {
+    int in_range = 1;
+    for (k = 0; k < p->rate_cats; ++k) in_range &= (params_indices[k] < p->rate_matrices);
+    for (k = 0; in_range && k < p->rate_cats; ++k)
+      if (!chain_rule_ok(who, p, params_indices[k])) return PLL_FAILURE;
+  }
+  double *d_q = (double *)malloc(sizeof(double) * p->rate_matrices * (s * s + s + np + s));
+  if (!d_q)
+  {
+    pll_set_error(PLL_ERROR_MEM_ALLOC, "Unable to allocate enough memory.");
+    return pll_batch_fail(who);
+  }
+  double *d_root = d_q + (size_t)p->rate_matrices * s * s, *sub = d_root + (size_t)p->rate_matrices * s, *fr = sub + (size_t)p->rate_matrices * np;
+  const branch_outputs_t out = {NULL, NULL, NULL, NULL, NULL, 0, d_q, d_freqs ? d_root : NULL, 1};
+  /* the list checks, the refusals and the device call; then what the chain rule asks of the used sets - everything before
+   * the caller's arrays are touched */
+  int ok = branch_call(who, p, branches, count, params_indices, &out);
+  for (m = 0; ok && m < p->rate_matrices; ++m)
+  {
+    int used = 0;
+    for (k = 0; k < p->rate_cats; ++k) used |= (params_indices[k] == m);
+    if (!used)
+    {
+      memset(sub + (size_t)m * np, 0, sizeof(double) * np);
+      memset(fr + (size_t)m * s, 0, sizeof(double) * s);
+      continue;
+    }
+    ok = pll_gpu_subst_gradient_from_dq(p, m, d_q + (size_t)m * s * s, d_freqs ? d_root + (size_t)m * s : NULL, sub + (size_t)m * np, fr + (size_t)m * s);
+  }
+  if (ok)
+  {
+    if (d_subst) memcpy(d_subst, sub, sizeof(double) * p->rate_matrices * np);
+    if (d_freqs) memcpy(d_freqs, fr, sizeof(double) * p->rate_matrices * s);
+  }
+  free(d_q);
+  return ok ? PLL_SUCCESS : PLL_FAILURE;
 }

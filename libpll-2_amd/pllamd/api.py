@@ -308,6 +308,9 @@ _GPU_PROTOS = {
         C.c_int, [PartitionP, C.POINTER(Branch), C.c_uint, c_uint_p, c_double_p, c_double_p, c_double_p]),
     "pll_gpu_rate_gradient": (
         C.c_int, [PartitionP, C.POINTER(Branch), C.c_uint, c_uint_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "pll_gpu_qmatrix_gradient": (C.c_int, [PartitionP, C.POINTER(Branch), C.c_uint, c_uint_p, c_double_p, c_double_p]),
+    "pll_gpu_subst_gradient_from_dq": (C.c_int, [PartitionP, C.c_uint, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "pll_gpu_subst_gradient": (C.c_int, [PartitionP, C.POINTER(Branch), C.c_uint, c_uint_p, c_double_p, c_double_p]),
     "pll_gpu_edge_category_posteriors": (
         C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "pll_gpu_category_weights_em": (

@@ -267,6 +267,35 @@ def rate_gradient(lib, partition, rows, params_indices, want_rates=True, want_sc
     return {"d_rates": rates, "d_scale": float(scale[0]), "d_cat": cat, "d_f": d}
 
 
+def qmatrix_gradient(lib, partition, rows, params_indices, want_root=True):
+    """pll_gpu_qmatrix_gradient: rows as branch_derivatives; (d_q [rate_matrices, states, states], d_root [rate_matrices,
+    states]) of -lnL from one call - d_root stays NaN with want_root=False (NULL). libpll_amd.so only."""
+    rows = list(rows)
+    part = partition.contents
+    M, S = int(part.rate_matrices), int(part.states)
+    d_q, d_root = np.full((M, S, S), np.nan), np.full((M, S), np.nan)
+    pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+    if not lib.pll_gpu_qmatrix_gradient(partition, api.make_branches(rows), len(rows), api.uptr(pi), api.dptr(d_q),
+                                        api.dptr(d_root) if want_root else None):
+        raise RuntimeError(f"pll_gpu_qmatrix_gradient: [{lib.errno()}] {lib.errmsg()}")
+    return d_q, d_root
+
+
+def subst_gradient(lib, partition, rows, params_indices, want_subst=True, want_freqs=True):
+    """pll_gpu_subst_gradient: rows as branch_derivatives; (d_subst [rate_matrices, states (states - 1) / 2], d_freqs
+    [rate_matrices, states]) of -lnL - NaN where not asked for (NULL). Gradients only where the rows name every branch of the
+    tree once, each end oriented towards its branch. libpll_amd.so only."""
+    rows = list(rows)
+    part = partition.contents
+    M, S = int(part.rate_matrices), int(part.states)
+    d_subst, d_freqs = np.full((M, S * (S - 1) // 2), np.nan), np.full((M, S), np.nan)
+    pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+    if not lib.pll_gpu_subst_gradient(partition, api.make_branches(rows), len(rows), api.uptr(pi), api.dptr(d_subst) if want_subst else None,
+                                      api.dptr(d_freqs) if want_freqs else None):
+        raise RuntimeError(f"pll_gpu_subst_gradient: [{lib.errno()}] {lib.errmsg()}")
+    return d_subst, d_freqs
+
+
 def branch_derivatives_per_edge(lib, partition, rows, params_indices, sumtable=None):
     """the same values the way every libpll offers them: per row pll_update_sumtable into one caller-owned table, then
     pll_compute_likelihood_derivatives at the row's length. The table (sites * rate_cats * states_padded doubles, 64-byte
