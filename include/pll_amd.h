@@ -1278,7 +1278,9 @@ int pll_gpu_last_update_replayed(const pll_partition_t *partition);
  * the producers of its children does not read those children back) - bench.py's roofline numerator */
 double pll_gpu_last_algorithmic_bytes(const pll_partition_t *partition);
 /* CLVs (with their scalers) that the last step computed and has not stored on the device: the 32 tip x tip parents of a
- * balanced 64-taxon DNA traversal evaluated together with its root edge as one launch (PLL_AMD_LAZY_CHERRIES=0: always 0).
+ * balanced 64-taxon DNA traversal evaluated together with its root edge as one launch (PLL_AMD_LAZY_CHERRIES=0: always 0) -
+ * or, from the second step on of a loop that reads no CLV between its steps, all 56 CLVs of its eight 8-tip subtrees, levels
+ * 1 to 3 (PLL_AMD_LAZY_SUBTREES=0: never more than 32; unset: for 20 000 entries and more).
  * Every call that reads one of them, overwrites it or changes its tip codes stores them first, in one launch; the same
  * traversal again simply recomputes them, and a change of a matrix they read leaves them pending (they keep the old one).
  * Nothing a caller has to do - the number says why a read launched something */

@@ -47,6 +47,10 @@ struct ChainPlan
   double tree_bytes = 0.0; // of that one launch: codes in, every CLV and scaler it stores out, nothing read back
   // the list's 32 tip x tip ops as planned: what the lean form of the launch leaves unstored (pllgpu_ctx::pending)
   std::vector<pllgpu_op_t> cherries;
+  // ... and the 56 ops of the eight groups, what its deep form leaves unstored (kernels_dna.h: TreeStores::TopsOnly): group
+  // after group in kernel order - aa, ab, a, ba, bb, b, p - so that a seven-op group launch can be built from them alone
+  std::vector<pllgpu_op_t> subtrees;
+  double tree_bytes_deep = 0.0; // of the launch in its deep form: codes in, levels 4 and 5 out
 };
 
 static void drop_chain_plan(pllgpu_ctx *c)
@@ -108,7 +112,7 @@ static int launch_chain_plan(pllgpu_ctx *c, const ChainPlan &pl, bool hold)
   {
     c->chain_held = c->tree_held = true;
     c->last_launches = 0;
-    c->last_bytes = pl.tree_bytes;
+    c->last_bytes = c->tree_deep ? pl.tree_bytes_deep : pl.tree_bytes; // (decided by pllgpu_update_partials for this step)
     return 0;
   }
   for (const CC16Launch &l : pl.cc16)
@@ -364,6 +368,17 @@ static bool use_tree(const pllgpu_ctx *c, unsigned entries, unsigned count)
   return entries >= kTreeMinEntries;
 }
 
+// The deep form of that launch (nothing of the eight groups stored, kernels_dna.h: TreeStores::TopsOnly) for a plan whose
+// own list came again while what its last launch left unstored was still pending: a loop that reads no CLV between its
+// steps. By the tree launch's own size rule unless PLL_AMD_LAZY_SUBTREES says 0 / 1 - a tree launch forced below the
+// threshold stays in its lean form (profiles/dna_tree_lazy_subtrees.md).
+static bool use_deep_tree(const pllgpu_ctx *c, unsigned entries)
+{
+  if (!c->lazy_cherries) return false;
+  if (c->lazy_subtrees >= 0) return c->lazy_subtrees != 0;
+  return entries >= kTreeMinEntries;
+}
+
 // what a plan's descriptors are built from: the list, its partition, every chain op resolved
 struct ChainBuild
 {
@@ -521,11 +536,13 @@ static void plan_tree(const pllgpu_ctx *c, const ChainBuild &b, unsigned count, 
   if (pl->cc.size() != 1u || pl->cc[0].n != 8u || pl->cc[0].lk != CK_FCC || !pl->cc16.empty()) return;
   if (pl->held_from != 0 || pl->stages.empty()) return; // both chains wait for the evaluation
   std::vector<int> group_of(count, -1);
+  std::vector<char> in_group(count, 0); // the two inner x inner ops under a group parent
   for (size_t gi = 0; gi < 8u; ++gi)
   {
     const FusedGroup &g = part.groups[gi];
     if (g.lk != CK_FCC || g.rk != CK_FCC || g.absorbed) return;
     group_of[g.p] = (int)gi; // (build_cc_launches kept the list's order: pack.g[gi])
+    in_group[g.a] = in_group[g.b] = 1;
   }
   unsigned seen = 0;
   for (unsigned k = 0; k < 2u; ++k)
@@ -555,11 +572,18 @@ static void plan_tree(const pllgpu_ctx *c, const ChainBuild &b, unsigned count, 
   for (unsigned i = 0; i < count; ++i)
     if ((ops[i].flags & PLLGPU_OP_LEFT_TIP) && (ops[i].flags & PLLGPU_OP_RIGHT_TIP)) pl->cherries.push_back(ops[i]);
   if (pl->cherries.size() != 32u) return; // (eight complete groups: cannot happen)
+  for (size_t gi = 0; gi < 8u; ++gi)
+  {
+    const FusedGroup &g = part.groups[gi];
+    for (int i : {g.aa, g.ab, g.a, g.ba, g.bb, g.b, (int)g.p}) pl->subtrees.push_back(ops[i]);
+  }
   for (unsigned i = 0; i < count; ++i)
   {
     const bool lt = (ops[i].flags & PLLGPU_OP_LEFT_TIP) != 0, rt = (ops[i].flags & PLLGPU_OP_RIGHT_TIP) != 0;
     // the lean form reads a cherry's two codes and stores nothing of it
     pl->tree_bytes += (c->lazy_cherries && lt && rt) ? 2.0 * ops[i].parent_entries : op_traffic(c, ops[i], lt, rt);
+    // the deep form stores the ops above the groups only
+    pl->tree_bytes_deep += (lt && rt) ? 2.0 * ops[i].parent_entries : group_of[i] >= 0 || in_group[i] ? 0.0 : op_traffic(c, ops[i], lt, rt);
   }
   pl->tree = true;
 }

@@ -934,9 +934,19 @@ __device__ __forceinline__ void dna_cherry(const TOp &t, size_t off, unsigned n,
   if (STORE) dna_store<true>(t.parent, t.pscaler, off, n, valid, mode, v, sc);
 }
 
-// one child of the group parent: CK_INNER / CK_TIP from HBM, or CK_FCC formed here (STORE_CHERRIES = false: the two
-// tip x tip parents under it are not stored, the inner x inner op over them is)
-template <int KIND, bool STORE_CHERRIES = true>
+// what a launch over complete 8-tip subtrees stores of them: everything; everything but the tip x tip parents (the lean
+// form); or nothing at all - the group parents exist in registers and LDS only (k_edge_dna_tree's deep form, which stores
+// the ops ABOVE the groups). One body, the same arithmetic: whatever is stored has the same bits in every form.
+enum class TreeStores
+{
+  All,
+  NoCherries,
+  TopsOnly
+};
+
+// one child of the group parent: CK_INNER / CK_TIP from HBM, or CK_FCC formed here (ST != All: the two tip x tip parents
+// under it are not stored; TopsOnly: neither is the inner x inner op over them)
+template <int KIND, TreeStores ST = TreeStores::All>
 __device__ __forceinline__ void dna_cc_child(const FOp &pop, bool left_side, const FOp &cop, const TOp &x, const TOp &y, size_t off,
                                              unsigned n, bool valid, int scale_mode, double (&v)[4][4], uint4 &sc)
 {
@@ -945,10 +955,10 @@ __device__ __forceinline__ void dna_cc_child(const FOp &pop, bool left_side, con
     double vx[4][4], vy[4][4];
     uint4 scx, scy;
     int mode;
-    dna_cherry<STORE_CHERRIES>(x, off, n, valid, scale_mode, vx, scx);
-    dna_cherry<STORE_CHERRIES>(y, off, n, valid, scale_mode, vy, scy);
+    dna_cherry<ST == TreeStores::All>(x, off, n, valid, scale_mode, vx, scx);
+    dna_cherry<ST == TreeStores::All>(y, off, n, valid, scale_mode, vy, scy);
     dna_combine(cop, scale_mode, vx, scx, vy, scy, v, sc, mode);
-    dna_store<true>(cop.parent, cop.pscaler, off, n, valid, mode, v, sc);
+    if (ST != TreeStores::TopsOnly) dna_store<true>(cop.parent, cop.pscaler, off, n, valid, mode, v, sc);
   }
   else
   {
@@ -972,8 +982,9 @@ __global__ __launch_bounds__(256) void k_partials_dna_cc(const CCPack pack, unsi
     double va[4][4], vb[4][4], v[4][4];
     uint4 sca, scb, sc;
     int mode;
-    dna_cc_child<LK, STORE_CHERRIES>(g.p, true, g.a, g.aa, g.ab, w.off, w.n, w.valid, scale_mode, va, sca);
-    dna_cc_child<RK, STORE_CHERRIES>(g.p, false, g.b, g.ba, g.bb, w.off, w.n, w.valid, scale_mode, vb, scb);
+    constexpr TreeStores ST = STORE_CHERRIES ? TreeStores::All : TreeStores::NoCherries; // (two forms: its chains read the group parents from HBM)
+    dna_cc_child<LK, ST>(g.p, true, g.a, g.aa, g.ab, w.off, w.n, w.valid, scale_mode, va, sca);
+    dna_cc_child<RK, ST>(g.p, false, g.b, g.ba, g.bb, w.off, w.n, w.valid, scale_mode, vb, scb);
     dna_combine(g.p, scale_mode, va, sca, vb, scb, v, sc, mode);
     dna_store_parent(stream_parent != 0, g.p.parent, g.p.pscaler, w.off, w.n, w.valid, mode, v, sc);
   }
@@ -1948,21 +1959,21 @@ __device__ __forceinline__ void dna_tree_get(const double (*xv)[64], const uint4
 // of 128; so it takes 115 (tools/kernel_resources.py) - four waves per SIMD, two workgroups per CU - without one. That figure
 // is how this compiler happens to schedule the code: check it again after a change of toolchain. The results do not depend
 // on it. The top stays in v / sc.
-template <bool STORE_CHERRIES>
+template <TreeStores ST>
 __device__ __forceinline__ void dna_cc8_parked(const CCGroup &g, double (*xv)[64], uint4 *xs, unsigned lane, size_t off, unsigned n, bool valid,
                                                int scale_mode, double (&v)[4][4], uint4 &sc)
 {
   double vb[4][4], u[4][4];
   uint4 scb, scu;
   int mode;
-  dna_cc_child<CK_FCC, STORE_CHERRIES>(g.p, true, g.a, g.aa, g.ab, off, n, valid, scale_mode, v, sc);
+  dna_cc_child<CK_FCC, ST>(g.p, true, g.a, g.aa, g.ab, off, n, valid, scale_mode, v, sc);
   dna_tree_put(xv, xs, lane, v, sc);
   asm volatile("" ::: "memory"); // (the reload below is not folded into the store above: in practice the values leave the registers)
-  dna_cc_child<CK_FCC, STORE_CHERRIES>(g.p, false, g.b, g.ba, g.bb, off, n, valid, scale_mode, vb, scb);
+  dna_cc_child<CK_FCC, ST>(g.p, false, g.b, g.ba, g.bb, off, n, valid, scale_mode, vb, scb);
   asm volatile("" ::: "memory");
   dna_tree_get(xv, xs, lane, v, sc);
   dna_combine(g.p, scale_mode, v, sc, vb, scb, u, scu, mode);
-  dna_store<true>(g.p.parent, g.p.pscaler, off, n, valid, mode, u, scu);
+  if (ST != TreeStores::TopsOnly) dna_store<true>(g.p.parent, g.p.pscaler, off, n, valid, mode, u, scu);
 #pragma unroll
   for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -1989,11 +2000,14 @@ __device__ __forceinline__ void dna_tree_up(const TOp &op, const double (*xv)[64
 
 // entries: of every CLV of the list - the sites, and behind them the per-state entries of an ascertainment-bias partition,
 // which are computed and stored like sites and enter no site likelihood (as in chain_edge_body).
-// STORE_CHERRIES = false, the lean form: the 32 tip x tip parents (g.aa, g.ab, g.ba, g.bb of every group) are formed and
+// ST = NoCherries, the lean form: the 32 tip x tip parents (g.aa, g.ab, g.ba, g.bb of every group) are formed and
 // passed up in registers as always and NOT stored - 32 of the 62 CLVs + scalers, 51 % of what the full form writes. Everything
 // from the level-2 parents upwards, the arithmetic, the exchange, the tile sums and the ticket are the same code: the same
 // bits. The context remembers the 32 ops as pending and stores them when somebody asks (pllgpu.hip: materialise_pending).
-template <bool STORE_CHERRIES>
+// ST = TopsOnly, the deep form: nothing of the eight groups is stored - 56 of the 62 ops, no store at all before the first
+// barrier; the six ops of levels 4 and 5 are stored as always (6 x 132 B per site instead of 30 x 132 B). The 56 are pending
+// in the same way, and one seven-op group launch stores them (k_partials_dna_cc<CK_FCC, CK_FCC>).
+template <TreeStores ST>
 __global__ __launch_bounds__(512) void k_edge_dna_tree(const DevEdge e, const TreePack pack, unsigned entries, int scale_mode, unsigned xcd_order)
 {
   // a slot of 9 KB per wave: 72 KB, two workgroups per CU
@@ -2013,7 +2027,7 @@ __global__ __launch_bounds__(512) void k_edge_dna_tree(const DevEdge e, const Tr
   const TreeEnd &end = pack.end[wave >> 2];
   double v[4][4];
   uint4 sc;
-  dna_cc8_parked<STORE_CHERRIES>(end.g[wave & 3u], xv[wave], xs[wave], lane, off, n, valid, scale_mode, v, sc);
+  dna_cc8_parked<ST>(end.g[wave & 3u], xv[wave], xs[wave], lane, off, n, valid, scale_mode, v, sc);
   // every barrier below is met by all waves that have not left yet; they order LDS traffic only (lds_barrier: the stores
   // to HBM stay in flight)
   // round 1, level 4: odd waves -> even waves

@@ -195,6 +195,8 @@ struct RellState
   unsigned long long total = 0, not_one = 0;
 };
 
+constexpr unsigned kMaxPending = 56; // ops a tree launch may leave unstored (pllgpu_ctx::pending): eight seven-op groups, 32 of them tip x tip
+
 struct pllgpu_ctx
 {
   unsigned long long alloc_epoch = 1; // moves whenever one of this context's device blocks is (re)allocated or freed
@@ -318,7 +320,7 @@ struct pllgpu_ctx
   struct ChainPlan *plan = nullptr; // the last chain plan, re-launched as is when the same list comes again
   bool chain_held = false;          // the plan's last stage has not been launched yet (chain tail, kernels_dna.h)
   bool tree_held = false;           // ... and neither has its stage 1: the whole plan waits (ChainPlan::tree; implies chain_held)
-  // Lazy cherries: the whole-traversal launch ran in its lean form (k_edge_dna_tree<false>) and did not store the list's 32
+  // Lazy cherries: the whole-traversal launch ran in its lean form (k_edge_dna_tree<NoCherries>) and did not store the list's 32
   // tip x tip parents. They are PENDING: a representation, not work in flight - each is a function of two tip code vectors
   // and two matrices that are on the device and have not changed since (every entry point that could read a pending CLV or
   // scaler, overwrite it or change one of its inputs stores them first: materialise_pending). Never non-empty while
@@ -326,8 +328,14 @@ struct pllgpu_ctx
   // A matrix one of them reads may change all the same (the model-parameter loop rewrites every matrix between two steps,
   // a branch-length pass the evaluated edge's): the 64 matrices of the step are copied aside first, device to device in
   // one small launch (keep_pending_matrices), and the pending ops are stored from the copies if they are stored at all.
+  // Lazy subtrees: inside a loop that reads no CLV between its steps (the plan's own list again while its ops are still
+  // pending) the launch runs in its deep form and stores nothing of the eight 8-tip groups: 56 ops pending, 112 matrices.
   bool lazy_cherries = true;          // PLL_AMD_LAZY_CHERRIES=0: the launch stores everything
-  std::vector<pllgpu_op_t> pending;   // the ops as planned: parent CLV, scaler, tip and matrix indices
+  int lazy_subtrees = -1;             // PLL_AMD_LAZY_SUBTREES: the deep form -1 by size (chain_plan.h: use_deep_tree), 0 never, 1 at any size
+  bool tree_deep = false;             // the held whole traversal, if evaluated in one launch, takes the deep form (set by every update call)
+  std::vector<pllgpu_op_t> pending;   // the ops as planned: parent CLV, scaler, tip and matrix indices - the 32 tip x tip ops,
+                                      // or the 56 group ops in group order (ChainPlan::subtrees)
+  bool pending_deep = false;          // ... the latter: stored by one seven-op group launch
   const struct ChainPlan *pending_plan = nullptr; // the plan they belong to: its own list again recomputes them all
   DevBuf<double> pending_mats;        // op i's left and right matrix as they were at the step: slots 2i, 2i + 1 ...
   bool pending_mats_kept = false;     // ... once one of them was about to change (else the ops read c->pmat)
@@ -526,6 +534,9 @@ static void derive_geometry(pllgpu_ctx *c)
   c->lazy_cherries = true;
   if (const char *v = getenv("PLL_AMD_LAZY_CHERRIES"))
     if (*v) c->lazy_cherries = *v != '0';
+  c->lazy_subtrees = -1;
+  if (const char *v = getenv("PLL_AMD_LAZY_SUBTREES"))
+    if (*v) c->lazy_subtrees = *v != '0' ? 1 : 0;
   if (const char *v = getenv("PLL_AMD_NO_FUSE_CC"))
     if (*v && *v != '0') c->fuse_cc = false;
   c->chains = c->fuse;
@@ -689,7 +700,7 @@ extern "C" pllgpu_ctx_t *pllgpu_create(const pllgpu_geometry_t *geo, int device)
   if (c->pmat.ensure(c->pm_stride * (geo->prob_matrices + 2)) || c->freqs.ensure((size_t)geo->rate_matrices * geo->states_padded) ||
       c->rate_weights.ensure(geo->rate_cats) || c->prop_invar.ensure(geo->rate_matrices) ||
       c->pattern_weights.ensure(geo->sites_alloc) || c->persite.ensure(geo->sites_alloc) ||
-      c->block_sums.ensure(4096) || c->counter.ensure(4) || (c->dna_fast && c->lazy_cherries && c->pending_mats.ensure(c->pm_stride * 64u)) || c->rep_sync.ensure((size_t)kRepOps + 1) || c->rep_changed.ensure(1))
+      c->block_sums.ensure(4096) || c->counter.ensure(4) || (c->dna_fast && c->lazy_cherries && c->pending_mats.ensure(c->pm_stride * 2u * kMaxPending)) || c->rep_sync.ensure((size_t)kRepOps + 1) || c->rep_changed.ensure(1))
   {
     pllgpu_destroy(c);
     return nullptr;
@@ -807,7 +818,7 @@ extern "C" void pllgpu_destroy(pllgpu_ctx_t *c)
 static int flush_deferred(pllgpu_ctx *c, bool keep_pending = false);
 static int matrices_change(pllgpu_ctx *c, const unsigned *indices, unsigned first, unsigned count);
 static int materialise_pending(pllgpu_ctx *c);
-static void set_pending(pllgpu_ctx *c, const struct ChainPlan *pl);
+static void set_pending(pllgpu_ctx *c, const struct ChainPlan *pl, bool deep = false);
 #define CHECK_CTX_KEEP(c)                    \
   if (!(c)) return fail(PLLGPU_EINVAL, "null context"); \
   DeviceScope device_scope_(c);              \
@@ -1824,9 +1835,10 @@ static bool held_work_reads_matrices(const pllgpu_ctx *c, const MatrixSet &ms)
   return false;
 }
 
-static void set_pending(pllgpu_ctx *c, const ChainPlan *pl)
+static void set_pending(pllgpu_ctx *c, const ChainPlan *pl, bool deep)
 {
-  c->pending = pl->cherries;
+  c->pending = deep ? pl->subtrees : pl->cherries;
+  c->pending_deep = deep;
   c->pending_plan = pl;
   c->pending_mats_kept = false;
 }
@@ -1834,6 +1846,7 @@ static void set_pending(pllgpu_ctx *c, const ChainPlan *pl)
 static void drop_pending(pllgpu_ctx *c)
 {
   c->pending.clear();
+  c->pending_deep = false;
   c->pending_plan = nullptr;
   c->pending_mats_kept = false;
 }
@@ -1846,11 +1859,11 @@ static bool clv_is_pending(const pllgpu_ctx *c, unsigned clv)
   return false;
 }
 
-// The matrices the pending ops read, as they are now, into slots of their own: one launch of 2 x 32 blocks, 32 KB for
-// 4 states x 4 rates. Once per step at the most - from then on no change of a matrix concerns what is pending.
+// The matrices the pending ops read, as they are now, into slots of their own: one launch of 2 x 32 or 2 x 56 blocks, 32
+// or 56 KB for 4 states x 4 rates. Once per step at the most - from then on no change of a matrix concerns what is pending.
 struct MatrixCopies
 {
-  unsigned short src[2 * 32];
+  unsigned short src[2 * kMaxPending];
 };
 __global__ void k_keep_matrices(const double *__restrict__ pmat, double *__restrict__ kept, MatrixCopies mc, unsigned stride)
 {
@@ -1864,7 +1877,7 @@ static int keep_pending_matrices(pllgpu_ctx *c)
   if (c->pending.empty() || c->pending_mats_kept) return 0;
   const unsigned n = (unsigned)c->pending.size();
   MatrixCopies mc;
-  if (2u * n > sizeof mc.src / sizeof mc.src[0] || c->geo.prob_matrices > 65535u) return materialise_pending(c); // (cannot happen: 32 ops)
+  if (2u * n > sizeof mc.src / sizeof mc.src[0] || c->geo.prob_matrices > 65535u) return materialise_pending(c); // (cannot happen: 32 or 56 ops)
   for (unsigned i = 0; i < n; ++i)
   {
     mc.src[2 * i] = (unsigned short)c->pending[i].left_matrix;
@@ -1897,9 +1910,47 @@ static int matrices_change(pllgpu_ctx *c, const unsigned *indices, unsigned firs
 // the matrices as they are there or as they were kept - those of the step, since nothing that changes them gets past
 // matrices_change or this. The kept plan is not touched; the counters of the last update call stay what they were, the
 // launch is counted. On an error they stay pending.
+// A deep pending set - the 56 ops of eight complete groups, seven by seven as ChainPlan::subtrees lists them - is stored by
+// the seven-op group launch in its full form (k_partials_dna_cc<CK_FCC, CK_FCC>: what the two-launch route stores), its
+// descriptors resolved again here like the others'.
+static int materialise_pending_groups(pllgpu_ctx *c)
+{
+  const size_t ngroups = c->pending.size() / 7u;
+  if (c->pending.size() != ngroups * 7u || ngroups == 0 || ngroups > (size_t)kMaxCCGroups) return fail(PLLGPU_ERUNTIME, "pending groups out of shape");
+  CCPack pack;
+  memset(&pack, 0, sizeof pack);
+  for (size_t gi = 0; gi < ngroups; ++gi)
+  {
+    CCGroup &cg = pack.g[gi];
+    TOp *tops[7] = {&cg.aa, &cg.ab, nullptr, &cg.ba, &cg.bb, nullptr, nullptr};
+    FOp *fops[7] = {nullptr, nullptr, &cg.a, nullptr, nullptr, &cg.b, &cg.p};
+    for (size_t k = 0; k < 7u; ++k)
+    {
+      const size_t i = gi * 7u + k;
+      DevOp d;
+      if (int rc = resolve_op(c, c->pending[i], d)) return rc; // (the buffers exist: the plan resolved them)
+      if (c->pending_mats_kept)
+      {
+        d.lmat = c->pending_mats.p + (2 * i) * c->pm_stride;
+        d.rmat = c->pending_mats.p + (2 * i + 1) * c->pm_stride;
+      }
+      if (tops[k])
+        to_top(d, *tops[k]);
+      else
+        to_fop(d, *fops[k]);
+    }
+  }
+  if (int rc = launch_cc(c, pack, (unsigned)ngroups, c->pending[0].parent_entries, CK_FCC, CK_FCC)) return rc;
+  ++c->last_launches;
+  if (int rc = launch_status()) return rc;
+  drop_pending(c);
+  return 0;
+}
+
 static int materialise_pending(pllgpu_ctx *c)
 {
   if (c->pending.empty()) return 0;
+  if (c->pending_deep) return materialise_pending_groups(c);
   OpPack pack;
   unsigned nops = 0, maxent = 0;
   auto launch = [&]() -> int {
@@ -2260,6 +2311,9 @@ extern "C" int pllgpu_update_partials(pllgpu_ctx_t *c, const pllgpu_op_t *ops, u
   // or overwrite them: stored first. Compared BEFORE anything is flushed.
   const bool replay = c->plan && c->chains && c->fuse && !c->any_aos && c->plan->epoch == c->alloc_epoch && c->plan->key.size() == count &&
                       memcmp(c->plan->key.data(), ops, count * sizeof(pllgpu_op_t)) == 0;
+  // Such a caller read nothing since the plan's last launch: a loop. Its next one-launch evaluation may leave the whole
+  // 8-tip groups unstored (k_edge_dna_tree<TopsOnly>) - decided here, for last_bytes is read before the evaluation.
+  c->tree_deep = replay && c->pending_plan == c->plan && !c->pending.empty() && c->plan->tree && use_deep_tree(c, c->plan->entries);
   if (replay && c->pending_plan == c->plan) drop_pending(c);
   // (the same list while it is still held: the traversal goes out, and what it would store only to be recomputed below
   // stays unstored)
@@ -2373,6 +2427,7 @@ struct ChainTailCall
   ChainPack pack; // in_kernarg: heads[0] = hp, heads[1] = hc and their steps
   const TreePack *tree = nullptr; // the held plan is a whole traversal (ChainPlan::tree): k_edge_dna_tree, nothing above is read
   bool lean = false;              // ... in the form that leaves the 32 tip x tip parents unstored (pllgpu_ctx::pending)
+  bool deep = false;              // ... and the rest of the eight groups as well (lean too)
 };
 
 static void launch_edge_chain(pllgpu_ctx *c, const DevEdge &e, const ChainTailCall &t)
@@ -2380,9 +2435,17 @@ static void launch_edge_chain(pllgpu_ctx *c, const DevEdge &e, const ChainTailCa
   const ChainPlan &pl = *c->plan;
   dim3 grid((pl.entries + 63) / 64), block(256);
   if (t.tree) // a workgroup of eight waves per tile, tiles in the XCD-aware order
-    with_bools(!t.lean, false, [&](auto STORE, auto) {
-      hipLaunchKernelGGL(k_edge_dna_tree<STORE()>, xcd_grid(grid.x, 1), dim3(512), 0, c->stream, e, *t.tree, pl.entries, c->gg.scale_mode, c->xcd_order);
-    });
+  {
+    auto go = [&](auto ST) {
+      hipLaunchKernelGGL(k_edge_dna_tree<ST()>, xcd_grid(grid.x, 1), dim3(512), 0, c->stream, e, *t.tree, pl.entries, c->gg.scale_mode, c->xcd_order);
+    };
+    if (t.deep)
+      go(std::integral_constant<TreeStores, TreeStores::TopsOnly>());
+    else if (t.lean)
+      go(std::integral_constant<TreeStores, TreeStores::NoCherries>());
+    else
+      go(std::integral_constant<TreeStores, TreeStores::All>());
+  }
   else if (t.in_kernarg)
     with_chain_variant(c->gg.scale_mode, t.variant, [&](auto SMV, auto C0, auto S1, auto C1) {
       hipLaunchKernelGGL((k_edge_dna_chain_pack<SMV(), C0(), S1(), C1()>), grid, block, 0, c->stream, e, t.pack, pl.entries);
@@ -2836,15 +2899,16 @@ extern "C" int pllgpu_edge_loglikelihood(pllgpu_ctx_t *c, const pllgpu_edge_t *e
       tp.end[1] = c->plan->tree_end[held_c];
       ct.tree = &tp;
       ct.lean = c->lazy_cherries;
+      ct.deep = ct.lean && c->tree_deep;
     }
     else if (int brc = build_chain_tail(c, ed, e, held_p, held_c, ct))
       return brc;
     rc = run_lnl(c, e, ed->child_is_tip != 0, false, ed->freqs_indices, persite_host, lnl_out, ed->device_result, nullptr, &ct);
     if (rc == 0 && ct.lean)
     {
-      // issued: from here on the cherries are pending (on a failure ClaimedWork sends the plan out the ordinary way, which
-      // stores everything: nothing pending)
-      set_pending(c, c->plan);
+      // issued: from here on the cherries - or the whole groups - are pending (on a failure ClaimedWork sends the plan out
+      // the ordinary way, which stores everything: nothing pending)
+      set_pending(c, c->plan, ct.deep);
     }
   }
   else if (use_tail)
