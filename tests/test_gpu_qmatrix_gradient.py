@@ -6,8 +6,8 @@ Inputs: every edge of UTree(taxa, PCG64(7)) over the insertion tests' alignments
 tree's own lengths (gradient_cases.prepare: the parent is the root-side end). The criterion for d_q and d_root is
 |got - exp| <= DTOL * abs + 4e-15 * sites elementwise, abs the same sum with every term's absolute value.
 
-Observed on an MI355X: see the docstrings of test_parity_with_the_restatement, test_variants and
-test_gradient_against_the_reference_lnl."""
+Observed on an MI355X: see the docstrings of test_parity_with_the_restatement, test_variants,
+test_variants_at_the_long_walk and test_gradient_against_the_reference_lnl."""
 import functools
 
 import numpy as np
@@ -16,6 +16,7 @@ import pytest
 import category_common as CC
 import gradient_cases as GC
 import insertion_cases as IC
+import long_walk_cases as LW
 import qmatrix_gradient_cases as QC
 from deriv_common import DTOL
 from pllamd import api, driver
@@ -25,6 +26,18 @@ pytestmark = pytest.mark.gpu
 TAXA = 7
 SHAPES = {"4x4": (4, 4), "4x1": (4, 1), "4x3": (4, 3), "5x4": (5, 4), "20x4": (20, 4), "61x2": (61, 2)}
 PARITY = [(s, n) for s in ("4x4", "20x4") for n in (1, 63, 64, 65, 300)] + [(s, 65) for s in ("4x1", "4x3", "5x4", "61x2")]
+# shapes beside SHAPES (which other tests run whole): more than four rate categories - a wave of the generic kernel takes two
+# (4 x 8, two accumulator blocks per wave) - 5 x 7, the shape the kernel's static_assert names, state counts at a multiple of
+# 16 (no padding rows; 64 x 2 fills the largest legal LDS, 140 288 bytes, with eight accumulator blocks per wave) and one
+# above it (17: 15 padding rows, two 16-row blocks)
+MORE_SHAPES = {"4x8": (4, 8), "5x7": (5, 7), "16x4": (16, 4), "64x2": (64, 2), "17x2": (17, 2)}
+PARITY += [(s, 65) for s in MORE_SHAPES]
+# the smallest site counts at which a wave (4 x 4) or a workgroup walks a second tile (long_walk_cases.qg_walk restates the
+# rule: T tiles, w per walk, B workgroups per branch) - 4x4 16 385: 257, 2, 33; 20x4 1 025: 17, 2, 9; 20x4 3 137: 50, 4, 13;
+# 5x4 4 097: 65, 2, 33; 61x2 257: 5, 2, 3 (eight accumulator blocks per wave); 4x8 4 097: 65, 2, 33. The last workgroup holds
+# fewer tiles than the others, the last tile one site
+LONG_WALK = [("4x4", 16385), ("20x4", 1025), ("20x4", 3137), ("5x4", 4097), ("61x2", 257), ("4x8", 4097)]
+PARITY += LONG_WALK
 _REF = None  # the reference library of the session (functools.cache keys must be hashable)
 
 
@@ -35,7 +48,7 @@ def _reference_library(ref_lib):
 
 
 def _dims(shape, sites, taxa=TAXA):
-    return SHAPES[shape] + (taxa, sites)
+    return (SHAPES.get(shape) or MORE_SHAPES[shape]) + (taxa, sites)
 
 
 @functools.lru_cache(maxsize=None)
@@ -156,7 +169,12 @@ def test_parity_with_the_restatement(amd_lib, shape, sites):
     """d_q and d_root of every edge's list against the restatement. Observed on an MI355X, worst fraction of the bound:
     d_q below 0.0005 at 4 states (every site count, 4 x 1, 4 x 3) and at 5 x 4; 20 x 4 0.000 / 0.006 / 0.002 / 0.002 / 0.002
     at 1 / 63 / 64 / 65 / 300 sites; 61 x 2 0.024; d_root below 0.0005 everywhere (the device differs from the restatement
-    by rounding, 1e-13 to 1e-12 of the absolute-value sum, and DTOL is 1e-10 of it)."""
+    by rounding, 1e-13 to 1e-12 of the absolute-value sum, and DTOL is 1e-10 of it).
+    MORE_SHAPES at 65 sites: d_q below 0.0005 at 4 x 8 and 5 x 7, 0.001 at 16 x 4, 0.004 at 17 x 2, 0.047 at 64 x 2. LONG_WALK:
+    d_q below 0.0005 at 4 x 4 x 16 385, 20 x 4 x 1 025, 5 x 4 x 4 097 and 4 x 8 x 4 097, 0.001 at 20 x 4 x 3 137, 0.024 at
+    61 x 2 x 257; d_root below 0.0005 everywhere."""
+    if (shape, sites) in LONG_WALK:
+        assert LW.qg_walk(*_dims(shape, sites)[:2], sites)[1] >= 2, "the walk is one tile long: nothing new is tested"
     _assert_parity(_dims(shape, sites), None, amd_lib)
 
 
@@ -170,6 +188,22 @@ def test_variants(amd_lib, shape, variant):
     0.0005 everywhere): 4 x 4 below 0.0005 in every variant; 20 x 4 0.002 pattern weights, 0.001 pinv, 0.002 / 0.001 written
     per-site / per-rate counts, 0.002 pattern tips, 0.001 dense, 0.001 tip as parent, 0.001 two matrices, 0.011 JC69."""
     dims = _dims(shape, 65)
+    d_q, d_root = _assert_parity(dims, variant, amd_lib, root=VARIANTS[variant][2])
+    if variant == "two_matrices":
+        assert (d_q[1] == 0.0).all() and (d_root[1] == 0.0).all() and np.abs(d_q[0]).max() > 0 and np.abs(d_q[2]).max() > 0
+        assert not np.allclose(d_q[0], d_q[2], rtol=1e-3)
+    if variant == "rate_counts":
+        plain = _restated(dims, None)["d_q"]
+        assert not np.allclose(plain, _restated(dims, variant)["d_q"], rtol=1e-6), "the written counts change nothing"
+
+
+@pytest.mark.parametrize("variant", ["pattern_tip", "rate_counts", "two_matrices"])
+@pytest.mark.parametrize("shape,sites", [("20x4", 1025), ("4x4", 16385)])
+def test_variants_at_the_long_walk(amd_lib, shape, sites, variant):
+    """the tip decode, the per-rate excess factor and the second rate matrix inside the second pass of the tile walk.
+    Observed on an MI355X, worst fraction of the bound: d_q 0.001 with two matrices at 20 x 4 x 1 025, below 0.0005 in the
+    other five cases; d_root below 0.0005 everywhere."""
+    dims = _dims(shape, sites)
     d_q, d_root = _assert_parity(dims, variant, amd_lib, root=VARIANTS[variant][2])
     if variant == "two_matrices":
         assert (d_q[1] == 0.0).all() and (d_root[1] == 0.0).all() and np.abs(d_q[0]).max() > 0 and np.abs(d_q[2]).max() > 0
@@ -376,3 +410,12 @@ def test_refusals_with_a_device(amd_lib):
             assert (d_q == SENTINEL).all()
     finally:
         del SHAPES["61x4"]
+    # the two boundaries beside it: 20 x 5 needs 174 208 bytes of LDS, more than 160 KB; 61 x 3 more than eight accumulator
+    # blocks per wave (and 209 120 bytes)
+    for states, rate_cats in ((20, 5), (61, 3)):
+        with _bed(amd_lib, (states, rate_cats, TAXA, 17), 0) as b:
+            rows = GC.prepare(b)
+            d_q, d_root = np.full((1, states, states), SENTINEL), np.full((1, states), SENTINEL)
+            assert amd_lib.pll_gpu_qmatrix_gradient(b.p, api.make_branches(rows), len(rows), api.uptr(b.fi), api.dptr(d_q), api.dptr(d_root)) == 0
+            assert amd_lib.errno() == unsup and "LDS" in amd_lib.errmsg(), (states, rate_cats, amd_lib.errno(), amd_lib.errmsg())
+            assert (d_q == SENTINEL).all() and (d_root == SENTINEL).all()
