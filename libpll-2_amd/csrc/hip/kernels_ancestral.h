@@ -30,7 +30,7 @@
 //                                  (16 with tip codes) loads of the tile are issued before the arithmetic, the lane's
 //                                  four results are 32 contiguous bytes and leave as two 16-byte stores (a wave writes
 //                                  2 KB contiguous).
-//   k_ancestral_tiled<ICH, CTIP>   any other shape, as k_edge_tiled: one workgroup per tile, wave w owns the rate
+//   k_ancestral_tiled<ICH, CTIP>   any other shape, k_edge_tiled's walk (gen_tile): one workgroup per tile, wave w owns the rate
 //                                  categories w, w + nw, ...; instead of one scalar per wave the per-state partial
 //                                  sums sit in LDS ([wave][state][lane]), are added in wave order (deterministic),
 //                                  normalised, and the tile's 64 x S results leave as one contiguous block.
@@ -111,23 +111,19 @@ __global__ __launch_bounds__(256) void k_ancestral_tiled(const DevAncestral a, c
 {
   extern __shared__ double anc_lds[];
   const DevEdge &e = a.e;
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned lane = gen_lane(), wave = gen_wave();
   const unsigned nw = blockDim.x >> 6;
-  const unsigned ntiles = (e.sites + 63u) / 64u;
   double *mine = anc_lds + (size_t)wave * g.S * 64u + lane; // [state] at stride 64
   double *rowsum = anc_lds + (size_t)nw * g.S * 64u;        // [wave][lane]
 
   for (unsigned t = 0; t < tiles_per_block; ++t)
   {
-    const unsigned tile = blockIdx.x * tiles_per_block + t;
-    if (tile >= ntiles) break; // whole workgroup
-    const unsigned n = tile * 64u + lane;
-    const unsigned nn = n < e.sites ? n : e.sites - 1; // tail lanes redo the last site, store nothing
-    unsigned long long cmask = 0;
-    if (CTIP) cmask = tip_mask(tipmap, e.ctip[nn]);
+    if (!gen_has_tile(tiles_per_block, t, e.sites)) break;
+    const GenTile w = gen_tile(tiles_per_block, t, e.sites);
+    const unsigned tile = w.tile, nn = w.nn; // tail lanes redo the last site, store nothing
+    const unsigned long long cmask = CTIP ? tip_mask(tipmap, e.ctip[nn]) : 0ull;
     const double *__restrict__ px = e.parent + tiled_base(nn, g.tile_sz);
-    const double *__restrict__ cx = CTIP ? nullptr : e.child + tiled_base(nn, g.tile_sz);
+    const GenEnd ce = gen_end(e.mat, CTIP, e.child, nn, g, cmask);
 
     const unsigned scal = e.per_rate ? scaler_min(e.pscaler, nn, e.cscaler, nn, g.R) : 0u;
 
@@ -140,7 +136,7 @@ __global__ __launch_bounds__(256) void k_ancestral_tiled(const DevAncestral a, c
       for (unsigned c = 0; c < g.nchunks; ++c)
       {
         double B[ICH];
-        contract<ICH, CTIP>(B, e.mat, k, c, g, CTIP ? nullptr : cx + (size_t)k * g.S * 64, cmask);
+        end_contract<ICH>(B, ce, k, c, g);
         cdouble_p pi = as_const(e.freqs) + (size_t)e.fidx[k] * g.SP + c * ICH;
         const double *pk = px + ((size_t)k * g.S + c * ICH) * 64;
         double *dst = mine + (size_t)(c * ICH) * 64u;
@@ -163,10 +159,10 @@ __global__ __launch_bounds__(256) void k_ancestral_tiled(const DevAncestral a, c
     for (unsigned j = wave; j < g.S; j += nw)
     {
       double *col = anc_lds + (size_t)j * 64u + lane;
-      double v = col[0];
-      for (unsigned q = 1; q < nw; ++q) v += col[(size_t)q * g.S * 64u];
-      col[0] = v;
-      part += v;
+      double v[1];
+      wave_order_sums(v, col, nw, (size_t)g.S * 64u);
+      col[0] = v[0];
+      part += v[0];
     }
     rowsum[wave * 64u + lane] = part;
     lds_barrier();
@@ -178,9 +174,9 @@ __global__ __launch_bounds__(256) void k_ancestral_tiled(const DevAncestral a, c
     for (unsigned idx = threadIdx.x; idx < count; idx += blockDim.x)
     {
       const unsigned site = idx / g.S, j = idx - site * g.S;
-      double sum = rowsum[site];
-      for (unsigned q = 1; q < nw; ++q) sum += rowsum[q * 64u + site];
-      o[idx] = anc_lds[(size_t)j * 64u + site] / sum;
+      double sum[1];
+      wave_order_sums(sum, rowsum + site, nw);
+      o[idx] = anc_lds[(size_t)j * 64u + site] / sum[0];
     }
     lds_barrier(); // the slots are rewritten by the next tile
   }

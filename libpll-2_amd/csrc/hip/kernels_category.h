@@ -28,7 +28,7 @@
 //   A  k_category_dna<CTIP> / k_category_tiled<ICH, CTIP>   one launch: the table u as [k][sites rounded up to 64] and
 //      one count word c[n] per site into scratch; cat_lnl, when asked, into its staging buffer in the host's layout
 //      [n][k]. The 4 x 4 form is k_ancestral_dna's walk (lane = site, every load of the tile before the arithmetic);
-//      the tiled form is k_ancestral_tiled's (one workgroup per tile, wave w owns the categories w, w + nw, ...) - but
+//      the tiled form is gen_tile's walk and k_edge_tiled's rate term (one workgroup per tile, wave w owns the categories w, w + nw, ...) - but
 //      the sum over the states is lane-local here: no LDS, no barrier.
 //   B  k_category_mix   lane = site, min(ceil(sites / 256), 1024) workgroups of 256 walking the 256-site tiles at that
 //      stride: reads the table (whole-wave contiguous per category), mixes it under ONE ROW of weights read from device
@@ -118,22 +118,18 @@ __global__ __launch_bounds__(256) void k_category_tiled(const DevCategory a, con
                                                         unsigned tiles_per_block)
 {
   const DevEdge &e = a.e;
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned wave = gen_wave();
   const unsigned nw = blockDim.x >> 6;
-  const unsigned ntiles = (e.sites + 63u) / 64u;
 
   for (unsigned t = 0; t < tiles_per_block; ++t)
   {
-    const unsigned tile = blockIdx.x * tiles_per_block + t;
-    if (tile >= ntiles) break; // whole workgroup
-    const unsigned n = tile * 64u + lane;
-    const bool valid = n < e.sites;
-    const unsigned nn = valid ? n : e.sites - 1; // tail lanes redo the last site, store nothing
-    unsigned long long cmask = 0;
-    if (CTIP) cmask = tip_mask(tipmap, e.ctip[nn]);
+    if (!gen_has_tile(tiles_per_block, t, e.sites)) break;
+    const GenTile w = gen_tile(tiles_per_block, t, e.sites);
+    const unsigned nn = w.nn; // tail lanes redo the last site, store nothing
+    const bool valid = w.valid;
+    const unsigned long long cmask = CTIP ? tip_mask(tipmap, e.ctip[nn]) : 0ull;
     const double *__restrict__ px = e.parent + tiled_base(nn, g.tile_sz);
-    const double *__restrict__ cx = CTIP ? nullptr : e.child + tiled_base(nn, g.tile_sz);
+    const GenEnd ce = gen_end(e.mat, CTIP, e.child, nn, g, cmask);
 
     const unsigned scal = site_scalings(e.pscaler, nn, e.cscaler, nn, g.R, e.per_rate);
     if (wave == 0 && valid) a.count[nn] = scal;
@@ -144,12 +140,9 @@ __global__ __launch_bounds__(256) void k_category_tiled(const DevCategory a, con
       for (unsigned c = 0; c < g.nchunks; ++c)
       {
         double B[ICH];
-        contract<ICH, CTIP>(B, e.mat, k, c, g, CTIP ? nullptr : cx + (size_t)k * g.S * 64, cmask);
+        end_contract<ICH>(B, ce, k, c, g);
         cdouble_p pi = as_const(e.freqs) + (size_t)e.fidx[k] * g.SP + c * ICH;
-        const double *pk = px + ((size_t)k * g.S + c * ICH) * 64;
-#pragma unroll
-        for (int i = 0; i < ICH; ++i)
-          if (c * ICH + i < g.S) tr = fma(__builtin_nontemporal_load(pk + (size_t)i * 64) * pi[i], B[i], tr);
+        tr = rate_term_add<ICH>(tr, px + ((size_t)k * g.S + c * ICH) * 64, 64u, pi, B, c, g);
       }
       if (!valid) continue;
       const unsigned sk = e.per_rate ? scaler_sum_rate(e.pscaler, nn, e.cscaler, nn, g.R, k) : scal;

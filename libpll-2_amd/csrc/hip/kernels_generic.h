@@ -423,6 +423,184 @@ __device__ __forceinline__ void edge_rate_add(const DevEdge &e, const GenGeo &g,
 }
 
 // ------------------------------------------------------------------------------------------------
+// What the kernels over the tiled layout share besides the contraction (k_edge_tiled below, kernels_insertion.h,
+// kernels_placement.h, kernels_quartet.h, kernels_gradient.h, kernels_qgradient.h, kernels_ancestral.h,
+// kernels_category.h). The order of these operations is what makes a batched call's value the per-edge call's, bit for
+// bit: each is written here once.
+
+// A thread's place in its workgroup: lane = site of the tile, the waves split the tile's rate categories (wave-uniform: it
+// lives in a scalar register)
+__device__ __forceinline__ unsigned gen_lane() { return threadIdx.x & 63u; }
+__device__ __forceinline__ unsigned gen_wave() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+
+// The tile a workgroup is at
+struct GenTile
+{
+  unsigned lane, wave, tile;
+  unsigned n;   // the lane's site; past the end where !valid
+  unsigned nn;  // ... clamped to the last one (lanes past the end compute, and store nothing)
+  bool valid;
+};
+
+// Tile t of the tiles_per_block a workgroup walks: is there one (the same for the whole workgroup) ...
+__device__ __forceinline__ bool gen_has_tile(unsigned tiles_per_block, unsigned t, unsigned sites)
+{
+  return blockIdx.x * tiles_per_block + t < (sites + 63u) / 64u;
+}
+
+// ... and the thread's place in it
+__device__ __forceinline__ GenTile gen_tile(unsigned tiles_per_block, unsigned t, unsigned sites)
+{
+  GenTile w;
+  w.lane = gen_lane();
+  w.wave = gen_wave();
+  w.tile = blockIdx.x * tiles_per_block + t;
+  w.n = w.tile * 64u + w.lane;
+  w.valid = w.n < sites;
+  w.nn = w.valid ? w.n : sites - 1;
+  return w;
+}
+
+// One end of a branch as a contraction reads it at site nn: a tip given by codes (mask = the site's state mask) or a tiled
+// CLV (x = the site in it, null for a tip). Which of the two is wave-uniform.
+struct GenEnd
+{
+  const double *mat; // PT layout
+  bool tip;
+  const double *__restrict__ x;
+  unsigned long long mask;
+};
+
+__device__ __forceinline__ GenEnd gen_end(const double *mat, bool tip, const double *clv, unsigned nn, const GenGeo &g, unsigned long long mask)
+{
+  GenEnd r;
+  r.mat = mat;
+  r.tip = tip;
+  r.x = tip ? nullptr : clv + tiled_base(nn, g.tile_sz);
+  r.mask = mask;
+  return r;
+}
+
+// acc = (P x) of one end, (rate k, chunk ch)
+template <int ICH>
+__device__ __forceinline__ void end_contract(double (&acc)[ICH], const GenEnd &a, unsigned k, unsigned ch, const GenGeo &g)
+{
+  if (a.tip) // wave-uniform
+    contract<ICH, true>(acc, a.mat, k, ch, g, nullptr, a.mask);
+  else
+    contract<ICH, false>(acc, a.mat, k, ch, g, a.x + (size_t)k * g.S * 64, 0ull);
+}
+
+// the values of the node above two ends, (rate k, chunk ch), unscaled: v[i] = A_i B_i
+template <int ICH>
+__device__ __forceinline__ void end_product(double (&v)[ICH], const GenEnd &a, const GenEnd &b, unsigned k, unsigned ch, const GenGeo &g)
+{
+  double B[ICH];
+  end_contract<ICH>(v, a, k, ch, g);
+  end_contract<ICH>(B, b, k, ch, g);
+#pragma unroll
+  for (int i = 0; i < ICH; ++i) v[i] *= B[i];
+}
+
+// Pass 1 of a node that exists inside a kernel only, rate k: its products chunk by chunk, parked at
+// park[rate][state][lane] (LDS) where keep says so. Returns the lane's "all below 2^-256" of the rate.
+template <int ICH>
+__device__ __forceinline__ bool node_first_pass(const GenEnd &a, const GenEnd &b, unsigned k, const GenGeo &g, double *park, unsigned keep, unsigned lane)
+{
+  bool small = true;
+  for (unsigned ch = 0; ch < g.nchunks; ++ch)
+  {
+    double v[ICH];
+    end_product<ICH>(v, a, b, k, ch, g);
+    double *dst = park + ((size_t)k * g.S + ch * ICH) * 64u + lane;
+#pragma unroll
+    for (int i = 0; i < ICH; ++i)
+      if (ch * ICH + i < g.S)
+      {
+        small = small && (v[i] < PLLGPU_SCALE_THRESHOLD);
+        if (keep) dst[(size_t)i * 64] = v[i];
+      }
+  }
+  return small;
+}
+
+// ... and pass 2's way back to them: the parked values, or (keep == 0) the products formed again - same arithmetic, same bits
+template <int ICH>
+__device__ __forceinline__ void parked_or_product(double (&v)[ICH], const GenEnd &a, const GenEnd &b, unsigned k, unsigned ch, const GenGeo &g,
+                                                  const double *park, unsigned keep, unsigned lane)
+{
+  if (keep)
+  {
+    const double *src = park + ((size_t)k * g.S + ch * ICH) * 64u + lane;
+#pragma unroll
+    for (int i = 0; i < ICH; ++i) v[i] = ch * ICH + i < g.S ? src[(size_t)i * 64] : 0.0;
+  }
+  else
+    end_product<ICH>(v, a, b, k, ch, g);
+}
+
+// Scaling counts of a site under such a node, whose decisions of every rate stand in flags[rate][lane] behind a barrier:
+// the children's counts (lsc, rsc), the node's own, the count of the end across the edge (ssc). Rate k's ...
+__device__ __forceinline__ unsigned node_rate_scalings(const unsigned *lsc, const unsigned *rsc, const unsigned *ssc, unsigned nn, unsigned R, unsigned k,
+                                                       const unsigned char (&flags)[kMaxRates][64], unsigned lane)
+{
+  return scaler_sum_rate(lsc, nn, rsc, nn, R, k) + flags[k][lane] + scaler_sum_rate(ssc, nn, nullptr, 0, R, k);
+}
+
+// ... and the site's: the smallest of the rates' (per-rate scalers), or the per-site counts and the node's one decision,
+// site_small (true and unused under per-rate scalers)
+__device__ __forceinline__ unsigned node_site_scalings(int per_rate, const unsigned *lsc, const unsigned *rsc, const unsigned *ssc, unsigned nn, unsigned R,
+                                                       const unsigned char (&flags)[kMaxRates][64], unsigned lane, bool &site_small)
+{
+  site_small = true;
+  if (per_rate)
+  {
+    unsigned scal = 0xFFFFFFFFu;
+    for (unsigned k = 0; k < R; ++k) scal = min(scal, node_rate_scalings(lsc, rsc, ssc, nn, R, k, flags, lane));
+    return scal;
+  }
+  for (unsigned k = 0; k < R; ++k) site_small = site_small && flags[k][lane];
+  return scaler_sum(lsc, nn, rsc, nn) + (site_small ? 1u : 0u) + scaler_sum(ssc, nn, nullptr, 0);
+}
+
+// The rate term tr = sum_i (a_i pi_i) B_i over the chunks, ascending states: a_i pi_i is rounded before it meets B_i, then
+// one fma each. a_i of chunk ch is the parent end's CLV entry (pk = state ch * ICH of the rate, states xs apart; a read-once
+// stream) ...
+template <int ICH>
+__device__ __forceinline__ double rate_term_add(double tr, const double *pk, unsigned xs, cdouble_p pi, const double (&B)[ICH], unsigned ch, const GenGeo &g)
+{
+#pragma unroll
+  for (int i = 0; i < ICH; ++i)
+    if (ch * ICH + i < g.S) tr = fma(__builtin_nontemporal_load(pk + (size_t)i * xs) * pi[i], B[i], tr);
+  return tr;
+}
+
+// ... or the unscaled value v_i of a node formed in the kernel, rescaled first where its scaling decision says so
+template <int ICH>
+__device__ __forceinline__ double rate_term_add(double tr, const double (&v)[ICH], bool rescale, cdouble_p pi, const double (&B)[ICH], unsigned ch,
+                                                const GenGeo &g)
+{
+#pragma unroll
+  for (int i = 0; i < ICH; ++i)
+    if (ch * ICH + i < g.S) tr = fma((rescale ? v[i] * PLLGPU_SCALE_FACTOR : v[i]) * pi[i], B[i], tr);
+  return tr;
+}
+
+// N values' partial sums of a lane, one per wave, added in wave order: s[v] = first[v * value_stride + w * wave_stride] over
+// w = 0 .. nw - 1 (the defaults: part[N][4][64] in LDS, first = &part[0][0][lane])
+template <int N>
+__device__ __forceinline__ void wave_order_sums(double (&s)[N], const double *first, unsigned nw, size_t wave_stride = 64, size_t value_stride = 4 * 64)
+{
+#pragma unroll
+  for (int v = 0; v < N; ++v) s[v] = first[v * value_stride];
+  for (unsigned w = 1; w < nw; ++w)
+  {
+#pragma unroll
+    for (int v = 0; v < N; ++v) s[v] += first[v * value_stride + w * wave_stride];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // edge / root log-likelihood, any states/rates, tiled layout. Workgroup = one tile at a time; wave
 // w of min(R,4) owns the rate categories w, w+nw, ... : it forms (P c)_i in chunks exactly like the
 // update kernel, dots it with p_i * pi_i, applies the per-rate scaler excess, the rate weight and
@@ -437,19 +615,16 @@ __global__ __launch_bounds__(256) void k_edge_tiled(const DevEdge e, const GenGe
                                                     unsigned tiles_per_block)
 {
   __shared__ double part[2][4][64];
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned lane = gen_lane(), wave = gen_wave();
   const unsigned nw = blockDim.x >> 6;
-  const unsigned ntiles = (e.sites + 63u) / 64u;
   double acc = 0.0;
 
   for (unsigned t = 0; t < tiles_per_block; ++t)
   {
-    const unsigned tile = blockIdx.x * tiles_per_block + t;
-    if (tile >= ntiles) break; // whole workgroup
-    const unsigned n = tile * 64u + lane;
-    const bool valid = n < e.sites;
-    const unsigned nn = valid ? n : e.sites - 1;
+    if (!gen_has_tile(tiles_per_block, t, e.sites)) break;
+    const GenTile w = gen_tile(tiles_per_block, t, e.sites);
+    const unsigned n = w.n, nn = w.nn;
+    const bool valid = w.valid;
     unsigned pe = nn, ce = nn;
     if (GATHER)
     {
@@ -489,9 +664,7 @@ __global__ __launch_bounds__(256) void k_edge_tiled(const DevEdge e, const GenGe
         }
         cdouble_p pi = as_const(e.freqs) + (size_t)fi * g.SP + c * ICH;
         const double *pk = px + (size_t)k * pks + (size_t)(c * ICH) * pxs;
-#pragma unroll
-        for (int i = 0; i < ICH; ++i)
-          if (c * ICH + i < g.S) tr = fma(__builtin_nontemporal_load(pk + (size_t)i * pxs) * pi[i], B[i], tr);
+        tr = rate_term_add<ICH>(tr, pk, pxs, pi, B, c, g);
       }
       if (e.per_rate) tr = rate_scaled(tr, scaler_sum_rate(e.pscaler, pe, e.cscaler, ce, g.R, k), scal);
       edge_rate_add(e, g, k, tr, nn, terma, terminv);
@@ -501,13 +674,9 @@ __global__ __launch_bounds__(256) void k_edge_tiled(const DevEdge e, const GenGe
     __syncthreads();
     if (wave == 0 && valid)
     {
-      double ta = part[0][0][lane], ti = part[1][0][lane];
-      for (unsigned w = 1; w < nw; ++w)
-      {
-        ta += part[0][w][lane];
-        ti += part[1][w][lane];
-      }
-      const double site = finish_site(ta, ti, scal, e.is_root) * (double)e.pattern_weights[n];
+      double s[2]; // terma, terminv
+      wave_order_sums(s, &part[0][0][lane], nw);
+      const double site = finish_site(s[0], s[1], scal, e.is_root) * (double)e.pattern_weights[n];
       if (e.persite) e.persite[n] = site;
       acc += site;
     }

@@ -175,9 +175,9 @@ __global__ __launch_bounds__(256) void k_gradient_dna(const DevEdge e, const Dev
 }
 
 // ------------------------------------------------------------------------------------------------
-// Every other shape (up to 64 states, any rate count): k_insertion_tiled's structure - workgroup = one tile of one branch
-// at a time, wave w of min(R, 4) owns the rate categories w, w + nw, ..., the contraction is kernels_generic.h's and a tip
-// is decoded through the tipmap. The branch's diag table stands in LDS ([R][S][4]: 7.8 KB at 61 x 4). A wave leaves its
+// Every other shape (up to 64 states, any rate count): the tiled kernels' walk (kernels_generic.h: gen_tile) - workgroup =
+// one tile of one branch at a time, wave w of min(R, 4) owns the rate categories w, w + nw, ... - and their end_product:
+// a tip is decoded through the tipmap. The branch's diag table stands in LDS ([R][S][4]: 7.8 KB at 61 x 4). A wave leaves its
 // rates' share of the site's (L, L', L'') in LDS; wave 0 adds the shares in wave order and forms the site's two terms.
 // CAT: L of a site exists only once the waves' shares are added, so a wave parks the c1 w of its categories in LDS
 // (cshare, [R][64]) and, after the barrier, adds the shares of L in wave 0's order and sums pw * (-(c1 w) / L) per category
@@ -192,13 +192,11 @@ __global__ __launch_bounds__(256) void k_gradient_tiled(const DevEdge e, const D
   extern __shared__ double ldiag[]; // [R][S][4]; CAT: then cshare [R][64] and acat [R][64]
   const BranchDesc b = branch_get(branches, blockIdx.y);
   branch_diag(dg, b.t, ldiag);
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned lane = gen_lane(), wave = gen_wave();
   double *const cshare = ldiag + (size_t)g.R * g.S * 4, *const acat = cshare + (size_t)g.R * 64;
   // (through the scalar path by hand: branch_diag's per-lane stride has the workgroup size in a vector register, and a rate
   // loop stepping by a vector register reads its matrix coefficients with vector loads)
   const unsigned nw = __builtin_amdgcn_readfirstlane(blockDim.x >> 6);
-  const unsigned ntiles = (e.sites + 63u) / 64u;
   const bool ltip = b.ltip != nullptr, rtip = b.rtip != nullptr; // wave-uniform
   const unsigned *lsc = e.per_rate ? b.lscaler : nullptr, *rsc = e.per_rate ? b.rscaler : nullptr;
   double a1 = 0.0, a2 = 0.0;
@@ -207,16 +205,13 @@ __global__ __launch_bounds__(256) void k_gradient_tiled(const DevEdge e, const D
 
   for (unsigned t = 0; t < tiles_per_block; ++t)
   {
-    const unsigned tile = blockIdx.x * tiles_per_block + t;
-    if (tile >= ntiles) break; // whole workgroup
-    const unsigned n = tile * 64u + lane;
-    const bool valid = n < e.sites;
-    const unsigned nn = valid ? n : e.sites - 1;
+    if (!gen_has_tile(tiles_per_block, t, e.sites)) break;
+    const GenTile w = gen_tile(tiles_per_block, t, e.sites);
+    const unsigned n = w.n, nn = w.nn;
+    const bool valid = w.valid;
     const unsigned long long lmask = ltip ? tip_mask(tipmap, b.ltip[nn]) : 0ull;
     const unsigned long long rmask = rtip ? tip_mask(tipmap, b.rtip[nn]) : 0ull;
-    const size_t base = tiled_base(nn, g.tile_sz);
-    const double *__restrict__ lx = ltip ? nullptr : b.left + base;
-    const double *__restrict__ rx = rtip ? nullptr : b.right + base;
+    const GenEnd le = gen_end(m1, ltip, b.left, nn, g, lmask), re = gen_end(m2, rtip, b.right, nn, g, rmask);
     const unsigned mn = e.per_rate ? scaler_min(lsc, nn, rsc, nn, g.R) : 0u;
     const int inv = e.invariant ? e.invariant[nn] : -1;
 
@@ -227,21 +222,14 @@ __global__ __launch_bounds__(256) void k_gradient_tiled(const DevEdge e, const D
       double c0 = 0.0, c1 = 0.0, c2 = 0.0;
       for (unsigned ch = 0; ch < g.nchunks; ++ch)
       {
-        double A[ICH], B[ICH];
-        if (ltip)
-          contract<ICH, true>(A, m1, k, ch, g, nullptr, lmask);
-        else
-          contract<ICH, false>(A, m1, k, ch, g, lx + (size_t)k * g.S * 64, 0ull);
-        if (rtip)
-          contract<ICH, true>(B, m2, k, ch, g, nullptr, rmask);
-        else
-          contract<ICH, false>(B, m2, k, ch, g, rx + (size_t)k * g.S * 64, 0ull);
+        double v[ICH];
+        end_product<ICH>(v, le, re, k, ch, g);
         const double *dk = ldiag + ((size_t)k * g.S + ch * ICH) * 4; // wave-uniform addresses: LDS broadcast
 #pragma unroll
         for (int i = 0; i < ICH; ++i)
           if (ch * ICH + i < g.S)
           {
-            const double s = A[i] * B[i] * f;
+            const double s = v[i] * f;
             c0 = fma(s, dk[i * 4 + 0], c0);
             c1 = fma(s, dk[i * 4 + 1], c1);
             c2 = fma(s, dk[i * 4 + 2], c2);
@@ -257,21 +245,16 @@ __global__ __launch_bounds__(256) void k_gradient_tiled(const DevEdge e, const D
     __syncthreads();
     if (wave == 0 && valid)
     {
-      double s0 = part[0][0][lane], s1 = part[1][0][lane], s2 = part[2][0][lane];
-      for (unsigned w = 1; w < nw; ++w)
-      {
-        s0 += part[0][w][lane];
-        s1 += part[1][w][lane];
-        s2 += part[2][w][lane];
-      }
-      deriv_site_add(s0, s1, s2, (double)e.pattern_weights[n], a1, a2);
+      double s[3];
+      wave_order_sums(s, &part[0][0][lane], nw);
+      deriv_site_add(s[0], s[1], s[2], (double)e.pattern_weights[n], a1, a2);
     }
     if (CAT && valid)
     {
-      double s0 = part[0][0][lane]; // the site's L, as wave 0 adds it
-      for (unsigned w = 1; w < nw; ++w) s0 += part[0][w][lane];
+      double s[1]; // the site's L, as wave 0 adds it
+      wave_order_sums(s, &part[0][0][lane], nw);
       const double pw = (double)e.pattern_weights[n];
-      for (unsigned k = wave; k < g.R; k += nw) acat[k * 64u + lane] += pw * (-cshare[k * 64u + lane] / s0);
+      for (unsigned k = wave; k < g.R; k += nw) acat[k * 64u + lane] += pw * (-cshare[k * 64u + lane] / s[0]);
     }
     __syncthreads(); // part[] is reused by the next tile
   }

@@ -116,15 +116,16 @@ __global__ __launch_bounds__(256) void k_insertion_dna(const DevEdge e, const In
 
 // ------------------------------------------------------------------------------------------------
 // Every other shape (up to 64 states, any rate count): workgroup = one tile of one candidate at a time, wave w of
-// min(R, 4) owns the rate categories w, w + nw, ... as in k_partials_tiled / k_edge_tiled, and the contraction is theirs
-// (kernels_generic.h: contract).
+// min(R, 4) owns the rate categories w, w + nw, ... as in k_partials_tiled / k_edge_tiled, and the pieces are the tiled
+// kernels' shared ones (kernels_generic.h: gen_tile, end_product, node_first_pass, node_site_scalings, parked_or_product,
+// wave_order_sums; rate_term_add's loop stands written out in pass 2, see there).
 //   pass 1  the inserted node's values A_i B_i of the wave's rates, with the "all below 2^-256" flag per (rate, lane);
 //           the values stay in LDS, node[rate][state][lane] - 61 x 4 x 64 x 8 B = 125 KB of the 160 KB at the widest
 //           supported shape, one workgroup per CU there - where the scaling decision, which needs every rate of the
 //           site, finds all of them after one barrier;
 //   pass 2  the decision (per site: all rates; per rate: that rate) is added to the two children's counts, the
 //           values are rescaled by 2^256 as they are read back - BEFORE they meet the subtree side - and contracted with
-//           pi_i (P_s x_s)_i exactly as k_edge_tiled does.
+//           pi_i (P_s x_s)_i in rate_term_add's order, k_edge_tiled's.
 // A shape whose tile does not fit (keep == 0: R x S > 288) computes the products a second time in pass 2 instead of
 // keeping them: same arithmetic, same bits, no LDS.
 template <int ICH, bool STIP>
@@ -135,78 +136,29 @@ __global__ __launch_bounds__(256) void k_insertion_tiled(const DevEdge e, const 
   __shared__ double part[2][4][64];
   extern __shared__ double node[]; // keep: [rate][state][lane]
   const InsCand c = ins_get(cands, blockIdx.y);
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned lane = gen_lane(), wave = gen_wave();
   const unsigned nw = blockDim.x >> 6;
-  const unsigned ntiles = (e.sites + 63u) / 64u;
   const bool ltip = c.ltip != nullptr, rtip = c.rtip != nullptr; // wave-uniform
   const unsigned *lsc = ltip ? nullptr : c.lscaler, *rsc = rtip ? nullptr : c.rscaler, *ssc = STIP ? nullptr : e.cscaler;
   double acc = 0.0;
 
   for (unsigned t = 0; t < tiles_per_block; ++t)
   {
-    const unsigned tile = blockIdx.x * tiles_per_block + t;
-    if (tile >= ntiles) break; // whole workgroup
-    const unsigned n = tile * 64u + lane;
-    const bool valid = n < e.sites;
-    const unsigned nn = valid ? n : e.sites - 1;
+    if (!gen_has_tile(tiles_per_block, t, e.sites)) break;
+    const GenTile w = gen_tile(tiles_per_block, t, e.sites);
+    const unsigned nn = w.nn;
+    // the two ends of the candidate, whose product is the inserted node, and the subtree end
     const unsigned long long lmask = ltip ? tip_mask(tipmap, c.ltip[nn]) : 0ull;
     const unsigned long long rmask = rtip ? tip_mask(tipmap, c.rtip[nn]) : 0ull;
     const unsigned long long smask = STIP ? tip_mask(tipmap, e.ctip[nn]) : 0ull;
-    const size_t base = tiled_base(nn, g.tile_sz);
-    const double *__restrict__ lx = ltip ? nullptr : c.left + base;
-    const double *__restrict__ rx = rtip ? nullptr : c.right + base;
-    const double *__restrict__ sx = STIP ? nullptr : e.child + base;
+    const GenEnd le = gen_end(c.lmat, ltip, c.left, nn, g, lmask), re = gen_end(c.rmat, rtip, c.right, nn, g, rmask), se = gen_end(e.mat, STIP, e.child, nn, g, smask);
 
-    // the inserted node's values of (rate k, chunk ch), unscaled: v[i] = A_i B_i
-    auto product = [&](unsigned k, unsigned ch, double (&v)[ICH]) {
-      double B[ICH];
-      if (ltip)
-        contract<ICH, true>(v, c.lmat, k, ch, g, nullptr, lmask);
-      else
-        contract<ICH, false>(v, c.lmat, k, ch, g, lx + (size_t)k * g.S * 64, 0ull);
-      if (rtip)
-        contract<ICH, true>(B, c.rmat, k, ch, g, nullptr, rmask);
-      else
-        contract<ICH, false>(B, c.rmat, k, ch, g, rx + (size_t)k * g.S * 64, 0ull);
-#pragma unroll
-      for (int i = 0; i < ICH; ++i) v[i] *= B[i];
-    };
-
-    for (unsigned k = wave; k < g.R; k += nw)
-    {
-      bool small = true;
-      for (unsigned ch = 0; ch < g.nchunks; ++ch)
-      {
-        double v[ICH];
-        product(k, ch, v);
-        double *dst = node + ((size_t)k * g.S + ch * ICH) * 64u + lane;
-#pragma unroll
-        for (int i = 0; i < ICH; ++i)
-          if (ch * ICH + i < g.S)
-          {
-            small = small && (v[i] < PLLGPU_SCALE_THRESHOLD);
-            if (keep) dst[(size_t)i * 64] = v[i];
-          }
-      }
-      flags[k][lane] = small ? 1 : 0;
-    }
+    for (unsigned k = wave; k < g.R; k += nw) flags[k][lane] = node_first_pass<ICH>(le, re, k, g, node, keep, lane) ? 1 : 0;
     __syncthreads(); // every rate's flag, and the values the wave itself parked
 
     // the site's scaling count: the children's, the inserted node's own decision, the subtree end's
-    bool site_small = true;
-    unsigned scal;
-    if (e.per_rate)
-    {
-      scal = 0xFFFFFFFFu;
-      for (unsigned k = 0; k < g.R; ++k)
-        scal = min(scal, scaler_sum_rate(lsc, nn, rsc, nn, g.R, k) + flags[k][lane] + scaler_sum_rate(ssc, nn, nullptr, 0, g.R, k));
-    }
-    else
-    {
-      for (unsigned k = 0; k < g.R; ++k) site_small = site_small && flags[k][lane];
-      scal = scaler_sum(lsc, nn, rsc, nn) + (site_small ? 1u : 0u) + scaler_sum(ssc, nn, nullptr, 0);
-    }
+    bool site_small;
+    const unsigned scal = node_site_scalings(e.per_rate, lsc, rsc, ssc, nn, g.R, flags, lane, site_small);
 
     double terma = 0.0, terminv = 0.0;
     for (unsigned k = wave; k < g.R; k += nw)
@@ -217,36 +169,26 @@ __global__ __launch_bounds__(256) void k_insertion_tiled(const DevEdge e, const 
       for (unsigned ch = 0; ch < g.nchunks; ++ch)
       {
         double v[ICH], B[ICH];
-        if (keep)
-        {
-          const double *src = node + ((size_t)k * g.S + ch * ICH) * 64u + lane;
-#pragma unroll
-          for (int i = 0; i < ICH; ++i) v[i] = ch * ICH + i < g.S ? src[(size_t)i * 64] : 0.0;
-        }
-        else
-          product(k, ch, v);
-        contract<ICH, STIP>(B, e.mat, k, ch, g, STIP ? nullptr : sx + (size_t)k * g.S * 64, smask);
+        parked_or_product<ICH>(v, le, re, k, ch, g, node, keep, lane);
+        end_contract<ICH>(B, se, k, ch, g);
+        // rate_term_add's node form, written out: through the call the 20-state inner instantiation needs 170 registers, two
+        // more than the 168 at which three waves share a SIMD
         cdouble_p pi = as_const(e.freqs) + (size_t)fi * g.SP + ch * ICH;
 #pragma unroll
         for (int i = 0; i < ICH; ++i)
           if (ch * ICH + i < g.S) tr = fma((rescale ? v[i] * PLLGPU_SCALE_FACTOR : v[i]) * pi[i], B[i], tr);
       }
-      if (e.per_rate)
-        tr = rate_scaled(tr, scaler_sum_rate(lsc, nn, rsc, nn, g.R, k) + flags[k][lane] + scaler_sum_rate(ssc, nn, nullptr, 0, g.R, k), scal);
+      if (e.per_rate) tr = rate_scaled(tr, node_rate_scalings(lsc, rsc, ssc, nn, g.R, k, flags, lane), scal);
       edge_rate_add(e, g, k, tr, nn, terma, terminv);
     }
     part[0][wave][lane] = terma;
     part[1][wave][lane] = terminv;
     __syncthreads();
-    if (wave == 0 && valid)
+    if (wave == 0 && w.valid)
     {
-      double ta = part[0][0][lane], ti = part[1][0][lane];
-      for (unsigned w = 1; w < nw; ++w)
-      {
-        ta += part[0][w][lane];
-        ti += part[1][w][lane];
-      }
-      acc += finish_site(ta, ti, scal, 0) * (double)e.pattern_weights[n];
+      double s[2]; // terma, terminv
+      wave_order_sums(s, &part[0][0][lane], nw);
+      acc += finish_site(s[0], s[1], scal, 0) * (double)e.pattern_weights[w.n];
     }
     __syncthreads(); // flags[], part[] and node[] are reused by the next tile
   }

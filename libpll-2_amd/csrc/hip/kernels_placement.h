@@ -167,9 +167,9 @@ __global__ __launch_bounds__(256) void k_placement_dna(const DevEdge e, const In
 }
 
 // ------------------------------------------------------------------------------------------------
-// Every other shape: pass 1 of k_insertion_tiled as it stands (the inserted node's products into the LDS tile, the flags,
-// one barrier, the scaling decision); pass 2 once per query of the chunk over the same tile. (rescale ? v 2^256 : v) pi
-// is formed once per value and meets every query's (P x)_i in k_insertion_tiled's order of states. keep == 0 (the tile
+// Every other shape: the inserted node as k_insertion_tiled forms it (kernels_generic.h: node_first_pass into the LDS tile,
+// the flags, one barrier, node_site_scalings); pass 2 once per query of the chunk over the same tile. (rescale ? v 2^256 : v) pi
+// is formed once per value and meets every query's (P x)_i in rate_term_add's order of states. keep == 0 (the tile
 // does not fit beside the per-query words) forms the products again in pass 2, once per chunk.
 // What belongs to one query of the chunk - the lane's state mask, the wave's running rate term, its two site sums, wave
 // 0's sum over the tiles - lives in LDS (7 KB per query) and the loops over the chunk are not unrolled: the registers
@@ -187,10 +187,8 @@ __global__ __launch_bounds__(256) void k_placement_tiled(const DevEdge e, const 
   __shared__ double qacc[QCH][64];              // [query][lane], wave 0 only
   extern __shared__ double node[];              // keep: [rate][state][lane]
   const InsCand c = ins_get(cands, blockIdx.y);
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned lane = gen_lane(), wave = gen_wave();
   const unsigned nw = blockDim.x >> 6;
-  const unsigned ntiles = (e.sites + 63u) / 64u;
   const bool ltip = c.ltip != nullptr, rtip = c.rtip != nullptr; // wave-uniform
   const unsigned *lsc = ltip ? nullptr : c.lscaler, *rsc = rtip ? nullptr : c.rscaler, *ssc = nullptr; // a tip end has no scaler
   const unsigned q0 = blockIdx.z * QCH;
@@ -200,67 +198,21 @@ __global__ __launch_bounds__(256) void k_placement_tiled(const DevEdge e, const 
 
   for (unsigned t = 0; t < tiles_per_block; ++t)
   {
-    const unsigned tile = blockIdx.x * tiles_per_block + t;
-    if (tile >= ntiles) break; // whole workgroup
-    const unsigned n = tile * 64u + lane;
-    const bool valid = n < e.sites;
-    const unsigned nn = valid ? n : e.sites - 1;
+    if (!gen_has_tile(tiles_per_block, t, e.sites)) break;
+    const GenTile w = gen_tile(tiles_per_block, t, e.sites);
+    const unsigned nn = w.nn;
+    // the two ends of the candidate, whose product is the inserted node
     const unsigned long long lmask = ltip ? tip_mask(tipmap, c.ltip[nn]) : 0ull;
     const unsigned long long rmask = rtip ? tip_mask(tipmap, c.rtip[nn]) : 0ull;
     for (unsigned j = wave; j < nqh; j += nw) qmask[j][lane] = tip_mask(tipmap, plc_row(qrows, q0 + j)[nn]); // read after the barrier
-    const size_t base = tiled_base(nn, g.tile_sz);
-    const double *__restrict__ lx = ltip ? nullptr : c.left + base;
-    const double *__restrict__ rx = rtip ? nullptr : c.right + base;
+    const GenEnd le = gen_end(c.lmat, ltip, c.left, nn, g, lmask), re = gen_end(c.rmat, rtip, c.right, nn, g, rmask);
 
-    // the inserted node's values of (rate k, chunk ch), unscaled: v[i] = A_i B_i
-    auto product = [&](unsigned k, unsigned ch, double (&v)[ICH]) {
-      double B[ICH];
-      if (ltip)
-        contract<ICH, true>(v, c.lmat, k, ch, g, nullptr, lmask);
-      else
-        contract<ICH, false>(v, c.lmat, k, ch, g, lx + (size_t)k * g.S * 64, 0ull);
-      if (rtip)
-        contract<ICH, true>(B, c.rmat, k, ch, g, nullptr, rmask);
-      else
-        contract<ICH, false>(B, c.rmat, k, ch, g, rx + (size_t)k * g.S * 64, 0ull);
-#pragma unroll
-      for (int i = 0; i < ICH; ++i) v[i] *= B[i];
-    };
-
-    for (unsigned k = wave; k < g.R; k += nw)
-    {
-      bool small = true;
-      for (unsigned ch = 0; ch < g.nchunks; ++ch)
-      {
-        double v[ICH];
-        product(k, ch, v);
-        double *dst = node + ((size_t)k * g.S + ch * ICH) * 64u + lane;
-#pragma unroll
-        for (int i = 0; i < ICH; ++i)
-          if (ch * ICH + i < g.S)
-          {
-            small = small && (v[i] < PLLGPU_SCALE_THRESHOLD);
-            if (keep) dst[(size_t)i * 64] = v[i];
-          }
-      }
-      flags[k][lane] = small ? 1 : 0;
-    }
+    for (unsigned k = wave; k < g.R; k += nw) flags[k][lane] = node_first_pass<ICH>(le, re, k, g, node, keep, lane) ? 1 : 0;
     __syncthreads(); // every rate's flag, every query's mask, and the values the wave itself parked
 
     // the site's scaling count: the children's and the inserted node's own decision
-    bool site_small = true;
-    unsigned scal;
-    if (e.per_rate)
-    {
-      scal = 0xFFFFFFFFu;
-      for (unsigned k = 0; k < g.R; ++k)
-        scal = min(scal, scaler_sum_rate(lsc, nn, rsc, nn, g.R, k) + flags[k][lane] + scaler_sum_rate(ssc, nn, nullptr, 0, g.R, k));
-    }
-    else
-    {
-      for (unsigned k = 0; k < g.R; ++k) site_small = site_small && flags[k][lane];
-      scal = scaler_sum(lsc, nn, rsc, nn) + (site_small ? 1u : 0u) + scaler_sum(ssc, nn, nullptr, 0);
-    }
+    bool site_small;
+    const unsigned scal = node_site_scalings(e.per_rate, lsc, rsc, ssc, nn, g.R, flags, lane, site_small);
 
     for (unsigned j = 0; j < nqh; ++j) part[j][0][wave][lane] = part[j][1][wave][lane] = 0.0; // terma, terminv
     for (unsigned k = wave; k < g.R; k += nw)
@@ -271,14 +223,8 @@ __global__ __launch_bounds__(256) void k_placement_tiled(const DevEdge e, const 
       for (unsigned ch = 0; ch < g.nchunks; ++ch)
       {
         double v[ICH];
-        if (keep)
-        {
-          const double *src = node + ((size_t)k * g.S + ch * ICH) * 64u + lane;
-#pragma unroll
-          for (int i = 0; i < ICH; ++i) v[i] = ch * ICH + i < g.S ? src[(size_t)i * 64] : 0.0;
-        }
-        else
-          product(k, ch, v);
+        parked_or_product<ICH>(v, le, re, k, ch, g, node, keep, lane);
+        // rate_term_add's a_i pi_i of a node, in place: formed once for every query of the chunk, then its fma per query
         cdouble_p pi = as_const(e.freqs) + (size_t)fi * g.SP + ch * ICH;
 #pragma unroll
         for (int i = 0; i < ICH; ++i)
@@ -299,27 +245,22 @@ __global__ __launch_bounds__(256) void k_placement_tiled(const DevEdge e, const 
       for (unsigned j = 0; j < nqh; ++j)
       {
         double tr = rate_term[j][wave][lane], terma = part[j][0][wave][lane], terminv = part[j][1][wave][lane];
-        if (e.per_rate)
-          tr = rate_scaled(tr, scaler_sum_rate(lsc, nn, rsc, nn, g.R, k) + flags[k][lane] + scaler_sum_rate(ssc, nn, nullptr, 0, g.R, k), scal);
+        if (e.per_rate) tr = rate_scaled(tr, node_rate_scalings(lsc, rsc, ssc, nn, g.R, k, flags, lane), scal);
         edge_rate_add(e, g, k, tr, nn, terma, terminv);
         part[j][0][wave][lane] = terma;
         part[j][1][wave][lane] = terminv;
       }
     }
     __syncthreads();
-    if (wave == 0 && valid)
+    if (wave == 0 && w.valid)
     {
 #pragma unroll 1
       for (unsigned j = 0; j < nqh; ++j)
       {
-        double ta = part[j][0][0][lane], ti = part[j][1][0][lane];
-        for (unsigned w = 1; w < nw; ++w)
-        {
-          ta += part[j][0][w][lane];
-          ti += part[j][1][w][lane];
-        }
+        double s[2]; // terma, terminv
+        wave_order_sums(s, &part[j][0][0][lane], nw);
         double acc = qacc[j][lane];
-        acc += finish_site(ta, ti, scal, 0) * (double)e.pattern_weights[n];
+        acc += finish_site(s[0], s[1], scal, 0) * (double)e.pattern_weights[w.n];
         qacc[j][lane] = acc;
       }
     }

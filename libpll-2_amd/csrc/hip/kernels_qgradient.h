@@ -26,7 +26,7 @@
 //   4 states x 4 categories (k_qgradient_dna): the lane owns a site, 16 accumulators per category in registers, a wave
 //   reduction at the end, the four waves added in wave order.
 //   every other shape (k_qgradient_mfma): the waves split the categories and form A and B per site with
-//   kernels_generic.h's contraction, as k_gradient_tiled does, but park them in LDS ([category][state][site], rows 65
+//   kernels_generic.h's end_contract over k_gradient_tiled's walk (gen_tile), but park them in LDS ([category][state][site], rows 65
 //   doubles apart: the lane-per-site stores and the operand reads below are both free of bank conflicts). Once the
 //   site's L is known the contraction over the tile's 64 sites runs on the fp64 matrix pipe: v_mfma_f64_16x16x4_f64,
 //   lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15], register t of the result is D[(l >> 4) + 4 t][l & 15]
@@ -203,10 +203,8 @@ __global__ __launch_bounds__(256) void k_qgradient_mfma(const DevEdge e, const D
   // the padding rows (states S .. Spad) stay zero: nothing below writes them
   for (unsigned idx = threadIdx.x; idx < 2u * g.R * Spad * kQgRow; idx += 256u) tA[idx] = 0.0;
   branch_diag(dg, b.t, ldiag); // (ends with a barrier)
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned lane = gen_lane(), wave = gen_wave();
   const unsigned r16 = lane & 15u, q4 = lane >> 4;
-  const unsigned ntiles = (e.sites + 63u) / 64u;
   const bool ltip = b.ltip != nullptr, rtip = b.rtip != nullptr; // wave-uniform
   const unsigned *lsc = e.per_rate ? b.lscaler : nullptr, *rsc = e.per_rate ? b.rscaler : nullptr;
   qg_double4 acc[NACC];
@@ -215,16 +213,13 @@ __global__ __launch_bounds__(256) void k_qgradient_mfma(const DevEdge e, const D
 
   for (unsigned t = 0; t < tiles_per_block; ++t)
   {
-    const unsigned tile = blockIdx.x * tiles_per_block + t;
-    if (tile >= ntiles) break; // whole workgroup
-    const unsigned n = tile * 64u + lane;
-    const bool valid = n < e.sites;
-    const unsigned nn = valid ? n : e.sites - 1;
+    if (!gen_has_tile(tiles_per_block, t, e.sites)) break;
+    const GenTile w = gen_tile(tiles_per_block, t, e.sites);
+    const unsigned nn = w.nn;
+    const bool valid = w.valid;
     const unsigned long long lmask = ltip ? tip_mask(tipmap, b.ltip[nn]) : 0ull;
     const unsigned long long rmask = rtip ? tip_mask(tipmap, b.rtip[nn]) : 0ull;
-    const size_t base = tiled_base(nn, g.tile_sz);
-    const double *__restrict__ lx = ltip ? nullptr : b.left + base;
-    const double *__restrict__ rx = rtip ? nullptr : b.right + base;
+    const GenEnd le = gen_end(m1, ltip, b.left, nn, g, lmask), re = gen_end(m2, rtip, b.right, nn, g, rmask);
     const unsigned mn = e.per_rate ? scaler_min(lsc, nn, rsc, nn, g.R) : 0u;
     const int inv = e.invariant ? e.invariant[nn] : -1;
 
@@ -236,14 +231,8 @@ __global__ __launch_bounds__(256) void k_qgradient_mfma(const DevEdge e, const D
       for (unsigned ch = 0; ch < g.nchunks; ++ch)
       {
         double A[ICH], B[ICH];
-        if (ltip)
-          contract<ICH, true>(A, m1, k, ch, g, nullptr, lmask);
-        else
-          contract<ICH, false>(A, m1, k, ch, g, lx + (size_t)k * g.S * 64, 0ull);
-        if (rtip)
-          contract<ICH, true>(B, m2, k, ch, g, nullptr, rmask);
-        else
-          contract<ICH, false>(B, m2, k, ch, g, rx + (size_t)k * g.S * 64, 0ull);
+        end_contract<ICH>(A, le, k, ch, g);
+        end_contract<ICH>(B, re, k, ch, g);
         const double *dk = ldiag + ((size_t)k * g.S + ch * ICH) * 4; // wave-uniform addresses: LDS broadcast
         double *oa = tA + ((size_t)k * Spad + ch * ICH) * kQgRow + lane, *ob = tB + ((size_t)k * Spad + ch * ICH) * kQgRow + lane;
 #pragma unroll

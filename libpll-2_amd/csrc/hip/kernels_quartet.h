@@ -243,9 +243,9 @@ __global__ __launch_bounds__(256, 2) void k_quartet_dna(const DevEdge e, const Q
 }
 
 // ------------------------------------------------------------------------------------------------
-// Every other shape (up to 64 states, any rate count): k_insertion_tiled's structure - workgroup = one tile of one quartet
-// at a time, wave w of min(R, 4) owns the rate categories w, w + nw, ..., the contraction is kernels_generic.h's - once per
-// arrangement:
+// Every other shape (up to 64 states, any rate count): the tiled kernels' shared pieces (kernels_generic.h: gen_tile,
+// node_first_pass, parked_or_product, rate_term_add, wave_order_sums) - workgroup = one tile of one quartet
+// at a time, wave w of min(R, 4) owns the rate categories w, w + nw, ... - once per arrangement:
 //   pass 1  both nodes' unscaled values A_i B_i of the wave's rates, with the "all below 2^-256" flag per (node, rate, lane);
 //   pass 2  after one barrier every rate's flags are known: the site's count is the four ends' counts plus both nodes' own
 //           decisions (per-rate scalers: the minimum over the rates, terms brought to it with rate_scaled). Rate by rate the
@@ -265,21 +265,17 @@ __global__ __launch_bounds__(256) void k_quartet_tiled(const DevEdge e, const Qu
   __shared__ double part[2][4][64];
   extern __shared__ double node[]; // keep: [2][rate][state][lane]; else [wave][state][lane]
   const QuartetDesc q = quartet_get(quartets, blockIdx.y);
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned lane = gen_lane(), wave = gen_wave();
   const unsigned nw = blockDim.x >> 6;
-  const unsigned ntiles = (e.sites + 63u) / 64u;
   const size_t node_sz = (size_t)g.R * g.S * 64u;
   double acc[3] = {0.0, 0.0, 0.0};
 
   for (unsigned t = 0; t < tiles_per_block; ++t)
   {
-    const unsigned tile = blockIdx.x * tiles_per_block + t;
-    if (tile >= ntiles) break; // whole workgroup
-    const unsigned n = tile * 64u + lane;
-    const bool valid = n < e.sites;
-    const unsigned nn = valid ? n : e.sites - 1;
-    const size_t base = tiled_base(nn, g.tile_sz);
+    if (!gen_has_tile(tiles_per_block, t, e.sites)) break;
+    const GenTile w = gen_tile(tiles_per_block, t, e.sites);
+    const unsigned tile = w.tile, nn = w.nn;
+    const bool valid = w.valid;
     const unsigned long long mask[4] = {q.end[0].tip ? tip_mask(tipmap, q.end[0].tip[nn]) : 0ull, q.end[1].tip ? tip_mask(tipmap, q.end[1].tip[nn]) : 0ull,
                                         q.end[2].tip ? tip_mask(tipmap, q.end[2].tip[nn]) : 0ull, q.end[3].tip ? tip_mask(tipmap, q.end[3].tip[nn]) : 0ull};
     const unsigned *const esc[4] = {q.end[0].tip ? nullptr : q.end[0].scaler, q.end[1].tip ? nullptr : q.end[1].scaler,
@@ -296,55 +292,18 @@ __global__ __launch_bounds__(256) void k_quartet_tiled(const DevEdge e, const Qu
       const unsigned long long mb0 = z == 1 ? mask[1] : mask[2], mb1 = ww == 2 ? mask[2] : mask[3];
       const bool decides1 = quartet_pair_decides(q.tt_rule, 0, y), decides2 = quartet_pair_decides(q.tt_rule, z, ww);
 
-      // (P x) of one end, (rate k, chunk ch)
-      auto applied = [&](const QEnd &x, unsigned long long m, unsigned k, unsigned ch, double (&v)[ICH]) __attribute__((always_inline)) {
-        if (x.tip) // wave-uniform
-          contract<ICH, true>(v, x.mat, k, ch, g, nullptr, m);
-        else
-          contract<ICH, false>(v, x.mat, k, ch, g, x.clv + base + (size_t)k * g.S * 64, 0ull);
-      };
-      // a node of (rate k, chunk ch), unscaled: v[i] = A_i B_i
-      auto product1 = [&](unsigned k, unsigned ch, double (&v)[ICH]) __attribute__((always_inline)) {
-        double B[ICH];
-        applied(a0, ma0, k, ch, v);
-        applied(a1, ma1, k, ch, B);
-#pragma unroll
-        for (int i = 0; i < ICH; ++i) v[i] *= B[i];
-      };
-      auto product2 = [&](unsigned k, unsigned ch, double (&v)[ICH]) __attribute__((always_inline)) {
-        double B[ICH];
-        applied(b0, mb0, k, ch, v);
-        applied(b1, mb1, k, ch, B);
-#pragma unroll
-        for (int i = 0; i < ICH; ++i) v[i] *= B[i];
-      };
+      // the ends as the contraction reads them: the first node is above ea0 and ea1, the second above eb0 and eb1
+      const GenEnd ea0 = gen_end(a0.mat, a0.tip != nullptr, a0.clv, nn, g, ma0), ea1 = gen_end(a1.mat, a1.tip != nullptr, a1.clv, nn, g, ma1);
+      const GenEnd eb0 = gen_end(b0.mat, b0.tip != nullptr, b0.clv, nn, g, mb0), eb1 = gen_end(b1.mat, b1.tip != nullptr, b1.clv, nn, g, mb1);
       // the ends' counts of rate k (per-rate scalers) under both nodes
       auto below_rate = [&](unsigned k) __attribute__((always_inline)) {
         return scaler_sum_rate(esc[0], nn, esc[1], nn, g.R, k) + scaler_sum_rate(esc[2], nn, esc[3], nn, g.R, k);
       };
-      // pass 1 of one node: its flag of rate k, its values parked where keep says so
-      auto first_pass = [&](auto &&product, double *park, bool decides, unsigned char (&flag)[kMaxRates][64], unsigned k) __attribute__((always_inline)) {
-        bool small = true;
-        for (unsigned ch = 0; ch < g.nchunks; ++ch)
-        {
-          double v[ICH];
-          product(k, ch, v);
-          double *dst = park + ((size_t)k * g.S + ch * ICH) * 64u + lane;
-#pragma unroll
-          for (int i = 0; i < ICH; ++i)
-            if (ch * ICH + i < g.S)
-            {
-              small = small && (v[i] < PLLGPU_SCALE_THRESHOLD);
-              if (keep) dst[(size_t)i * 64] = v[i];
-            }
-        }
-        flag[k][lane] = (small && decides) ? 1 : 0;
-      };
 
       for (unsigned k = wave; k < g.R; k += nw)
       {
-        first_pass(product1, node, decides1, flags[0], k);
-        first_pass(product2, node + node_sz, decides2, flags[1], k);
+        flags[0][k][lane] = (node_first_pass<ICH>(ea0, ea1, k, g, node, keep, lane) && decides1) ? 1 : 0;
+        flags[1][k][lane] = (node_first_pass<ICH>(eb0, eb1, k, g, node + node_sz, keep, lane) && decides2) ? 1 : 0;
       }
       __syncthreads(); // every rate's flags
 
@@ -376,13 +335,7 @@ __global__ __launch_bounds__(256) void k_quartet_tiled(const DevEdge e, const Qu
         {
           double v[ICH];
           double *at = second + (size_t)ch * ICH * 64u;
-          if (keep)
-          {
-#pragma unroll
-            for (int i = 0; i < ICH; ++i) v[i] = ch * ICH + i < g.S ? at[(size_t)i * 64] : 0.0;
-          }
-          else
-            product2(k, ch, v);
+          parked_or_product<ICH>(v, eb0, eb1, k, ch, g, node + node_sz, keep, lane);
           if (keep && !rescale2) continue; // as parked
 #pragma unroll
           for (int i = 0; i < ICH; ++i)
@@ -393,19 +346,9 @@ __global__ __launch_bounds__(256) void k_quartet_tiled(const DevEdge e, const Qu
         for (unsigned ch = 0; ch < g.nchunks; ++ch)
         {
           double v[ICH], B[ICH];
-          if (keep)
-          {
-            const double *src = node + ((size_t)k * g.S + ch * ICH) * 64u + lane;
-#pragma unroll
-            for (int i = 0; i < ICH; ++i) v[i] = ch * ICH + i < g.S ? src[(size_t)i * 64] : 0.0;
-          }
-          else
-            product1(k, ch, v);
+          parked_or_product<ICH>(v, ea0, ea1, k, ch, g, node, keep, lane);
           contract<ICH, false>(B, q.inner, k, ch, g, second, 0ull);
-          cdouble_p pi = as_const(e.freqs) + (size_t)fi * g.SP + ch * ICH;
-#pragma unroll
-          for (int i = 0; i < ICH; ++i)
-            if (ch * ICH + i < g.S) tr = fma((rescale1 ? v[i] * PLLGPU_SCALE_FACTOR : v[i]) * pi[i], B[i], tr);
+          tr = rate_term_add<ICH>(tr, v, rescale1, as_const(e.freqs) + (size_t)fi * g.SP + ch * ICH, B, ch, g);
         }
         if (e.per_rate) tr = rate_scaled(tr, below_rate(k) + flags[0][k][lane] + flags[1][k][lane], scal);
         edge_rate_add(e, g, k, tr, nn, terma, terminv);
@@ -415,13 +358,9 @@ __global__ __launch_bounds__(256) void k_quartet_tiled(const DevEdge e, const Qu
       __syncthreads();
       if (wave == 0 && (valid || PS))
       {
-        double ta = part[0][0][lane], ti = part[1][0][lane];
-        for (unsigned w = 1; w < nw; ++w)
-        {
-          ta += part[0][w][lane];
-          ti += part[1][w][lane];
-        }
-        const double u = finish_site(ta, ti, scal, 0), pw = (double)e.pattern_weights[nn];
+        double s[2]; // terma, terminv
+        wave_order_sums(s, &part[0][0][lane], nw);
+        const double u = finish_site(s[0], s[1], scal, 0), pw = (double)e.pattern_weights[nn];
         if constexpr (PS) quartet_site_store(ps, e, a, tile, nn, valid, u, u * pw);
         if (valid)
         {

@@ -1426,6 +1426,10 @@ static int resolve_op(pllgpu_ctx *c, const pllgpu_op_t &o, DevOp &d)
   return 0;
 }
 
+// the workgroup of every kernel over the tiled layout: one wave per rate category of the tile, up to 4
+static unsigned tiled_waves(const pllgpu_ctx *c) { return std::min(c->gg.R, 4u); }
+static unsigned tiled_threads(const pllgpu_ctx *c) { return 64u * tiled_waves(c); }
+
 template <int ICH>
 static void launch_generic(pllgpu_ctx *c, const OpPack &pack, unsigned nops, unsigned maxent, unsigned kind, bool gather)
 {
@@ -1433,7 +1437,7 @@ static void launch_generic(pllgpu_ctx *c, const OpPack &pack, unsigned nops, uns
   const unsigned tiles = (maxent + 63) / 64;
   const unsigned long long *tm = tipmap_ptr(c);
   // tip children: room in LDS for the staged matrices of every wave (kernels_generic.h: tip_stage)
-  const unsigned nw = std::min(c->gg.R, 4u);
+  const unsigned nw = tiled_waves(c);
   const bool stage = kind != 0 && c->gg.S * c->gg.SPT <= 1024u && !c->no_tip_columns;
   const unsigned tip_lds = stage ? 1u : 0u;
   size_t lds = stage ? (size_t)2 * nw * (c->gg.S + 1u) * (c->gg.SPT | 1u) * sizeof(double) : 0;
@@ -2389,9 +2393,8 @@ template <int ICH>
 static void launch_edge_generic(pllgpu_ctx *c, const DevEdge &e, unsigned blocks, unsigned tpw, bool ctip, bool gather)
 {
   const unsigned long long *tm = tipmap_ptr(c);
-  const unsigned threads = 64u * std::min(c->gg.R, 4u); // one wave per rate category of the tile, up to 4
   with_bools(ctip, gather, [&](auto CT, auto GA) {
-    hipLaunchKernelGGL((k_edge_tiled<ICH, CT(), GA()>), dim3(blocks), dim3(threads), 0, c->stream, e, c->gg, tm, tpw);
+    hipLaunchKernelGGL((k_edge_tiled<ICH, CT(), GA()>), dim3(blocks), dim3(tiled_threads(c)), 0, c->stream, e, c->gg, tm, tpw);
   });
 }
 
@@ -2489,17 +2492,22 @@ static int launch_edge_mfma(pllgpu_ctx *c, DevEdge &e, bool ctip, bool gather)
   return 0;
 }
 
-// The tile walk of every kernel that sums over the sites (the edge evaluation and each batched call): the grid's x axis
-// and the tiles each wave or workgroup walks. The order of every sum follows from it, so it depends on the site count
-// and the shape alone, and this is the only place it is written.
+// The tile walk of every kernel whose grid is cut by the site count alone (the edge evaluation, each batched call, the
+// per-site tables): the grid's x axis and the tiles each wave or workgroup walks, at most max_blocks workgroups' worth.
+// The order of every sum over the sites follows from it, so it depends on the site count and the shape alone. Every such
+// walk goes through this function; the three bounds in use are named here and in qgradient_walk.
 struct TileWalk
 {
   unsigned blocks, tiles_per;
 };
 
-static TileWalk tile_walk(const pllgpu_ctx *c)
+constexpr unsigned kSumBlocks = 1024;   // kernels that sum over the sites: a slot per workgroup to add up
+constexpr unsigned kTableBlocks = 4096; // kernels that leave a table per site (ancestral states, category likelihoods): a read
+                                        // stream with a short store, one tile per wave as long as that is no more (kernels_dna.h, "Tiles per wave")
+
+static TileWalk tile_walk(const pllgpu_ctx *c, unsigned max_blocks = kSumBlocks)
 {
-  const unsigned tiles = (c->geo.sites + 63) / 64, max_blocks = 1024;
+  const unsigned tiles = (c->geo.sites + 63) / 64;
   TileWalk w;
   if (c->dna_fast)
   {
@@ -2950,6 +2958,9 @@ constexpr size_t kInsMaxSlots = (size_t)4 << 20;  // 32 MB of partial sums per l
 constexpr size_t kInsLdsMax = 144 * 1024;         // the inserted node's tile in LDS, beside the kernel's static 8 KB
 constexpr size_t kPlcLdsMax = 126 * 1024;         // ... beside k_placement_tiled's static 32 KB (the flags, 7 KB per query of the chunk, the hand-off's words)
 
+// keep (1) or form again in pass 2 (0): do the node tiles a workgroup would park, `bytes` of them, fit the kernel's share of LDS?
+static unsigned keep_in_lds(size_t bytes, size_t limit) { return bytes <= limit ? 1u : 0u; }
+
 // Scratch that no kept plan points at: (re)allocating it must not move the context's allocation epoch, or the first
 // batched call would drop every cached launch plan of the partition.
 struct ScratchEpoch
@@ -3096,10 +3107,10 @@ static int launch_insertions(pllgpu_ctx *c, DevEdge e, const TileWalk &w, const 
     });
   else
   {
-    const unsigned threads = 64u * std::min(c->gg.R, 4u);
-    size_t lds = (size_t)c->gg.tile_sz * sizeof(double);
-    const unsigned keep = lds <= kInsLdsMax ? 1u : 0u;
-    if (!keep) lds = 0;
+    const unsigned threads = tiled_threads(c);
+    const size_t node_bytes = (size_t)c->gg.tile_sz * sizeof(double);
+    const unsigned keep = keep_in_lds(node_bytes, kInsLdsMax);
+    const size_t lds = keep ? node_bytes : 0;
     const unsigned long long *tm = tipmap_ptr(c);
     with_ich(c->ich, [&](auto ICH) {
       with_bools(stip, false, [&](auto ST, auto) {
@@ -3176,10 +3187,10 @@ static int launch_placements(pllgpu_ctx *c, DevEdge e, const PlacementCut &k, un
     hipLaunchKernelGGL((k_placement_dna<kPlcDnaChunk>), grid, dim3(256), 0, c->stream, e, dc, rows, nq, count, c->gg.scale_mode, k.tiles_per);
   else
   {
-    const unsigned threads = 64u * std::min(c->gg.R, 4u);
-    size_t lds = (size_t)c->gg.tile_sz * sizeof(double);
-    const unsigned keep = lds <= kPlcLdsMax ? 1u : 0u;
-    if (!keep) lds = 0;
+    const unsigned threads = tiled_threads(c);
+    const size_t node_bytes = (size_t)c->gg.tile_sz * sizeof(double);
+    const unsigned keep = keep_in_lds(node_bytes, kPlcLdsMax);
+    const size_t lds = keep ? node_bytes : 0;
     const unsigned long long *tm = tipmap_ptr(c);
     with_ich(c->ich, [&](auto ICH) {
       raise_lds_limit(reinterpret_cast<const void *>(&k_placement_tiled<ICH(), kPlcTiledChunk>), c->device, lds);
@@ -3274,16 +3285,15 @@ static int launch_quartets(pllgpu_ctx *c, DevEdge e, const TileWalk &w, const pl
     });
   else
   {
-    const unsigned nw = std::min(c->gg.R, 4u);
     const size_t node_bytes = (size_t)c->gg.R * c->gg.S * 64u * sizeof(double);
     // both nodes of an arrangement in LDS, or (recompute path) one rate of the second node per wave
-    const unsigned keep = 2 * node_bytes <= kInsLdsMax ? 1u : 0u;
-    const size_t lds = keep ? 2 * node_bytes : (size_t)nw * c->gg.S * 64u * sizeof(double);
+    const unsigned keep = keep_in_lds(2 * node_bytes, kInsLdsMax);
+    const size_t lds = keep ? 2 * node_bytes : (size_t)tiled_waves(c) * c->gg.S * 64u * sizeof(double);
     const unsigned long long *tm = tipmap_ptr(c);
     with_ich(c->ich, [&](auto ICH) {
       with_bools(sites, false, [&](auto PS, auto) {
         raise_lds_limit(reinterpret_cast<const void *>(&k_quartet_tiled<ICH(), PS()>), c->device, lds);
-        hipLaunchKernelGGL((k_quartet_tiled<ICH(), PS()>), dim3(w.blocks, n), dim3(64u * nw), lds, c->stream, e, dq, c->gg, tm, count, w.tiles_per, keep, ps);
+        hipLaunchKernelGGL((k_quartet_tiled<ICH(), PS()>), dim3(w.blocks, n), dim3(tiled_threads(c)), lds, c->stream, e, dq, c->gg, tm, count, w.tiles_per, keep, ps);
       });
     });
   }
@@ -3662,13 +3672,12 @@ static int launch_branches(pllgpu_ctx *c, DevEdge e, const TileWalk &w, const De
     });
   else
   {
-    const unsigned nw = std::min(c->gg.R, 4u);
     const size_t lds = branch_lds(c, cat);
     const unsigned long long *tm = tipmap_ptr(c);
     with_ich(c->ich, [&](auto ICH) {
       with_bools(cat, false, [&](auto CAT, auto) {
         raise_lds_limit(reinterpret_cast<const void *>(&k_gradient_tiled<ICH(), CAT()>), c->device, lds);
-        hipLaunchKernelGGL((k_gradient_tiled<ICH(), CAT()>), dim3(w.blocks, n), dim3(64u * nw), lds, c->stream, e, dg, db, m1, m2, c->gg, tm, count,
+        hipLaunchKernelGGL((k_gradient_tiled<ICH(), CAT()>), dim3(w.blocks, n), dim3(tiled_threads(c)), lds, c->stream, e, dg, db, m1, m2, c->gg, tm, count,
                            w.tiles_per);
       });
     });
@@ -3805,21 +3814,9 @@ static_assert(kQgMaxBlocks == PLLGPU_QGRADIENT_MAX_BLOCKS && kQgLdsMax == PLLGPU
 // (include/pll_amd_device.h states the rule)
 static TileWalk qgradient_walk(const pllgpu_ctx *c)
 {
-  const unsigned tiles = (c->geo.sites + 63) / 64;
-  TileWalk w;
-  if (c->dna_fast)
-  {
-    w.tiles_per = (tiles + 4 * kQgMaxBlocks - 1) / (4 * kQgMaxBlocks);
-    w.blocks = (tiles + 4 * w.tiles_per - 1) / (4 * w.tiles_per);
-  }
-  else
-  {
-    const unsigned spad = (c->geo.states + 15u) / 16u * 16u;
-    const unsigned bmax = std::min(kQgMaxBlocks, std::max(4u, 16384u / (spad * spad)));
-    w.tiles_per = (tiles + bmax - 1) / bmax;
-    w.blocks = (tiles + w.tiles_per - 1) / w.tiles_per;
-  }
-  return w;
+  if (c->dna_fast) return tile_walk(c, kQgMaxBlocks);
+  const unsigned spad = (c->geo.states + 15u) / 16u * 16u;
+  return tile_walk(c, std::min(kQgMaxBlocks, std::max(4u, 16384u / (spad * spad))));
 }
 
 // the accumulator blocks a wave of k_qgradient_mfma holds -> fn(Int<NACC>)
@@ -3937,36 +3934,32 @@ extern "C" int pllgpu_qmatrix_gradient(pllgpu_ctx_t *c, const pllgpu_branch_t *b
 }
 
 // ---- marginal ancestral states (kernels_ancestral.h) -------------------------------------------------------
-template <int ICH>
-static void launch_ancestral_generic(pllgpu_ctx *c, const DevAncestral &a, unsigned blocks, unsigned tpw, bool ctip)
+// One launch that leaves a table per site (ancestral states here, the category likelihoods below): the 4 x 4 form or the
+// tiled one of the shape, over tile_walk's table form, for a child end that is a tip or not. dna(CT, w) and
+// tiled(ICH, CT, w) launch the two forms.
+template <class Dna, class Tiled>
+static void launch_site_table(pllgpu_ctx *c, bool ctip, Dna &&dna, Tiled &&tiled)
 {
-  const unsigned long long *tm = tipmap_ptr(c);
-  const unsigned nw = std::min(c->gg.R, 4u); // one wave per rate category of the tile, up to 4
-  const size_t lds = ((size_t)nw * c->gg.S * 64u + (size_t)nw * 64u) * sizeof(double);
+  const TileWalk w = tile_walk(c, kTableBlocks);
   with_bools(ctip, false, [&](auto CT, auto) {
-    raise_lds_limit(reinterpret_cast<const void *>(&k_ancestral_tiled<ICH, CT()>), c->device, lds);
-    hipLaunchKernelGGL((k_ancestral_tiled<ICH, CT()>), dim3(blocks), dim3(64u * nw), lds, c->stream, a, c->gg, tm, tpw);
+    if (c->dna_fast)
+      dna(CT, w);
+    else
+      with_ich(c->ich, [&](auto ICH) { tiled(ICH, CT, w); });
   });
 }
 
-// the call's one launch: the 4 x 4 form or the tiled one, tile walk as launch_edge
+// the call's one launch
 static void launch_ancestral(pllgpu_ctx *c, const DevAncestral &a, bool ctip)
 {
-  const unsigned tiles = (c->geo.sites + 63) / 64;
-  const unsigned max_blocks = 1024;
-  if (c->dna_fast)
-  {
-    // one tile per wave up to 4096 workgroups (kernels_dna.h, "Tiles per wave"): the kernel is a read stream with a short store
-    const unsigned tpw = (tiles + 4 * 4 * max_blocks - 1) / (4 * 4 * max_blocks);
-    const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
-    with_bools(ctip, false, [&](auto CT, auto) {
-      hipLaunchKernelGGL((k_ancestral_dna<CT()>), dim3(blocks), dim3(256), 0, c->stream, a, tpw);
-    });
-    return;
-  }
-  const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
-  const unsigned blocks = (tiles + tpw - 1) / tpw;
-  with_ich(c->ich, [&](auto ICH) { launch_ancestral_generic<ICH()>(c, a, blocks, tpw, ctip); });
+  launch_site_table(
+      c, ctip, [&](auto CT, const TileWalk &w) { hipLaunchKernelGGL((k_ancestral_dna<CT()>), dim3(w.blocks), dim3(256), 0, c->stream, a, w.tiles_per); },
+      [&](auto ICH, auto CT, const TileWalk &w) {
+        const unsigned nw = tiled_waves(c);
+        const size_t lds = ((size_t)nw * c->gg.S * 64u + (size_t)nw * 64u) * sizeof(double);
+        raise_lds_limit(reinterpret_cast<const void *>(&k_ancestral_tiled<ICH(), CT()>), c->device, lds);
+        hipLaunchKernelGGL((k_ancestral_tiled<ICH(), CT()>), dim3(w.blocks), dim3(64u * nw), lds, c->stream, a, c->gg, tipmap_ptr(c), w.tiles_per);
+      });
 }
 
 extern "C" int pllgpu_node_ancestral(pllgpu_ctx_t *c, const pllgpu_edge_t *ed, double *host_out, void *device_out)
@@ -4063,31 +4056,14 @@ static int category_begin(pllgpu_ctx *c, const pllgpu_edge_t *ed, const char *no
   return 0;
 }
 
-template <int ICH>
-static void launch_category_generic(pllgpu_ctx *c, const DevCategory &a, unsigned blocks, unsigned tpw, bool ctip)
-{
-  const unsigned long long *tm = tipmap_ptr(c);
-  const unsigned nw = std::min(c->gg.R, 4u); // one wave per rate category of the tile, up to 4
-  with_bools(ctip, false, [&](auto CT, auto) {
-    hipLaunchKernelGGL((k_category_tiled<ICH, CT()>), dim3(blocks), dim3(64u * nw), 0, c->stream, a, c->gg, tm, tpw);
-  });
-}
-
-// stage A: the 4 x 4 form or the tiled one, tile walk as launch_ancestral
+// stage A
 static int launch_category_table(pllgpu_ctx *c, const CategoryCall &k)
 {
-  const unsigned tiles = (c->geo.sites + 63) / 64;
-  const unsigned max_blocks = 1024;
-  if (c->dna_fast)
-  {
-    const unsigned tpw = (tiles + 4 * 4 * max_blocks - 1) / (4 * 4 * max_blocks);
-    const unsigned blocks = (tiles + 4 * tpw - 1) / (4 * tpw);
-    with_bools(k.ctip, false, [&](auto CT, auto) { hipLaunchKernelGGL((k_category_dna<CT()>), dim3(blocks), dim3(256), 0, c->stream, k.a, tpw); });
-    return launched(c);
-  }
-  const unsigned tpw = (tiles + 4 * max_blocks - 1) / (4 * max_blocks);
-  const unsigned blocks = (tiles + tpw - 1) / tpw;
-  with_ich(c->ich, [&](auto ICH) { launch_category_generic<ICH()>(c, k.a, blocks, tpw, k.ctip); });
+  launch_site_table(
+      c, k.ctip, [&](auto CT, const TileWalk &w) { hipLaunchKernelGGL((k_category_dna<CT()>), dim3(w.blocks), dim3(256), 0, c->stream, k.a, w.tiles_per); },
+      [&](auto ICH, auto CT, const TileWalk &w) {
+        hipLaunchKernelGGL((k_category_tiled<ICH(), CT()>), dim3(w.blocks), dim3(tiled_threads(c)), 0, c->stream, k.a, c->gg, tipmap_ptr(c), w.tiles_per);
+      });
   return launched(c);
 }
 

@@ -129,7 +129,7 @@ def _kinds_rows(bed, dense):
     rows = rows + GC.flipped(rows)
     if dense:
         lay = bed.lay
-        assert bed.lib.pll_set_tip_clv(bed.p, lay.T, api.dptr(_dense_tip(bed.sites, bed.states)), 1), (bed.lib.errno(), bed.lib.errmsg())
+        assert bed.lib.pll_set_tip_clv(bed.p, lay.T, api.dptr(_dense_tip(bed.sites, bed.states)), 0), (bed.lib.errno(), bed.lib.errmsg())
         inner = next(r for r in rows if r[0] >= lay.tips and r[1] >= 0)
         extra = [(lay.T, IC.NONE, lay.T + 1, IC.NONE, 0.1), (inner[0], inner[1], lay.T, IC.NONE, 0.2)]
         rows = rows + extra + GC.flipped(extra)
