@@ -417,7 +417,10 @@ int pllgpu_qmatrix_gradient(pllgpu_ctx_t *ctx, const pllgpu_branch_t *branches, 
  * are not used. Exactly one of the outputs is non-NULL: host_out - the table is copied back and the call waits;
  * device_out - sites * states doubles of DEVICE memory, the call returns once the kernel is enqueued on the
  * context's stream. One launch, counted into pllgpu_last_launch_count. With per-rate scalers the counts of both
- * ends are honoured (kernels_ancestral.h), which the reference does not do. */
+ * ends are honoured (kernels_ancestral.h), which the reference does not do.
+ * The cutting rule is stage A's of pllgpu_edge_category_posteriors below: 4 x 4 with T = ceil(sites / 64), w =
+ * ceil(T / 16384) tiles per wave, ceil(T / (4 w)) workgroups of 256; every other shape w = ceil(T / 4096) tiles per
+ * workgroup, ceil(T / w) workgroups of 64 min(rate_cats, 4). */
 int pllgpu_node_ancestral(pllgpu_ctx_t *ctx, const pllgpu_edge_t *edge, double *host_out, void *device_out);
 
 /* The per-category site likelihoods of an edge and what model optimisation makes of them (kernels_category.h). With

@@ -200,7 +200,8 @@ __global__ __launch_bounds__(256) void k_partials_lean(const OpPack pack, const 
     {
       request(item + 1u, nxt.le, op.left, op.ltip, LTIP, on.xl, on.pl, on.cl);
       request(item + 1u, nxt.re, op.right, op.rtip, RTIP, on.xr, on.pr, on.cr);
-      if (GATHER && item + 2u < item_end) entries_of(item + 2u, nn2);
+      // (a tip child is read through its entries in a plain launch too: its codes are tip[entry])
+      if ((GATHER || LTIP || RTIP) && item + 2u < item_end) entries_of(item + 2u, nn2);
     }
     const unsigned e0 = item * 32u + 2u * col;
     const bool valid[2] = {e0 < op.entries, e0 + 1u < op.entries};
