@@ -1096,6 +1096,54 @@ int pll_gpu_subst_gradient(pll_partition_t *partition, const pll_gpu_branch_t *b
                            const unsigned int *params_indices,
                            double *d_subst /* [rate_matrices][states (states-1)/2] or NULL */,
                            double *d_freqs /* [rate_matrices][states] or NULL */);
+/* ---- maximum-likelihood distances between tips --------------------------
+ * The input of every distance method (NJ / BIONJ starting and guide trees, pre-filters for placement, saturation checks):
+ * for every two tips of a list the branch length that maximises the likelihood of the two sequences alone, under the
+ * partition's own model - in one call, without a CLV, a sumtable or a launch per evaluation.
+ * For x = tips[i], y = tips[j], i < j: distance[i][j] is the t at which the safeguarded Newton recipe of
+ * pll_gpu_optimize_branch_length (above; restated in pllamd/newton.py) stops when it is applied to the function that
+ * pll_update_sumtable(partition, x, y, PLL_SCALE_BUFFER_NONE, PLL_SCALE_BUFFER_NONE, params_indices, ..) followed by
+ * pll_compute_likelihood_derivatives evaluates, with x in the left role (contraction matrix 1) and y in the right; the same
+ * t_start, t_min, t_max, tolerance and max_iters for every pair; options->matrix_index must be -1. d_f / dd_f are the
+ * derivatives of -lnL at the returned distance (the last point evaluated), status one of PLL_GPU_NEWTON_*, iterations the
+ * derivative evaluations performed. [i][j] and [j][i] of every array receive the same bits from one computation, diagonal
+ * entries are 0, and a tip that appears twice makes an ordinary pair (AT_MIN, or CONVERGED on a flat function).
+ * p_distance: with n_ab the summed pattern weight of the sites where the pair shows the codes (a, b), the sum of n_ab over
+ * the code pairs whose state sets are disjoint, divided by the sum over the code pairs in which neither code is the
+ * all-states set; 0 where that denominator is 0. Two integer sums and one division.
+ * How: a site's sumtable row depends on its pair of codes alone, so the alignment enters only through n_ab. A workgroup
+ * counts one pair's n_ab in one pass over the two code rows and runs the whole iteration on that table; nothing is
+ * written to device memory but the answers. A pair's bits depend on its own two code rows, the model and the options
+ * alone - not on the list, the position in it or how the list is cut into launches.
+ * Every tip must be given by codes: a PLL_ATTRIB_PATTERN_TIP tip, or a tip set through pll_set_tip_states / an indicator
+ * pll_set_tip_clv that the device holds as codes. Nothing in the partition is written (an invalid eigensystem is computed
+ * first, as pll_update_sumtable does); what pll_update_partials holds back is launched first. Synchronous: one copy back,
+ * one wait. pll_gpu_last_launch_count reports the launches (the rule: include/pll_amd_device.h, pllgpu_pairwise_distances).
+ * PLL_SUCCESS, or PLL_FAILURE with pll_errno, the usual line on stderr and every output untouched. Everything is refused
+ * before anything is flushed or launched, in this order: PLL_ERROR_PARAM_INVALID for a NULL partition, out or
+ * out->distance; with count > 0 for a NULL tips, params_indices or options, a tips[i] >= tips, the option checks of
+ * pll_gpu_optimize_branch_length, matrix_index != -1, a params_indices[k] >= rate_matrices, a tip not given by codes (a
+ * dense pll_set_tip_clv tip, a partition without tip codes); PLL_ERROR_GPU_UNSUPPORTED for PLL_ATTRIB_SITE_REPEATS and
+ * ascertainment-bias partitions, for prop_invar > 0 of a used rate matrix (the invariant-site term is a property of the
+ * alignment column, not of the code pair), for a device code table beyond the limit (at most PLLGPU_DISTANCE_MAX_CODES =
+ * 128 codes and the LDS rule of include/pll_amd_device.h: 16 codes for 4 states, one per distinct state set otherwise -
+ * a 61-state alignment with ambiguity codes has about 64) and for pattern weights that add up to 2^32 or more;
+ * PLL_ERROR_GPU_UNAVAILABLE without a device. count == 0 succeeds at once (after the first check; nothing else is read,
+ * nothing written); count == 1 passes every check and succeeds without a launch, its one diagonal entry set to 0.
+ * Not offered: invariant sites, site repeats, ascertainment bias, distances that involve inner nodes, the NJ tree itself. */
+typedef struct pll_gpu_distances
+{
+  double *distance;          /* [count*count], required: D[x*count+y], symmetric, 0 on the diagonal */
+  double *p_distance;        /* NULL or [count*count] */
+  double *d_f, *dd_f;        /* NULL or [count*count]: derivatives of -lnL at the returned distance */
+  int *status;               /* NULL or [count*count]: PLL_GPU_NEWTON_* */
+  unsigned int *iterations;  /* NULL or [count*count]: derivative evaluations performed */
+} pll_gpu_distances_t;
+
+int pll_gpu_pairwise_distances(pll_partition_t *partition, const unsigned int *tips, unsigned int count,
+                               const unsigned int *params_indices, const pll_gpu_newton_t *options,
+                               const pll_gpu_distances_t *out);
+
 /* ---- rate-category posteriors, site rates and EM weight steps ----------
  * The per-category site likelihoods of one edge - what every evaluation kernel mixes away in registers - and what model
  * optimisation makes of them: FreeRate (+R) and mixture (LG4X) weights, empirical-Bayes site rates, a pinv step. The

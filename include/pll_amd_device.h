@@ -539,6 +539,49 @@ typedef struct pllgpu_newton_result
 int pllgpu_optimize_branch_length(pllgpu_ctx_t *ctx, unsigned int slot, const unsigned int *params_indices,
                                   unsigned int eval_sites, const pllgpu_newton_t *options, pllgpu_newton_result_t *result,
                                   double *trace);
+
+/* Maximum-likelihood distances between the tips of a list (kernels_distance.h; include/pll_amd.h, pll_gpu_pairwise_distances,
+ * holds the definitions): for list positions x < y the branch length at which the recipe of pllgpu_optimize_branch_length
+ * stops on the tip-tip function of (tips[x], tips[y]), tips[x] in the left role (contraction matrix 0 of
+ * pllgpu_aux_matrix_upload), with the options of `options` for every pair; matrix_index must be -1. Every tip must have
+ * codes on the device (pllgpu_tipchars_upload) and, for other than 4 states, the code -> mask map must be there
+ * (pllgpu_tipmap_upload). The outputs are [count][count] host arrays, [x][y] and [y][x] written from one computation, the
+ * diagonal 0; all but distance may be NULL. Nothing the context holds is written.
+ * Two things the context cannot see are the caller's to hold: prop_invar of every used rate matrix is 0 (the invariant term
+ * belongs to the alignment column, not to the code pair) and the pattern weights add up to less than 2^32 (the counts are
+ * 32-bit words). The host layer refuses both.
+ * The checks, before held work is launched or anything else happens, in this order: PLLGPU_EINVAL for a NULL out or
+ * distance, with count > 0 a NULL tips, params_indices or options, a tips[i] >= tips, options out of range (those of
+ * pllgpu_optimize_branch_length, and matrix_index != -1), a params_indices[k] out of range, a tip without codes on the
+ * device; PLLGPU_EUNSUPPORTED for ascertainment-bias entries, class-compressed CLVs anywhere in the context, and a code
+ * table beyond the limit. The limit. C = the codes in use (16 for 4 states, else 1 + the highest code with a non-empty
+ * mask). A workgroup keeps the diag table of its pair and at least one table of C^2 counts in LDS:
+ *   C <= PLLGPU_DISTANCE_MAX_CODES   and   PLLGPU_DISTANCE_LDS_BYTES = 32 R states + 4 (C^2 | 1) <= PLLGPU_DISTANCE_LDS_MAX.
+ * (61 states x 4 categories with 64 codes: 24 KB.) Where there is room a workgroup keeps 2, 4, ... 256 such tables, up to 36 KB
+ * of them, one per thread modulo their number: counts are integers, so their number changes no bit.
+ * The cutting rule. One workgroup per pair, grid (count, rows): workgroup (y, x - row0) serves the pair x < y and every
+ * other one returns at once. A launch carries whole rows of the pair matrix,
+ *   rows = max(1, min(65535, floor(PLLGPU_DISTANCE_MAX_PAIRS / count)))   rows per launch,
+ * ceil((count - 1) / rows) launches behind ONE launch of k_distance_code_vectors: 1 + ceil((count - 1) / rows) in all
+ * (counted into pllgpu_last_launch_count), no host wait between them, one copy back of all 6 count^2 values, one wait. A
+ * pair's bits depend on its two code rows, the model and the options alone.
+ * count == 0 succeeds at once, nothing but out and distance looked at; count == 1 succeeds without a launch once the
+ * arguments themselves have passed (the checks up to params_indices), the one diagonal entry of every output set to 0.
+ * PLL_AMD_DISTANCE_PAIRS in the environment of the context's creation lowers PLLGPU_DISTANCE_MAX_PAIRS in the rule above
+ * (tests: a small list over several launches). */
+#define PLLGPU_DISTANCE_MAX_CODES 128
+#define PLLGPU_DISTANCE_LDS_MAX (158ul * 1024ul)
+#define PLLGPU_DISTANCE_LDS_BYTES(S, R, C) (32ul * (R) * (S) + 4ul * (((C) * (C)) | 1ul))
+#define PLLGPU_DISTANCE_MAX_PAIRS (1u << 20)
+typedef struct pllgpu_distances
+{
+  double *distance, *p_distance, *d_f, *dd_f;
+  int *status;
+  unsigned int *iterations;
+} pllgpu_distances_t;
+int pllgpu_pairwise_distances(pllgpu_ctx_t *ctx, const unsigned int *tips, unsigned int count, const unsigned int *params_indices,
+                              const pllgpu_newton_t *options, const pllgpu_distances_t *out);
+
 /* (L, L', L'') of the per-state extra entries at the branch length of the LAST
  * pllgpu_likelihood_derivatives call on this context, and their scaling counts
  * (src/core_derivatives.c:864-891). Synchronises. */

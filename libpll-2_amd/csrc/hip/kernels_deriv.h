@@ -265,39 +265,32 @@ __device__ __forceinline__ bool newton_point(const DevNewton &n, double &t)
   return n.state->status == kNewtonRunning;
 }
 
-// The step, by thread 0 of the workgroup that arrived last: binary64 in exactly the operations written here (no
-// contraction, correctly rounded division), plain stores - the next launch starts behind the kernel boundary.
-__device__ __forceinline__ void newton_advance(const DevNewton &n, double t, double d, double dd)
+// a run's state before its first evaluation
+__device__ __forceinline__ void newton_open(NewtonState &s, double t_min, double t_max)
+{
+  s.lo = t_min;
+  s.hi = t_max;
+  s.iterations = 0;
+  s.lo_open = s.hi_open = 1u;
+}
+
+// The recipe's step after the evaluation (d, dd) at t - the one copy, for the run that takes a launch per evaluation
+// (newton_advance) and the one that stays inside a kernel (kernels_distance.h): binary64 in exactly the operations
+// written here (no contraction, correctly rounded division).
+__device__ __forceinline__ void newton_step(NewtonState &s, double t, double d, double dd, double t_min, double t_max, double tolerance,
+                                            unsigned max_iters)
 {
 #pragma clang fp contract(off)
-  NewtonState s;
-  if (n.first)
-  {
-    s.lo = n.t_min;
-    s.hi = n.t_max;
-    s.iterations = 0;
-    s.lo_open = s.hi_open = 1u;
-  }
-  else
-    s = *n.state;
-  if (s.iterations < PLLGPU_NEWTON_MAX_ITERS) // always: a run ends at max_iters <= PLLGPU_NEWTON_MAX_ITERS evaluations
-  {
-    double *row = n.trace + (size_t)3 * s.iterations;
-    row[0] = t;
-    row[1] = d;
-    row[2] = dd;
-  }
   s.iterations += 1;
   s.t = t;
   s.d_f = d;
   s.dd_f = dd;
-  s.matrix = n.matrix;
   s.status = kNewtonRunning;
-  if (fabs(d) < n.tolerance)
+  if (fabs(d) < tolerance)
     s.status = PLLGPU_NEWTON_CONVERGED;
-  else if (d > 0.0 && t == n.t_min)
+  else if (d > 0.0 && t == t_min)
     s.status = PLLGPU_NEWTON_AT_MIN;
-  else if (!(d > 0.0) && t == n.t_max)
+  else if (!(d > 0.0) && t == t_max)
     s.status = PLLGPU_NEWTON_AT_MAX;
   else
   {
@@ -318,11 +311,31 @@ __device__ __forceinline__ void newton_advance(const DevNewton &n, double t, dou
       cand = s.hi_open ? s.hi : 0.5 * (s.lo + s.hi);
     if (cand == t)
       s.status = PLLGPU_NEWTON_STALLED;
-    else if (s.iterations == n.max_iters)
+    else if (s.iterations == max_iters)
       s.status = PLLGPU_NEWTON_MAXITER; // t stays the last point evaluated
     else
       s.t = cand;
   }
+}
+
+// The step, by thread 0 of the workgroup that arrived last: plain stores - the next launch starts behind the kernel
+// boundary.
+__device__ __forceinline__ void newton_advance(const DevNewton &n, double t, double d, double dd)
+{
+  NewtonState s;
+  if (n.first)
+    newton_open(s, n.t_min, n.t_max);
+  else
+    s = *n.state;
+  if (s.iterations < PLLGPU_NEWTON_MAX_ITERS) // always: a run ends at max_iters <= PLLGPU_NEWTON_MAX_ITERS evaluations
+  {
+    double *row = n.trace + (size_t)3 * s.iterations;
+    row[0] = t;
+    row[1] = d;
+    row[2] = dd;
+  }
+  s.matrix = n.matrix;
+  newton_step(s, t, d, dd, n.t_min, n.t_max, n.tolerance, n.max_iters);
   *n.state = s;
 }
 

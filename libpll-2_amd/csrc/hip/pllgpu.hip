@@ -39,6 +39,7 @@
 #include "kernels_rell.h"
 #include "kernels_gradient.h"
 #include "kernels_qgradient.h"
+#include "kernels_distance.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
@@ -260,6 +261,7 @@ struct pllgpu_ctx
   DevBuf<double> eigenvals, rates, diag; // derivatives: [rate_matrices][SP], [R], [R][S][4]
   DevBuf<double> newton;                 // pllgpu_optimize_branch_length: the state record (NewtonState), then the trace
   unsigned newton_batch = 8;             // ... and how many evaluations it enqueues between two polls (tools/newton_device_latency.py)
+  unsigned distance_pairs = PLLGPU_DISTANCE_MAX_PAIRS; // pllgpu_pairwise_distances: cells of the pair matrix per launch; PLL_AMD_DISTANCE_PAIRS lowers it (tests)
   unsigned rell_range = kRellRange;      // k_rell_draw's sites per workgroup; PLL_AMD_RELL_RANGE lowers it (tests: a small case over several ranges)
   DevBuf<double> evecs, ievecs, brlen;   // device P-matrices: [rate_matrices][S][SP] x 2, staged branch lengths
   DevBuf<unsigned> mindex;               // staged matrix indices
@@ -556,6 +558,8 @@ static void derive_geometry(pllgpu_ctx *c)
     if (atoll(v) >= 1) c->resample_bytes = std::min<size_t>((size_t)atoll(v), PLLGPU_RESAMPLE_MAX_BYTES);
   if (const char *v = getenv("PLL_AMD_RELL_RANGE")) // tests: sites per workgroup of k_rell_draw, a multiple of 4
     if (atoll(v) >= 4) c->rell_range = (unsigned)std::min<long long>(atoll(v) / 4 * 4, kRellRange);
+  if (const char *v = getenv("PLL_AMD_DISTANCE_PAIRS")) // tests: a small list over several launches
+    if (atoll(v) >= 1) c->distance_pairs = (unsigned)std::min<long long>(atoll(v), PLLGPU_DISTANCE_MAX_PAIRS);
   c->subtrees = c->dna_fast;
   if (const char *v = getenv("PLL_AMD_NO_SUBTREES")) // A/B switch: the bottom levels under site repeats go level by level
     if (*v && *v != '0') c->subtrees = false;
@@ -4349,6 +4353,123 @@ extern "C" double pllgpu_timer_stop(pllgpu_ctx_t *c)
     return -1.0;
   }
   return (double)ms;
+}
+
+// ---- maximum-likelihood distances between tips (kernels_distance.h) ------------------------------------------------
+// the private count tables of a workgroup: as many as fit kDistCountBytes (a power of two, at most one per thread), one at
+// least; an odd number of words apart
+constexpr size_t kDistCountBytes = 36 * 1024;
+
+extern "C" int pllgpu_pairwise_distances(pllgpu_ctx_t *c, const unsigned *tips, unsigned count, const unsigned *params_indices,
+                                         const pllgpu_newton_t *opt, const pllgpu_distances_t *out)
+{
+  CHECK_CTX_KEEP(c);
+  c->last_launches = 0;
+  static const char noun[] = "pairwise distances";
+  const pllgpu_geometry_t &g = c->geo;
+  if (!out || !out->distance) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
+  if (!count) return 0;
+  if (!tips || !params_indices || !opt) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
+  for (unsigned i = 0; i < count; ++i)
+    if (tips[i] >= g.tips) return fail(PLLGPU_EINVAL, "%s: tips[%u] = %u is no tip", noun, i, tips[i]);
+  if (!(opt->t_min >= 0) || !(opt->t_min <= opt->t_max) || !std::isfinite(opt->t_max) || !std::isfinite(opt->t_start) || !(opt->tolerance > 0) ||
+      opt->max_iters < 1 || opt->max_iters > PLLGPU_NEWTON_MAX_ITERS || opt->matrix_index != -1)
+    return fail(PLLGPU_EINVAL, "%s: options out of range", noun);
+  if (int rc = check_rate_indices(c, "params_indices", params_indices)) return rc;
+  if (count == 1)
+  {
+    // no pair: the one diagonal entry
+    out->distance[0] = 0.0;
+    if (out->p_distance) out->p_distance[0] = 0.0;
+    if (out->d_f) out->d_f[0] = 0.0;
+    if (out->dd_f) out->dd_f[0] = 0.0;
+    if (out->status) out->status[0] = 0;
+    if (out->iterations) out->iterations[0] = 0u;
+    return 0;
+  }
+  for (unsigned i = 0; i < count; ++i)
+    if (!c->tipchars[tips[i]].p) return fail(PLLGPU_EINVAL, "%s: tip %u has no codes on the device", noun, tips[i]);
+  if (int rc = refuse_ascertainment(c, noun)) return rc;
+  if (int rc = refuse_compressed(c, noun)) return rc;
+  const unsigned S = g.states, R = g.rate_cats;
+  const unsigned ncodes = S == 4 ? 16u : c->tip_ncodes;
+  const size_t diag_bytes = (size_t)R * S * 4 * sizeof(double);
+  if (ncodes > PLLGPU_DISTANCE_MAX_CODES || PLLGPU_DISTANCE_LDS_BYTES((size_t)S, (size_t)R, (size_t)ncodes) > PLLGPU_DISTANCE_LDS_MAX)
+    return fail(PLLGPU_EUNSUPPORTED, "%s: a code table of %u codes at %u states x %u rate categories (at most %u codes and %lu bytes of LDS)", noun, ncodes,
+                S, R, (unsigned)PLLGPU_DISTANCE_MAX_CODES, PLLGPU_DISTANCE_LDS_MAX);
+  if (!ncodes || (S != 4 && !c->tipmap_set)) return fail(PLLGPU_EINVAL, "%s: the code -> state mask map was not uploaded", noun);
+  if (!c->eigenvals.p || !c->rates.p) return fail(PLLGPU_EINVAL, "eigenvalues / category rates were not uploaded");
+  DevEdge e;
+  if (int rc = batch_edge(c, e, params_indices)) return rc;
+
+  const size_t cc = (size_t)count * count, uw = (size_t)2 * ncodes * R * S;
+  if (int rc = batch_scratch(c, e, uw, 0, 6 * cc, (size_t)count * sizeof(const unsigned char *))) return rc;
+  const int up = stage_up<const unsigned char *>(c, c->ins_cands.p, count, [&](const unsigned char *&row, unsigned i) {
+    row = c->tipchars[tips[i]].p;
+    return 0;
+  });
+  if (up) return up;
+  HIP_TRY(hipMemsetAsync(c->ins_results.p, 0, 6 * cc * sizeof(double), c->stream)); // the diagonals
+
+  const double *m1 = c->pmat.p + (size_t)g.prob_matrices * c->pm_stride, *m2 = m1 + c->pm_stride;
+  const unsigned long long *tm = S == 4 ? nullptr : c->tipmap.p;
+  hipLaunchKernelGGL(k_distance_code_vectors, dim3((unsigned)((uw + 255) / 256)), dim3(256), 0, c->stream, m1, m2, tm, ncodes, S, c->gg.SPT, R,
+                     c->ins_partials.p);
+  if (int rc = launched(c)) return rc;
+
+  DevDiag dg;
+  memset(&dg, 0, sizeof dg);
+  for (unsigned k = 0; k < R; ++k) dg.fidx[k] = (unsigned char)params_indices[k];
+  dg.eigenvals = c->eigenvals.p;
+  dg.rates = c->rates.p;
+  dg.prop_invar = c->prop_invar.p;
+  dg.S = S;
+  dg.SP = g.states_padded;
+  dg.R = R;
+  DevDistance d;
+  memset(&d, 0, sizeof d);
+  d.rows = reinterpret_cast<const unsigned char *const *>(c->ins_cands.p);
+  d.pattern_weights = e.pattern_weights;
+  d.uw = c->ins_partials.p;
+  d.tipmap = tm;
+  d.freqs = e.freqs;
+  d.rate_weights = e.rate_weights;
+  d.results = c->ins_results.p;
+  d.t_first = std::min(std::max(opt->t_start, opt->t_min), opt->t_max);
+  d.t_min = opt->t_min;
+  d.t_max = opt->t_max;
+  d.tolerance = opt->tolerance;
+  d.max_iters = opt->max_iters;
+  d.sites = g.sites;
+  d.count = count;
+  d.ncodes = ncodes;
+  d.copy_stride = (ncodes * ncodes) | 1u;
+  const size_t table = (size_t)d.copy_stride * sizeof(unsigned);
+  const size_t room = std::min<size_t>(std::max(kDistCountBytes, table), PLLGPU_DISTANCE_LDS_MAX - diag_bytes);
+  d.copies = 1u;
+  while (d.copies < 256u && (size_t)2 * d.copies * table <= room) d.copies *= 2u;
+  memcpy(d.fidx, e.fidx, sizeof d.fidx);
+  const size_t lds = diag_bytes + (size_t)d.copies * table;
+  raise_lds_limit(reinterpret_cast<const void *>(&k_pairwise_distances), c->device, lds);
+  // the cutting rule (include/pll_amd_device.h states it): whole rows of the pair matrix
+  const unsigned rows_per = std::max(1u, std::min(65535u, c->distance_pairs / count));
+  for (unsigned row0 = 0; row0 + 1 < count; row0 += rows_per)
+  {
+    d.row0 = row0;
+    hipLaunchKernelGGL(k_pairwise_distances, dim3(count, std::min(rows_per, count - 1 - row0)), dim3(256), lds, c->stream, d, dg);
+    if (int rc = launched(c)) return rc;
+  }
+  std::vector<double> host(6 * cc);
+  if (int rc = results_down(c, host.data(), host.size())) return rc;
+  memcpy(out->distance, host.data(), cc * sizeof(double));
+  if (out->p_distance) memcpy(out->p_distance, host.data() + cc, cc * sizeof(double));
+  if (out->d_f) memcpy(out->d_f, host.data() + 2 * cc, cc * sizeof(double));
+  if (out->dd_f) memcpy(out->dd_f, host.data() + 3 * cc, cc * sizeof(double));
+  if (out->status)
+    for (size_t i = 0; i < cc; ++i) out->status[i] = (int)host[4 * cc + i];
+  if (out->iterations)
+    for (size_t i = 0; i < cc; ++i) out->iterations[i] = (unsigned)host[5 * cc + i];
+  return 0;
 }
 
 extern "C" unsigned pllgpu_last_launch_count(const pllgpu_ctx_t *c) { return c ? c->last_launches : 0; }

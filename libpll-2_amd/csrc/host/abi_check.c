@@ -136,6 +136,15 @@ AT(pll_gpu_newton_result_t, host_waits, 28);
 AT(pll_gpu_newton_result_t, status, 32);
 _Static_assert(PLL_GPU_NEWTON_MAX_ITERS == PLLGPU_NEWTON_MAX_ITERS && PLL_GPU_NEWTON_MAXITER == PLLGPU_NEWTON_MAXITER, "Newton constants");
 
+/* the outputs of pll_gpu_pairwise_distances, mirrored field for field by the device layer and by pllamd/api.py */
+_Static_assert(sizeof(pll_gpu_distances_t) == 48 && sizeof(pllgpu_distances_t) == 48, "pll_gpu_distances_t size");
+AT(pll_gpu_distances_t, distance, 0);
+AT(pll_gpu_distances_t, p_distance, 8);
+AT(pll_gpu_distances_t, d_f, 16);
+AT(pll_gpu_distances_t, dd_f, 24);
+AT(pll_gpu_distances_t, status, 32);
+AT(pll_gpu_distances_t, iterations, 40);
+
 /* queries the Python binding declares by hand (pllamd/api.py): the prototypes it assumes */
 _Static_assert(_Generic(&pll_gpu_pending_clvs, unsigned int (*)(const pll_partition_t *): 1, default: 0) &&
                _Generic(&pllgpu_pending_clvs, unsigned (*)(const pllgpu_ctx_t *): 1, default: 0), "pll_gpu_pending_clvs prototype");

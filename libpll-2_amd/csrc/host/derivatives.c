@@ -66,7 +66,7 @@ static int slot_of(pll_amd_ext_t *x, const double *key, int create)
 /* eigensystems, category rates, prop_invar, frequencies: whatever is stale */
 static int flush_deriv_model(pll_partition_t *p, pll_amd_ext_t *x) { return pll_flush_eigen(p, x); }
 
-static int flush_aux_matrices(pll_partition_t *p, pll_amd_ext_t *x, const unsigned int *params_indices)
+int pll_flush_aux_matrices(pll_partition_t *p, pll_amd_ext_t *x, const unsigned int *params_indices)
 {
   const unsigned int s = p->states, sp = p->states_padded, r = p->rate_cats;
   unsigned int k, i, j;
@@ -143,7 +143,7 @@ int pll_update_sumtable(pll_partition_t *p, unsigned int parent_clv_index, unsig
     /* the reference reads whatever eigensystem is stored; an invalid one is computed here */
     if (!p->eigen_decomp_valid[params_indices[k]] && !pll_update_eigen(p, params_indices[k])) return PLL_FAILURE;
   }
-  if (!flush_deriv_model(p, x) || !flush_aux_matrices(p, x, params_indices)) return fail_loudly("pll_update_sumtable");
+  if (!flush_deriv_model(p, x) || !pll_flush_aux_matrices(p, x, params_indices)) return fail_loudly("pll_update_sumtable");
   if (!pll_flush_clv(p, x, parent_clv_index) || !pll_flush_clv(p, x, child_clv_index) ||
       (!ptip && !pll_flush_scaler(p, x, parent_scaler_index)) || (!ctip && !pll_flush_scaler(p, x, child_scaler_index)) ||
       !pll_flush_repeats(p, x, parent_clv_index) || !pll_flush_repeats(p, x, child_clv_index))
@@ -502,7 +502,7 @@ static int branch_call(const char *who, pll_partition_t *p, const pll_gpu_branch
   /* the reference reads whatever eigensystem is stored; an invalid one is computed here, as pll_update_sumtable does */
   for (k = 0; k < p->rate_cats; ++k)
     if (!p->eigen_decomp_valid[params_indices[k]] && !pll_update_eigen(p, params_indices[k])) return PLL_FAILURE;
-  if (!flush_deriv_model(p, x) || !flush_aux_matrices(p, x, params_indices)) return pll_batch_fail(who);
+  if (!flush_deriv_model(p, x) || !pll_flush_aux_matrices(p, x, params_indices)) return pll_batch_fail(who);
 
   /* every named end current on the device, each index once */
   pll_batch_seen_t seen;

@@ -133,6 +133,9 @@ int pll_flush_clv(pll_partition_t *p, pll_amd_ext_t *x, unsigned int clv_index);
 int pll_flush_scaler(pll_partition_t *p, pll_amd_ext_t *x, int scaler_index);
 /* model arrays + eigensystems + category rates: what the derivative and P-matrix kernels read */
 int pll_flush_eigen(pll_partition_t *p, pll_amd_ext_t *x);
+/* the two sumtable contraction matrices of params_indices (derivatives.c), rebuilt and uploaded when an eigensystem, a
+ * frequency vector or params_indices changed; the eigensystems must be valid and flushed (pll_flush_eigen) */
+int pll_flush_aux_matrices(pll_partition_t *p, pll_amd_ext_t *x, const unsigned int *params_indices);
 /* the category rates alone */
 int pll_flush_rates(pll_partition_t *p, pll_amd_ext_t *x);
 /* class maps of the parents of `ops` on the device, dependency level by level (repeats.c) */

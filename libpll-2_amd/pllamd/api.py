@@ -198,6 +198,18 @@ class NewtonResult(C.Structure):
     ]
 
 
+class Distances(C.Structure):
+    """pll_gpu_distances_t (include/pll_amd.h): the [count][count] outputs of pll_gpu_pairwise_distances"""
+    _fields_ = [
+        ("distance", c_double_p),
+        ("p_distance", c_double_p),
+        ("d_f", c_double_p),
+        ("dd_f", c_double_p),
+        ("status", C.POINTER(C.c_int)),
+        ("iterations", c_uint_p),
+    ]
+
+
 NEWTON_MAX_ITERS = 64
 NEWTON_CONVERGED, NEWTON_AT_MIN, NEWTON_AT_MAX, NEWTON_STALLED, NEWTON_MAXITER = 0, 1, 2, 3, 4
 
@@ -317,6 +329,7 @@ _GPU_PROTOS = {
         C.c_int, [PartitionP, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p, c_double_p, C.c_uint, c_double_p, c_double_p]),
     "pll_gpu_optimize_branch_length": (
         C.c_int, [PartitionP, C.c_int, C.c_int, c_uint_p, c_double_p, C.POINTER(Newton), C.POINTER(NewtonResult), c_double_p]),
+    "pll_gpu_pairwise_distances": (C.c_int, [PartitionP, c_uint_p, C.c_uint, c_uint_p, C.POINTER(Newton), C.POINTER(Distances)]),
     "pll_gpu_last_algorithmic_bytes": (C.c_double, [PartitionP]),
     "pll_gpu_sync_repeats": (C.c_int, [PartitionP, C.c_int]),
     "pll_gpu_sync_all": (C.c_int, [PartitionP]),

@@ -296,6 +296,35 @@ def subst_gradient(lib, partition, rows, params_indices, want_subst=True, want_f
     return d_subst, d_freqs
 
 
+DISTANCE_OUTPUTS = ("distance", "p_distance", "d_f", "dd_f", "status", "iterations")
+
+
+def newton_options(t_start, t_min, t_max, tolerance, max_iters, matrix_index=-1):
+    """pll_gpu_newton_t from its fields"""
+    return api.Newton(float(t_start), float(t_min), float(t_max), float(tolerance), int(max_iters), int(matrix_index))
+
+
+def pairwise_distances(lib, partition, tips, params_indices, options, want=DISTANCE_OUTPUTS, fill=None):
+    """pll_gpu_pairwise_distances: tips = the tip indices of the list, options = an api.Newton (newton_options). A dict of
+    [count, count] arrays: `distance` always, the others of `want` (p_distance, d_f, dd_f float64; status int32; iterations
+    uint32) - the rest is handed over as NULL. `fill`: what every array holds before the call, cast to its type (tests: outputs stay untouched
+    on a failure; the arrays then travel in the exception's `outputs`). libpll_amd.so only."""
+    tips = np.ascontiguousarray(tips, dtype=np.uint32)
+    n = len(tips)
+    pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+    dtypes = {"status": np.int32, "iterations": np.uint32}
+    out = {name: np.full((n, n), 0.0 if fill is None else fill).astype(dtypes.get(name, np.float64))
+           for name in DISTANCE_OUTPUTS if name == "distance" or name in want}
+    rec = api.Distances()
+    for name, a in out.items():
+        setattr(rec, name, a.ctypes.data_as(dict(api.Distances._fields_)[name]))
+    if not lib.pll_gpu_pairwise_distances(partition, api.uptr(tips), n, api.uptr(pi), C.byref(options), C.byref(rec)):
+        err = RuntimeError(f"pll_gpu_pairwise_distances: [{lib.errno()}] {lib.errmsg()}")
+        err.outputs = out
+        raise err
+    return out
+
+
 def branch_derivatives_per_edge(lib, partition, rows, params_indices, sumtable=None):
     """the same values the way every libpll offers them: per row pll_update_sumtable into one caller-owned table, then
     pll_compute_likelihood_derivatives at the row's length. The table (sites * rate_cats * states_padded doubles, 64-byte
