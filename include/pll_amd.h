@@ -1130,7 +1130,7 @@ int pll_gpu_subst_gradient(pll_partition_t *partition, const pll_gpu_branch_t *b
  * a 61-state alignment with ambiguity codes has about 64) and for pattern weights that add up to 2^32 or more;
  * PLL_ERROR_GPU_UNAVAILABLE without a device. count == 0 succeeds at once (after the first check; nothing else is read,
  * nothing written); count == 1 passes every check and succeeds without a launch, its one diagonal entry set to 0.
- * Not offered: invariant sites, site repeats, ascertainment bias, distances that involve inner nodes, the NJ tree itself. */
+ * Not offered: invariant sites, site repeats, ascertainment bias, distances that involve inner nodes. */
 typedef struct pll_gpu_distances
 {
   double *distance;          /* [count*count], required: D[x*count+y], symmetric, 0 on the diagonal */
@@ -1143,6 +1143,54 @@ typedef struct pll_gpu_distances
 int pll_gpu_pairwise_distances(pll_partition_t *partition, const unsigned int *tips, unsigned int count,
                                const unsigned int *params_indices, const pll_gpu_newton_t *options,
                                const pll_gpu_distances_t *out);
+
+/* ---- neighbour-joining and BIONJ trees from distances ------------------------------------
+ * The starting or guide tree of a distance matrix, joined on the device: pll_gpu_nj_tree from a matrix the caller holds,
+ * pll_gpu_distance_tree from the tips of a partition - pll_gpu_pairwise_distances and the join in one call, the matrix
+ * staying on the device unless distances_out asks for it. flags: 0 = NJ (Saitou & Nei 1987 in the form of Studier & Keppler
+ * 1988), PLL_GPU_NJ_BIONJ = BIONJ (Gascuel 1997).
+ * The tree: the tips are the nodes 0 .. count-1 in input order, the inner node made by join s (s = 0, 1, ...) is count + s,
+ * and the last inner node, 2 count - 3, joins the three nodes that remain. parent[v] is the label of v's parent, length[v]
+ * the branch to it; parent[2 count - 3] = -1 and length[2 count - 3] = 0. Lengths are what the algorithm gives: negative
+ * ones are neither clamped nor flagged.
+ * The definition is pllamd/nj.py, a numpy restatement usable without a device, which the kernels follow operation for
+ * operation (every product rounded before it is added). With r active nodes, r > 3, and the row sums R_i = sum_k d_ik:
+ *   Q_ij = (r-2) d_ij - (R_i + R_j);   the pair of minimal Q is joined, i the node with the smaller label;
+ *   l_i = d_ij / 2 + (R_i - R_j) / (2 (r-2)),   l_j = d_ij - l_i;
+ *   NJ:    d_uk = ((d_ik + d_jk) - d_ij) / 2,   R_u = ((R_i + R_j) - r d_ij) / 2;
+ *   BIONJ: V starts as D; lambda = 1/2 + sum_{k != i,j} (V_jk - V_ik) / (2 (r-2) V_ij), clamped to [0, 1], 1/2 where
+ *          V_ij = 0; d_uk = lambda (d_ik - l_i) + (1 - lambda) (d_jk - l_j), evaluated as
+ *          (d_jk - l_j) + lambda ((d_ik - l_i) - (d_jk - l_j)): exact where the two sides agree (an additive matrix);
+ *          V_uk = (lambda V_ik + (1 - lambda) V_jk) - lambda (1 - lambda) V_ij;
+ *          R_u = B + lambda (A - B), A = (R_i - d_ij) - (r-2) l_i, B = (R_j - d_ij) - (r-2) l_j;
+ *   the row sums are carried forward: R_k <- ((R_k - d_ik) - d_jk) + d_uk;
+ *   three nodes a, b, c: l_a = ((d_ab + d_ac) - d_bc) / 2, and likewise for b and c.
+ * Two rules make the answer a function of the input alone. Ties: among equal minimal Q the pair whose (smaller label,
+ * larger label) comes first lexicographically. Four nodes left: Q_ab = Q_cd holds for every split, so only the three pairs
+ * that contain the active node with the smallest label are searched.
+ * How: two launches per join on one stream with no host wait between joins (the rule: include/pll_amd_device.h,
+ * pllgpu_nj_tree); pll_gpu_nj_last_launch_count reports those of the calling thread's last pll_gpu_nj_tree,
+ * pll_gpu_last_launch_count(partition) those of pll_gpu_distance_tree, distances and join together.
+ * pll_gpu_nj_tree needs no partition: it owns a stream on `device` (-1: PLL_AMD_DEVICE, else the thread's current device)
+ * for the length of the call, as pll_compress_site_patterns does. Working set on the device: 8 count^2 bytes, twice that for
+ * BIONJ.
+ * PLL_SUCCESS, or PLL_FAILURE with pll_errno, the usual line on stderr and parent, length and distances_out untouched.
+ * pll_gpu_nj_tree refuses, before anything is launched, with PLL_ERROR_PARAM_INVALID: a NULL distances, parent or length;
+ * count < 3; unknown flag bits; an entry [x][y], x < y, that is negative or not finite (one pass on the host);
+ * PLL_ERROR_GPU_UNAVAILABLE without a device; PLL_ERROR_MEM_ALLOC when the device has no room.
+ * pll_gpu_distance_tree makes every check of pll_gpu_pairwise_distances in its order (parent and length in the place of
+ * out), then PLL_ERROR_PARAM_INVALID for count < 3 and unknown flag bits.
+ * Not offered: row-minimum caches (RapidNJ), single precision, relaxed NJ. */
+#define PLL_GPU_NJ_BIONJ 1u
+int pll_gpu_nj_tree(const double *distances /* [count][count]; only [x][y], x < y, is read */, unsigned int count,
+                    unsigned int flags, int device, int *parent /* [2 count - 2] */, double *length /* [2 count - 2] */);
+int pll_gpu_distance_tree(pll_partition_t *partition, const unsigned int *tips, unsigned int count,
+                          const unsigned int *params_indices, const pll_gpu_newton_t *options, unsigned int flags,
+                          int *parent, double *length, double *distances_out /* NULL or [count][count] */);
+unsigned int pll_gpu_nj_last_launch_count(void);
+/* milliseconds between the first and the last launch of the calling thread's last join, measured by device events on the
+ * stream it ran on (without the copies up and back); -1 if none ran */
+double pll_gpu_nj_last_device_ms(void);
 
 /* ---- rate-category posteriors, site rates and EM weight steps ----------
  * The per-category site likelihoods of one edge - what every evaluation kernel mixes away in registers - and what model

@@ -582,6 +582,40 @@ typedef struct pllgpu_distances
 int pllgpu_pairwise_distances(pllgpu_ctx_t *ctx, const unsigned int *tips, unsigned int count, const unsigned int *params_indices,
                               const pllgpu_newton_t *options, const pllgpu_distances_t *out);
 
+/* Neighbour-joining (flags 0) and BIONJ (PLLGPU_NJ_BIONJ) trees from distances (kernels_nj.h; include/pll_amd.h,
+ * pll_gpu_nj_tree, holds the tree format and pllamd/nj.py the definition, operation for operation).
+ * pllgpu_nj_tree needs no context: it owns a stream and its blocks on `device` (-1: PLL_AMD_DEVICE, else the calling
+ * thread's current device) for the length of the call, copies host_dist ([count][count]; only [x][y], x < y, is read) up and
+ * parent / length ([2 count - 2] each) back, and leaves the thread's device as it found it. pllgpu_distance_tree is
+ * pllgpu_pairwise_distances' checks and launches followed by the same join on the distance block where it lies (the first
+ * count^2 doubles of the call's results); the join's working set comes from the context's block pool and returns to it,
+ * nothing the context holds is written, and host_dist_or_NULL receives the [count][count] distances. Both are one routine on
+ * (device matrix, stream, block). Synchronous: one wait at the end; outputs are written only on success.
+ * Working set: 8 count^2 bytes (twice that for BIONJ) + O(count).
+ * The launch rule. count == 3: ONE launch (the three-node step). count >= 4: one launch that copies the upper triangle into
+ * both halves of the working matrix and forms the first row sums, per join one search launch (ceil((r - 1) / rows)
+ * workgroups at r active nodes, rows = PLLGPU_NJ_ROWS, the last to take the step's ticket leaves the step's record) and one
+ * join launch (ceil(r / 256) workgroups), then the three-node step:
+ *   2 (count - 3) + 2   launches,
+ * no host wait between them. pllgpu_nj_last_launch_count reports them for the calling thread's last pllgpu_nj_tree (0 after a
+ * failure); pllgpu_distance_tree counts them into pllgpu_last_launch_count behind those of the distances.
+ * PLL_AMD_NJ_ROWS in the environment, read when a call starts, lowers PLLGPU_NJ_ROWS (tests: nine nodes over several search
+ * workgroups and the ticket); the answer's bits do not depend on it.
+ * The checks, before anything is launched: PLLGPU_EINVAL for a NULL host_dist, parent or length, count < 3, unknown flag
+ * bits, a device out of range; PLLGPU_ENODEVICE without a device. pllgpu_distance_tree: NULL parent or length, then the
+ * argument checks of pllgpu_pairwise_distances, then count < 3 and the flags, then the remaining checks of
+ * pllgpu_pairwise_distances. The entries' values are the host layer's to check (finite, not negative); a step whose
+ * criterion holds no number fails the call with PLLGPU_ERUNTIME instead of joining anything. */
+#define PLLGPU_NJ_BIONJ 1u
+#define PLLGPU_NJ_ROWS 8u
+int pllgpu_nj_tree(int device, const double *host_dist, unsigned int count, unsigned int flags, int *parent, double *length);
+int pllgpu_distance_tree(pllgpu_ctx_t *ctx, const unsigned int *tips, unsigned int count, const unsigned int *params_indices,
+                         const pllgpu_newton_t *options, unsigned int flags, int *parent, double *length, double *host_dist_or_NULL);
+unsigned int pllgpu_nj_last_launch_count(void);
+/* milliseconds from the first to the last launch of the calling thread's last join (either entry point), by device events
+ * on the call's stream; -1 when no join ran or the events could not be had (tools/nj_probe.py) */
+double pllgpu_nj_last_device_ms(void);
+
 /* (L, L', L'') of the per-state extra entries at the branch length of the LAST
  * pllgpu_likelihood_derivatives call on this context, and their scaling counts
  * (src/core_derivatives.c:864-891). Synchronises. */

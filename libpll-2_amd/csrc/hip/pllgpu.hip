@@ -40,6 +40,7 @@
 #include "kernels_gradient.h"
 #include "kernels_qgradient.h"
 #include "kernels_distance.h"
+#include "kernels_nj.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
@@ -4360,33 +4361,29 @@ extern "C" double pllgpu_timer_stop(pllgpu_ctx_t *c)
 // least; an odd number of words apart
 constexpr size_t kDistCountBytes = 36 * 1024;
 
-extern "C" int pllgpu_pairwise_distances(pllgpu_ctx_t *c, const unsigned *tips, unsigned count, const unsigned *params_indices,
-                                         const pllgpu_newton_t *opt, const pllgpu_distances_t *out)
+static const char kDistNoun[] = "pairwise distances";
+
+// the checks of the arguments themselves (count > 0), in the order include/pll_amd_device.h states
+static int distances_check_arguments(pllgpu_ctx *c, const unsigned *tips, unsigned count, const unsigned *params_indices, const pllgpu_newton_t *opt)
 {
-  CHECK_CTX_KEEP(c);
-  c->last_launches = 0;
-  static const char noun[] = "pairwise distances";
+  const char *const noun = kDistNoun;
   const pllgpu_geometry_t &g = c->geo;
-  if (!out || !out->distance) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
-  if (!count) return 0;
   if (!tips || !params_indices || !opt) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
   for (unsigned i = 0; i < count; ++i)
     if (tips[i] >= g.tips) return fail(PLLGPU_EINVAL, "%s: tips[%u] = %u is no tip", noun, i, tips[i]);
   if (!(opt->t_min >= 0) || !(opt->t_min <= opt->t_max) || !std::isfinite(opt->t_max) || !std::isfinite(opt->t_start) || !(opt->tolerance > 0) ||
       opt->max_iters < 1 || opt->max_iters > PLLGPU_NEWTON_MAX_ITERS || opt->matrix_index != -1)
     return fail(PLLGPU_EINVAL, "%s: options out of range", noun);
-  if (int rc = check_rate_indices(c, "params_indices", params_indices)) return rc;
-  if (count == 1)
-  {
-    // no pair: the one diagonal entry
-    out->distance[0] = 0.0;
-    if (out->p_distance) out->p_distance[0] = 0.0;
-    if (out->d_f) out->d_f[0] = 0.0;
-    if (out->dd_f) out->dd_f[0] = 0.0;
-    if (out->status) out->status[0] = 0;
-    if (out->iterations) out->iterations[0] = 0u;
-    return 0;
-  }
+  return check_rate_indices(c, "params_indices", params_indices);
+}
+
+// The remaining checks and every launch of a list of count >= 2 tips: the six [count][count] blocks are left in
+// ins_results, distance first, with nothing waited for. pllgpu_pairwise_distances copies them back; pllgpu_distance_tree
+// joins the first block where it lies.
+static int distances_enqueue(pllgpu_ctx *c, const unsigned *tips, unsigned count, const unsigned *params_indices, const pllgpu_newton_t *opt)
+{
+  const char *const noun = kDistNoun;
+  const pllgpu_geometry_t &g = c->geo;
   for (unsigned i = 0; i < count; ++i)
     if (!c->tipchars[tips[i]].p) return fail(PLLGPU_EINVAL, "%s: tip %u has no codes on the device", noun, tips[i]);
   if (int rc = refuse_ascertainment(c, noun)) return rc;
@@ -4459,6 +4456,30 @@ extern "C" int pllgpu_pairwise_distances(pllgpu_ctx_t *c, const unsigned *tips, 
     hipLaunchKernelGGL(k_pairwise_distances, dim3(count, std::min(rows_per, count - 1 - row0)), dim3(256), lds, c->stream, d, dg);
     if (int rc = launched(c)) return rc;
   }
+  return 0;
+}
+
+extern "C" int pllgpu_pairwise_distances(pllgpu_ctx_t *c, const unsigned *tips, unsigned count, const unsigned *params_indices,
+                                         const pllgpu_newton_t *opt, const pllgpu_distances_t *out)
+{
+  CHECK_CTX_KEEP(c);
+  c->last_launches = 0;
+  if (!out || !out->distance) return fail(PLLGPU_EINVAL, "%s: null argument", kDistNoun);
+  if (!count) return 0;
+  if (int rc = distances_check_arguments(c, tips, count, params_indices, opt)) return rc;
+  if (count == 1)
+  {
+    // no pair: the one diagonal entry
+    out->distance[0] = 0.0;
+    if (out->p_distance) out->p_distance[0] = 0.0;
+    if (out->d_f) out->d_f[0] = 0.0;
+    if (out->dd_f) out->dd_f[0] = 0.0;
+    if (out->status) out->status[0] = 0;
+    if (out->iterations) out->iterations[0] = 0u;
+    return 0;
+  }
+  if (int rc = distances_enqueue(c, tips, count, params_indices, opt)) return rc;
+  const size_t cc = (size_t)count * count;
   std::vector<double> host(6 * cc);
   if (int rc = results_down(c, host.data(), host.size())) return rc;
   memcpy(out->distance, host.data(), cc * sizeof(double));
@@ -4469,6 +4490,195 @@ extern "C" int pllgpu_pairwise_distances(pllgpu_ctx_t *c, const unsigned *tips, 
     for (size_t i = 0; i < cc; ++i) out->status[i] = (int)host[4 * cc + i];
   if (out->iterations)
     for (size_t i = 0; i < cc; ++i) out->iterations[i] = (unsigned)host[5 * cc + i];
+  return 0;
+}
+
+// ---- neighbour-joining / BIONJ trees (kernels_nj.h) -------------------------------------------------------------------
+constexpr unsigned kNjRows = PLLGPU_NJ_ROWS; // rows of the triangle per search workgroup; PLL_AMD_NJ_ROWS lowers it (tests)
+static thread_local unsigned t_nj_launches = 0;
+static thread_local double t_nj_device_ms = -1.0; // first to last launch of this thread's last join, by device events
+
+static unsigned nj_rows()
+{
+  unsigned rows = kNjRows;
+  if (const char *v = getenv("PLL_AMD_NJ_ROWS")) // tests: a small matrix over several search workgroups and the ticket
+    rows = (unsigned)std::min<long>(std::max<long>(1, atol(v)), (long)kNjRows);
+  return rows;
+}
+
+// bytes of the working set behind a 256-byte aligned block, and the block cut up
+static size_t nj_align(size_t b) { return (b + 255u) & ~(size_t)255u; }
+static size_t nj_scratch_bytes(unsigned count, unsigned flags)
+{
+  const size_t n = count, cc = n * n * sizeof(double);
+  return nj_align(cc) * ((flags & PLLGPU_NJ_BIONJ) ? 2u : 1u) + nj_align(n * sizeof(double)) + nj_align(4 * n * sizeof(double)) +
+         2 * nj_align(n * sizeof(unsigned)) + nj_align(n * sizeof(NjKey)) + nj_align(sizeof(NjRecord)) + nj_align(2 * n * sizeof(int)) +
+         nj_align(2 * n * sizeof(double)) + nj_align(sizeof(unsigned));
+}
+
+static DevNj nj_carve(unsigned char *block, unsigned count, unsigned flags, unsigned rows)
+{
+  const size_t n = count, cc = n * n * sizeof(double);
+  DevNj d;
+  memset(&d, 0, sizeof d);
+  auto take = [&](size_t bytes) {
+    unsigned char *p = block;
+    block += nj_align(bytes);
+    return p;
+  };
+  d.D = (double *)take(cc);
+  d.V = (flags & PLLGPU_NJ_BIONJ) ? (double *)take(cc) : nullptr;
+  d.R = (double *)take(n * sizeof(double));
+  d.snap = (double *)take(4 * n * sizeof(double));
+  d.label = (unsigned *)take(n * sizeof(unsigned));
+  d.tickets = (unsigned *)take(n * sizeof(unsigned));
+  d.partials = (NjKey *)take(n * sizeof(NjKey));
+  d.record = (NjRecord *)take(sizeof(NjRecord));
+  d.parent = (int *)take(2 * n * sizeof(int));
+  d.length = (double *)take(2 * n * sizeof(double));
+  d.status = (unsigned *)take(sizeof(unsigned));
+  d.count = count;
+  d.rows = rows;
+  d.bionj = (flags & PLLGPU_NJ_BIONJ) ? 1u : 0u;
+  return d;
+}
+
+// The one routine behind both calls: the join of the device matrix `src` ([count][count], the upper triangle read) on
+// `stream`, in `block` (nj_scratch_bytes of it); parent and length are copied to the host and the stream is waited for.
+// Launches (the rule of include/pll_amd_device.h) are added to *launches.
+static int nj_run(hipStream_t stream, const double *src, unsigned count, unsigned flags, unsigned char *block, int *parent, double *length,
+                  unsigned *launches)
+{
+  const DevNj d = nj_carve(block, count, flags, nj_rows());
+  const size_t nodes = 2 * (size_t)count - 2;
+  // (the two events time the launches for tools/nj_probe.py; when they cannot be had the call runs without them)
+  struct Events
+  {
+    hipEvent_t first = nullptr, last = nullptr;
+    ~Events()
+    {
+      if (first) (void)hipEventDestroy(first);
+      if (last) (void)hipEventDestroy(last);
+    }
+  } ev;
+  t_nj_device_ms = -1.0;
+  if (hipEventCreate(&ev.first) != hipSuccess || hipEventCreate(&ev.last) != hipSuccess) (void)hipGetLastError();
+  HIP_TRY(hipMemsetAsync(d.status, 0, sizeof(unsigned), stream));
+  const bool timed = ev.first && ev.last && hipEventRecord(ev.first, stream) == hipSuccess;
+  if (count == 3)
+  {
+    hipLaunchKernelGGL(k_nj_final, dim3(1), dim3(64), 0, stream, d, src, (const unsigned *)nullptr);
+    ++*launches;
+  }
+  else
+  {
+    HIP_TRY(hipMemsetAsync(d.tickets, 0, (size_t)count * sizeof(unsigned), stream));
+    hipLaunchKernelGGL(k_nj_init, dim3(count), dim3(256), 0, stream, d, src);
+    ++*launches;
+    for (unsigned r = count, step = 0; r > 3; --r, ++step)
+    {
+      const unsigned search_wgs = (r - 1 + d.rows - 1) / d.rows; // rows 0 .. r-2 of the triangle hold pairs
+      hipLaunchKernelGGL(k_nj_search, dim3(search_wgs), dim3(256), 0, stream, d, r, step);
+      hipLaunchKernelGGL(k_nj_join, dim3((r + 255) / 256), dim3(256), 0, stream, d, r, step);
+      *launches += 2;
+    }
+    hipLaunchKernelGGL(k_nj_final, dim3(1), dim3(64), 0, stream, d, (const double *)d.D, (const unsigned *)d.label);
+    ++*launches;
+  }
+  HIP_TRY(hipGetLastError());
+  const bool timed_end = timed && hipEventRecord(ev.last, stream) == hipSuccess;
+  std::vector<int> hp(nodes);
+  std::vector<double> hl(nodes);
+  unsigned status = 0;
+  HIP_TRY(hipMemcpyAsync(hp.data(), d.parent, nodes * sizeof(int), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(hl.data(), d.length, nodes * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(&status, d.status, sizeof status, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  float ms = 0;
+  if (timed_end && hipEventElapsedTime(&ms, ev.first, ev.last) == hipSuccess) t_nj_device_ms = (double)ms;
+  if (status) return fail(PLLGPU_ERUNTIME, "neighbour joining: a step found no pair to join (the criterion is not a number)");
+  memcpy(parent, hp.data(), nodes * sizeof(int));
+  memcpy(length, hl.data(), nodes * sizeof(double));
+  return 0;
+}
+
+extern "C" unsigned pllgpu_nj_last_launch_count(void) { return t_nj_launches; }
+extern "C" double pllgpu_nj_last_device_ms(void) { return t_nj_device_ms; }
+
+extern "C" int pllgpu_nj_tree(int device, const double *host_dist, unsigned count, unsigned flags, int *parent, double *length)
+{
+  t_nj_launches = 0;
+  if (!host_dist || !parent || !length || count < 3 || (flags & ~PLLGPU_NJ_BIONJ))
+    return fail(PLLGPU_EINVAL, "neighbour joining: invalid argument (%u nodes, flags %#x)", count, flags);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+  {
+    (void)hipGetLastError();
+    return fail(PLLGPU_ENODEVICE, "no HIP device visible");
+  }
+  int prev = -1;
+  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  if (device < 0)
+  {
+    // PLL_AMD_DEVICE=<n>, else (unset or "auto") the calling thread's current device - like pllgpu_compress_patterns
+    const char *env = getenv("PLL_AMD_DEVICE");
+    device = (env && strcmp(env, "auto") != 0) ? atoi(env) : (prev >= 0 ? prev : 0);
+  }
+  if (device < 0 || device >= ndev) return fail(PLLGPU_EINVAL, "neighbour joining: device %d of %d", device, ndev);
+  const size_t cc = (size_t)count * count * sizeof(double);
+  hipStream_t stream = nullptr;
+  unsigned char *block = nullptr;
+  double *src = nullptr;
+  unsigned launches = 0;
+  auto run = [&]() -> int {
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    HIP_TRY(hipMalloc(&src, cc));
+    HIP_TRY(hipMalloc(&block, nj_scratch_bytes(count, flags)));
+    HIP_TRY(hipMemcpyAsync(src, host_dist, cc, hipMemcpyHostToDevice, stream));
+    return nj_run(stream, src, count, flags, block, parent, length, &launches);
+  };
+  const int rc = run();
+  if (rc && stream) (void)hipStreamSynchronize(stream); // nothing of the call is in flight when its blocks go
+  (void)hipFree(src);
+  (void)hipFree(block);
+  if (stream) (void)hipStreamDestroy(stream);
+  if (rc) (void)hipGetLastError();
+  if (prev >= 0 && prev != device) (void)hipSetDevice(prev); // leave the thread's device as found
+  t_nj_launches = rc ? 0 : launches;
+  return rc;
+}
+
+extern "C" int pllgpu_distance_tree(pllgpu_ctx_t *c, const unsigned *tips, unsigned count, const unsigned *params_indices,
+                                    const pllgpu_newton_t *opt, unsigned flags, int *parent, double *length, double *host_dist)
+{
+  CHECK_CTX_KEEP(c);
+  c->last_launches = 0;
+  if (!parent || !length) return fail(PLLGPU_EINVAL, "distance tree: null argument");
+  if (count)
+    if (int rc = distances_check_arguments(c, tips, count, params_indices, opt)) return rc;
+  if (count < 3 || (flags & ~PLLGPU_NJ_BIONJ)) return fail(PLLGPU_EINVAL, "distance tree: invalid argument (%u tips, flags %#x)", count, flags);
+  if (int rc = distances_enqueue(c, tips, count, params_indices, opt)) return rc;
+  // the working set comes from the context's block pool and goes back to it; no kept plan points at it
+  ScratchEpoch scratch_epoch_;
+  DevBuf<unsigned char> block;
+  if (block.ensure(nj_scratch_bytes(count, flags))) return PLLGPU_ENOMEM;
+  std::vector<double> dist;
+  int rc = 0;
+  if (host_dist)
+  {
+    dist.resize((size_t)count * count);
+    const hipError_t e = hipMemcpyAsync(dist.data(), c->ins_results.p, dist.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) rc = fail(PLLGPU_ERUNTIME, "distance tree: copy back failed: %s", hipGetErrorString(e));
+  }
+  unsigned launches = 0;
+  if (!rc) rc = nj_run(c->stream, c->ins_results.p, count, flags, block.p, parent, length, &launches);
+  if (rc) (void)hipStreamSynchronize(c->stream);
+  else ring_drained(c); // (nj_run has waited for the stream)
+  block.release();
+  if (rc) return rc;
+  c->last_launches += launches;
+  if (host_dist) memcpy(host_dist, dist.data(), dist.size() * sizeof(double));
   return 0;
 }
 

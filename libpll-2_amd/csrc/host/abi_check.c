@@ -148,3 +148,11 @@ AT(pll_gpu_distances_t, iterations, 40);
 /* queries the Python binding declares by hand (pllamd/api.py): the prototypes it assumes */
 _Static_assert(_Generic(&pll_gpu_pending_clvs, unsigned int (*)(const pll_partition_t *): 1, default: 0) &&
                _Generic(&pllgpu_pending_clvs, unsigned (*)(const pllgpu_ctx_t *): 1, default: 0), "pll_gpu_pending_clvs prototype");
+
+/* the tree calls (nj.c): the public flag is the device layer's, and pllamd/api.py assumes these prototypes */
+_Static_assert(PLL_GPU_NJ_BIONJ == PLLGPU_NJ_BIONJ, "NJ flags");
+_Static_assert(_Generic(&pll_gpu_nj_tree, int (*)(const double *, unsigned int, unsigned int, int, int *, double *): 1, default: 0) &&
+               _Generic(&pllgpu_nj_tree, int (*)(int, const double *, unsigned int, unsigned int, int *, double *): 1, default: 0),
+               "pll_gpu_nj_tree prototype");
+_Static_assert(_Generic(&pll_gpu_nj_last_launch_count, unsigned int (*)(void): 1, default: 0) &&
+               _Generic(&pll_gpu_nj_last_device_ms, double (*)(void): 1, default: 0), "pll_gpu_nj_last_* prototypes");

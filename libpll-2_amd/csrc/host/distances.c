@@ -16,17 +16,12 @@ static unsigned int code_count(const pll_partition_t *p, const pll_amd_ext_t *x)
   return (p->attributes & PLL_ATTRIB_PATTERN_TIP) ? p->maxstates : (x ? x->ctip_count : 0);
 }
 
-int pll_gpu_pairwise_distances(pll_partition_t *p, const unsigned int *tips, unsigned int count, const unsigned int *params_indices,
-                               const pll_gpu_newton_t *options, const pll_gpu_distances_t *out)
+/* every check of a list of count > 0 tips behind the one of the outputs, in the order include/pll_amd.h states, the
+ * device last; nothing is flushed (shared with pll_gpu_distance_tree, nj.c) */
+int pll_distances_check(const char *who, pll_partition_t *p, const unsigned int *tips, unsigned int count, const unsigned int *params_indices,
+                        const pll_gpu_newton_t *options, pll_amd_ext_t **ext)
 {
-  static const char who[] = "pll_gpu_pairwise_distances";
   unsigned int i, k;
-  if (!p || !out || !out->distance)
-  {
-    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition, out or out->distance is NULL", who);
-    return pll_batch_fail(who);
-  }
-  if (!count) return PLL_SUCCESS; /* no pair, no entry: nothing of the other arguments is read */
   if (!tips || !params_indices || !options)
   {
     pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: tips, params_indices or options is NULL", who);
@@ -84,9 +79,15 @@ int pll_gpu_pairwise_distances(pll_partition_t *p, const unsigned int *tips, uns
     pll_set_error(PLL_ERROR_GPU_UNSUPPORTED, "%s: the pattern weights add up to %llu; the counts are 32-bit words", who, wsum);
     return pll_batch_fail(who);
   }
-  pll_amd_ext_t *x = NULL;
-  if (!pll_batch_device(who, p, &x)) return PLL_FAILURE;
+  return pll_batch_device(who, p, ext);
+}
 
+/* the model, the contraction matrices and the code rows of the tips current on the device; the options in the device
+ * layer's form */
+int pll_distances_flush(const char *who, pll_partition_t *p, pll_amd_ext_t *x, const unsigned int *tips, unsigned int count,
+                        const unsigned int *params_indices, const pll_gpu_newton_t *options, pllgpu_newton_t *device_options)
+{
+  unsigned int i, k;
   if (count >= 2) /* (one tip is no pair: the device layer sets its diagonal entry and launches nothing) */
   {
     /* the reference reads whatever eigensystem is stored; an invalid one is computed here, as pll_update_sumtable does */
@@ -97,13 +98,30 @@ int pll_gpu_pairwise_distances(pll_partition_t *p, const unsigned int *tips, uns
     for (i = 0; i < count; ++i)
       if (!pll_flush_clv(p, x, tips[i])) return pll_batch_fail(who);
   }
+  device_options->t_start = options->t_start;
+  device_options->t_min = options->t_min;
+  device_options->t_max = options->t_max;
+  device_options->tolerance = options->tolerance;
+  device_options->max_iters = options->max_iters;
+  device_options->matrix_index = -1;
+  return PLL_SUCCESS;
+}
+
+int pll_gpu_pairwise_distances(pll_partition_t *p, const unsigned int *tips, unsigned int count, const unsigned int *params_indices,
+                               const pll_gpu_newton_t *options, const pll_gpu_distances_t *out)
+{
+  static const char who[] = "pll_gpu_pairwise_distances";
+  if (!p || !out || !out->distance)
+  {
+    pll_set_error(PLL_ERROR_PARAM_INVALID, "%s: partition, out or out->distance is NULL", who);
+    return pll_batch_fail(who);
+  }
+  if (!count) return PLL_SUCCESS; /* no pair, no entry: nothing of the other arguments is read */
+  pll_amd_ext_t *x = NULL;
   pllgpu_newton_t opt;
-  opt.t_start = options->t_start;
-  opt.t_min = options->t_min;
-  opt.t_max = options->t_max;
-  opt.tolerance = options->tolerance;
-  opt.max_iters = options->max_iters;
-  opt.matrix_index = -1;
+  if (!pll_distances_check(who, p, tips, count, params_indices, options, &x) ||
+      !pll_distances_flush(who, p, x, tips, count, params_indices, options, &opt))
+    return PLL_FAILURE;
   const pllgpu_distances_t dev = {out->distance, out->p_distance, out->d_f, out->dd_f, out->status, out->iterations};
   if (pllgpu_pairwise_distances(x->ctx, tips, count, params_indices, &opt, &dev) != 0)
   {

@@ -136,6 +136,12 @@ int pll_flush_eigen(pll_partition_t *p, pll_amd_ext_t *x);
 /* the two sumtable contraction matrices of params_indices (derivatives.c), rebuilt and uploaded when an eigensystem, a
  * frequency vector or params_indices changed; the eigensystems must be valid and flushed (pll_flush_eigen) */
 int pll_flush_aux_matrices(pll_partition_t *p, pll_amd_ext_t *x, const unsigned int *params_indices);
+/* pll_gpu_pairwise_distances in two parts (distances.c), shared with pll_gpu_distance_tree (nj.c): every check of a list of
+ * count > 0 tips, the device last, with the error convention of batch.c; then what the device reads brought up to date */
+int pll_distances_check(const char *who, pll_partition_t *p, const unsigned int *tips, unsigned int count, const unsigned int *params_indices,
+                        const pll_gpu_newton_t *options, pll_amd_ext_t **ext);
+int pll_distances_flush(const char *who, pll_partition_t *p, pll_amd_ext_t *x, const unsigned int *tips, unsigned int count,
+                        const unsigned int *params_indices, const pll_gpu_newton_t *options, pllgpu_newton_t *device_options);
 /* the category rates alone */
 int pll_flush_rates(pll_partition_t *p, pll_amd_ext_t *x);
 /* class maps of the parents of `ops` on the device, dependency level by level (repeats.c) */

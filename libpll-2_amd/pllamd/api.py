@@ -211,6 +211,7 @@ class Distances(C.Structure):
 
 
 NEWTON_MAX_ITERS = 64
+NJ_BIONJ = 1  # PLL_GPU_NJ_BIONJ
 NEWTON_CONVERGED, NEWTON_AT_MIN, NEWTON_AT_MAX, NEWTON_STALLED, NEWTON_MAXITER = 0, 1, 2, 3, 4
 
 assert C.sizeof(Insertion) == 24
@@ -330,6 +331,11 @@ _GPU_PROTOS = {
     "pll_gpu_optimize_branch_length": (
         C.c_int, [PartitionP, C.c_int, C.c_int, c_uint_p, c_double_p, C.POINTER(Newton), C.POINTER(NewtonResult), c_double_p]),
     "pll_gpu_pairwise_distances": (C.c_int, [PartitionP, c_uint_p, C.c_uint, c_uint_p, C.POINTER(Newton), C.POINTER(Distances)]),
+    "pll_gpu_nj_tree": (C.c_int, [c_double_p, C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_int), c_double_p]),
+    "pll_gpu_distance_tree": (
+        C.c_int, [PartitionP, c_uint_p, C.c_uint, c_uint_p, C.POINTER(Newton), C.c_uint, C.POINTER(C.c_int), c_double_p, c_double_p]),
+    "pll_gpu_nj_last_launch_count": (C.c_uint, []),
+    "pll_gpu_nj_last_device_ms": (C.c_double, []),
     "pll_gpu_last_algorithmic_bytes": (C.c_double, [PartitionP]),
     "pll_gpu_sync_repeats": (C.c_int, [PartitionP, C.c_int]),
     "pll_gpu_sync_all": (C.c_int, [PartitionP]),

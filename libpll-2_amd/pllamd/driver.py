@@ -325,6 +325,39 @@ def pairwise_distances(lib, partition, tips, params_indices, options, want=DISTA
     return out
 
 
+def nj_tree(lib, distances, flags=0, device=-1, fill=None):
+    """pll_gpu_nj_tree: (parent int32 [2n - 2], length float64 [2n - 2]) of the [n, n] matrix `distances` (only [x][y],
+    x < y, is read); flags 0 = NJ, api.NJ_BIONJ. `fill`: what both outputs hold before the call (tests: outputs stay
+    untouched on a failure; they then travel in the exception's `outputs`). libpll_amd.so only."""
+    d = np.ascontiguousarray(distances, dtype=np.float64)
+    n = d.shape[0]
+    assert d.shape == (n, n)
+    parent = np.full(max(2 * n - 2, 1), 0 if fill is None else fill, dtype=np.int32)
+    length = np.full(max(2 * n - 2, 1), 0.0 if fill is None else fill, dtype=np.float64)
+    if not lib.pll_gpu_nj_tree(api.dptr(d), n, int(flags), int(device), parent.ctypes.data_as(C.POINTER(C.c_int)), api.dptr(length)):
+        err = RuntimeError(f"pll_gpu_nj_tree: [{lib.errno()}] {lib.errmsg()}")
+        err.outputs = {"parent": parent, "length": length}
+        raise err
+    return parent, length
+
+
+def distance_tree(lib, partition, tips, params_indices, options, flags=0, want_distances=True, fill=None):
+    """pll_gpu_distance_tree: (parent, length, distances or None) of the tips of the list - pairwise_distances and nj_tree
+    in one call, the matrix staying on the device unless want_distances. libpll_amd.so only."""
+    tips = np.ascontiguousarray(tips, dtype=np.uint32)
+    n = len(tips)
+    pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+    parent = np.full(max(2 * n - 2, 1), 0 if fill is None else fill, dtype=np.int32)
+    length = np.full(max(2 * n - 2, 1), 0.0 if fill is None else fill, dtype=np.float64)
+    dist = np.full((n, n), 0.0 if fill is None else fill, dtype=np.float64) if want_distances else None
+    if not lib.pll_gpu_distance_tree(partition, api.uptr(tips), n, api.uptr(pi), C.byref(options), int(flags),
+                                     parent.ctypes.data_as(C.POINTER(C.c_int)), api.dptr(length), api.dptr(dist) if want_distances else None):
+        err = RuntimeError(f"pll_gpu_distance_tree: [{lib.errno()}] {lib.errmsg()}")
+        err.outputs = {"parent": parent, "length": length, "distances": dist}
+        raise err
+    return parent, length, dist
+
+
 def branch_derivatives_per_edge(lib, partition, rows, params_indices, sumtable=None):
     """the same values the way every libpll offers them: per row pll_update_sumtable into one caller-owned table, then
     pll_compute_likelihood_derivatives at the row's length. The table (sites * rate_cats * states_padded doubles, 64-byte
