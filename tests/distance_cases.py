@@ -173,6 +173,138 @@ def p_distance_by_sites(seq_a, seq_b, cmap, states, weights):
     return differ, compared
 
 
+COUNT_BUDGET = 36 * 1024  # "up to 36 KB of them": the private count tables of a workgroup
+LDS_MAX = 158 * 1024      # PLLGPU_DISTANCE_LDS_MAX
+
+
+def codes_in_use(states, seqs, cmap):
+    """C of include/pll_amd_device.h: 16 for 4 states, else a code per distinct state mask that the tips show"""
+    if states == 4:
+        return 16
+    return len(distances.encode(seqs, np.asarray(cmap, dtype=np.uint64), states)[1])
+
+
+def copies_by_rule(states, rate_cats, ncodes):
+    """the count tables a workgroup keeps, by the text of include/pll_amd_device.h: the diag table of 32 R S bytes and at
+    least one table of 4 (C^2 | 1) bytes must fit PLLGPU_DISTANCE_LDS_MAX with C <= PLLGPU_DISTANCE_MAX_CODES (else None: the
+    call is refused); where there is room 2, 4, ... 256 tables, up to 36 KB of them"""
+    diag, table = 32 * rate_cats * states, 4 * ((ncodes * ncodes) | 1)
+    if ncodes > MAX_CODES or diag + table > LDS_MAX:
+        return None
+    room = min(max(COUNT_BUDGET, table), LDS_MAX - diag)
+    copies = 1
+    while copies < 256 and 2 * copies * table <= room:
+        copies *= 2
+    return copies
+
+
+def lds_bytes_by_rule(states, rate_cats, ncodes):
+    """dynamic LDS of a launch by the same text: the diag table and copies_by_rule tables (None: refused)"""
+    copies = copies_by_rule(states, rate_cats, ncodes)
+    return None if copies is None else 32 * rate_cats * states + copies * 4 * ((ncodes * ncodes) | 1)
+
+
+# ---- inputs with exactly C codes ---------------------------------------------------------------------------------------
+def code_masks(states, ncodes, seed=5):
+    """ncodes distinct non-empty state masks in increasing order: the singletons (all of them from ncodes >= states on), the
+    all-states mask, then random proper subsets of 2 .. states - 1 states"""
+    masks = [1 << i for i in range(min(states, ncodes))]
+    if ncodes > states:
+        masks.append((1 << states) - 1)
+    rng = np.random.Generator(np.random.PCG64(seed + 1000 * states + ncodes))
+    seen = set(masks)
+    while len(masks) < ncodes:
+        bits = rng.integers(0, 2, size=states)
+        m = sum(1 << i for i in range(states) if bits[i])
+        if 2 <= int(bits.sum()) < states and m not in seen:
+            seen.add(m)
+            masks.append(m)
+    return sorted(masks)
+
+
+def generated(states, ncodes, tips, sites, seed=5):
+    """(sequences, charmap, exchangeabilities, frequencies) that show exactly ncodes codes. The character map gives the
+    bytes 1 .. ncodes the masks of code_masks in increasing order, so a byte b is code b - 1 under distances.encode (masks in
+    increasing order) and under either attribute set of the library (plain: the order in which tip 0 shows them; PATTERN_TIP:
+    the order of the bytes). Site s < ncodes of tip x shows byte 1 + (s + rot[x]) % ncodes, rot = 0, ncodes - 1, 1, 2: every
+    tip runs through all codes, and the pairs (0, 1) and (0, 2) meet in the corner cells (0, C-1) and (C-1, 0) of the table.
+    Site ncodes shows the last code in every tip: the corner (C-1, C-1). The rest are random."""
+    assert states != 4 and tips <= 4 and sites > ncodes > 2
+    cmap = np.zeros(256, dtype=np.uint64)
+    cmap[1:ncodes + 1] = np.array(code_masks(states, ncodes, seed), dtype=np.uint64)
+    rng = np.random.Generator(np.random.PCG64(seed + 31 * ncodes + states))
+    seqs = []
+    for x in range(tips):
+        run = 1 + (np.arange(ncodes) + (0, ncodes - 1, 1, 2)[x]) % ncodes
+        rest = rng.integers(1, ncodes + 1, size=sites - ncodes - 1)
+        seqs.append(np.concatenate([run, [ncodes], rest]).astype(np.uint8).tobytes())
+    ex, fr = W.synthetic_exch(states)
+    return seqs, cmap, ex, fr
+
+
+# (shape, codes, sites) of tests/test_gpu_distance_tables.py; four tips, except three at 61 states
+TABLE_SHAPES = {"5x3": (5, 3), "20x4": (20, 4), "61x49": (61, 49), "61x50": (61, 50)}
+TABLE_CASES = [("5x3", 5, 300), ("5x3", 8, 300), ("20x4", 68, 300), ("20x4", 96, 300), ("20x4", 127, 300), ("20x4", 128, 300),
+               ("61x49", 127, 160)]
+TABLE_REFUSED = [("61x50", 127, 160), ("20x4", 129, 300)]
+
+
+def table_tips(shape):
+    return 3 if shape.startswith("61") else 4
+
+
+def table_case(shape, ncodes, sites):
+    return generated(TABLE_SHAPES[shape][0], ncodes, table_tips(shape), sites)
+
+
+class Restated:
+    """pllamd/distances.py in the place of a library's per-pair path, on the model of an open Tips (either library: the
+    eigensystem is read from the partition) - the expectation where the reference cannot take the input (a byte >= 128)"""
+    sumtable = None
+
+    def __init__(self, bed, seqs, cmap):
+        self.codes, self.masks, self.w = restated(seqs, cmap, bed.states, bed.weights)
+        ev, iev, lam = bed.eigen()
+        self.U, self.Wv = distances.code_vectors(self.masks, bed.states, ev, iev, bed.freqs, bed.pi)
+        self.model = (lam, bed.rates.copy(), bed.rate_weights.copy(), bed.pi.copy())
+        self.states, self.n = bed.states, None
+
+    def table(self, x, y):
+        self.n = distances.code_pair_counts(self.codes[x], self.codes[y], self.w, len(self.masks))
+
+    def derivatives(self, edge, sumtable, t):
+        return distances.derivatives(self.n, self.U, self.Wv, *self.model, t)
+
+    def pair_derivatives(self, x, y, ts=T_POINTS):
+        self.table(x, y)
+        return [self.derivatives(None, None, t) for t in ts]
+
+    def pair_newton(self, x, y, t_start, t_min, t_max, tolerance, max_iters):
+        self.table(x, y)
+        return newton.host_newton(self, None, None, t_start, t_min, t_max, tolerance, max_iters)
+
+    def p_distance(self, x, y):
+        self.table(x, y)
+        return distances.p_distance(self.n, self.masks, self.states)
+
+
+WEIGHT_SITES, HEAVY, SECOND = 1027, 5, 700
+
+
+def weights_case(states):
+    """(sequences, charmap, exchangeabilities, frequencies, weights) of four tips at 1027 sites whose weights add up to
+    2^32 - 1: arange % 4, site 5 = 2^31, site 700 = the rest; tips 0 and 1 show at site 700 what they show at site 5, so that
+    one cell of their table counts more than 2^31, from two threads (quads 1 and 175) with different private tables"""
+    seqs, cmap, exch, freqs = sequences(states, 4, WEIGHT_SITES)
+    seqs = [bytearray(s) for s in seqs]
+    for x in (0, 1):
+        seqs[x][SECOND] = seqs[x][HEAVY]
+    w = np.arange(WEIGHT_SITES, dtype=np.int64) % 4
+    w[HEAVY], w[SECOND] = 1 << 31, 0
+    w[SECOND] = (1 << 32) - 1 - int(w.sum())
+    return [bytes(s) for s in seqs], cmap, exch, freqs, w.astype(np.uint32)
+
+
 def launches_by_rule(count, max_pairs=MAX_PAIRS):
     """the cutting rule of include/pll_amd_device.h, pllgpu_pairwise_distances: one launch for the code vectors, then whole
     rows of the pair matrix"""

@@ -57,6 +57,20 @@ def balanced(levels):
 
 MATRICES = {"additive": additive, "noisy": noisy, "ones": ones, "balanced": balanced}
 
+# rows of the triangle per search workgroup (PLL_AMD_NJ_ROWS) -> the (kind, n, flag) run under it in a child process. One
+# row: 599 search workgroups at the first step of 600 nodes, so the last arrival's loop over the partials takes a third
+# step of its 256 threads, then a second, then one, as the matrix shrinks, and the ties of ones(600) are settled across all
+# of them. Three rows: the last workgroup's list of rows ends early (598 = 3 x 199 + 1 rows at 599 nodes, ...).
+ROW_RUNS = {1: (("noisy", 600, "nj"), ("noisy", 600, "bionj"), ("ones", 600, "nj"), ("balanced", 6, "nj")),
+            3: (("noisy", 257, "nj"), ("noisy", 257, "bionj"), ("noisy", 600, "nj"), ("noisy", 600, "bionj"))}
+EXACT_KINDS = ("additive", "ones", "balanced")
+
+
+def search_workgroups(nodes, rows):
+    """the search workgroups of every step of a join of `nodes` nodes: ceil((r - 1) / rows), r = nodes .. 4
+    (include/pll_amd_device.h: rows 0 .. r-2 of the triangle hold pairs)"""
+    return [(r - 1 + rows - 1) // rows for r in range(nodes, 3, -1)]
+
 
 @functools.lru_cache(maxsize=None)
 def expected(kind, n, flag, long_double=False):

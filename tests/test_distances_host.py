@@ -203,8 +203,127 @@ def test_zero_count_succeeds_and_reads_nothing(amd_lib):
         assert amd_lib.pll_gpu_pairwise_distances(b.p, None, 0, None, None, None) == 0 and amd_lib.errno() == api.ERROR_PARAM_INVALID
 
 
+# ---- the edges of the count tables: the rule restated, and conditions on the inputs of test_gpu_distance_tables.py --------
+def test_the_header_still_states_the_rule():
+    dev = re.sub(r"\s*\n \*\s*", " ", open(os.path.join(ROOT, "include", "pll_amd_device.h")).read())
+    assert "PLLGPU_DISTANCE_LDS_BYTES = 32 R states + 4 (C^2 | 1) <= PLLGPU_DISTANCE_LDS_MAX" in dev
+    assert "a workgroup keeps 2, 4, ... 256 such tables, up to 36 KB of them" in dev and DC.COUNT_BUDGET == 36 * 1024
+    assert re.search(r"#define PLLGPU_DISTANCE_LDS_MAX \(158ul \* 1024ul\)", dev) and DC.LDS_MAX == 158 * 1024
+    assert re.search(r"#define PLLGPU_DISTANCE_LDS_BYTES\(S, R, C\) \(32ul \* \(R\) \* \(S\) \+ 4ul \* \(\(\(C\) \* \(C\)\) \| 1ul\)\)", dev)
+    hip = open(os.path.join(ROOT, "libpll-2_amd", "csrc", "hip", "pllgpu.hip")).read()
+    assert "constexpr size_t kDistCountBytes = 36 * 1024;" in hip
+    # the figures the issue of these tests was written with
+    assert DC.lds_bytes_by_rule(20, 4, 127) == 67076 and DC.lds_bytes_by_rule(61, 49, 127) == 160164 <= DC.LDS_MAX == 161792
+    assert DC.copies_by_rule(61, 50, 127) is None and DC.copies_by_rule(20, 4, 129) is None
+    assert [DC.copies_by_rule(20, 4, c) for c in (67, 68, 95, 96, 128)] == [2, 1, 1, 1, 1]
+    assert 4 * ((95 * 95) | 1) <= DC.COUNT_BUDGET < 4 * ((96 * 96) | 1)
+
+
+@pytest.mark.parametrize("shape,ncodes,sites", DC.TABLE_CASES + DC.TABLE_REFUSED)
+def test_the_generated_inputs_show_exactly_their_codes(shape, ncodes, sites):
+    """exactly C codes, a byte b being code b - 1; some pair has a count in each corner cell of the table"""
+    states = DC.TABLE_SHAPES[shape][0]
+    seqs, cmap, _, _ = DC.table_case(shape, ncodes, sites)
+    tips = DC.table_tips(shape)
+    assert len(seqs) == tips and all(len(s) == sites for s in seqs) and sites <= 300
+    codes, masks, w = DC.restated(seqs, cmap, states, np.ones(sites))
+    assert len(masks) == ncodes == DC.codes_in_use(states, seqs, cmap) and (np.diff(masks.astype(object)) > 0).all()
+    assert all((codes[x] == np.frombuffer(seqs[x], dtype=np.uint8) - 1).all() for x in range(tips))
+    assert all(set(codes[x][:ncodes]) == set(range(ncodes)) for x in range(tips))
+    assert sum(int(m) & (int(m) - 1) == 0 for m in masks) == min(states, ncodes)
+    assert ((1 << states) - 1 in [int(m) for m in masks]) == (ncodes > states)
+    corners = {(0, ncodes - 1): False, (ncodes - 1, 0): False, (ncodes - 1, ncodes - 1): False}
+    for x, y in DC.pairs(tips):
+        n = distances.code_pair_counts(codes[x], codes[y], w, ncodes)
+        for cell in corners:
+            corners[cell] |= bool(n[cell] > 0)
+    assert all(corners.values()), corners
+
+
+@pytest.mark.parametrize("shape,ncodes,sites", [c for c in DC.TABLE_CASES + DC.TABLE_REFUSED if c[1] <= 127])
+def test_the_restatement_against_the_reference_at_the_table_edges(ref_lib, shape, ncodes, sites):
+    """(a byte >= 128 cannot go through the reference, which indexes its character map with a signed char)"""
+    states, rate_cats = DC.TABLE_SHAPES[shape]
+    seqs, cmap, exch, freqs = DC.table_case(shape, ncodes, sites)
+    codes, masks, w = DC.restated(seqs, cmap, states, np.ones(sites))
+    with DC.Tips(ref_lib, states, rate_cats, seqs, cmap, exch, freqs) as b:
+        ev, iev, lam = b.eigen()
+        U, Wv = distances.code_vectors(masks, states, ev, iev, b.freqs, b.pi)
+        worst = 0.0
+        for x, y in DC.pairs(len(seqs)):
+            n = distances.code_pair_counts(codes[x], codes[y], w, ncodes)
+            exp = np.array(b.pair_derivatives(x, y))
+            got = np.array([distances.derivatives(n, U, Wv, lam, b.rates, b.rate_weights, b.pi, t) for t in DC.T_POINTS])
+            worst = max(worst, GC.worst(got, exp, sites))
+            assert GC.close(got, exp, sites), (shape, ncodes, x, y, GC.worst(got, exp, sites))
+    print(f"{shape} {ncodes} codes: the restatement's worst deviation is {worst:.3f} of the bound")
+
+
+def _generated_tips(shape, ncodes, sites, attrs):
+    states, rate_cats = DC.TABLE_SHAPES[shape]
+    return lambda lib: DC.Tips(lib, states, rate_cats, *DC.table_case(shape, ncodes, sites), attrs=attrs)
+
+
+@pytest.mark.parametrize("attrs", [api.PATTERN_TIP, 0], ids=["pattern_tip", "plain"])
+def test_the_limits_of_the_code_table_on_the_host(amd_lib, attrs):
+    """128 codes, and 61 x 49 at 127 codes, get as far as the missing device; 129 codes and 61 x 50 at 127 codes are refused"""
+    tips = (0, 1, 2)
+    for shape, ncodes, sites in (("20x4", 127, 300), ("20x4", 128, 300), ("61x49", 127, 160)):
+        _refused(amd_lib, api.ERROR_GPU_UNAVAILABLE, tips=tips, make=_generated_tips(shape, ncodes, sites, attrs))
+    for shape, ncodes, sites in DC.TABLE_REFUSED:
+        assert "tip codes" in _refused(amd_lib, api.ERROR_GPU_UNSUPPORTED, tips=tips, make=_generated_tips(shape, ncodes, sites, attrs))
+
+
+def test_every_size_class_of_the_count_tables_is_run():
+    """copies_by_rule over all cases of both GPU files: every number of tables the code can choose with these alphabets,
+    and dynamic LDS on both sides of 64 KB; a changed constant cannot silently move a case out of its class"""
+    import test_gpu_distances as old
+    classes, lds = set(), set()
+    for shape, tips, sites in {(c[0], c[2], c[3]) for c in old.CASES}:
+        states, rate_cats = old.SHAPES[shape]
+        seqs, cmap, _, _ = DC.sequences(states, tips, sites)
+        ncodes = DC.codes_in_use(states, seqs, cmap)
+        classes.add(DC.copies_by_rule(states, rate_cats, ncodes))
+        lds.add(DC.lds_bytes_by_rule(states, rate_cats, ncodes))
+    assert classes >= {2, 8, 32, 64} and max(lds) <= 64 * 1024
+    by_case = {c: DC.copies_by_rule(*DC.TABLE_SHAPES[c[0]], c[1]) for c in DC.TABLE_CASES}
+    assert by_case[("5x3", 5, 300)] == 256 and by_case[("5x3", 8, 300)] == 128
+    assert all(by_case[c] == 1 for c in DC.TABLE_CASES if c[1] >= 68)
+    assert classes | set(by_case.values()) >= {1, 2, 8, 32, 64, 128, 256}
+    for shape, ncodes, _ in DC.TABLE_CASES:
+        over = DC.lds_bytes_by_rule(*DC.TABLE_SHAPES[shape], ncodes) > 64 * 1024
+        assert over == (ncodes >= 127), (shape, ncodes)
+    assert DC.lds_bytes_by_rule(20, 4, 96) <= 64 * 1024 < DC.lds_bytes_by_rule(20, 4, 127)
+    # both sides of the 158 KB limit
+    assert DC.lds_bytes_by_rule(61, 49, 127) <= DC.LDS_MAX and all(DC.copies_by_rule(*DC.TABLE_SHAPES[s], c) is None for s, c, _ in DC.TABLE_REFUSED)
+    assert 32 * 50 * 61 + 4 * ((127 * 127) | 1) > DC.LDS_MAX
+
+
+@pytest.mark.parametrize("states,rate_cats", [(4, 4), (20, 4)])
+def test_the_heavy_weights_meet_in_one_cell_from_two_tables(ref_lib, states, rate_cats):
+    """conditions on distance_cases.weights_case: the weights add up to 2^32 - 1 (2^32 is refused), the pair (0, 1) has a cell
+    above 2^31 whose two heavy sites lie in the quads of two threads with different private tables - and with W = 2^32 - 1
+    the restatement stays within gradient_cases.close of the reference"""
+    seqs, cmap, exch, freqs, weights = DC.weights_case(states)
+    assert weights.dtype == np.uint32 and int(weights.astype(np.int64).sum()) == (1 << 32) - 1
+    assert int(weights[DC.HEAVY]) == 1 << 31 and int(weights[DC.SECOND]) == 2147482109
+    codes, masks, w = DC.restated(seqs, cmap, states, weights)
+    n = distances.code_pair_counts(codes[0], codes[1], w, len(masks))
+    cell = (codes[0][DC.HEAVY], codes[1][DC.HEAVY])
+    assert cell == (codes[0][DC.SECOND], codes[1][DC.SECOND]) and int(n[cell]) > 1 << 31
+    copies = DC.copies_by_rule(states, rate_cats, DC.codes_in_use(states, seqs, cmap))
+    assert copies > 1 and (DC.HEAVY // 4) % copies != (DC.SECOND // 4) % copies and DC.SECOND // 4 < 256 <= DC.WEIGHT_SITES // 4
+    with DC.Tips(ref_lib, states, rate_cats, seqs, cmap, exch, freqs, pattern_weights=weights) as b:
+        r = DC.Restated(b, seqs, cmap)
+        for x, y in DC.pairs(4):
+            exp, got = np.array(b.pair_derivatives(x, y)), np.array(r.pair_derivatives(x, y))
+            assert GC.close(got, exp, b.weight_sum), (x, y, GC.worst(got, exp, b.weight_sum))
+            differ, compared = DC.p_distance_by_sites(seqs[x], seqs[y], cmap, states, weights)
+            assert r.p_distance(x, y) == differ / compared
+
+
 # ---- pllamd/distances.py against the reference -------------------------------------------------------------------
-SHAPES = {"4x4": (4, 4), "5x3": (5, 3), "20x4": (20, 4)}
+SHAPES ={"4x4": (4, 4), "5x3": (5, 3), "20x4": (20, 4)}
 REF_TIPS, REF_SITES = 6, 130
 
 

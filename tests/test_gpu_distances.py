@@ -15,7 +15,9 @@ is the slope difference over the curvature, and the factor lets the curvature ha
 
 One workgroup serves one pair, so the "pair block" of the launch is one pair: tip counts 2 and 3 are one more than it in
 each direction; 9 tips are 36 workgroups. Site counts 1, 63, 64, 65, 130 and 1000: below, at and above a wave's stride, a
-tail that is no multiple of the four sites a thread reads at once, and several strides of the 256 threads.
+tail that is no multiple of the four sites a thread reads at once, and 250 quads of four sites: almost every one of the 256
+threads takes one step of the site loop, none a second (tests/test_gpu_distance_tables.py runs 1029 and 2051 sites, where
+threads take a second step, and the table sizes these cases leave out).
 
 Observed on an MI355X: the worst deviation of one evaluation is 0.05 of the bound (61 x 4 at t = 1.2), below 0.04 elsewhere."""
 import functools

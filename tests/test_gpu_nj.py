@@ -13,6 +13,9 @@ tests/test_nj_host.py::test_the_inputs_keep_their_gaps (2.348e-12, at 600 nodes,
 The kernels add in nj.py's order, so the observed fraction of the bound, which every case prints, is expected to be 0.
 
 Several workgroups and the ticket at 9 nodes: PLL_AMD_NJ_ROWS=2 in a fresh child process must give the default run's bits.
+Hundreds of them (nj_cases.ROW_RUNS): one row per workgroup at 600 nodes is 599 search workgroups, so the last arrival's
+loop over the partials takes up to three steps; three rows per workgroup leave the last workgroup fewer rows than the others.
+The fused call is also run with its distance launches cut into pieces (PLL_AMD_DISTANCE_PAIRS).
 The fused call at 9 tips x 130 sites, 4 x 4 and 20 x 4 (distance_cases): pll_gpu_distance_tree equals pll_gpu_nj_tree fed
 with the distance array of pll_gpu_pairwise_distances bit for bit, distances_out equals that array, and an inner CLV of the
 partition computed before the call has, downloaded after it, the bytes of the same CLV of a partition that made no such call.
@@ -87,6 +90,34 @@ def test_several_search_workgroups_give_the_same_bits(amd_lib):
         assert _same_bits((parent, length), NC.expected("noisy", 9, flag))
 
 
+@pytest.mark.parametrize("rows", list(NC.ROW_RUNS))
+def test_hundreds_of_search_workgroups_give_the_same_bits(amd_lib, rows):
+    """nj_cases.ROW_RUNS in one fresh child process per value of PLL_AMD_NJ_ROWS: at one row per workgroup 600 nodes start with
+    599 search workgroups, so the last arrival's loop over the partials takes three steps, later two, later one, and the ties
+    of the all-ones matrix are settled across all of them; at three rows the last workgroup's rows end early. Every result is
+    the default run's, bit for bit, in as many launches, and nj.py's (tests/test_nj_host.py holds the workgroup counts)"""
+    items = [f"{kind}:{n}:{flag}" for kind, n, flag in NC.ROW_RUNS[rows]]
+    env = dict(os.environ, PLL_AMD_NJ_ROWS=str(rows))
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "nj_rows_worker.py")] + items, env=env, capture_output=True, text=True,
+                         timeout=120)
+    assert run.returncode == 0, run.stderr[-2000:]
+    child = json.loads(run.stdout.strip().splitlines()[-1])
+    assert list(child) == items
+    for item, (kind, n, flag) in zip(items, NC.ROW_RUNS[rows]):
+        matrix = NC.MATRICES[kind](n)
+        parent, length = driver.nj_tree(amd_lib, matrix, NC.FLAGS[flag])
+        assert amd_lib.pll_gpu_nj_last_launch_count() == nj.launch_count(len(matrix))
+        assert child[item] == [parent.tobytes().hex(), length.tobytes().hex(), nj.launch_count(len(matrix))], item
+        exp_parent, exp_length = NC.expected(kind, n, flag)
+        assert np.array_equal(parent, exp_parent), item
+        if kind in NC.EXACT_KINDS:
+            assert length.tobytes() == exp_length.tobytes(), item
+        else:
+            worst = float(np.abs(length - exp_length).max())
+            print(f"{rows} rows, {item}: worst |length - expected| {worst:.3g} = {worst / BOUND:.3g} of the bound {BOUND:.3g}")
+            assert np.isfinite(length).all() and worst <= BOUND
+
+
 def test_refusals_with_a_device(amd_lib):
     with pytest.raises(RuntimeError) as err:
         driver.nj_tree(amd_lib, NC.noisy(5), 0, device=4096, fill=7)
@@ -153,6 +184,25 @@ def test_the_fused_call(amd_lib, flag, shape):
         assert _download(b) == clv_before
         # and the distances after the tree are the distances before it
         assert b.distances(range(TIPS), opt, want=())["distance"].tobytes() == dist.tobytes()
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("flag", list(NC.FLAGS))
+def test_the_fused_call_with_the_distances_cut_into_several_launches(amd_lib, flag, shape, monkeypatch):
+    """PLL_AMD_DISTANCE_PAIRS = 2 x tips when the partition is created: two rows of the pair matrix per launch, the join
+    behind the last of them - the uncut call's parent, length and distances, bit for bit, in the launches of both rules"""
+    opt = driver.newton_options(0.1, 1e-6, 100.0, 1e-8 * SITES, 32)
+    with _bed(amd_lib, shape) as b:
+        parent, length, dist = driver.distance_tree(amd_lib, b.p, range(TIPS), b.pi, opt, NC.FLAGS[flag])
+        assert b.launches() == DC.launches_by_rule(TIPS) + nj.launch_count(TIPS) == 2 + nj.launch_count(TIPS)
+    monkeypatch.setenv("PLL_AMD_DISTANCE_PAIRS", str(2 * TIPS))
+    with _bed(amd_lib, shape) as b:
+        cut = driver.distance_tree(amd_lib, b.p, range(TIPS), b.pi, opt, NC.FLAGS[flag])
+        assert b.launches() == DC.launches_by_rule(TIPS, 2 * TIPS) + nj.launch_count(TIPS) == 5 + nj.launch_count(TIPS)
+        assert _same_bits(cut[:2], (parent, length)) and cut[2].tobytes() == dist.tobytes()
+        assert b.distances(range(TIPS), opt, want=())["distance"].tobytes() == dist.tobytes()
+        assert b.launches() == 5
+    assert _same_bits((parent, length), nj.nj_tree(dist, NC.FLAGS[flag]))
 
 
 def test_the_fused_call_refuses_with_a_device(amd_lib):

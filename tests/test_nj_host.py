@@ -167,6 +167,30 @@ def test_the_launch_rule():
     assert "2 (count - 3) + 2" in dev and re.search(r"#define PLLGPU_NJ_ROWS \d+u", dev)
 
 
+def test_the_row_runs_stride_the_partial_loop():
+    """conditions on nj_cases.ROW_RUNS (tests/test_gpu_nj.py): the last arrival reduces the partials with 256 threads, so the
+    runs must hold a step with more than 512 search workgroups, one in (256, 512] and one in (64, 256] - and the default of
+    8 rows never leaves the first stride at these sizes, nor do the nine nodes over two rows"""
+    dev = open(os.path.join(ROOT, "include", "pll_amd_device.h")).read()
+    assert "#define PLLGPU_NJ_ROWS 8u" in dev
+    assert max(NC.search_workgroups(600, 8)) == 75 and max(NC.search_workgroups(9, 2)) == 4
+    assert NC.search_workgroups(9, 2) == [4, 4, 3, 3, 2, 2] and NC.search_workgroups(5, 1) == [4, 3]
+    for rows, runs in NC.ROW_RUNS.items():
+        counts = set()
+        for kind, n, flag in runs:
+            assert flag in NC.FLAGS
+            nodes = len(NC.MATRICES[kind](n))
+            counts |= set(NC.search_workgroups(nodes, rows))
+        if rows == 1:
+            assert max(counts) == 599
+            assert any(c > 512 for c in counts) and any(256 < c <= 512 for c in counts) and any(64 < c <= 256 for c in counts)
+        else:
+            # a last workgroup with fewer rows than the others, past one stride of the partial loop or not
+            assert any((r - 1) % rows for kind, n, flag in runs for r in range(4, n + 1))
+            assert max(counts) == 200 and 86 in counts
+    assert len(NC.balanced(6)) == 192
+
+
 # ---- the host layer of libpll_amd.so ---------------------------------------------------------------------------------
 def test_symbols_declared_exported_and_bound(amd_lib):
     hdr = open(os.path.join(ROOT, "include", "pll_amd.h")).read()
