@@ -1192,6 +1192,62 @@ unsigned int pll_gpu_nj_last_launch_count(void);
  * stream it ran on (without the copies up and back); -1 if none ran */
 double pll_gpu_nj_last_device_ms(void);
 
+/* ---- bootstrap trees from distances ------------------------------------------------------
+ * Felsenstein's bootstrap of the distance tree - hundreds to thousands of replicate trees of one alignment - without a
+ * host loop: all replicates have the same count, so their joins run in lockstep, one search / join launch pair serving
+ * step s of every one of them, and the distance kernel reads the alignment through one row of weights, so it is given
+ * many. Turning the trees into split supports or a consensus is the caller's.
+ *
+ * pll_gpu_nj_trees: `replicates` matrices in one call. Tree b - parent + b (2 count - 2), length + b (2 count - 2) - has
+ * bit for bit what pll_gpu_nj_tree gives on matrix b (distances + b count^2): its tree format, flags, tie rule and
+ * four-node rule, and pllamd/nj.py's bits on exact inputs. The launches do not depend on `replicates` as long as the
+ * matrices and working sets fit one chunk (the rule and the byte budget: include/pll_amd_device.h, pllgpu_nj_trees);
+ * pll_gpu_nj_last_launch_count reports chunks x (2 (count - 3) + 2), chunks x 1 at count == 3. It owns a stream and its
+ * blocks on `device` for the length of the call, as pll_gpu_nj_tree does.
+ * Refused before anything is launched, with every output untouched: PLL_ERROR_PARAM_INVALID for a NULL distances, parent
+ * or length, count < 3, unknown flag bits, or an entry [x][y], x < y, of any matrix that is negative or not finite;
+ * PLL_ERROR_GPU_UNAVAILABLE without a device; PLL_ERROR_MEM_ALLOC when the device has no room. replicates == 0 succeeds
+ * at once after the NULL, count and flag checks and writes nothing.
+ *
+ * pll_gpu_bootstrap_distance_trees: row b of every output is, bit for bit, what this sequence returns:
+ *   1. row first_replicate + b of pll_gpu_draw_replicate_weights(partition, seed, ...) - the absolute numbering of that
+ *      call: a call for rows 3..7 gives rows 3..7 of a call for rows 0..7;
+ *   2. pll_set_pattern_weights with that row;
+ *   3. pll_gpu_distance_tree(partition, tips, count, params_indices, options, flags, ...), out->distances its
+ *      distances_out and out->status the status array of pll_gpu_pairwise_distances;
+ * which is the composition of the definitions in pllamd/rell.py, pllamd/distances.py and pllamd/nj.py. But the partition's
+ * pattern weights are not written, and neither is anything else it holds - CLVs, scalers, matrices, the resampling state
+ * of other calls: the rows are drawn on the device where the distance kernel reads them and leave it only through
+ * out->weights. Per chunk of replicates (the cut, the byte budget and the launch rule: include/pll_amd_device.h,
+ * pllgpu_bootstrap_distance_trees) one draw launch, the distance launches, the joins and one wait;
+ * pll_gpu_last_launch_count reports the launches.
+ * PLL_SUCCESS, or PLL_FAILURE with pll_errno and the usual line on stderr. Refused before anything is flushed or launched,
+ * with every output untouched, in this order: PLL_ERROR_PARAM_INVALID for a NULL partition, out, out->parent or
+ * out->length; every check of pll_gpu_distance_tree, in its order; PLL_ERROR_PARAM_INVALID for pattern weights that add
+ * up to 0 (the refusal of pll_gpu_draw_replicate_weights). replicates == 0 succeeds after the first check and writes
+ * nothing. A device error after the checks may leave the rows of earlier chunks written.
+ * Not offered: split supports or a consensus of the trees; several pairs or replicates per workgroup; rows of weights
+ * supplied by the caller; site repeats, ascertainment bias and prop_invar > 0 (refused by the distance checks). */
+typedef struct pll_gpu_bootstrap_trees
+{
+  int *parent;            /* [replicates][2 count - 2], required */
+  double *length;         /* [replicates][2 count - 2], required */
+  double *distances;      /* NULL or [replicates][count][count] */
+  int *status;            /* NULL or [replicates][count][count]: PLL_GPU_NEWTON_* of every pair */
+  unsigned int *weights;  /* NULL or [replicates][sites]: the rows drawn */
+} pll_gpu_bootstrap_trees_t;
+
+int pll_gpu_nj_trees(const double *distances /* [replicates][count][count]; only [x][y], x < y, is read */,
+                     unsigned int count, unsigned int replicates, unsigned int flags, int device,
+                     int *parent /* [replicates][2 count - 2] */, double *length /* [replicates][2 count - 2] */);
+int pll_gpu_bootstrap_distance_trees(pll_partition_t *partition, const unsigned int *tips, unsigned int count,
+                                     const unsigned int *params_indices, const pll_gpu_newton_t *options,
+                                     unsigned int flags, unsigned long long seed, unsigned int first_replicate,
+                                     unsigned int replicates, const pll_gpu_bootstrap_trees_t *out);
+/* diagnosis (tools/bootstrap_trees_timing.py): device-event times of the last pll_gpu_bootstrap_distance_trees' first
+ * chunk, in ms - ms[0] the draw, ms[1] the distance launches, ms[2] the joins */
+int pll_gpu_bootstrap_last_times(const pll_partition_t *partition, double *ms);
+
 /* ---- rate-category posteriors, site rates and EM weight steps ----------
  * The per-category site likelihoods of one edge - what every evaluation kernel mixes away in registers - and what model
  * optimisation makes of them: FreeRate (+R) and mixture (LG4X) weights, empirical-Bayes site rates, a pinv step. The

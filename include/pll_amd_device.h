@@ -616,6 +616,66 @@ unsigned int pllgpu_nj_last_launch_count(void);
  * on the call's stream; -1 when no join ran or the events could not be had (tools/nj_probe.py) */
 double pllgpu_nj_last_device_ms(void);
 
+/* Many trees in one call (include/pll_amd.h, pll_gpu_nj_trees and pll_gpu_bootstrap_distance_trees,
+ * hold the contracts). All matrices of a call have the same count, so step s of every join has the same r: the four
+ * kernels take the replicate from the second grid dimension, replicate b's working set (matrices, row sums, labels,
+ * tickets, partials, step record, parent, length, status word) lying pllgpu_nj_scratch_bytes(count, flags) bytes times b
+ * behind the first. Tree b has bit for bit what pllgpu_nj_tree gives on matrix b; pllgpu_nj_tree IS this routine with one
+ * replicate.
+ * pllgpu_nj_trees: host_dist [replicates][count][count], parent / length [replicates][2 count - 2]; the checks and the
+ * device are pllgpu_nj_tree's, replicates == 0 succeeds behind the argument checks with nothing written. The replicates
+ * are cut into chunks of
+ *   n = min(replicates, 65535, max(1, floor(PLLGPU_NJ_BATCH_MAX_BYTES / (8 count^2 + pllgpu_nj_scratch_bytes))))
+ * matrices; a chunk is one copy up, one memset of all tickets and status words, the launch sequence of pllgpu_nj_tree with
+ * grids (x, n), one copy back each of parents, lengths and status words, one wait:
+ *   chunks x (2 (count - 3) + 2)   launches   (chunks x 1 at count == 3),
+ * whatever n is; pllgpu_nj_last_launch_count reports them. PLL_AMD_NJ_BATCH_BYTES in the environment, read when a call
+ * starts, lowers the budget (tests). A replicate whose search finds no pair fails the call with PLLGPU_ERUNTIME, the
+ * message naming the first such replicate; outputs are written only when every chunk has succeeded.
+ *
+ * pllgpu_bootstrap_distance_trees: for b < replicates, row first + b of pllgpu_replicate_weights_draw(seed) in the place
+ * of the pattern weights, pllgpu_pairwise_distances' launches under that row (k_pairwise_distances_rows: the one body of
+ * k_pairwise_distances over (weight row, result block), the replicate the grid's third dimension), and the join of the
+ * replicate's distance plane where it lies. Nothing the context holds is written, the pattern weights included; the rows
+ * never leave the device unless out->weights asks for them. With W = sites rounded up to 4 the replicates are cut into
+ * chunks of
+ *   n = min(replicates, 65535, max(1, floor(PLLGPU_BOOTSTRAP_MAX_BYTES / (4 W + 48 count^2 + pllgpu_nj_scratch_bytes))))
+ * whose blocks come from the context's block pool and return to it. PLL_AMD_BOOTSTRAP_BYTES in the environment of the
+ * context's creation lowers the budget (tests).
+ * The launch rule. Once per call: k_rell_cdf if the pattern weights were uploaded since the prefix sums were last formed
+ * (0 or 1), and ONE launch of k_distance_code_vectors. Per chunk, on the context's stream with no host wait inside: one
+ * k_rell_draw launch; the pair launches, each of at most P = PLLGPU_DISTANCE_MAX_PAIRS workgroups counted as cells x
+ * replicates and cut over replicates first, then over rows -
+ *   rows = max(1, min(65535, floor(P / count)));
+ *   rows >= count - 1 (a matrix fits a launch): ceil(n / m) launches of grid (count, count - 1, <= m),
+ *                                               m = max(1, min(65535, floor(P / (count (count - 1)))));
+ *   else: n x ceil((count - 1) / rows) launches of grid (count, <= rows, 1);
+ * then the 2 (count - 3) + 2 launches of the join (1 at count == 3); then the copies back that were asked for and one wait.
+ * Within a chunk the count depends on n through the cap P alone. pllgpu_last_launch_count reports the sum.
+ * The checks, before held work is launched: PLLGPU_EINVAL for a NULL out, parent or length; replicates == 0 succeeds here;
+ * then those of pllgpu_distance_tree in its order; then the sum of the pattern weights as pllgpu_replicate_weights_draw
+ * checks it (which may form the prefix sums: the host layer refuses a sum of 0 before that). Outputs of a chunk are written
+ * once the chunk has succeeded: after a device error in a later chunk the rows of earlier ones stay written.
+ * pllgpu_bootstrap_last_times: stream-event times of the last such call's first chunk, in ms - ms[0] the draw, ms[1] the
+ * pair launches, ms[2] the join (tools/bootstrap_trees_timing.py). */
+#define PLLGPU_NJ_BATCH_MAX_BYTES ((size_t)1 << 30)
+#define PLLGPU_BOOTSTRAP_MAX_BYTES ((size_t)1 << 30)
+typedef struct pllgpu_bootstrap_trees
+{
+  int *parent;
+  double *length;
+  double *distances;     /* NULL or [replicates][count][count] */
+  int *status;           /* NULL or [replicates][count][count] */
+  unsigned int *weights; /* NULL or [replicates][sites] */
+} pllgpu_bootstrap_trees_t;
+size_t pllgpu_nj_scratch_bytes(unsigned int count, unsigned int flags);
+int pllgpu_nj_trees(int device, const double *host_dist, unsigned int count, unsigned int replicates, unsigned int flags, int *parent,
+                    double *length);
+int pllgpu_bootstrap_distance_trees(pllgpu_ctx_t *ctx, const unsigned int *tips, unsigned int count, const unsigned int *params_indices,
+                                    const pllgpu_newton_t *options, unsigned int flags, unsigned long long seed, unsigned int first,
+                                    unsigned int replicates, const pllgpu_bootstrap_trees_t *out);
+int pllgpu_bootstrap_last_times(const pllgpu_ctx_t *ctx, double *ms);
+
 /* (L, L', L'') of the per-state extra entries at the branch length of the LAST
  * pllgpu_likelihood_derivatives call on this context, and their scaling counts
  * (src/core_derivatives.c:864-891). Synchronises. */

@@ -8,6 +8,12 @@
 // weights into a table of counts in LDS, then the whole safeguarded Newton iteration (kernels_deriv.h: newton_step) on
 // that table - an evaluation costs one row per code pair that occurs, not one per site. Nothing is written to HBM but the
 // pair's six answers; no workgroup waits for another, and the loop is bounded by max_iters.
+//
+// The alignment is read through one row of weights, so a pair can be served under many rows (pll_gpu_bootstrap_distance_trees,
+// DESIGN.md section 5.17): distance_pair is the one body over (weight row, result block); k_pairwise_distances calls it with
+// the partition's row, k_pairwise_distances_rows with row rep0 + blockIdx.z of a table of rows `wstride` words apart (the
+// layout k_rell_draw writes; a multiple of 4, so the uint4 loads stay aligned) and result block 6 count^2 doubles times that
+// row further on.
 #pragma once
 #include "kernels_common.h"
 #include "kernels_deriv.h"
@@ -16,7 +22,7 @@
 struct DevDistance
 {
   const unsigned char *const *rows;    // [count] the code row of every tip of the list
-  const unsigned *pattern_weights;     // [sites]
+  const unsigned *pattern_weights;     // [sites]; k_pairwise_distances_rows: [rows][wstride]
   const double *uw;                    // U [ncodes][R][S], then W [R][S][ncodes]
   const unsigned long long *tipmap;    // code -> state mask, or null: the code is the mask (4 states)
   const double *freqs, *rate_weights;  // the model as deriv_rate_add_share reads it (no prop_invar: refused)
@@ -24,6 +30,7 @@ struct DevDistance
   double t_first, t_min, t_max, tolerance;
   unsigned max_iters;
   unsigned sites, count, row0;         // the launch holds rows row0 .. row0 + gridDim.y of the pair matrix
+  unsigned rep0, wstride;              // k_pairwise_distances_rows: the launch holds the weight rows rep0 .. rep0 + gridDim.z
   unsigned ncodes;
   unsigned copies, copy_stride;        // private count tables in LDS: thread % copies owns one, copy_stride words apart
   unsigned char fidx[kMaxRates];
@@ -56,9 +63,11 @@ __device__ __forceinline__ void distance_count(unsigned *mine, unsigned ncodes, 
   if (w && a < ncodes && b < ncodes) atomicAdd(&mine[a * ncodes + b], w);
 }
 
-__global__ __launch_bounds__(256) void k_pairwise_distances(const DevDistance d, const DevDiag dg)
+// the pair (x, y) of list positions, x < y, under one row of weights: every thread of the workgroup calls
+__device__ __forceinline__ void distance_pair(const DevDistance &d, const DevDiag &dg, const unsigned *__restrict__ weights,
+                                              double *__restrict__ results)
 {
-  const unsigned x = d.row0 + blockIdx.y, y = blockIdx.x; // the pair (x, y) of list positions, x < y
+  const unsigned x = d.row0 + blockIdx.y, y = blockIdx.x;
   if (y <= x) return;
   __shared__ double ws[2][4];
   __shared__ unsigned psum[2];
@@ -80,7 +89,7 @@ __global__ __launch_bounds__(256) void k_pairwise_distances(const DevDistance d,
     unsigned *mine = counts + (threadIdx.x & (d.copies - 1u)) * d.copy_stride;
     const unsigned quads = d.sites / 4u;
     const unsigned *ra4 = reinterpret_cast<const unsigned *>(ra), *rb4 = reinterpret_cast<const unsigned *>(rb);
-    const uint4 *w4 = reinterpret_cast<const uint4 *>(d.pattern_weights);
+    const uint4 *w4 = reinterpret_cast<const uint4 *>(weights);
     for (unsigned q = threadIdx.x; q < quads; q += blockDim.x)
     {
       const unsigned a = ra4[q], b = rb4[q];
@@ -90,7 +99,7 @@ __global__ __launch_bounds__(256) void k_pairwise_distances(const DevDistance d,
       distance_count(mine, nc, (a >> 16) & 255u, (b >> 16) & 255u, w.z);
       distance_count(mine, nc, a >> 24, b >> 24, w.w);
     }
-    for (unsigned n = quads * 4u + threadIdx.x; n < d.sites; n += blockDim.x) distance_count(mine, nc, ra[n], rb[n], d.pattern_weights[n]);
+    for (unsigned n = quads * 4u + threadIdx.x; n < d.sites; n += blockDim.x) distance_count(mine, nc, ra[n], rb[n], weights[n]);
   }
   __syncthreads();
 
@@ -174,8 +183,19 @@ __global__ __launch_bounds__(256) void k_pairwise_distances(const DevDistance d,
                          : v == 3u ? st.dd_f
                          : v == 4u ? (double)st.status
                                    : (double)st.iterations;
-    double *block = d.results + (size_t)v * d.count * d.count;
+    double *block = results + (size_t)v * d.count * d.count;
     block[(size_t)x * d.count + y] = value;
     block[(size_t)y * d.count + x] = value;
   }
+}
+
+__global__ __launch_bounds__(256) void k_pairwise_distances(const DevDistance d, const DevDiag dg)
+{
+  distance_pair(d, dg, d.pattern_weights, d.results);
+}
+
+__global__ __launch_bounds__(256) void k_pairwise_distances_rows(const DevDistance d, const DevDiag dg)
+{
+  const size_t z = d.rep0 + blockIdx.z;
+  distance_pair(d, dg, d.pattern_weights + z * d.wstride, d.results + z * 6u * d.count * d.count);
 }

@@ -17,6 +17,12 @@
 // joins the last three nodes. No workgroup ever waits for another: the only hand-off is the ticket, and the seams between
 // search and join are launch boundaries.
 //
+// Several matrices of one size (pll_gpu_nj_trees, pll_gpu_bootstrap_distance_trees) are joined in
+// lockstep: step s of every one has the same r, so the grids above get a second dimension, the replicate. Replicate b's
+// working set - everything DevNj points at, its tickets, partials, record and status word included - lies `stride` bytes
+// times b behind replicate 0's, its input `src_stride` doubles times b behind the first (nj_replicate). The last workgroup
+// of a search is the last of its replicate: gridDim.x tickets per replicate and step.
+//
 // The row sums are carried forward (R_k <- R_k - d_ik - d_jk + d_uk); the first ones are added in slot order, one term at
 // a time, by one thread per row. Q_ij = (r-2) d_ij - (R_i + R_j): the sum of the two row sums is formed first, so that Q
 // is a function of the unordered pair. Every product is rounded before it is added.
@@ -49,10 +55,32 @@ struct DevNj
   int *parent;        // [2 count - 2]
   double *length;     // [2 count - 2]
   unsigned *status;   // != 0: a step found no pair (a criterion that is not a number)
+  size_t stride;      // bytes from a replicate's working set to the next one's
+  size_t src_stride;  // doubles from a replicate's input matrix to the next one's
   unsigned count;
   unsigned rows;      // rows of the triangle per search workgroup
   unsigned bionj;
 };
+
+// replicate b's working set: every pointer of replicate 0's, b strides further on
+__device__ __forceinline__ DevNj nj_replicate(const DevNj &base, unsigned b)
+{
+  DevNj n = base;
+  const size_t off = (size_t)b * base.stride;
+  auto shift = [off](auto *p) { return reinterpret_cast<decltype(p)>(reinterpret_cast<unsigned char *>(p) + off); };
+  n.D = shift(base.D);
+  n.V = base.V ? shift(base.V) : nullptr;
+  n.R = shift(base.R);
+  n.snap = shift(base.snap);
+  n.label = shift(base.label);
+  n.tickets = shift(base.tickets);
+  n.partials = shift(base.partials);
+  n.record = shift(base.record);
+  n.parent = shift(base.parent);
+  n.length = shift(base.length);
+  n.status = shift(base.status);
+  return n;
+}
 
 __device__ __forceinline__ bool nj_before(double q, unsigned long long labels, const NjKey &y)
 {
@@ -96,8 +124,10 @@ __device__ __forceinline__ NjKey nj_workgroup_min(NjKey k, NjKey *ws)
 
 // src: [count][count], only [x][y] with x < y is read. One workgroup per row x: both halves of D (and V) from the upper
 // triangle, the diagonal 0, label[x] = x; thread 0 adds the row's sum in slot order.
-__global__ __launch_bounds__(256) void k_nj_init(const DevNj n, const double *__restrict__ src)
+__global__ __launch_bounds__(256) void k_nj_init(const DevNj base, const double *__restrict__ src0)
 {
+  const DevNj n = nj_replicate(base, blockIdx.y);
+  const double *__restrict__ src = src0 + (size_t)blockIdx.y * base.src_stride;
   const unsigned x = blockIdx.x, c = n.count;
   for (unsigned y = threadIdx.x; y < c; y += blockDim.x)
   {
@@ -114,9 +144,10 @@ __global__ __launch_bounds__(256) void k_nj_init(const DevNj n, const double *__
   }
 }
 
-__global__ __launch_bounds__(256) void k_nj_search(const DevNj n, unsigned r, unsigned step)
+__global__ __launch_bounds__(256) void k_nj_search(const DevNj base, unsigned r, unsigned step)
 {
 #pragma clang fp contract(off)
+  const DevNj n = nj_replicate(base, blockIdx.y);
   __shared__ NjKey ws[4];
   __shared__ unsigned last;
   __shared__ NjRecord rec;
@@ -232,9 +263,10 @@ __device__ __forceinline__ double nj_lambda(const DevNj &n, const NjRecord &q, u
   return lambda;
 }
 
-__global__ __launch_bounds__(256) void k_nj_join(const DevNj n, unsigned r, unsigned step)
+__global__ __launch_bounds__(256) void k_nj_join(const DevNj base, unsigned r, unsigned step)
 {
 #pragma clang fp contract(off)
+  const DevNj n = nj_replicate(base, blockIdx.y);
   __shared__ double ws[4];
   const NjRecord q = *n.record;
   if (q.si >= r || q.sj >= r || q.si == q.sj) return; // the search found no pair (status says so)
@@ -311,12 +343,16 @@ __global__ __launch_bounds__(256) void k_nj_join(const DevNj n, unsigned r, unsi
   n.R[kn] = rk;
 }
 
-// the last three nodes, in the slots 0, 1, 2 of `d` (only [x][y], x < y, is read): one thread. label == null: the slots
-// are the labels (count == 3: `d` is the caller's matrix, nothing ran before).
-__global__ void k_nj_final(const DevNj n, const double *__restrict__ d, const unsigned *__restrict__ label)
+// the last three nodes, in the slots 0, 1, 2 of a matrix (only [x][y], x < y, is read): one thread per replicate. src ==
+// null: the working matrix and its labels. Else the replicate's input matrix, the slots being the labels (count == 3:
+// nothing ran before).
+__global__ void k_nj_final(const DevNj base, const double *__restrict__ src)
 {
 #pragma clang fp contract(off)
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const DevNj n = nj_replicate(base, blockIdx.y);
+  const double *d = src ? src + (size_t)blockIdx.y * base.src_stride : n.D;
+  const unsigned *label = src ? nullptr : n.label;
   const unsigned c = n.count, root = 2u * c - 3u;
   const double d01 = d[1], d02 = d[2], d12 = d[c + 2u];
   const unsigned l0 = label ? label[0] : 0u, l1 = label ? label[1] : 1u, l2 = label ? label[2] : 2u;

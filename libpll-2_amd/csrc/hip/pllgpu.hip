@@ -263,6 +263,8 @@ struct pllgpu_ctx
   DevBuf<double> newton;                 // pllgpu_optimize_branch_length: the state record (NewtonState), then the trace
   unsigned newton_batch = 8;             // ... and how many evaluations it enqueues between two polls (tools/newton_device_latency.py)
   unsigned distance_pairs = PLLGPU_DISTANCE_MAX_PAIRS; // pllgpu_pairwise_distances: cells of the pair matrix per launch; PLL_AMD_DISTANCE_PAIRS lowers it (tests)
+  size_t bootstrap_bytes = PLLGPU_BOOTSTRAP_MAX_BYTES; // pllgpu_bootstrap_distance_trees: device bytes of a chunk of replicates; PLL_AMD_BOOTSTRAP_BYTES lowers it (tests)
+  double bs_ms[3] = {0.0, 0.0, 0.0};     // ... and its first chunk's draw, distance launches and join, by stream events (rs_ev)
   unsigned rell_range = kRellRange;      // k_rell_draw's sites per workgroup; PLL_AMD_RELL_RANGE lowers it (tests: a small case over several ranges)
   DevBuf<double> evecs, ievecs, brlen;   // device P-matrices: [rate_matrices][S][SP] x 2, staged branch lengths
   DevBuf<unsigned> mindex;               // staged matrix indices
@@ -561,6 +563,8 @@ static void derive_geometry(pllgpu_ctx *c)
     if (atoll(v) >= 4) c->rell_range = (unsigned)std::min<long long>(atoll(v) / 4 * 4, kRellRange);
   if (const char *v = getenv("PLL_AMD_DISTANCE_PAIRS")) // tests: a small list over several launches
     if (atoll(v) >= 1) c->distance_pairs = (unsigned)std::min<long long>(atoll(v), PLLGPU_DISTANCE_MAX_PAIRS);
+  if (const char *v = getenv("PLL_AMD_BOOTSTRAP_BYTES")) // tests: a few replicates over several chunks
+    if (atoll(v) >= 1) c->bootstrap_bytes = std::min<size_t>((size_t)atoll(v), PLLGPU_BOOTSTRAP_MAX_BYTES);
   c->subtrees = c->dna_fast;
   if (const char *v = getenv("PLL_AMD_NO_SUBTREES")) // A/B switch: the bottom levels under site repeats go level by level
     if (*v && *v != '0') c->subtrees = false;
@@ -4377,10 +4381,8 @@ static int distances_check_arguments(pllgpu_ctx *c, const unsigned *tips, unsign
   return check_rate_indices(c, "params_indices", params_indices);
 }
 
-// The remaining checks and every launch of a list of count >= 2 tips: the six [count][count] blocks are left in
-// ins_results, distance first, with nothing waited for. pllgpu_pairwise_distances copies them back; pllgpu_distance_tree
-// joins the first block where it lies.
-static int distances_enqueue(pllgpu_ctx *c, const unsigned *tips, unsigned count, const unsigned *params_indices, const pllgpu_newton_t *opt)
+// The remaining checks of a list of tips: what the context holds for them
+static int distances_check_state(const pllgpu_ctx *c, const unsigned *tips, unsigned count)
 {
   const char *const noun = kDistNoun;
   const pllgpu_geometry_t &g = c->geo;
@@ -4390,23 +4392,41 @@ static int distances_enqueue(pllgpu_ctx *c, const unsigned *tips, unsigned count
   if (int rc = refuse_compressed(c, noun)) return rc;
   const unsigned S = g.states, R = g.rate_cats;
   const unsigned ncodes = S == 4 ? 16u : c->tip_ncodes;
-  const size_t diag_bytes = (size_t)R * S * 4 * sizeof(double);
   if (ncodes > PLLGPU_DISTANCE_MAX_CODES || PLLGPU_DISTANCE_LDS_BYTES((size_t)S, (size_t)R, (size_t)ncodes) > PLLGPU_DISTANCE_LDS_MAX)
     return fail(PLLGPU_EUNSUPPORTED, "%s: a code table of %u codes at %u states x %u rate categories (at most %u codes and %lu bytes of LDS)", noun, ncodes,
                 S, R, (unsigned)PLLGPU_DISTANCE_MAX_CODES, PLLGPU_DISTANCE_LDS_MAX);
   if (!ncodes || (S != 4 && !c->tipmap_set)) return fail(PLLGPU_EINVAL, "%s: the code -> state mask map was not uploaded", noun);
   if (!c->eigenvals.p || !c->rates.p) return fail(PLLGPU_EINVAL, "eigenvalues / category rates were not uploaded");
+  return 0;
+}
+
+// what the pair launches of a call share
+struct DistanceCall
+{
+  DevDistance d;
+  DevDiag dg;
+  size_t lds;
+};
+
+// Once per call, behind the checks: held work goes out, the scratch for `blocks` result blocks of 6 count^2 values, the code
+// rows of the list and ONE launch of k_distance_code_vectors.
+static int distances_begin(pllgpu_ctx *c, const unsigned *tips, unsigned count, const unsigned *params_indices, const pllgpu_newton_t *opt, size_t blocks,
+                           DistanceCall &k)
+{
+  const pllgpu_geometry_t &g = c->geo;
+  const unsigned S = g.states, R = g.rate_cats;
+  const unsigned ncodes = S == 4 ? 16u : c->tip_ncodes;
+  const size_t diag_bytes = (size_t)R * S * 4 * sizeof(double);
   DevEdge e;
   if (int rc = batch_edge(c, e, params_indices)) return rc;
 
   const size_t cc = (size_t)count * count, uw = (size_t)2 * ncodes * R * S;
-  if (int rc = batch_scratch(c, e, uw, 0, 6 * cc, (size_t)count * sizeof(const unsigned char *))) return rc;
+  if (int rc = batch_scratch(c, e, uw, 0, blocks * 6 * cc, (size_t)count * sizeof(const unsigned char *))) return rc;
   const int up = stage_up<const unsigned char *>(c, c->ins_cands.p, count, [&](const unsigned char *&row, unsigned i) {
     row = c->tipchars[tips[i]].p;
     return 0;
   });
   if (up) return up;
-  HIP_TRY(hipMemsetAsync(c->ins_results.p, 0, 6 * cc * sizeof(double), c->stream)); // the diagonals
 
   const double *m1 = c->pmat.p + (size_t)g.prob_matrices * c->pm_stride, *m2 = m1 + c->pm_stride;
   const unsigned long long *tm = S == 4 ? nullptr : c->tipmap.p;
@@ -4414,16 +4434,16 @@ static int distances_enqueue(pllgpu_ctx *c, const unsigned *tips, unsigned count
                      c->ins_partials.p);
   if (int rc = launched(c)) return rc;
 
-  DevDiag dg;
+  DevDiag &dg = k.dg;
   memset(&dg, 0, sizeof dg);
-  for (unsigned k = 0; k < R; ++k) dg.fidx[k] = (unsigned char)params_indices[k];
+  for (unsigned r = 0; r < R; ++r) dg.fidx[r] = (unsigned char)params_indices[r];
   dg.eigenvals = c->eigenvals.p;
   dg.rates = c->rates.p;
   dg.prop_invar = c->prop_invar.p;
   dg.S = S;
   dg.SP = g.states_padded;
   dg.R = R;
-  DevDistance d;
+  DevDistance &d = k.d;
   memset(&d, 0, sizeof d);
   d.rows = reinterpret_cast<const unsigned char *const *>(c->ins_cands.p);
   d.pattern_weights = e.pattern_weights;
@@ -4446,17 +4466,58 @@ static int distances_enqueue(pllgpu_ctx *c, const unsigned *tips, unsigned count
   d.copies = 1u;
   while (d.copies < 256u && (size_t)2 * d.copies * table <= room) d.copies *= 2u;
   memcpy(d.fidx, e.fidx, sizeof d.fidx);
-  const size_t lds = diag_bytes + (size_t)d.copies * table;
-  raise_lds_limit(reinterpret_cast<const void *>(&k_pairwise_distances), c->device, lds);
-  // the cutting rule (include/pll_amd_device.h states it): whole rows of the pair matrix
-  const unsigned rows_per = std::max(1u, std::min(65535u, c->distance_pairs / count));
-  for (unsigned row0 = 0; row0 + 1 < count; row0 += rows_per)
-  {
-    d.row0 = row0;
-    hipLaunchKernelGGL(k_pairwise_distances, dim3(count, std::min(rows_per, count - 1 - row0)), dim3(256), lds, c->stream, d, dg);
-    if (int rc = launched(c)) return rc;
-  }
+  k.lds = diag_bytes + (size_t)d.copies * table;
+  raise_lds_limit(reinterpret_cast<const void *>(&k_pairwise_distances), c->device, k.lds);
+  raise_lds_limit(reinterpret_cast<const void *>(&k_pairwise_distances_rows), c->device, k.lds);
   return 0;
+}
+
+// The pair launches of `nr` result blocks, the first nr of ins_results, with nothing waited for. wrows == nullptr: the one
+// block under the context's pattern weights (k_pairwise_distances). Else block z under row z of wrows, wstride words apart
+// (k_pairwise_distances_rows). The cutting rule (include/pll_amd_device.h states it): a launch holds at most distance_pairs
+// workgroups, cells x replicates - whole matrices of as many replicates as fit or, where one matrix does not fit, whole
+// rows of one replicate's.
+static int distances_launch(pllgpu_ctx *c, DistanceCall &k, const unsigned *wrows, unsigned wstride, unsigned nr)
+{
+  DevDistance &d = k.d;
+  const unsigned count = d.count;
+  HIP_TRY(hipMemsetAsync(c->ins_results.p, 0, (size_t)nr * 6 * count * count * sizeof(double), c->stream)); // the diagonals
+  const unsigned rows_per = std::max(1u, std::min(65535u, c->distance_pairs / count));
+  if (!wrows)
+  {
+    for (unsigned row0 = 0; row0 + 1 < count; row0 += rows_per)
+    {
+      d.row0 = row0;
+      hipLaunchKernelGGL(k_pairwise_distances, dim3(count, std::min(rows_per, count - 1 - row0)), dim3(256), k.lds, c->stream, d, k.dg);
+      if (int rc = launched(c)) return rc;
+    }
+    return 0;
+  }
+  d.pattern_weights = wrows;
+  d.wstride = wstride;
+  const bool whole = rows_per >= count - 1;
+  const unsigned reps_per = whole ? std::max(1u, std::min(65535u, c->distance_pairs / (count * (count - 1)))) : 1u;
+  for (unsigned rep0 = 0; rep0 < nr; rep0 += reps_per)
+    for (unsigned row0 = 0; row0 + 1 < count; row0 += rows_per)
+    {
+      d.rep0 = rep0;
+      d.row0 = row0;
+      hipLaunchKernelGGL(k_pairwise_distances_rows, dim3(count, std::min(rows_per, count - 1 - row0), std::min(reps_per, nr - rep0)), dim3(256), k.lds,
+                         c->stream, d, k.dg);
+      if (int rc = launched(c)) return rc;
+    }
+  return 0;
+}
+
+// The remaining checks and every launch of a list of count >= 2 tips: the six [count][count] blocks are left in
+// ins_results, distance first, with nothing waited for. pllgpu_pairwise_distances copies them back; pllgpu_distance_tree
+// joins the first block where it lies.
+static int distances_enqueue(pllgpu_ctx *c, const unsigned *tips, unsigned count, const unsigned *params_indices, const pllgpu_newton_t *opt)
+{
+  if (int rc = distances_check_state(c, tips, count)) return rc;
+  DistanceCall k;
+  if (int rc = distances_begin(c, tips, count, params_indices, opt, 1, k)) return rc;
+  return distances_launch(c, k, nullptr, 0, 1);
 }
 
 extern "C" int pllgpu_pairwise_distances(pllgpu_ctx_t *c, const unsigned *tips, unsigned count, const unsigned *params_indices,
@@ -4506,8 +4567,10 @@ static unsigned nj_rows()
   return rows;
 }
 
-// bytes of the working set behind a 256-byte aligned block, and the block cut up
+// bytes of a replicate's working set behind a 256-byte aligned block - the stride from one replicate's to the next one's -
+// and the block cut up. The tickets and the status word lie side by side: one memset serves both.
 static size_t nj_align(size_t b) { return (b + 255u) & ~(size_t)255u; }
+static size_t nj_zeroed_bytes(unsigned count) { return nj_align((size_t)count * sizeof(unsigned)) + sizeof(unsigned); }
 static size_t nj_scratch_bytes(unsigned count, unsigned flags)
 {
   const size_t n = count, cc = n * n * sizeof(double);
@@ -4516,7 +4579,10 @@ static size_t nj_scratch_bytes(unsigned count, unsigned flags)
          nj_align(2 * n * sizeof(double)) + nj_align(sizeof(unsigned));
 }
 
-static DevNj nj_carve(unsigned char *block, unsigned count, unsigned flags, unsigned rows)
+extern "C" size_t pllgpu_nj_scratch_bytes(unsigned count, unsigned flags) { return nj_scratch_bytes(count, flags); }
+
+// replicate 0's working set at `block`; src_stride: doubles between the input matrices
+static DevNj nj_carve(unsigned char *block, unsigned count, unsigned flags, unsigned rows, size_t src_stride)
 {
   const size_t n = count, cc = n * n * sizeof(double);
   DevNj d;
@@ -4531,85 +4597,120 @@ static DevNj nj_carve(unsigned char *block, unsigned count, unsigned flags, unsi
   d.R = (double *)take(n * sizeof(double));
   d.snap = (double *)take(4 * n * sizeof(double));
   d.label = (unsigned *)take(n * sizeof(unsigned));
-  d.tickets = (unsigned *)take(n * sizeof(unsigned));
   d.partials = (NjKey *)take(n * sizeof(NjKey));
   d.record = (NjRecord *)take(sizeof(NjRecord));
   d.parent = (int *)take(2 * n * sizeof(int));
   d.length = (double *)take(2 * n * sizeof(double));
+  d.tickets = (unsigned *)take(n * sizeof(unsigned));
   d.status = (unsigned *)take(sizeof(unsigned));
+  d.stride = nj_scratch_bytes(count, flags);
+  d.src_stride = src_stride;
   d.count = count;
   d.rows = rows;
   d.bionj = (flags & PLLGPU_NJ_BIONJ) ? 1u : 0u;
   return d;
 }
 
-// The one routine behind both calls: the join of the device matrix `src` ([count][count], the upper triangle read) on
-// `stream`, in `block` (nj_scratch_bytes of it); parent and length are copied to the host and the stream is waited for.
-// Launches (the rule of include/pll_amd_device.h) are added to *launches.
-static int nj_run(hipStream_t stream, const double *src, unsigned count, unsigned flags, unsigned char *block, int *parent, double *length,
-                  unsigned *launches)
+// what a batch of joins leaves on the host once its stream has been waited for
+struct NjBatch
 {
-  const DevNj d = nj_carve(block, count, flags, nj_rows());
-  const size_t nodes = 2 * (size_t)count - 2;
+  std::vector<int> parent;
+  std::vector<double> length;
+  std::vector<unsigned> status;
   // (the two events time the launches for tools/nj_probe.py; when they cannot be had the call runs without them)
-  struct Events
+  hipEvent_t first = nullptr, last = nullptr;
+  bool timed = false;
+  ~NjBatch()
   {
-    hipEvent_t first = nullptr, last = nullptr;
-    ~Events()
-    {
-      if (first) (void)hipEventDestroy(first);
-      if (last) (void)hipEventDestroy(last);
-    }
-  } ev;
+    if (first) (void)hipEventDestroy(first);
+    if (last) (void)hipEventDestroy(last);
+  }
+};
+
+// rows of `width` bytes, `nr` of them a replicate's stride apart on the device, to a dense host array: one copy
+static hipError_t nj_rows_down(hipStream_t stream, void *host, const void *dev, size_t width, size_t stride, unsigned nr)
+{
+  if (nr == 1) return hipMemcpyAsync(host, dev, width, hipMemcpyDeviceToHost, stream);
+  return hipMemcpy2DAsync(host, width, dev, stride, width, nr, hipMemcpyDeviceToHost, stream);
+}
+
+// The one routine behind every call, first half: the joins of the nr <= 65535 device matrices src, src + src_stride, ...
+// ([count][count] each, the upper triangle read) in lockstep on `stream`, in `block` (nr x nj_scratch_bytes of it), the
+// replicate the grids' second dimension; then parents, lengths and status words on their way to `out` in one copy each.
+// Nothing is waited for. Launches (the rule of include/pll_amd_device.h: they do not depend on nr) are added to *launches.
+static int nj_enqueue(hipStream_t stream, const double *src, size_t src_stride, unsigned nr, unsigned count, unsigned flags, unsigned char *block,
+                      NjBatch &out, unsigned *launches)
+{
+  const DevNj d = nj_carve(block, count, flags, nj_rows(), src_stride);
+  const size_t nodes = 2 * (size_t)count - 2;
   t_nj_device_ms = -1.0;
-  if (hipEventCreate(&ev.first) != hipSuccess || hipEventCreate(&ev.last) != hipSuccess) (void)hipGetLastError();
-  HIP_TRY(hipMemsetAsync(d.status, 0, sizeof(unsigned), stream));
-  const bool timed = ev.first && ev.last && hipEventRecord(ev.first, stream) == hipSuccess;
+  if (hipEventCreate(&out.first) != hipSuccess || hipEventCreate(&out.last) != hipSuccess) (void)hipGetLastError();
+  // every replicate's tickets and status word
+  if (nr == 1) HIP_TRY(hipMemsetAsync(d.tickets, 0, nj_zeroed_bytes(count), stream));
+  else HIP_TRY(hipMemset2DAsync(d.tickets, d.stride, 0, nj_zeroed_bytes(count), nr, stream));
+  const bool timed = out.first && out.last && hipEventRecord(out.first, stream) == hipSuccess;
   if (count == 3)
   {
-    hipLaunchKernelGGL(k_nj_final, dim3(1), dim3(64), 0, stream, d, src, (const unsigned *)nullptr);
+    hipLaunchKernelGGL(k_nj_final, dim3(1, nr), dim3(64), 0, stream, d, src);
     ++*launches;
   }
   else
   {
-    HIP_TRY(hipMemsetAsync(d.tickets, 0, (size_t)count * sizeof(unsigned), stream));
-    hipLaunchKernelGGL(k_nj_init, dim3(count), dim3(256), 0, stream, d, src);
+    hipLaunchKernelGGL(k_nj_init, dim3(count, nr), dim3(256), 0, stream, d, src);
     ++*launches;
     for (unsigned r = count, step = 0; r > 3; --r, ++step)
     {
       const unsigned search_wgs = (r - 1 + d.rows - 1) / d.rows; // rows 0 .. r-2 of the triangle hold pairs
-      hipLaunchKernelGGL(k_nj_search, dim3(search_wgs), dim3(256), 0, stream, d, r, step);
-      hipLaunchKernelGGL(k_nj_join, dim3((r + 255) / 256), dim3(256), 0, stream, d, r, step);
+      hipLaunchKernelGGL(k_nj_search, dim3(search_wgs, nr), dim3(256), 0, stream, d, r, step);
+      hipLaunchKernelGGL(k_nj_join, dim3((r + 255) / 256, nr), dim3(256), 0, stream, d, r, step);
       *launches += 2;
     }
-    hipLaunchKernelGGL(k_nj_final, dim3(1), dim3(64), 0, stream, d, (const double *)d.D, (const unsigned *)d.label);
+    hipLaunchKernelGGL(k_nj_final, dim3(1, nr), dim3(64), 0, stream, d, (const double *)nullptr);
     ++*launches;
   }
   HIP_TRY(hipGetLastError());
-  const bool timed_end = timed && hipEventRecord(ev.last, stream) == hipSuccess;
-  std::vector<int> hp(nodes);
-  std::vector<double> hl(nodes);
-  unsigned status = 0;
-  HIP_TRY(hipMemcpyAsync(hp.data(), d.parent, nodes * sizeof(int), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(hl.data(), d.length, nodes * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(&status, d.status, sizeof status, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  float ms = 0;
-  if (timed_end && hipEventElapsedTime(&ms, ev.first, ev.last) == hipSuccess) t_nj_device_ms = (double)ms;
-  if (status) return fail(PLLGPU_ERUNTIME, "neighbour joining: a step found no pair to join (the criterion is not a number)");
-  memcpy(parent, hp.data(), nodes * sizeof(int));
-  memcpy(length, hl.data(), nodes * sizeof(double));
+  out.timed = timed && hipEventRecord(out.last, stream) == hipSuccess;
+  out.parent.resize(nr * nodes);
+  out.length.resize(nr * nodes);
+  out.status.assign(nr, 0u);
+  HIP_TRY(nj_rows_down(stream, out.parent.data(), d.parent, nodes * sizeof(int), d.stride, nr));
+  HIP_TRY(nj_rows_down(stream, out.length.data(), d.length, nodes * sizeof(double), d.stride, nr));
+  HIP_TRY(nj_rows_down(stream, out.status.data(), d.status, sizeof(unsigned), d.stride, nr));
   return 0;
+}
+
+// ... second half, once the stream has been waited for: the trees into parent / length ([nr][2 count - 2] each), unless a
+// replicate's search found no pair; `first` is replicate 0's number in the call
+static int nj_finish(NjBatch &b, unsigned first, int *parent, double *length)
+{
+  float ms = 0;
+  if (b.timed && hipEventElapsedTime(&ms, b.first, b.last) == hipSuccess) t_nj_device_ms = (double)ms;
+  for (size_t r = 0; r < b.status.size(); ++r)
+    if (b.status[r])
+      return fail(PLLGPU_ERUNTIME, "neighbour joining: a step of replicate %u found no pair to join (the criterion is not a number)", first + (unsigned)r);
+  memcpy(parent, b.parent.data(), b.parent.size() * sizeof(int));
+  memcpy(length, b.length.data(), b.length.size() * sizeof(double));
+  return 0;
+}
+
+static int nj_run(hipStream_t stream, const double *src, size_t src_stride, unsigned nr, unsigned first, unsigned count, unsigned flags,
+                  unsigned char *block, int *parent, double *length, unsigned *launches)
+{
+  NjBatch b;
+  if (int rc = nj_enqueue(stream, src, src_stride, nr, count, flags, block, b, launches)) return rc;
+  HIP_TRY(hipStreamSynchronize(stream));
+  return nj_finish(b, first, parent, length);
 }
 
 extern "C" unsigned pllgpu_nj_last_launch_count(void) { return t_nj_launches; }
 extern "C" double pllgpu_nj_last_device_ms(void) { return t_nj_device_ms; }
 
-extern "C" int pllgpu_nj_tree(int device, const double *host_dist, unsigned count, unsigned flags, int *parent, double *length)
+extern "C" int pllgpu_nj_trees(int device, const double *host_dist, unsigned count, unsigned replicates, unsigned flags, int *parent, double *length)
 {
   t_nj_launches = 0;
   if (!host_dist || !parent || !length || count < 3 || (flags & ~PLLGPU_NJ_BIONJ))
     return fail(PLLGPU_EINVAL, "neighbour joining: invalid argument (%u nodes, flags %#x)", count, flags);
+  if (!replicates) return 0;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
   {
@@ -4625,18 +4726,33 @@ extern "C" int pllgpu_nj_tree(int device, const double *host_dist, unsigned coun
     device = (env && strcmp(env, "auto") != 0) ? atoi(env) : (prev >= 0 ? prev : 0);
   }
   if (device < 0 || device >= ndev) return fail(PLLGPU_EINVAL, "neighbour joining: device %d of %d", device, ndev);
-  const size_t cc = (size_t)count * count * sizeof(double);
+  // the chunks: matrices and working sets of one stay under the budget
+  size_t budget = PLLGPU_NJ_BATCH_MAX_BYTES;
+  if (const char *v = getenv("PLL_AMD_NJ_BATCH_BYTES")) // tests: a few small matrices over several chunks
+    if (atoll(v) >= 1) budget = std::min<size_t>((size_t)atoll(v), PLLGPU_NJ_BATCH_MAX_BYTES);
+  const size_t cc = (size_t)count * count, nodes = 2 * (size_t)count - 2, scratch = nj_scratch_bytes(count, flags);
+  const unsigned per_chunk = (unsigned)std::min<size_t>(std::min(replicates, 65535u), std::max<size_t>(1, budget / (cc * sizeof(double) + scratch)));
   hipStream_t stream = nullptr;
   unsigned char *block = nullptr;
   double *src = nullptr;
   unsigned launches = 0;
+  // (several chunks: the outputs are written once every one has succeeded)
+  std::vector<int> hp(per_chunk < replicates ? replicates * nodes : 0);
+  std::vector<double> hl(hp.size());
   auto run = [&]() -> int {
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc(&src, cc));
-    HIP_TRY(hipMalloc(&block, nj_scratch_bytes(count, flags)));
-    HIP_TRY(hipMemcpyAsync(src, host_dist, cc, hipMemcpyHostToDevice, stream));
-    return nj_run(stream, src, count, flags, block, parent, length, &launches);
+    HIP_TRY(hipMalloc(&src, per_chunk * cc * sizeof(double)));
+    HIP_TRY(hipMalloc(&block, per_chunk * scratch));
+    for (unsigned r0 = 0; r0 < replicates; r0 += per_chunk)
+    {
+      const unsigned nr = std::min(per_chunk, replicates - r0);
+      HIP_TRY(hipMemcpyAsync(src, host_dist + r0 * cc, nr * cc * sizeof(double), hipMemcpyHostToDevice, stream));
+      int *p = hp.empty() ? parent : hp.data() + r0 * nodes;
+      double *l = hl.empty() ? length : hl.data() + r0 * nodes;
+      if (int rc = nj_run(stream, src, cc, nr, r0, count, flags, block, p, l, &launches)) return rc;
+    }
+    return 0;
   };
   const int rc = run();
   if (rc && stream) (void)hipStreamSynchronize(stream); // nothing of the call is in flight when its blocks go
@@ -4646,7 +4762,17 @@ extern "C" int pllgpu_nj_tree(int device, const double *host_dist, unsigned coun
   if (rc) (void)hipGetLastError();
   if (prev >= 0 && prev != device) (void)hipSetDevice(prev); // leave the thread's device as found
   t_nj_launches = rc ? 0 : launches;
+  if (!rc && !hp.empty())
+  {
+    memcpy(parent, hp.data(), hp.size() * sizeof(int));
+    memcpy(length, hl.data(), hl.size() * sizeof(double));
+  }
   return rc;
+}
+
+extern "C" int pllgpu_nj_tree(int device, const double *host_dist, unsigned count, unsigned flags, int *parent, double *length)
+{
+  return pllgpu_nj_trees(device, host_dist, count, 1, flags, parent, length);
 }
 
 extern "C" int pllgpu_distance_tree(pllgpu_ctx_t *c, const unsigned *tips, unsigned count, const unsigned *params_indices,
@@ -4672,13 +4798,108 @@ extern "C" int pllgpu_distance_tree(pllgpu_ctx_t *c, const unsigned *tips, unsig
     if (e != hipSuccess) rc = fail(PLLGPU_ERUNTIME, "distance tree: copy back failed: %s", hipGetErrorString(e));
   }
   unsigned launches = 0;
-  if (!rc) rc = nj_run(c->stream, c->ins_results.p, count, flags, block.p, parent, length, &launches);
+  if (!rc) rc = nj_run(c->stream, c->ins_results.p, 0, 1, 0, count, flags, block.p, parent, length, &launches);
   if (rc) (void)hipStreamSynchronize(c->stream);
   else ring_drained(c); // (nj_run has waited for the stream)
   block.release();
   if (rc) return rc;
   c->last_launches += launches;
   if (host_dist) memcpy(host_dist, dist.data(), dist.size() * sizeof(double));
+  return 0;
+}
+
+// ---- bootstrap trees from distances ---------------------------------------------------------
+// Per chunk of replicates, on the context's stream with no host wait inside: k_rell_draw into rows of rs_w, the pair
+// launches under those rows into a chunk's result blocks, the joins of the distance planes where they lie, the copies back
+// that were asked for, one wait. The cut and the launch rule: include/pll_amd_device.h.
+extern "C" int pllgpu_bootstrap_distance_trees(pllgpu_ctx_t *c, const unsigned *tips, unsigned count, const unsigned *params_indices,
+                                               const pllgpu_newton_t *opt, unsigned flags, unsigned long long seed, unsigned first,
+                                               unsigned replicates, const pllgpu_bootstrap_trees_t *out)
+{
+  CHECK_CTX_KEEP(c);
+  static const char noun[] = "bootstrap distance trees";
+  c->last_launches = 0;
+  if (!out || !out->parent || !out->length) return fail(PLLGPU_EINVAL, "%s: null argument", noun);
+  if (!replicates) return 0;
+  if (count)
+    if (int rc = distances_check_arguments(c, tips, count, params_indices, opt)) return rc;
+  if (count < 3 || (flags & ~PLLGPU_NJ_BIONJ)) return fail(PLLGPU_EINVAL, "%s: invalid argument (%u tips, flags %#x)", noun, count, flags);
+  if (int rc = distances_check_state(c, tips, count)) return rc;
+  if (int rc = rell_cdf_current(c)) return rc;
+  if (int rc = rell_check_total(c, noun)) return rc;
+
+  const unsigned sites = c->geo.sites, wstride = (sites + 3u) / 4u * 4u;
+  const size_t cc = (size_t)count * count, nodes = 2 * (size_t)count - 2, scratch = nj_scratch_bytes(count, flags);
+  const size_t per_replicate = (size_t)wstride * sizeof(unsigned) + 6 * cc * sizeof(double) + scratch;
+  const unsigned per_chunk = (unsigned)std::min<size_t>(std::min(replicates, 65535u), std::max<size_t>(1, c->bootstrap_bytes / per_replicate));
+  DistanceCall k;
+  if (int rc = distances_begin(c, tips, count, params_indices, opt, per_chunk, k)) return rc;
+  ScratchEpoch scratch_epoch_;
+  DevBuf<unsigned char> block;
+  // whatever ends the call, the chunk's blocks go back to the pool once nothing of it is in flight
+  struct GiveBack
+  {
+    pllgpu_ctx *c;
+    DevBuf<unsigned char> &block;
+    bool waited = false;
+    ~GiveBack()
+    {
+      if (!waited) (void)hipStreamSynchronize(c->stream);
+      block.release();
+      c->rs_w.release();
+      c->ins_results.release();
+    }
+  } give_back{c, block};
+  if (block.ensure(per_chunk * scratch) || c->rs_w.ensure((size_t)per_chunk * wstride)) return PLLGPU_ENOMEM;
+  if (int rc = resample_events(c)) return rc;
+  std::vector<double> dist(out->distances ? per_chunk * cc : 0), status(out->status ? per_chunk * cc : 0);
+  const size_t plane = cc * sizeof(double);
+
+  for (unsigned r0 = 0; r0 < replicates; r0 += per_chunk)
+  {
+    const unsigned nr = std::min(per_chunk, replicates - r0);
+    const bool timed = r0 == 0;
+    give_back.waited = false;
+    if (timed) HIP_TRY(hipEventRecord(c->rs_ev[0], c->stream));
+    if (int rc = launch_rell_draw(c, seed, first + r0, nr, wstride)) return rc;
+    if (timed) HIP_TRY(hipEventRecord(c->rs_ev[1], c->stream));
+    if (int rc = distances_launch(c, k, c->rs_w.p, wstride, nr)) return rc;
+    if (timed) HIP_TRY(hipEventRecord(c->rs_ev[2], c->stream));
+    NjBatch trees;
+    unsigned launches = 0;
+    if (int rc = nj_enqueue(c->stream, c->ins_results.p, 6 * cc, nr, count, flags, block.p, trees, &launches)) return rc;
+    if (timed) HIP_TRY(hipEventRecord(c->rs_ev[3], c->stream));
+    // plane 0 (the distances) and plane 4 (the status words) of every replicate's block: one copy each
+    if (out->distances) HIP_TRY(hipMemcpy2DAsync(dist.data(), plane, c->ins_results.p, 6 * plane, plane, nr, hipMemcpyDeviceToHost, c->stream));
+    if (out->status)
+      HIP_TRY(hipMemcpy2DAsync(status.data(), plane, c->ins_results.p + 4 * cc, 6 * plane, plane, nr, hipMemcpyDeviceToHost, c->stream));
+    if (out->weights)
+    {
+      if (int rc = rell_rows_down(c, out->weights + (size_t)r0 * sites, nr, wstride)) return rc; // (its wait is the chunk's)
+    }
+    else
+      HIP_TRY(stream_wait(c));
+    give_back.waited = true;
+    if (int rc = nj_finish(trees, r0, out->parent + r0 * nodes, out->length + r0 * nodes)) return rc;
+    c->last_launches += launches;
+    if (out->distances) memcpy(out->distances + r0 * cc, dist.data(), nr * plane);
+    if (out->status)
+      for (size_t i = 0; i < nr * cc; ++i) out->status[r0 * cc + i] = (int)status[i];
+    if (timed)
+      for (int t = 0; t < 3; ++t)
+      {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->rs_ev[t], c->rs_ev[t + 1]));
+        c->bs_ms[t] = (double)ms;
+      }
+  }
+  return 0;
+}
+
+extern "C" int pllgpu_bootstrap_last_times(const pllgpu_ctx_t *c, double *ms)
+{
+  if (!c || !ms) return fail(PLLGPU_EINVAL, "null argument");
+  for (int t = 0; t < 3; ++t) ms[t] = c->bs_ms[t];
   return 0;
 }
 

@@ -145,6 +145,14 @@ AT(pll_gpu_distances_t, dd_f, 24);
 AT(pll_gpu_distances_t, status, 32);
 AT(pll_gpu_distances_t, iterations, 40);
 
+/* the outputs of pll_gpu_bootstrap_distance_trees, likewise */
+_Static_assert(sizeof(pll_gpu_bootstrap_trees_t) == 40 && sizeof(pllgpu_bootstrap_trees_t) == 40, "pll_gpu_bootstrap_trees_t size");
+AT(pll_gpu_bootstrap_trees_t, parent, 0);
+AT(pll_gpu_bootstrap_trees_t, length, 8);
+AT(pll_gpu_bootstrap_trees_t, distances, 16);
+AT(pll_gpu_bootstrap_trees_t, status, 24);
+AT(pll_gpu_bootstrap_trees_t, weights, 32);
+
 /* queries the Python binding declares by hand (pllamd/api.py): the prototypes it assumes */
 _Static_assert(_Generic(&pll_gpu_pending_clvs, unsigned int (*)(const pll_partition_t *): 1, default: 0) &&
                _Generic(&pllgpu_pending_clvs, unsigned (*)(const pllgpu_ctx_t *): 1, default: 0), "pll_gpu_pending_clvs prototype");

@@ -210,6 +210,17 @@ class Distances(C.Structure):
     ]
 
 
+class BootstrapTrees(C.Structure):
+    """pll_gpu_bootstrap_trees_t (include/pll_amd.h): the [replicates][...] outputs of pll_gpu_bootstrap_distance_trees"""
+    _fields_ = [
+        ("parent", C.POINTER(C.c_int)),
+        ("length", c_double_p),
+        ("distances", c_double_p),
+        ("status", C.POINTER(C.c_int)),
+        ("weights", c_uint_p),
+    ]
+
+
 NEWTON_MAX_ITERS = 64
 NJ_BIONJ = 1  # PLL_GPU_NJ_BIONJ
 NEWTON_CONVERGED, NEWTON_AT_MIN, NEWTON_AT_MAX, NEWTON_STALLED, NEWTON_MAXITER = 0, 1, 2, 3, 4
@@ -334,6 +345,12 @@ _GPU_PROTOS = {
     "pll_gpu_nj_tree": (C.c_int, [c_double_p, C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_int), c_double_p]),
     "pll_gpu_distance_tree": (
         C.c_int, [PartitionP, c_uint_p, C.c_uint, c_uint_p, C.POINTER(Newton), C.c_uint, C.POINTER(C.c_int), c_double_p, c_double_p]),
+    "pll_gpu_nj_trees": (C.c_int, [c_double_p, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.POINTER(C.c_int), c_double_p]),
+    "pll_gpu_bootstrap_distance_trees": (
+        C.c_int, [PartitionP, c_uint_p, C.c_uint, c_uint_p, C.POINTER(Newton), C.c_uint, C.c_ulonglong, C.c_uint, C.c_uint,
+                  C.POINTER(BootstrapTrees)]),
+    "pll_gpu_bootstrap_last_times": (C.c_int, [PartitionP, c_double_p]),
+    "pllgpu_nj_scratch_bytes": (C.c_size_t, [C.c_uint, C.c_uint]),  # device layer: a replicate's working set (tests restate the byte budgets)
     "pll_gpu_nj_last_launch_count": (C.c_uint, []),
     "pll_gpu_nj_last_device_ms": (C.c_double, []),
     "pll_gpu_last_algorithmic_bytes": (C.c_double, [PartitionP]),
@@ -502,3 +519,47 @@ def dptr(a):
 
 def uptr(a):
     return a.ctypes.data_as(c_uint_p)
+
+
+def nj_trees(lib, distances, flags=0, device=-1, fill=None):
+    """pll_gpu_nj_trees: (parent int32 [B, 2n - 2], length float64 [B, 2n - 2]) of the [B, n, n] matrices `distances` (only
+    [b][x][y], x < y, is read) from one call; row b is what pll_gpu_nj_tree gives on matrix b. flags 0 = NJ, NJ_BIONJ.
+    `fill`: what both outputs hold before the call (tests: outputs stay untouched on a failure; they then travel in the
+    exception's `outputs`). libpll_amd.so only."""
+    d = np.ascontiguousarray(distances, dtype=np.float64)
+    reps, n = d.shape[0], d.shape[1]
+    assert d.shape == (reps, n, n)
+    parent = np.full((reps, max(2 * n - 2, 1)), 0 if fill is None else fill, dtype=np.int32)
+    length = np.full((reps, max(2 * n - 2, 1)), 0.0 if fill is None else fill, dtype=np.float64)
+    if not lib.pll_gpu_nj_trees(dptr(d), n, reps, int(flags), int(device), parent.ctypes.data_as(C.POINTER(C.c_int)), dptr(length)):
+        err = RuntimeError(f"pll_gpu_nj_trees: [{lib.errno()}] {lib.errmsg()}")
+        err.outputs = {"parent": parent, "length": length}
+        raise err
+    return parent, length
+
+
+BOOTSTRAP_OPTIONAL = ("distances", "status", "weights")
+
+
+def bootstrap_distance_trees(lib, partition, tips, params_indices, options, flags, seed, first_replicate, replicates,
+                             want=BOOTSTRAP_OPTIONAL, fill=None):
+    """pll_gpu_bootstrap_distance_trees: a dict of parent int32 [B, 2n - 2], length float64 [B, 2n - 2] and, for the names
+    in `want`, distances float64 [B, n, n], status int32 [B, n, n], weights uint32 [B, sites] - row b what
+    pll_gpu_distance_tree returns under row first_replicate + b of pll_gpu_draw_replicate_weights(seed). What is not wanted
+    is handed over as NULL. `fill` as in nj_trees. libpll_amd.so only."""
+    tips = np.ascontiguousarray(tips, dtype=np.uint32)
+    n, reps, sites = len(tips), int(replicates), int(partition.contents.sites)
+    pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+    shapes = {"parent": ((reps, max(2 * n - 2, 1)), np.int32), "length": ((reps, max(2 * n - 2, 1)), np.float64),
+              "distances": ((reps, n, n), np.float64), "status": ((reps, n, n), np.int32), "weights": ((reps, sites), np.uint32)}
+    out = {name: np.full(shape, 0 if fill is None else fill).astype(dtype) for name, (shape, dtype) in shapes.items()
+           if name in ("parent", "length") or name in want}
+    rec = BootstrapTrees()
+    for name, a in out.items():
+        setattr(rec, name, a.ctypes.data_as(dict(BootstrapTrees._fields_)[name]))
+    if not lib.pll_gpu_bootstrap_distance_trees(partition, uptr(tips), n, uptr(pi), C.byref(options), int(flags), int(seed), int(first_replicate),
+                                                reps, C.byref(rec)):
+        err = RuntimeError(f"pll_gpu_bootstrap_distance_trees: [{lib.errno()}] {lib.errmsg()}")
+        err.outputs = out
+        raise err
+    return out
